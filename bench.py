@@ -8,7 +8,7 @@ lakonlab/pipelines/arcflux_pipeline.py:457-510.  Text encoders and the VAE are o
  and outside the timed region; prompt embeddings are synthetic, weights are random-init of
 the exact architecture (no network for checkpoints).
 
-    python bench.py --gpus N --steps K --warmup W [--model flux|qwen] [--train]
+    python bench.py --gpus N --steps K --warmup W [--model flux|qwen] [--train] [--full] [--dump-outputs DIR]
 
 N > 1: one replica per GPU.  Launched under torchrun (RANK / WORLD_SIZE in the environment) the script is one rank; launched
 bare (`python bench.py --gpus N`) it re-executes itself under `python -m torch.distributed.run --nproc-per-node N` and
@@ -16,9 +16,16 @@ fails loudly when the box has fewer than N GPUs -- the line never reports n_gpus
 --train times the distillation iteration instead (BASELINE.json configs[3] / [4]: FLUX 4 samples/GPU, Qwen 2 samples/GPU
 with the true-CFG teacher; data parallel, the adapter-gradient all-reduce over RCCL is inside the timed region).
 
-Prints ONE JSON line (rank 0) with the `roofline` object of the dominant kernel (the bf16 MFMA GEMM,
-timed live with HIP events on the launch stream) and a `cpu_baseline` object (the fp32 CPU oracle's
-FluxTransformerBlock on the host cores -- BASELINE.json configs[0] -- extrapolated by FLOPs).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and nothing else.  --full adds what takes measurements of its own: the
+`roofline` object of the dominant kernel (the bf16 MFMA GEMM, timed live with HIP events on the launch stream) and of the attention
+and transport-step kernels, the attention-backward probe of --train, the extra objects of a one-GPU FLUX run (Qwen-Image inference,
+the distillation iterations, prompt -> image) and a `cpu_baseline` object (the fp32 CPU oracle's FluxTransformerBlock on the host
+cores -- BASELINE.json configs[0] -- extrapolated by FLOPs).
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64): the 2-NFE latents
+of inference, the scalars of the iteration's info and a seeded sample of the updated trainable parameters of --train.  Inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -248,12 +255,41 @@ def train_main(args, rank, world, dev, dist):
             'allreduce_bytes_per_step': int(ds.params.numel()) * 4 if world > 1 else 0,
             'max_mem_gb': torch.cuda.max_memory_allocated() / 2 ** 30, 'last_step': info,
         }
-        try:      # the attention backward of ONE (sample, layer) at this workload's sequence length, alone on the chip (the kernel DESIGN 4.3 is about; HIP events, 10 calls)
-            line['attn_backward'] = _attn_backward_probe(dev, T + N_IMG)
-        except Exception as e:              # noqa: BLE001
-            line['attn_backward'] = {'error': f'{type(e).__name__}: {e}'}
+        if args.dump_outputs:
+            # what train_step returns (its timing entry aside) and the trainable set it updated
+            dump_outputs(args.dump_outputs, {**{k: torch.tensor([float(info[k])], dtype=torch.float64)
+                                                for k in ('loss', 'grad_norm', 'lr', 'teacher_ratio', 'skipped')},
+                                             'trainable_params_sample': _seeded_sample(ds.params)})
+        if args.full:
+            try:      # the attention backward of ONE (sample, layer) at this workload's sequence length, alone on the chip (the kernel DESIGN 4.3 is about; HIP events, 10 calls)
+                line['attn_backward'] = _attn_backward_probe(dev, T + N_IMG)
+            except Exception as e:              # noqa: BLE001
+                line['attn_backward'] = {'error': f'{type(e).__name__}: {e}'}
         return line
     return None
+
+
+DUMP_MAX_ELEMS = 1 << 22           # 16 MB of float32 per array: a larger output is dumped as a fixed, seeded sample
+
+
+def _seeded_sample(t, n=DUMP_MAX_ELEMS, seed=0):
+    """`t` flattened, or -- when it has more than `n` elements -- the elements at `n` sorted indices drawn from `seed` (the same
+    elements in every run with the same shapes)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(0, flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array (float64 stays float64, everything else is written as float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        np.save(os.path.join(out_dir, f'{name}.npy'), a.numpy())
 
 
 def _attn_backward_probe(dev, S, H=24, calls=10):
@@ -288,19 +324,26 @@ def parse_args(argv=None):
     ap.add_argument('--teacher-fp8', action='store_true', help='--train: frozen teacher forwards on the fp8 MFMA (configs[4]); the line says so in dtype')
     ap.add_argument('--streams', type=int, default=1, help='images in flight per GPU (one HIP stream + engine context each, shared weights); '
                                                            '1 = the canonical line, 2 fills the under-filled last rounds: +3.8 %% (r02)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='N = 1 FLUX run: skip the extra objects (Qwen inference, the two distillation iterations, prompt -> image)')
+    ap.add_argument('--full', action='store_true', help='also measure what takes runs of its own: per-kernel roofline objects (HIP events in the '
+                                                        'timed region), the extra objects of a one-GPU FLUX run and the CPU baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the last timed step\'s outputs as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full, N = 1 FLUX run: skip the extra objects (Qwen inference, the two distillation iterations, prompt -> image)')
     ap.add_argument('--e2e', action='store_true', help='only the prompt -> image object of --model (encoders + 2 NFE + VAE)')
-    ap.add_argument('--no-profile', action='store_true', help='do not record per-launch HIP events')
+    ap.add_argument('--no-profile', action='store_true', help='--full: do not record per-launch HIP events')
     ap.add_argument('--profile-stride', type=int, default=8, help='HIP event pair on one GEMM / attention launch in N inside the timed region (1: every launch, which costs 1.8 %% of the step)')
     ap.add_argument('--no-prepare-steps', action='store_true', help='recompute the AdaLN conditioning inside every transformer call (A/B)')
     ap.add_argument('--fp8', action='store_true', help='OPTIONAL reduced-precision mode: block linears on the fp8 MFMA (not the headline: the line says dtype fp8)')
     ap.add_argument('--master-port', type=int, default=None, help='rendezvous port of the self-launch (default: derived from the pid)')
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.e2e:
+        ap.error('--dump-outputs covers the inference and --train paths, not --e2e')
     if args.steps is None:
         args.steps = 2 if args.train else 5
     if args.warmup is None:
         args.warmup = 1 if args.train else 2
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     return args
 
 
@@ -352,8 +395,8 @@ def main(argv=None):
         line = train_main(args, rank, world, dev, dist)
     else:
         line = infer_main(args, args.model, rank, world, dev, dist)
-        if rank == 0 and world == 1 and args.model == 'flux' and not args.no_extras and not args.fp8 and args.streams == 1:
-            # The driver times ONE default run: after the FLUX headline (whose timed region is over) the same process measures the
+        if args.full and rank == 0 and world == 1 and args.model == 'flux' and not args.no_extras and not args.fp8 and args.streams == 1:
+            # --full: after the FLUX headline (whose timed region is over) the same process measures the
             # other configs BASELINE.json names -- Qwen-Image inference (configs[2]), one FLUX distillation iteration (configs[3]) and one Qwen-Image
             # distillation iteration with the fp8 forwards (configs[4]) --
             # and attaches them as extra objects.  The headline's value / ms_per_step / steps are untouched.
@@ -361,6 +404,7 @@ def main(argv=None):
             gc.collect()
             torch.cuda.empty_cache()
             ex = argparse.Namespace(**vars(args))
+            ex.dump_outputs = None                  # the dump is the headline's last step, not an extra's
             KEYS_T = ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'warmup', 'dtype', 'config', 'roofline', 'attn_backward', 'backward_schedule',
                       'allreduce_exposed_ms_per_step', 'allreduce_bytes_per_step', 'max_mem_gb')
 
@@ -398,7 +442,7 @@ def main(argv=None):
                     line['e2e'][m] = {'error': f'{type(e).__name__}: {e}'}
                 gc.collect()
                 torch.cuda.empty_cache()
-        if rank == 0 and not args.no_cpu_baseline and world == 1:
+        if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
             try:
                 line['cpu_baseline'] = cpu_baseline()
             except Exception as e:                  # noqa: BLE001  (the headline line must still be printed)
@@ -540,7 +584,7 @@ def infer_main(args, model, rank, world, dev, dist):
 
     for _ in range(args.warmup):
         one_image()
-    prof = not args.no_profile and len(engines) == 1      # per-launch durations overlap with several images in flight
+    prof = args.full and not args.no_profile and len(engines) == 1      # per-launch durations overlap with several images in flight
     stride = max(1, getattr(args, 'profile_stride', 8))
     eng.profile(stride if prof else False)
     barrier()
@@ -555,10 +599,12 @@ def infer_main(args, model, rank, world, dev, dist):
         tt = torch.tensor([dt], device=host_or_device(dist, dev))
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'latents': res})          # the 2-NFE latents of the last timed image
     # the analytic transport step alone (SURVEY 8d asks for its GB/s): 50 launches between two events on the launch stream -- includes
     # the ~1-2 us boundary between dependent launches, so it under-states the kernel (rocprof: profiles/r03_*)
     step_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         outs = engines[0](lat.bfloat16(), tvec[0], ctx, pooled, guidance, hp, wp)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(5):
@@ -615,7 +661,8 @@ def infer_main(args, model, rank, world, dev, dist):
                     'bound': 'mfma', 'kernel': 'afx::a3::attention_v3_kernel', 'achieved': a2, 'peak': MFMA_BF16_PEAK_TF,
                     'unit': 'TFLOP/s', 'frac': a2 / MFMA_BF16_PEAK_TF, 'launches': att_n,
                     'avg_launch_us': att_ms * 1e3 / att_n, 'share_of_step_time': att_ms * stride * 1e-3 / dt}
-        line['roofline_step'] = step_gbs
+        if args.full:
+            line['roofline_step'] = step_gbs
         return line
     return None
 

@@ -360,6 +360,7 @@ def main():
              u_pred=captured['u_t_pred'], u_tgt=captured['u_t'], timesteps=captured['timesteps'])
 
     golden_sampler()
+    golden_configs()
 
 
 def golden_sampler():
@@ -398,6 +399,29 @@ def golden_sampler():
         if buckets is not None:
             out[f'c{ci}_buckets'] = np.array(buckets, dtype=np.int64)
     np.savez_compressed(os.path.join(OUT, 'g8_sampler.npz'), **out)
+
+
+
+def golden_configs():
+    """G10: the two experiment configs (configs/flux/arcflux_2nfe_k16.py, configs/qwen/arcqwen_2nfe_k16.py) as this repository's
+    config reader loads them (``_base_`` files merged underneath): the merged key / value tree only, tuples tagged, as JSON."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from arcflow_amd.train import config as CFG
+
+    def enc(v):
+        if isinstance(v, dict):
+            return {k: enc(x) for k, x in v.items()}
+        if isinstance(v, tuple):
+            return {'__tuple__': [enc(x) for x in v]}
+        if isinstance(v, list):
+            return [enc(x) for x in v]
+        return v
+    cfgs = os.path.join(os.path.dirname(REF), 'configs')
+    out = {name: enc(CFG.load_config(os.path.join(cfgs, name))) for name in ('flux/arcflux_2nfe_k16.py', 'qwen/arcqwen_2nfe_k16.py')}
+    with open(os.path.join(OUT, 'g10_configs.json'), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
 
 
 if __name__ == '__main__':

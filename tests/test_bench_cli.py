@@ -50,3 +50,51 @@ def test_train_mode_defaults():
     import bench
     a = bench.parse_args(['--train', '--model', 'qwen'])
     assert a.train and a.steps == 2 and a.warmup == 1 and a.batch is None
+
+
+def test_plain_run_is_the_headline_and_full_is_opt_in():
+    import bench
+    a = bench.parse_args(['--steps', '4', '--warmup', '1'])
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 1
+    a = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert a.full and a.dump_outputs == 'out'
+    for bad in (['--steps', '0'], ['--warmup', '-1'], ['--e2e', '--dump-outputs', 'out']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_float_npy_and_seeded_sample(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    s1, s2 = bench._seeded_sample(big), bench._seeded_sample(big.clone())
+    assert s1.numel() == bench.DUMP_MAX_ELEMS and torch.equal(s1, s2)          # the same elements in every run
+    assert bool((s1[1:] >= s1[:-1]).all())
+    small = torch.randn(3, 5)
+    assert torch.equal(bench._seeded_sample(small), small.reshape(-1))
+    bench.dump_outputs(str(tmp_path / 'd'), {'lat': small.bfloat16(), 'loss': torch.tensor([0.5], dtype=torch.float64)})
+    lat, loss = np.load(tmp_path / 'd' / 'lat.npy'), np.load(tmp_path / 'd' / 'loss.npy')
+    assert lat.dtype == np.float32 and lat.shape == (3, 5) and np.allclose(lat, small.bfloat16().float().numpy())
+    assert loss.dtype == np.float64 and loss.tolist() == [0.5]
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_latents(tmp_path):
+    """A plain `bench.py` run prints the headline alone and --dump-outputs writes the last timed image's latents."""
+    import json
+    import subprocess
+    import numpy as np
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--dump-outputs', str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    ln = lines[0]
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in ln, k
+    assert ln['steps'] == 2 and ln['warmup'] == 1 and ln['value'] > 0 and ln['ms_per_step'] > 0
+    assert not {'roofline', 'roofline_step', 'cpu_baseline', 'qwen', 'e2e'} & set(ln)
+    lat = np.load(out / 'latents.npy')
+    assert lat.dtype == np.float32 and lat.shape == (1, 4096, 64) and np.isfinite(lat).all()

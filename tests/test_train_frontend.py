@@ -1,4 +1,5 @@
 """Training front-end: sampler vs the reference class (golden g8), config reader, prompt cache."""
+import json
 import os
 import pickle
 
@@ -90,11 +91,22 @@ def test_config_reader_merges_bases_and_maps_to_distill_config(tmp_path):
     assert dc3.teacher_fp8 and dc3.student_fp8
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/configs'), reason='reference tree not present')
+def _golden_config(name):
+    """One reference experiment config as the config reader merged it (fixture G10, tests/golden/make_golden.py)."""
+    def dec(v):
+        if isinstance(v, dict):
+            return tuple(dec(x) for x in v['__tuple__']) if set(v) == {'__tuple__'} else {k: dec(x) for k, x in v.items()}
+        if isinstance(v, list):
+            return [dec(x) for x in v]
+        return v
+    with open(os.path.join(os.path.dirname(GOLD), 'g10_configs.json')) as f:
+        return dec(json.load(f)[name])
+
+
 def test_reference_configs_load():
-    for path, fam, nd, tgs, decay in (('/root/reference/configs/flux/arcflux_2nfe_k16.py', 'flux', 19, 1.0, 2000),
-                                       ('/root/reference/configs/qwen/arcqwen_2nfe_k16.py', 'qwen', 60, 4.0, 1000)):
-        f, eng, dc, run = CFG.distill_setup(CFG.load_config(path))
+    for name, fam, nd, tgs, decay in (('flux/arcflux_2nfe_k16.py', 'flux', 19, 1.0, 2000),
+                                       ('qwen/arcqwen_2nfe_k16.py', 'qwen', 60, 4.0, 1000)):
+        f, eng, dc, run = CFG.distill_setup(_golden_config(name))
         assert (f, eng['num_double'], dc.teacher_guidance_scale, dc.num_decay_iters) == (fam, nd, tgs, decay)
         assert dc.lora_rank == 256 and dc.lora_dropout == 0.05 and dc.lr == 1e-4 and dc.grad_clip == 50.0 and dc.loss_scale == 30.0 and dc.nfe == 2
 

@@ -11,7 +11,7 @@ done
 for r in $(seq 1 $ROUNDS); do
   for s in "$@"; do
     if [ -n "$s" ]; then export ARCFLOW_HIP_LIB=$LIBDIR/libarcflow_hip$s.so; else unset ARCFLOW_HIP_LIB; fi
-    echo -n "fp8 forward, lib '$s'  "; timeout 300 python bench.py --fp8 --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python tools/bench_brief.py
+    echo -n "fp8 forward, lib '$s'  "; timeout 300 python bench.py --full --fp8 --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python tools/bench_brief.py
   done
 done 2>&1 | tee $OUT/ab_fp8_forward.log
 for r in 1 2; do

@@ -12,6 +12,6 @@ done
 for r in $(seq 1 $ROUNDS); do
   for s in "$@"; do
     if [ -n "$s" ]; then export ARCFLOW_HIP_LIB=$LIBDIR/libarcflow_hip$s.so; else unset ARCFLOW_HIP_LIB; fi
-    echo -n "lib '$s'  "; timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras ${AB_ARGS} 2>/dev/null | python tools/bench_brief.py
+    echo -n "lib '$s'  "; timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras ${AB_ARGS} 2>/dev/null | python tools/bench_brief.py
   done
 done 2>&1 | tee $OUT/ab.log

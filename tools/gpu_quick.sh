@@ -8,13 +8,14 @@ tail -4 $OUT/pytest.log
 if [ -n "$1" ]; then timeout 600 python tools/microbench.py "$@" 2>&1 | grep -v amdgpu.ids | tee $OUT/micro.log; fi
 for r in 1 2 3; do
   if [ -n "$VAR" ] && [ "$VAR" != "-" ]; then
-    echo -n "$VAR=0 "; env $VAR=0 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
-    echo -n "$VAR=1 "; env $VAR=1 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
+    echo -n "$VAR=0 "; env $VAR=0 timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
+    echo -n "$VAR=1 "; env $VAR=1 timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
   else
-    timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
+    timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python tools/bench_brief.py
   fi
 done 2>&1 | tee $OUT/ab.log
+R=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/stats -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/bench_under_rocprof.log 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $R/$OUT/bench_under_rocprof.log 2>/dev/null
 cd $GRAFT_REPO_ROOT
 f=$(ls $OUT/stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cut -c1-150 $f | head -12

@@ -7,6 +7,6 @@ mkdir -p $OUT
 tail -5 $OUT/pytest.log
 timeout 600 python tools/microbench.py gemm attn elem > $OUT/micro.log 2>&1
 cat $OUT/micro.log | grep -v amdgpu.ids
-timeout 600 python bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 python tools/bench_brief.py < $OUT/bench.json
 (python bench.py --gpus 2 --steps 1; echo "exit=$?") > $OUT/bench_gpus2.log 2>&1; tail -2 $OUT/bench_gpus2.log
