@@ -39,21 +39,32 @@ __global__ __launch_bounds__(256) void norm_rows_kernel(const bf16_t* __restrict
   const bf16_t* xr = x + (int64_t)row * ldx;
   const int nch = D >> 3;
   float v[16][8];
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int ch = i * 64 + lane;
     if (ch < nch) {
       unpack8(*reinterpret_cast<const u32x4_t*>(xr + ch * 8), v[i]);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { s1 += v[i][e]; s2 += v[i][e] * v[i][e]; }
+      for (int e = 0; e < 8; ++e) s1 += v[i][e];
     }
   }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  const float mean = rms ? 0.f : s1 / D;
-  const float var = rms ? s2 / D : s2 / D - mean * mean;
-  const float rstd = rsqrtf(var + eps);
+  const float mean = rms ? 0.f : wave_sum(s1) / D;
+  // the variance from the centred values (already in registers): the one-pass s2 / D - mean^2 cancels in fp32 when |mean| >> std
+  // (rows offset by 64 std lost ~1e-3 of rstd)
+  float s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int ch = i * 64 + lane;
+    if (ch < nch) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = v[i][e] - mean;
+        s2 += d * d;
+      }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(s2) / D + eps);
   bf16_t* yr = y + (int64_t)row * ldy;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {

@@ -977,10 +977,14 @@ __global__ __launch_bounds__(256) void gelu_kernel(const bf16_t* __restrict__ pr
     unpack8(*reinterpret_cast<const u32x4_t*>(dh + r * ldh + c * 8), d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
+      // sigmoid form: 0.5 (1 + tanh u) = s = sigmoid(2u), 0.5 (1 - tanh^2 u) = 2 s (1 - s).  a = exp(-2|u|) <= 1 cannot overflow, and
+      // both s and 1 - s come from a product, never a difference (the tanh form's 1 + t, t -> -1, lost gelu' for x below about -3)
       const float u = 0.7978845608028654f * (x[e] + 0.044715f * x[e] * x[e] * x[e]);
-      const float t = 1.0f - 2.0f / (__expf(2.0f * u) + 1.0f);
+      const float a = __expf(-2.0f * fabsf(u));
+      const float p = 1.0f / (1.0f + a);
+      const float s = u >= 0.f ? p : a * p, sm = u >= 0.f ? a * p : p;
       const float du = 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x[e] * x[e]);
-      o[e] = d[e] * (0.5f * (1.0f + t) + 0.5f * x[e] * (1.0f - t * t) * du);
+      o[e] = d[e] * (s + 2.0f * x[e] * s * sm * du);
     }
   }
   *reinterpret_cast<u32x4_t*>(out + r * ldo + c * 8) = pack8(o);

@@ -27,6 +27,48 @@ def _cuda(t: torch.Tensor, dtype) -> torch.Tensor:
     return t.to(dtype).contiguous()
 
 
+# Argument checks of the training-step wrappers: the kernels take a base pointer and a row stride and trust everything else, so a
+# transposed view, a wrong dtype or a short accumulator would give wrong numbers (or touch memory past the tensor) without an error.
+def _mat(t: torch.Tensor, dtype, name: str, shape=None) -> torch.Tensor:
+    """A [rows, cols] operand read row by row: 2-D, on the GPU, ``dtype``, unit inner stride (any row stride)."""
+    if t.device.type != 'cuda':
+        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    if t.dim() != 2 or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f'{name}: need a 2-D {dtype} tensor with unit inner stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name}: shape {tuple(t.shape)} != {tuple(shape)}')
+    return t
+
+
+def _acc(t: torch.Tensor, shape, name: str) -> torch.Tensor:
+    """An fp32 accumulator written through a flat index: contiguous, exactly ``shape``."""
+    if t.device.type != 'cuda':
+        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name}: need a contiguous float32 accumulator of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype} '
+                         f'strides {t.stride()}')
+    return t
+
+
+def _rows_f32(v: torch.Tensor, R: int, C: int, rows_per_batch: int, name: str) -> torch.Tensor:
+    """A per-batch fp32 row vector (gate / scale) [C] or [Bg, C] -> [Bg, C] with unit inner stride.  A row-strided fp32 view is passed
+    as it is (its rows 16-byte aligned: the kernels read it in float4); several rows need rows_per_batch with R == rows_per_batch * Bg."""
+    if v.device.type != 'cuda':
+        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    if v.dim() == 1:
+        v = v[None]
+    if v.dim() != 2 or v.shape[1] != C:
+        raise ValueError(f'{name}: need [{C}] or [batch, {C}], got {tuple(v.shape)}')
+    if not (v.dtype == torch.float32 and v.stride(1) == 1 and v.stride(0) % 4 == 0 and v.data_ptr() % 16 == 0):
+        v = v.to(torch.float32).contiguous()
+    if rows_per_batch > 0:
+        if R != rows_per_batch * v.shape[0]:
+            raise ValueError(f'{name}: {R} rows != rows_per_batch {rows_per_batch} x {v.shape[0]} {name} rows')
+    elif v.shape[0] != 1:
+        raise ValueError(f'{name}: {v.shape[0]} {name} rows need rows_per_batch')
+    return v
+
+
 def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: str = 'none',
            gelu_col0: int = 0, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
            rows_per_batch: int = 0, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None,
@@ -456,6 +498,9 @@ def transpose(x, pad_to: int = 1):
 def coldot(a, b, out_accum):
     """out_accum[c] += sum_r a[r,c] * b[r,c]   (a, b bf16 row-strided views, out fp32 [C])."""
     lib = _lib.load()
+    _mat(a, torch.bfloat16, 'coldot a')
+    _mat(b, torch.bfloat16, 'coldot b', a.shape)
+    _acc(out_accum, (a.shape[1],), 'coldot out_accum')
     _lib.check(lib.afx_coldot_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(out_accum), a.shape[0], a.shape[1], _s()))
     return out_accum
 
@@ -463,9 +508,15 @@ def coldot(a, b, out_accum):
 def gate_residual(y, gate, res, out=None):
     """out = res + gate[c] * y   (y, res bf16 [R,C], gate fp32 [C])."""
     lib = _lib.load()
+    _mat(y, torch.bfloat16, 'gate_residual y')
+    _mat(res, torch.bfloat16, 'gate_residual res', y.shape)
+    gate = _cuda(gate, torch.float32)
+    if tuple(gate.shape) != (y.shape[1],):
+        raise ValueError(f'gate_residual gate: need [{y.shape[1]}], got {tuple(gate.shape)}')
     if out is None:
         out = torch.empty(y.shape[0], y.shape[1], dtype=torch.bfloat16, device=y.device)
-    _lib.check(lib.afx_gate_residual_bf16(_p(y), y.stride(0), _p(_cuda(gate, torch.float32)), _p(res), res.stride(0), _p(out), out.stride(0),
+    _mat(out, torch.bfloat16, 'gate_residual out', y.shape)
+    _lib.check(lib.afx_gate_residual_bf16(_p(y), y.stride(0), _p(gate), _p(res), res.stride(0), _p(out), out.stride(0),
                                           y.shape[0], y.shape[1], _s()))
     return out
 
@@ -473,18 +524,32 @@ def gate_residual(y, gate, res, out=None):
 def gemv_t(x, w, out_accum):
     """out_accum[b,k] += sum_n x[b,n] w[n,k]   (x fp32 [B<=4, N], w bf16 [N, K], out fp32 [B, K])."""
     lib = _lib.load()
+    _mat(x, torch.float32, 'gemv_t x')
+    _mat(w, torch.bfloat16, 'gemv_t w')
+    if w.shape[0] != x.shape[1]:
+        raise ValueError(f'gemv_t: x {tuple(x.shape)} and w {tuple(w.shape)} do not agree on N')
+    _acc(out_accum, (x.shape[0], w.shape[1]), 'gemv_t out_accum')
     _lib.check(lib.afx_gemv_t_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(out_accum), x.shape[0], x.shape[1], w.shape[1], _s()))
     return out_accum
 
 
 def colsum(x, out_accum):
+    """out_accum[c] += sum_r x[r,c]   (x bf16 row-strided view, out fp32 [C])."""
     lib = _lib.load()
+    _mat(x, torch.bfloat16, 'colsum x')
+    _acc(out_accum, (x.shape[1],), 'colsum out_accum')
     _lib.check(lib.afx_colsum_bf16(_p(x), x.stride(0), _p(out_accum), x.shape[0], x.shape[1], _s()))
     return out_accum
 
 
 def normout_backward(x, dxn, dmod_accum, rows_per_batch: int):
+    """dmod_accum[b, 0] += sum_rows(b) dxn * LN(x), dmod_accum[b, 1] += sum_rows(b) dxn   (x, dxn bf16 [R, D] views, dmod fp32 [R / rows_per_batch, 2, D])."""
     lib = _lib.load()
+    _mat(x, torch.bfloat16, 'normout_backward x')
+    _mat(dxn, torch.bfloat16, 'normout_backward dxn', x.shape)
+    if rows_per_batch < 1 or x.shape[0] % rows_per_batch:
+        raise ValueError(f'normout_backward: {x.shape[0]} rows are not a whole number of batch entries of {rows_per_batch}')
+    _acc(dmod_accum, (x.shape[0] // rows_per_batch, 2, x.shape[1]), 'normout_backward dmod_accum')
     _lib.check(lib.afx_normout_backward(_p(x), x.stride(0), _p(dxn), dxn.stride(0), _p(dmod_accum), x.shape[0], x.shape[1],
                                         rows_per_batch, _s()))
     return dmod_accum
@@ -493,19 +558,31 @@ def normout_backward(x, dxn, dmod_accum, rows_per_batch: int):
 def normout_backward_split(x, dxn, d_scale_accum, d_shift_accum):
     """d_scale_accum[D] += sum_rows dxn * LN(x), d_shift_accum[D] += sum_rows dxn (all rows one batch entry; fp32 vectors, e.g. slices of a larger buffer)."""
     lib = _lib.load()
-    assert d_scale_accum.is_contiguous() and d_shift_accum.is_contiguous() and d_scale_accum.dtype == torch.float32
+    _mat(x, torch.bfloat16, 'normout_backward_split x')
+    _mat(dxn, torch.bfloat16, 'normout_backward_split dxn', x.shape)
+    _acc(d_scale_accum, (x.shape[1],), 'normout_backward_split d_scale_accum')
+    _acc(d_shift_accum, (x.shape[1],), 'normout_backward_split d_shift_accum')
     _lib.check(lib.afx_normout_backward_split(_p(x), x.stride(0), _p(dxn), dxn.stride(0), _p(d_scale_accum), _p(d_shift_accum), x.shape[0], x.shape[1], _s()))
 
 
 def outer_accum(dmod, x, dW_accum):
+    """dW_accum[j, k] += sum_b dmod[b, j] x[b, k]   (dmod [B, J], x [B, Kd], dW fp32 [J, Kd])."""
     lib = _lib.load()
+    dmod, x = _cuda(dmod, torch.float32), _cuda(x, torch.float32)
+    if dmod.dim() != 2 or x.dim() != 2 or x.shape[0] != dmod.shape[0]:
+        raise ValueError(f'outer_accum: dmod {tuple(dmod.shape)} and x {tuple(x.shape)} need the same batch')
     B, J = dmod.shape
-    _lib.check(lib.afx_outer_accum(_p(_cuda(dmod, torch.float32)), _p(_cuda(x, torch.float32)), _p(dW_accum), B, J, x.shape[1], _s()))
+    _acc(dW_accum, (J, x.shape[1]), 'outer_accum dW_accum')
+    _lib.check(lib.afx_outer_accum(_p(dmod), _p(x), _p(dW_accum), B, J, x.shape[1], _s()))
     return dW_accum
 
 
 def sumsq(x, out_accum):
+    """out_accum[0] += sum x^2   (x fp32, contiguous)."""
     lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f'sumsq x: need a contiguous float32 tensor, got {x.dtype} strides {x.stride()}')
+    _acc(out_accum, (1,), 'sumsq out_accum')
     _lib.check(lib.afx_sumsq(_p(x), _p(out_accum), x.numel(), _s()))
     return out_accum
 
@@ -625,12 +702,15 @@ def attention_bwd(q, k, v, o, dout, lse):
 def ln_modulate_backward(x, dxn, scale, rows_per_batch: int = 0, dres=None, out=None):
     """dx = dres + LN^T(dxn * (1 + scale[b])); x, dxn [R,D] bf16 (row-strided views allowed), scale [B,D] f32."""
     lib = _lib.load()
+    _mat(x, torch.bfloat16, 'ln_modulate_backward x')
     R, D = x.shape
+    _mat(dxn, torch.bfloat16, 'ln_modulate_backward dxn', x.shape)
+    if dres is not None:
+        _mat(dres, torch.bfloat16, 'ln_modulate_backward dres', x.shape)
     if out is None:
         out = torch.empty(R, D, dtype=torch.bfloat16, device=x.device)
-    scale = _cuda(scale, torch.float32)
-    if scale.dim() == 1:
-        scale = scale[None]
+    _mat(out, torch.bfloat16, 'ln_modulate_backward out', x.shape)
+    scale = _rows_f32(scale, R, D, rows_per_batch, 'scale')
     _lib.check(lib.afx_ln_modulate_backward(_p(x), x.stride(0), _p(dxn), dxn.stride(0), _p(scale), scale.stride(0),
                                             rows_per_batch if rows_per_batch > 0 else max(R, 1), _p(dres),
                                             0 if dres is None else dres.stride(0), _p(out), out.stride(0), R, D, _s()))
@@ -642,10 +722,23 @@ def qk_norm_rope(x, w_txt, w_img, cos, sin, n_txt: int, out=None, dy=None):
     lib = _lib.load()
     B, S, HD = x.shape
     H = HD // 128
-    x2 = x.reshape(B * S, HD) if x.is_contiguous() else x.view(B * S, HD)
+    if HD % 128 or not 0 <= n_txt <= S:
+        raise ValueError(f'qk_norm_rope: need whole 128-wide heads and 0 <= n_txt <= S, got {tuple(x.shape)}, n_txt {n_txt}')
+    x2 = _mat(x.reshape(B * S, HD) if x.is_contiguous() else x.view(B * S, HD), torch.bfloat16, 'qk_norm_rope x')
     if out is None:
         out = torch.empty(B * S, HD, dtype=torch.bfloat16, device=x.device)
-    dy2 = None if dy is None else dy.view(B * S, HD)
+    _mat(out, torch.bfloat16, 'qk_norm_rope out', (B * S, HD))
+    dy2 = None
+    if dy is not None:
+        if tuple(dy.shape) != (B, S, HD):
+            raise ValueError(f'qk_norm_rope dy: shape {tuple(dy.shape)} != {(B, S, HD)}')
+        dy2 = _mat(dy.view(B * S, HD), torch.bfloat16, 'qk_norm_rope dy')
+    for t, name in ((cos, 'cos'), (sin, 'sin')):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (S, 64):
+            raise ValueError(f'qk_norm_rope {name}: need a contiguous float32 [{S}, 64] table, got {tuple(t.shape)} {t.dtype}')
+    for t, name in ((w_txt, 'w_txt'), (w_img, 'w_img')):
+        if t.numel() != 128:
+            raise ValueError(f'qk_norm_rope {name}: need 128 weights, got {tuple(t.shape)}')
     _lib.check(lib.afx_qk_norm_rope_oop_bf16(_p(x2), x2.stride(0), _p(out), out.stride(0), _p(dy2),
                                              0 if dy2 is None else dy2.stride(0), _p(_cuda(w_txt, torch.float32)),
                                              _p(_cuda(w_img, torch.float32)), _p(cos), _p(sin), B, S, n_txt, H,
@@ -656,9 +749,13 @@ def qk_norm_rope(x, w_txt, w_img, cos, sin, n_txt: int, out=None, dy=None):
 def gelu(pre, dh=None, out=None):
     """h = gelu_tanh(pre) or, with dh, dpre = dh * gelu'(pre); [R,C] bf16 row-strided views."""
     lib = _lib.load()
+    _mat(pre, torch.bfloat16, 'gelu pre')
     R, Cc = pre.shape
+    if dh is not None:
+        _mat(dh, torch.bfloat16, 'gelu dh', pre.shape)
     if out is None:
         out = torch.empty(R, Cc, dtype=torch.bfloat16, device=pre.device)
+    _mat(out, torch.bfloat16, 'gelu out', pre.shape)
     _lib.check(lib.afx_gelu_bf16(_p(pre), pre.stride(0), _p(dh), 0 if dh is None else dh.stride(0), _p(out), out.stride(0), R, Cc, _s()))
     return out
 
@@ -666,13 +763,15 @@ def gelu(pre, dh=None, out=None):
 def add_scale(a, b=None, gate=None, rows_per_batch: int = 0, out=None):
     """out = (a (+ b)) * gate[batch]; a, b [R,C] bf16 row-strided, gate [B,C] f32."""
     lib = _lib.load()
+    _mat(a, torch.bfloat16, 'add_scale a')
     R, Cc = a.shape
+    if b is not None:
+        _mat(b, torch.bfloat16, 'add_scale b', a.shape)
     if out is None:
         out = torch.empty(R, Cc, dtype=torch.bfloat16, device=a.device)
+    _mat(out, torch.bfloat16, 'add_scale out', a.shape)
     if gate is not None:
-        gate = _cuda(gate, torch.float32)
-        if gate.dim() == 1:
-            gate = gate[None]
+        gate = _rows_f32(gate, R, Cc, rows_per_batch, 'gate')
     _lib.check(lib.afx_add_scale_bf16(_p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), _p(gate),
                                       0 if gate is None else gate.stride(0), rows_per_batch if rows_per_batch > 0 else max(R, 1),
                                       _p(out), out.stride(0), R, Cc, _s()))

@@ -1,7 +1,9 @@
 """Prompt encoders (arcflow_amd/text_encoders.py) against the real transformers modules (fp32, CPU, random-init small
 configs of the same architecture): T5 v1.1 encoder, CLIP text model, Qwen2.5-VL language model."""
+import numpy as np
 import pytest
 import torch
+from bf16_parity import U32, check_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -18,25 +20,33 @@ def _bf16_weights(m):
     return m
 
 
-@pytest.mark.parametrize('S', [64, 77, 200])
-def test_attention_ext_vs_torch(S):
+# (H, Hkv, head_dim, causal, relative-position bias): toy configurations, then the production encoders
+_ATTN_TOY = [(4, 4, 64, False, True), (3, 3, 64, True, False), (8, 2, 128, True, False), (2, 2, 128, False, False)]
+_T5_XXL, _CLIP_L, _QWEN25_LM = (64, 64, 64, False, True), (12, 12, 64, True, False), (28, 4, 128, True, False)
+
+
+@pytest.mark.parametrize('S,configs', [pytest.param(64, _ATTN_TOY, id='64'), pytest.param(77, _ATTN_TOY, id='77'),
+                                       pytest.param(200, _ATTN_TOY, id='200'), pytest.param(512, [_T5_XXL], id='t5xxl-512'),
+                                       pytest.param(77, [_CLIP_L], id='clipl-77'), pytest.param(512, [_QWEN25_LM], id='qwen25-512'),
+                                       pytest.param(333, [_QWEN25_LM], id='qwen25-333')])
+def test_attention_ext_vs_torch(S, configs):
     import ctypes as C
     from arcflow_amd import _lib
     from arcflow_amd.text_encoders import _p, _s
     lib = _lib.load()
     g = torch.Generator().manual_seed(S)
-    for (H, Hkv, d, causal, use_bias) in [(4, 4, 64, False, True), (3, 3, 64, True, False), (8, 2, 128, True, False), (2, 2, 128, False, False)]:
+    for (H, Hkv, d, causal, use_bias) in configs:
         Dq, Dk = H * d, Hkv * d
         qkv = (torch.randn(S, Dq + 2 * Dk, generator=g) * 0.7).bfloat16()
         scale = 1.0 if use_bias else d ** -0.5
         bias = (torch.randn(H, 2 * S - 1, generator=g)) if use_bias else None
-        q = qkv[:, :Dq].float().view(S, H, d).transpose(0, 1)
-        k = qkv[:, Dq:Dq + Dk].float().view(S, Hkv, d).transpose(0, 1).repeat_interleave(H // Hkv, 0)
-        v = qkv[:, Dq + Dk:].float().view(S, Hkv, d).transpose(0, 1).repeat_interleave(H // Hkv, 0)
+        q = qkv[:, :Dq].double().view(S, H, d).transpose(0, 1)
+        k = qkv[:, Dq:Dq + Dk].double().view(S, Hkv, d).transpose(0, 1).repeat_interleave(H // Hkv, 0)
+        v = qkv[:, Dq + Dk:].double().view(S, Hkv, d).transpose(0, 1).repeat_interleave(H // Hkv, 0)
         s = q @ k.transpose(1, 2) * scale
         idx = torch.arange(S)
         if use_bias:
-            s = s + bias[:, (idx[None, :] - idx[:, None]) + S - 1]
+            s = s + bias.double()[:, (idx[None, :] - idx[:, None]) + S - 1]
         if causal:
             s = s.masked_fill(idx[None, :] > idx[:, None], float('-inf'))
         ref = (torch.softmax(s, -1) @ v).transpose(0, 1).reshape(S, Dq)
@@ -48,6 +58,114 @@ def test_attention_ext_vs_torch(S):
                                               scale, int(causal), _p(None if bias is None else bias.cuda()), _s()))
         assert _rel(o, ref) < 1.5e-2, (H, Hkv, d, causal, use_bias, _rel(o, ref))
 
+
+
+# ------------------------------------------------------------------------------------------ row kernels of afx_text.hip at the encoders' widths
+# Against fp64 from the same bf16 inputs.  Element-wise kernels: every element within one bf16 ulp (+ the fp32 rounding of a sum that can
+# cancel, where said) and >= 99 % equal to the reference rounded to nearest even -- a systematic relative error e shifts ~e / 5.4e-3 of the
+# elements, so 3e-3 fails.  norm_rows: one bf16 ulp plus fp32 eps x D x the row's input scale (|x| rstd |w| + |b|), >= 98 % rounded like
+# the reference: a 1e-3 error of rstd fails it.
+def _text_lib():
+    from arcflow_amd import _lib
+    from arcflow_amd.text_encoders import _p, _s
+    return _lib, _lib.load(), _p, _s
+
+
+def _gen(seed):
+    return torch.Generator(device='cuda').manual_seed(seed)
+
+
+@pytest.mark.parametrize('D,rms,eps,offset', [(768, False, 1e-5, 0.0), (768, False, 1e-5, 80.0), (4096, True, 1e-6, 0.0), (3584, True, 1e-6, 0.0),
+                                              (8192, True, 1e-6, 0.0), (8192, False, 1e-5, 0.0)])
+def test_norm_rows_vs_fp64(D, rms, eps, offset):
+    """LayerNorm (CLIP-L: 768, eps 1e-5, with bias) and RMSNorm (T5-XXL 4096, Qwen2.5 3584, eps 1e-6), the documented maximum D = 8192
+    (16 chunks per lane), a row-strided input and output, and LayerNorm rows whose mean is 64x their standard deviation."""
+    _lib, lib, _p, _s = _text_lib()
+    R = 333
+    g = _gen(D + int(rms) + int(offset))
+    x = (torch.randn(R, D + 64, generator=g, device='cuda') * (1.0 if offset else 2.0) + (offset or 0.3)).bfloat16()[:, 32:32 + D]
+    if offset:
+        assert bool((x.double().mean(-1) >= 64 * x.double().std(-1)).all())
+    w = (1 + 0.3 * torch.randn(D, generator=g, device='cuda')).bfloat16().float()
+    b = None if rms else (0.5 * torch.randn(D, generator=g, device='cuda')).bfloat16().float()
+    obuf = torch.full((R, D + 48), 3.0, dtype=torch.bfloat16, device='cuda')
+    y = obuf[:, 8:8 + D]
+    _lib.check(lib.afx_norm_rows_bf16(_p(x), x.stride(0), _p(y), y.stride(0), R, D, _p(w), _p(b), eps, int(rms), _s()))
+    assert bool((obuf[:, :8] == 3.0).all() and (obuf[:, 8 + D:] == 3.0).all())
+    xd = x.double()
+    mean = 0.0 if rms else xd.mean(-1, keepdim=True)
+    var = (xd * xd).mean(-1, keepdim=True) if rms else ((xd - mean) ** 2).mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    ref = (xd - mean) * rstd * w.double() + (0.0 if b is None else b.double())
+    row_scale = (xd.abs() * rstd * w.double().abs()).amax(-1, keepdim=True) + (0.0 if b is None else b.double().abs().max())
+    check_bf16(y, ref, floor=U32 * D * row_scale, min_equal=0.98, what=f'norm_rows D={D} rms={rms} offset={offset}')
+
+
+@pytest.mark.parametrize('F,act,gated', [(10240, 2, True), (18944, 1, True), (3072, 3, False)])
+def test_act_mul_vs_fp64(F, act, gated):
+    """T5-XXL's gated gelu-tanh (F = 10240, gate at column F), Qwen2.5's gated SiLU (18944) and CLIP's quick_gelu (3072), read from rows
+    of stride 2F, written into a column view of a wider output."""
+    _lib, lib, _p, _s = _text_lib()
+    M = 256
+    g = _gen(F + act)
+    x = (torch.randn(M, 2 * F, generator=g, device='cuda') * 3).clamp(-9.5, 9.5).bfloat16()
+    obuf = torch.full((M, F + 64), -2.0, dtype=torch.bfloat16, device='cuda')
+    out = obuf[:, 32:32 + F]
+    _lib.check(lib.afx_act_mul_bf16(_p(x), x.stride(0), _p(out), out.stride(0), M, F, F if gated else -1, act, _s()))
+    assert bool((obuf[:, :32] == -2.0).all() and (obuf[:, 32 + F:] == -2.0).all())
+    a = x[:, :F].double()
+    if act == 1:
+        r = a * torch.sigmoid(a)
+    elif act == 2:
+        r = a * torch.sigmoid(2 * (2.0 / np.pi) ** 0.5 * (a + 0.044715 * a ** 3))      # = 0.5 a (1 + tanh u), without fp64's cancellation for a < -5
+    else:
+        r = a * torch.sigmoid(1.702 * a)
+    if gated:
+        r = r * x[:, F:].double()
+    check_bf16(out, r, what=f'act_mul F={F} act={act}')
+
+
+def test_rope_half_qwen_row_in_place():
+    """Rotate-half RoPE in place on the 28 q + 4 k heads of 128 of a Qwen2.5 qkv row (v's 4 heads follow and must come back untouched)."""
+    _lib, lib, _p, _s = _text_lib()
+    S, H, Hkv, d = 333, 28, 4, 128
+    g = _gen(S)
+    width = (H + 2 * Hkv) * d
+    qkv = (torch.randn(S, width + 64, generator=g, device='cuda') + 0.1).bfloat16()
+    before = qkv.clone()
+    pos = torch.arange(S, device='cuda', dtype=torch.float64)[:, None]
+    inv = 1.0 / (1e6 ** (torch.arange(0, d, 2, device='cuda', dtype=torch.float64) / d))
+    ang = pos * inv[None]
+    cos, sin = torch.cos(ang).float().contiguous(), torch.sin(ang).float().contiguous()
+    view = qkv[:, :width]
+    _lib.check(lib.afx_rope_half_bf16(_p(view), view.stride(0), _p(cos), _p(sin), S, H + Hkv, d, _s()))
+    assert torch.equal(qkv[:, (H + Hkv) * d:], before[:, (H + Hkv) * d:])
+    x = before[:, :(H + Hkv) * d].double().view(S, H + Hkv, d)
+    a, b = x[..., :d // 2], x[..., d // 2:]
+    c, s_ = cos.double()[:, None], sin.double()[:, None]
+    ref = torch.cat([a * c - b * s_, b * c + a * s_], -1)
+    # two products and a sum in fp32: where the sum cancels, their roundings (2 u of |a c| + |b s|) show
+    floor = 2 * U32 * torch.cat([(a * c).abs() + (b * s_).abs(), (b * c).abs() + (a * s_).abs()], -1)
+    check_bf16(qkv[:, :(H + Hkv) * d].view(S, H + Hkv, d), ref, floor=floor, what='rope_half')
+
+
+@pytest.mark.parametrize('V,D,S,with_pos', [(32128, 4096, 512, False), (49408, 768, 77, True)])
+def test_embed_rows_last_row(V, D, S, with_pos):
+    """Embedding gather with ids that include the last vocabulary row: T5-XXL without positions (bit-exact copy), CLIP-L with its
+    position table (one fp32 add, then the bf16 rounding)."""
+    _lib, lib, _p, _s = _text_lib()
+    g = _gen(V)
+    table = torch.randn(V, D, generator=g, device='cuda').bfloat16()
+    ids = torch.randint(0, V, (S,), generator=g, device='cuda', dtype=torch.int32)
+    ids[0], ids[S // 2], ids[-1] = V - 1, 0, V - 1
+    pos = (0.3 * torch.randn(S, D, generator=g, device='cuda')).bfloat16() if with_pos else None
+    out = torch.empty(S, D, dtype=torch.bfloat16, device='cuda')
+    _lib.check(lib.afx_embed_rows_bf16(_p(table), _p(ids), _p(pos), _p(out), S, D, _s()))
+    rows = table[ids.long()]
+    if pos is None:
+        assert torch.equal(out, rows)
+    else:
+        check_bf16(out, rows.double() + pos.double(), what='embed_rows + pos')
 
 def test_t5_encoder_vs_transformers():
     from transformers import T5Config, T5EncoderModel
