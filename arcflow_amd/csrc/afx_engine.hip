@@ -63,10 +63,6 @@ struct afx_ctx {
   bool finalized = false;
   std::vector<DoubleW> dbl;
   std::vector<SingleW> sgl;
-  // side stream for the weight-streaming modulation GEMV (HBM-bound, 6.5 GB for FLUX): it runs under the first blocks' MFMA work
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int mod_overlap = -1;          // -1: read AFX_MOD_OVERLAP on first use (default off)
   char* ws = nullptr;
   int64_t ws_bytes = 0;
   int D = 0;
@@ -75,7 +71,6 @@ struct afx_ctx {
   uint16_t* ckpt = nullptr;   // optional [num_blocks][B*S, D] block-input checkpoints (gradient checkpointing)
   bool fp8 = false;            // block linears on the fp8 MFMA (afx_set_fp8_linear)
   int fp8_mx = -1;             // fp8: block-scaled activations, quantisation in the producers' epilogues (AFX_FP8_MX=0: one scale per row + a pass per GEMM)
-  bool sk_flags_dirty = false; // a new workspace was bound: its stream-K flag words are cleared on the next forward's stream
   const float* temb_override = nullptr;   // optional [B, D] f32 replacing timestep_embedder(t) (training student with its LoRA pair)
   // conditioning of several denoising steps prepared in one pass over the stacked modulation matrix (afx_mmdit_prepare_steps)
   int prep_steps = 0, prep_B = 0, prep_use = -1;
@@ -138,8 +133,6 @@ struct ModLayout {
 constexpr int AFX_PREP_ROWS = 8;      // (steps x samples) one modulation pass can serve: the GEMV's batch limit
 
 struct Workspace {
-  uint32_t* sk_flags;   // stream-K GEMM tail (afx_gemm.hip): 1024 flag words at offset 0 (zeroed by afx_set_workspace, re-armed by the kernel)
-  float* sk_slab;       //   + 256 fp32 accumulator slabs of one 256x256 tile each
   uint16_t *X, *Xn, *F, *Vt, *head;
   float *sincos, *tmp, *temb, *semb, *mod, *pooled;
   float *prep_temb, *prep_semb, *prep_mod;   // [AFX_PREP_ROWS][D], [..][D], [..][n_mod]: prepared steps (step-major, then sample)
@@ -163,9 +156,7 @@ Workspace carve(const afx_ctx* c, char* base, int B, int N, int T) {
     off += align256(bytes);
     return p;
   };
-  w.sk_flags = (uint32_t*)take(GEMM_SK_FLAG_BYTES);          // FIRST: its offset must not depend on the shape
-  w.sk_slab = (float*)take(GEMM_SK_SLAB_BYTES);
-  w.prep_temb = (float*)take((int64_t)AFX_PREP_ROWS * D * 4);       // (shape-independent offsets: they outlive a forward)
+  w.prep_temb = (float*)take((int64_t)AFX_PREP_ROWS * D * 4);       // FIRST (shape-independent offsets: they outlive a forward)
   w.prep_semb = (float*)take((int64_t)AFX_PREP_ROWS * D * 4);
   w.prep_mod = (float*)take((int64_t)AFX_PREP_ROWS * c->n_mod * 4);
   w.X = (uint16_t*)take(R * D * 2);
@@ -253,9 +244,6 @@ int afx_create(const afx_model_desc* desc, afx_ctx** out) {
 int afx_destroy(afx_ctx* ctx) {
   if (ctx) {
     for (auto& r : ctx->prof_pool) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->side) (void)hipStreamDestroy(ctx->side);
   }
   delete ctx;
   return AFX_OK;
@@ -348,11 +336,6 @@ int64_t afx_workspace_bytes(const afx_ctx* ctx, int32_t batch, int32_t n_img, in
 int afx_set_workspace(afx_ctx* ctx, void* dptr, int64_t bytes) {
   if (!ctx || !dptr || bytes <= 0) return fail(AFX_E_INVALID, "bad workspace");
   if (((uintptr_t)dptr & 255) != 0) return fail(AFX_E_INVALID, "workspace must be 256-byte aligned");
-  if (bytes < GEMM_SK_FLAG_BYTES) return fail(AFX_E_WORKSPACE, "workspace too small");
-  // The stream-K hand-off flags at the head of the workspace must start cleared (the kernel re-arms them).  The clear is issued on
-  // the stream of the NEXT forward (sk_flags_dirty), not here on the NULL stream: torch side streams are non-blocking, so a memset
-  // here would be unordered against a kernel still using a recycled allocator block and against the first forward.
-  ctx->sk_flags_dirty = true;
   ctx->ws = (char*)dptr;
   ctx->ws_bytes = bytes;
   ctx->prep_steps = 0;                                       // prepared steps lived in the old workspace
@@ -405,16 +388,11 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
     return fail(AFX_E_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)ws.total,
                 (long long)c->ws_bytes);
   hipStream_t st = (hipStream_t)stream_;
-  if (c->sk_flags_dirty) {
-    HIP_TRY(hipMemsetAsync(c->ws, 0, GEMM_SK_FLAG_BYTES, st));
-    c->sk_flags_dirty = false;
-  }
   const int64_t D = c->D;
   const int H = d.heads, S = N + T;
   const int64_t R = (int64_t)B * S;
   ModLayout ml{D, d.num_double, d.num_single};
   const int64_t ldm = c->n_mod;
-  int overlap_join_block = -1;          // >= 0: the side-stream modulation GEMV must be joined in front of this block
 
   const bool use_prep = c->prep_use >= 0 && c->prep_use < c->prep_steps && c->prep_B == B && stage != 2 && c->temb_override == nullptr;
   const int prep_k = c->prep_use;
@@ -447,41 +425,13 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   }
   HIP_TRY(launch_silu(ws.temb, ws.semb, (int64_t)B * D, st));
   // Every AdaLN modulation vector of the whole network in one weight-streaming pass over the stacked [n_mod, D] matrix
-  // (6.5 GB for FLUX: 1.3 ms of pure HBM streaming).  Only the first blocks' rows are needed right away: those run on the
-  // forward's stream; with AFX_MOD_OVERLAP=1 the rest streams on a side stream under the embedders' and first blocks' MFMA work
-  // and is joined in front of the first block that reads it (fork / join by events).  OFF by default: measured 140.2 vs 139.5 ms
-  // per image (r02c) -- the GEMMs lose more to the shared HBM / issue slots than the 1.3 ms the stream hides.
-  if (c->mod_overlap < 0) {
-    const char* e = getenv("AFX_MOD_OVERLAP");
-    c->mod_overlap = (e && e[0] == '1') ? 1 : 0;     // opt-in: measured -0.5 % on FLUX (r02c: the stream steals HBM + issue slots from the GEMMs)
-  }
-  const int nblocks = d.num_double + d.num_single;
-  const int head_blocks = 2;                                  // blocks whose modulation rows stay on the main stream
-  int64_t rows_main = c->n_mod;
-  overlap_join_block = -1;
-  if (c->mod_overlap && stage == 0 && nblocks > head_blocks + 2) {
-    rows_main = head_blocks <= d.num_double ? ml.dbl(head_blocks, 0, 0) : ml.sgl(head_blocks - d.num_double, 0);
-    if (!c->side) {
-      HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventRecord(c->ev_fork, st));                  // semb is ready
-    HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    const uint16_t* mw = W16(c, "mod.weight");
-    const uint16_t* mb = W16(c, "mod.bias");
-    HIP_TRY(launch_gemv(ws.semb, mw + rows_main * D, mb + rows_main, ws.mod + rows_main, B, (int)(c->n_mod - rows_main), (int)D, 0, 0,
-                        c->side, ldm));
-    if (W16(c, "mod_final.weight") != nullptr)
-      HIP_TRY(launch_gemv(ws.semb, W16(c, "mod_final.weight"), W16(c, "mod_final.bias"), ws.mod + ml.fin(0), B, (int)(2 * D),
-                          (int)D, 0, 0, c->side, ldm));
-    HIP_TRY(hipEventRecord(c->ev_join, c->side));
-    overlap_join_block = head_blocks;
-  }
-  HIP_TRY(launch_gemv(ws.semb, W16(c, "mod.weight"), W16(c, "mod.bias"), ws.mod, B, (int)rows_main, (int)D, 0, 0, st, ldm));
+  // (6.5 GB for FLUX: 1.3 ms of pure HBM streaming), on the forward's stream.  (Measured and dropped, r02c: the rows of all but the first blocks
+  // on a side stream under the embedders' and first blocks' MFMA work, 140.2 vs 139.5 ms per image -- the GEMMs lose more to the shared HBM / issue
+  // slots than the 1.3 ms the stream hides.)
+  HIP_TRY(launch_gemv(ws.semb, W16(c, "mod.weight"), W16(c, "mod.bias"), ws.mod, B, (int)c->n_mod, (int)D, 0, 0, st, ldm));
   // a separately bound norm_out.linear (the distillation student trains its own copy while the teacher keeps the
   // frozen one inside the stacked matrix: lakonlab/configs/flux/arcflux_2nfe_k16.py:20-25 freeze_exclude 'norm_out')
-  if (overlap_join_block < 0 && W16(c, "mod_final.weight") != nullptr)
+  if (W16(c, "mod_final.weight") != nullptr)
     HIP_TRY(launch_gemv(ws.semb, W16(c, "mod_final.weight"), W16(c, "mod_final.bias"), ws.mod + ml.fin(0), B, (int)(2 * D),
                         (int)D, 0, 0, st, ldm));
   }   // conditioning
@@ -512,13 +462,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   }   // stage != 2
   if (stage == 1) return AFX_OK;       // the caller runs the blocks itself on the exported token matrix
 
-  auto join_side = [&](int blk) -> int {
-    if (overlap_join_block >= 0 && blk >= overlap_join_block) {
-      HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-      overlap_join_block = -1;
-    }
-    return AFX_OK;
-  };
   // fp8 with block-scaled activations: every block GEMM reads e4m3 rows + one E8M0 byte per row and 128 columns.  The D-wide
   // operands are quantised into q8n / mxn (by the pass below until their producers write them), the wide ones (mlp hidden, [O | mlp]) leave
   // the producing GEMM's epilogue in q8 / mxw.
@@ -606,7 +549,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
           p.res = C + row0 * ldc; p.ldr = ldc;
         }
       }
-    gb.sk_slab = ws.sk_slab; gb.sk_flags = ws.sk_flags;
     // A launch costs ceil(rounds) x tile area: a SHORT text stream (Qwen-Image: 128 rows) costs the grouped launch a whole row of half-empty tiles --
     // at N = 12288, 4096 + 128 rows are 816 tiles of 256x256 (3.2 -> 4 rounds; the launcher settles for 1024 tiles of 288x192 = 4 rounds) where the image rows
     // alone are 768 = exactly 3.  split_txt (bit per launch kind: 1 qkv, 2 out, 4 mlp1, 8 mlp2; AFX_SPLIT_TXT overrides): the text problems go out as a launch
@@ -620,7 +562,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
     if ((split_mask & kind) != 0 && T > 0 && N > 0 && !mx && !c->fp8) {
       GemmBatch gi{}, gt{};
       for (int j = 0; j < gb.nprob; ++j) ((j & 1) ? gt : gi).p[((j & 1) ? gt : gi).nprob++] = gb.p[j];
-      gi.sk_slab = gt.sk_slab = ws.sk_slab; gi.sk_flags = gt.sk_flags = ws.sk_flags;
       { ProfScope ps_(c, st, 0, gemm_flops(gi)); HIP_TRY(launch_gemm(gi, st)); }
       { ProfScope ps_(c, st, 0, gemm_flops(gt)); HIP_TRY(launch_gemm(gt, st)); }
       return AFX_OK;
@@ -651,7 +592,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   for (int i = 0; stage == 0 && i < d.num_double; ++i) {
     const DoubleW& bw = c->dbl[i];
     const float* qkn = bw.qkn;          // [img_q, img_k, txt_q, txt_k][128]
-    if ((rc = join_side(i))) return rc;
     if (c->ckpt) HIP_TRY(hipMemcpyAsync(c->ckpt + (int64_t)i * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, st));
     if ((rc = stream_norm(i, 0, 1))) return rc;
     if (vt_fuse) {                        // per sample: img k, q, v^T + txt k, q, v^T = 6 problems in one launch
@@ -685,7 +625,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   for (int i = 0; stage == 0 && i < d.num_single; ++i) {
     const SingleW& bw = c->sgl[i];
     const float* qkn = bw.qkn;          // [q, k][128]
-    if ((rc = join_side(d.num_double + i))) return rc;
     if (c->ckpt)
       HIP_TRY(hipMemcpyAsync(c->ckpt + (int64_t)(d.num_double + i) * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, st));
     bool sgl_fused = false;
@@ -727,7 +666,6 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
       f.qk_D = (int)D; f.qk_wq = qkn; f.qk_wk = qkn + 128;
       f.rope_cos = rope_cos; f.rope_sin = rope_sin; f.rope_row0 = 0; f.rope_period = (int)S; f.rope_rows = (int)S;
     }
-    gb.sk_slab = ws.sk_slab; gb.sk_flags = ws.sk_flags;
     { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
     if (vt_fuse && B + 3 <= GEMM_MAX_PROBLEMS) {
     } else if (qk_fuse)
@@ -755,10 +693,8 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
       o.A = (const uint16_t*)ws.q8; o.lda = 5 * D; o.W = (const uint16_t*)bw.out.wq; o.fp8 = 1; o.a_scale = ws.qs;
       o.w_scale = bw.out.wscale;
     }
-    go.sk_slab = ws.sk_slab; go.sk_flags = ws.sk_flags;
     { ProfScope ps_(c, st, 0, gemm_flops(go)); HIP_TRY(launch_gemm(go, st)); }
   }
-  if (stage == 0 && (rc = join_side(1 << 30))) return rc;      // short trunks: the head reads the norm_out rows
 
   // ---- norm_out (scale first) + velocity head on the image tokens --------------------------------------
   for (int b = 0; b < B; ++b)
@@ -1062,8 +998,6 @@ int afx_linear_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, cons
                              stream);
 }
 
-int64_t afx_linear_sk_ws_bytes(void) { return GEMM_SK_FLAG_BYTES + GEMM_SK_SLAB_BYTES; }
-int afx_linear_sk_last_split(void) { return last_sk_cus(); }
 int afx_gemm_dropres_available(void) { return gemm_dropres_available() ? 1 : 0; }
 int afx_gemm_set_mode(int32_t impl, int32_t tile) {
   gemm_set_mode(impl, tile);
@@ -1078,29 +1012,10 @@ int afx_attn_bwd_set_impl(int32_t impl) {
   return 0;
 }
 
-static int linear_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                       int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
-                       int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, const void* pre, int64_t ldp,
-                       void* sk_ws, void* stream);
-
-int afx_linear_bf16_sk(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                       int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
-                       int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, void* sk_ws, void* stream) {
-  if (!sk_ws || ((uintptr_t)sk_ws & 255) != 0) return fail(AFX_E_INVALID, "afx_linear_bf16_sk: sk_ws must be a 256-byte aligned device buffer");
-  return linear_impl(A, lda, W, ldw, bias, C, ldc, M, N, K, epi, gelu_col0, gate, ldg, rows_per_batch, res, ldr, nullptr, 0, sk_ws, stream);
-}
-
 int afx_linear_bf16_pre(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
                         int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
                         int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, const void* pre, int64_t ldp,
                         void* stream) {
-  return linear_impl(A, lda, W, ldw, bias, C, ldc, M, N, K, epi, gelu_col0, gate, ldg, rows_per_batch, res, ldr, pre, ldp, nullptr, stream);
-}
-
-static int linear_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                       int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
-                       int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, const void* pre, int64_t ldp,
-                       void* sk_ws, void* stream) {
   if (!A || !W || !C) return fail(AFX_E_INVALID, "null argument to afx_linear_bf16");
   if (pre && ldp % 8) return fail(AFX_E_INVALID, "afx_linear_bf16_pre: ldp %% 8 == 0");
   if (M < 0 || N < 0 || K <= 0 || K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8)
@@ -1116,11 +1031,6 @@ static int linear_impl(const void* A, int64_t lda, const void* W, int64_t ldw, c
   p.C = (uint16_t*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epi; p.gelu_col0 = gelu_col0;
   p.gate = gate; p.ldg = ldg; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.res = (const uint16_t*)res; p.ldr = ldr;
   p.pre = (const uint16_t*)pre; p.ldp = ldp;
-  if (sk_ws) {
-    gb.sk_flags = (uint32_t*)sk_ws;
-    gb.sk_slab = (float*)((char*)sk_ws + GEMM_SK_FLAG_BYTES);
-    gb.sk_force = 1;
-  }
   HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
   return AFX_OK;
 }

@@ -1,8 +1,7 @@
 // Grouped bf16 GEMM for gfx950:  C = epi(A . W^T + bias),  A [M,K] and W [N,K] both K-contiguous
 // (the nn.Linear layout), fp32 accumulation on v_mfma_f32_16x16x32_bf16.
 //
-// Two kernels share the tile geometry (the 8-phase v2 is the product path; the plain 2-stage kernel stays as the
-// simple reference for A/B runs, AFX_GEMM_IMPL=1).  Variants that were measured and dropped: the v2 schedule on
+// The 8-phase kernel (v2) and the one-wave-per-SIMD kernel (v3) below.  Variants of v2 that were measured and dropped: the v2 schedule on
 // v_mfma_f32_32x32x16_bf16 (-12 %: the 2-deep accumulator chains stall), 2 phases of 32 MFMAs per K-tile (+3 % on
 // cache-resident operands but -7 % in the real forward, where the halved DMA lead time meets HBM latency), LDS reads
 // levelled 8/4/8/4 over the phases (0 %), one barrier per K-tile with every wave interleaving its own ds_reads / DMA with
@@ -19,7 +18,7 @@
 //   * two LDS stages (2 x 64 KiB): tile t+1 streams in while tile t feeds 64 MFMAs per wave.
 //   * epilogue: the 8-phase kernel accumulates C^T (operands swapped) and pairs lanes with v_permlane16_swap, so bias /
 //     GELU / gate*x+residual and the C store are 16 B per lane straight from registers (12.1 k -> 7.9 k cycles against
-//     the LDS transpose the simple kernel still uses).
+//     an LDS transpose).
 //   * several problems (image + text stream, or per-sample slices) share one launch; the 1-D
 //     grid is remapped so every XCD owns a contiguous run of tiles (private-L2 reuse of A/W panels).
 #include <cstdlib>
@@ -36,98 +35,15 @@ namespace afx {
 
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int GEMM_THREADS = 512;
-constexpr int TILE_BYTES = BM * BK * 2;                 // 32 KiB per operand tile
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;             // A + W
-constexpr int EPI_LD = 68;                              // fp32 row stride of the epilogue patch
-constexpr int EPI_WAVE_BYTES = 64 * EPI_LD * 4;         // 17408
-constexpr int GEMM_LDS_BYTES = 8 * EPI_WAVE_BYTES;      // 139264 >= 2 * STAGE_BYTES (131072)
+constexpr int GEMM_LDS_BYTES = 139264;                  // dynamic LDS of an 8-phase launch (its two stages of A + W tiles use 131072)
 constexpr int GROUP_M = 6;                              // super-row height of the tile order
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
 
-// Stage one 256x64 bf16 tile (rows row0.., columns k0..k0+63) into LDS by DMA.
-AFX_DEV void stage_tile(const bf16_t* __restrict__ base, int64_t ld, int row0, int nrows, int k0,
-                        char* lds_tile, int tid, int wave) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = i * GEMM_THREADS + tid;       // 16-byte chunk index inside the tile
-    const int r = p >> 3;                       // tile row
-    const int c = (p & 7) ^ ((r >> 1) & 7);     // logical chunk stored at physical chunk p&7
-    int gr = row0 + r;
-    gr = gr < nrows ? gr : nrows - 1;           // clamp: rows past the edge are never stored
-    const bf16_t* src = base + (int64_t)gr * ld + k0 + c * 8;
-    char* dst = lds_tile + (i * GEMM_THREADS + wave * 64) * 16;   // wave-uniform base
-    __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)dst, 16, 0, 0);
-  }
-}
-
 AFX_DEV bf16x8_t lds_frag(const char* tile, int row, int chunk) {
   const int phys = chunk ^ ((row >> 1) & 7);
   return *reinterpret_cast<const bf16x8_t*>(tile + row * 128 + phys * 16);
-}
-
-// Row-contiguous part of the epilogue, shared by every kernel variant: each lane owns 8 consecutive
-// columns of 8 rows of the wave's 64x64 fp32 patch; bias / GELU / gate*x+residual are applied here and C is
-// stored 16 B per lane (bf16) or 2 x 16 B (fp32 output, optionally accumulated -- weight gradients).
-AFX_DEV void epi_store_rows(const GemmProblem& P, const float* patch, int row0, int gcol, bool col_ok, int er, int ec,
-                            const float (&bias)[8]) {
-#pragma unroll
-  for (int ps = 0; ps < 8; ++ps) {
-    const int lr = ps * 8 + er;
-    const int grow = row0 + lr;
-    if (grow < P.M && col_ok) {
-      const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(patch + lr * EPI_LD + ec);
-      const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(patch + lr * EPI_LD + ec + 4);
-      float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] += bias[e];
-      if (P.pre != nullptr) {
-        float pr[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(P.pre + (int64_t)grow * P.ldp + gcol), pr);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += pr[e];
-      }
-      if (P.epi == EPI_GELU) {
-        if (gcol >= P.gelu_col0) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(v[e]);
-        }
-      } else if (P.epi == EPI_GATE_RES) {
-        float g[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};      // gate == nullptr: plain residual add
-        if (P.gate != nullptr) {
-          const float* gp = P.gate + (int64_t)(grow / P.rows_per_batch) * P.ldg + gcol;
-          const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(gp);
-          const f32x4_t g1 = *reinterpret_cast<const f32x4_t*>(gp + 4);
-          g[0] = g0[0]; g[1] = g0[1]; g[2] = g0[2]; g[3] = g0[3]; g[4] = g1[0]; g[5] = g1[1]; g[6] = g1[2]; g[7] = g1[3];
-        }
-        const u32x4_t rw = *reinterpret_cast<const u32x4_t*>(P.res + (int64_t)grow * P.ldr + gcol);
-        float rr[8];
-        unpack8(rw, rr);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = rr[e] + g[e] * v[e];
-      }
-      if (P.conv_wp > 0) {        // convolution on the padded grid: keep the 1-pixel border zero for the next layer
-        const int yy = grow / P.conv_wp, xx = grow - yy * P.conv_wp;
-        if (yy == 0 || yy == P.conv_hp - 1 || xx == 0 || xx == P.conv_wp - 1) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = 0.f;
-        }
-      }
-      if (P.out_f32 == 0) {
-        *reinterpret_cast<u32x4_t*>(P.C + (int64_t)grow * P.ldc + gcol) = pack8(v);
-      } else {
-        float* cp = reinterpret_cast<float*>(P.C) + (int64_t)grow * P.ldc + gcol;
-        f32x4_t o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-        if (P.out_f32 == 2) {
-          o0 += *reinterpret_cast<const f32x4_t*>(cp);
-          o1 += *reinterpret_cast<const f32x4_t*>(cp + 4);
-        }
-        *reinterpret_cast<f32x4_t*>(cp) = o0;
-        *reinterpret_cast<f32x4_t*>(cp + 4) = o1;
-      }
-    }
-  }
 }
 
 // LDS-free epilogue of the 8-phase kernel.  Its MFMAs are issued with the operands swapped (W fragment as "A"), so the
@@ -196,7 +112,7 @@ struct AccLit {
 };
 #define AFX_INL __attribute__((always_inline))
 
-// Tail hook (round 6, gemm_kernel_v3's V3_TAIL): the LAST K-tile's MFMAs are issued from inside the epilogue, row tile by row tile -- hk(-1) behind the
+// Tail hook (round 6, gemm_kernel_v3's TAIL): the LAST K-tile's MFMAs are issued from inside the epilogue, row tile by row tile -- hk(-1) behind the
 // epilogue's preamble (row tile 0, under the latency of the bias / residual / gate requests), then ONE MFMA of row tile ii + 1 at each of the 4 NS "points" of
 // row tile ii's steps (behind the exchange, behind the bias add, behind the activation, behind the store), so the matrix pipe works under the epilogue's VALU
 // and store issue instead of in front of it.  Point code = ii * (4 NS) + 4 st + q.  hk.all() = every remaining MFMA at once (epilogues without points).
@@ -703,9 +619,6 @@ AFX_DEV void epi_store_qk(const GemmProblem& P, f32x4_t (&acc)[MI][8], int row_b
   epi_store_qk_acc<MI, FP8, HK>(P, AccArr<MI, 8>{acc}, row_base, col_base, frow, fq, wn, hk);
 }
 
-#ifndef V3_F32_EPI
-#define V3_F32_EPI 1
-#endif
 template <int MI, int NJ, bool SWAP, bool FP8, bool PRE, class HK, class ACC>
 AFX_DEV void epi_store_fast_any_acc(const GemmProblem& P, const ACC& acc, int row_base, int col_base, int frow, int fq, const HK& hk) {
   if constexpr (NJ == 8 && SWAP && !PRE) {
@@ -720,7 +633,7 @@ AFX_DEV void epi_store_fast_any_acc(const GemmProblem& P, const ACC& acc, int ro
       if (region == 2) { epi_store_qk_acc<MI, FP8, HK>(P, acc, row_base, col_base, frow, fq, P.qk_wq, hk); return; }
     }
   }
-  if constexpr (SWAP && !FP8 && !PRE && V3_F32_EPI && !(MI == 8 && NJ == 4) && NJ % 2 == 0) {      // (8 x 4 is the 8-phase kernel's patch: it keeps its own)
+  if constexpr (SWAP && !FP8 && !PRE && !(MI == 8 && NJ == 4) && NJ % 2 == 0) {      // (8 x 4 is the 8-phase kernel's patch: it keeps its own)
     if (P.out_f32 == 1 || P.out_f32 == 2) { hk.all(); epi_store_f32_acc<MI, NJ>(P, acc, row_base, col_base, frow, fq); return; }
   }
   if (P.epi == EPI_GATE_RES) {
@@ -732,12 +645,9 @@ AFX_DEV void epi_store_fast_any_acc(const GemmProblem& P, const ACC& acc, int ro
     // The per-lane test `column >= gelu_col0` made every one of the 32 steps its own basic block behind an exec-mask branch (a lone wave pays ~30 cycles of
     // refetch per taken branch, and no step overlaps the next one's exchange / loads): 14.6 k cycles per 256 x 256 tile against 10.2 k without GELU.  A wave's
     // columns are (in every launch of the forward) all activated or none: decide once, wave-uniformly, and run straight-line code.
-#ifndef AFX_GELU_PER_LANE         // (-DAFX_GELU_PER_LANE: the per-lane test everywhere, for A/B builds)
     if (col_base >= P.gelu_col0) epi_store_fast_acc<EPI_GELU_ALL, MI, NJ, SWAP, FP8, PRE, false, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
     else if (col_base + 16 * NJ <= P.gelu_col0) epi_store_fast_acc<EPI_NONE, MI, NJ, SWAP, FP8, PRE, false, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
-    else
-#endif
-    epi_store_fast_acc<EPI_GELU, MI, NJ, SWAP, FP8, PRE, false, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
+    else epi_store_fast_acc<EPI_GELU, MI, NJ, SWAP, FP8, PRE, false, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
   }
   else if (SWAP && !FP8 && !PRE && !(MI == 8 && NJ == 4) && P.bias_rows) epi_store_fast_acc<EPI_NONE, MI, NJ, SWAP, false, false, true, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
   else epi_store_fast_acc<EPI_NONE, MI, NJ, SWAP, FP8, PRE, false, false, false, false, HK>(P, acc, row_base, col_base, frow, fq, hk);
@@ -866,103 +776,6 @@ AFX_DEV void epi_store_direct(const GemmProblem& P, f32x4_t (&acc)[8][4], int ro
   }
 }
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(const GemmBatch batch) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-
-  // ---- which tile of which problem --------------------------------------------------------
-  int wg = xcd_remap(blockIdx.x, gridDim.x);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-    if (i < batch.nprob && wg >= batch.p[i].tile_start) pi = i;
-  const GemmProblem& P = batch.p[pi];
-  wg -= P.tile_start;
-  const int GM_ = batch.group_m;
-  const int per_group = GM_ * P.tiles_n;
-  const int grp = wg / per_group;
-  const int first_m = grp * GM_;
-  const int gsz = min(P.tiles_m - first_m, GM_);
-  const int in_grp = wg - grp * per_group;
-  const int tm = first_m + in_grp % gsz;
-  const int tn = in_grp / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  const bf16_t* __restrict__ A = P.A;
-  const bf16_t* __restrict__ W = P.W;
-  const int nk = P.K / BK;
-
-  f32x4_t acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  // ---- main loop -------------------------------------------------------------------------
-  stage_tile(A, P.lda, m0, P.M, 0, smem, tid, wave);
-  stage_tile(W, P.ldw, n0, P.N, 0, smem + TILE_BYTES, tid, wave);
-  AFX_SYNC_DMA();       // drains the DMA (explicit vmcnt(0)) and releases the work-group
-
-  const int frow = lane & 15, fq = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    char* sa = smem + cur * STAGE_BYTES;
-    char* sw = sa + TILE_BYTES;
-    if (kt + 1 < nk) {
-      char* na = smem + (cur ^ 1) * STAGE_BYTES;
-      stage_tile(A, P.lda, m0, P.M, (kt + 1) * BK, na, tid, wave);
-      stage_tile(W, P.ldw, n0, P.N, (kt + 1) * BK, na + TILE_BYTES, tid, wave);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8_t bfr[4], afr[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bfr[j] = lds_frag(sw, wn * 64 + j * 16 + frow, kk * 4 + fq);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) afr[i] = lds_frag(sa, wm * 128 + i * 16 + frow, kk * 4 + fq);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    AFX_SYNC_DMA();     // next stage landed (explicit vmcnt(0)) and every wave is done with this one
-  }
-
-  // ---- epilogue: transpose through LDS, fused bias / activation / gated residual ------------
-  float* patch = reinterpret_cast<float*>(smem + wave * EPI_WAVE_BYTES);
-  const int er = lane >> 3;          // row within an 8-row pass
-  const int ec = (lane & 7) * 8;     // first of 8 consecutive columns
-  const int gcol = n0 + wn * 64 + ec;
-  const bool col_ok = gcol < P.N;
-
-  float bias[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) bias[e] = 0.f;
-  if (P.bias != nullptr && col_ok) {
-    const u32x4_t bw = *reinterpret_cast<const u32x4_t*>(P.bias + gcol);
-    unpack8(bw, bias);
-  }
-
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          patch[(i * 16 + fq * 4 + r) * EPI_LD + j * 16 + frow] = acc[h * 4 + i][j][r];
-    __syncthreads();
-    epi_store_rows(P, patch, m0 + wm * 128 + h * 64, gcol, col_ok, er, ec, bias);
-  }
-}
-
-
 // =================================================================================================
 // v2: 8-phase schedule -- two wave groups ping-pong on every SIMD, 4-deep counted DMA pipeline.
 //
@@ -1020,89 +833,18 @@ AFX_DEV void stage_half(const char* p0, const char* p1, int64_t kbyte, char* slo
 // (unit block scales; 2x the bf16 rate) covers the whole K-tile of a 16x16 output tile: the DMA / LDS / swizzle / phase code is
 // byte-for-byte the bf16 one, a phase is 8 MFMAs instead of 16.  The contraction order inside the instruction is free as
 // long as both operands agree, so lane (row, fq) simply feeds the two 16-byte chunks fq and 4 + fq it already reads.
-// ---- Stream-K tail (batch.sk_cus > 0) -----------------------------------------------------------------------------------
-// 216 / 648 / 864 tiles on 256 CUs leave the last "round" of a launch 84 % / 53 % / 38 % full.  With sk_cus = C CUs per XCD and
-// T = tiles / 8 tiles per XCD, every XCD runs its first full = floor(T / C) * C tiles as whole tiles (work-groups in dispatch
-// order, exactly as before) and splits the remaining rem = T - full tiles EVENLY over C more work-groups: the rem * nk K-tile
-// units are one linear range cut into C contiguous pieces, so a work-group computes (at most) the tail of one tile and the
-// head of the next.  The work-group that reaches a tile's last K-tile owns it (epilogue); a piece that stops short dumps its
-// raw fp32 accumulators (256 KB, lane-major: owner and helper share the lane <-> element map, no transposition) with 16-byte
-// write-through (sc1) stores into its slab and raises its flag; the owner polls the flags of the work-groups before it (one
-// lane, relaxed, s_sleep), ONE agent-scope acquire, adds the slabs and runs the normal epilogue.  Every work-group computes its
-// publishing piece FIRST, and an owner only ever waits for work-groups with a LOWER id: no cycle, no wait inside a publisher.
-// Hand-off protocol = cdna_hip_programming.md Guideline 16 R1 (sc1 payload, every wave drains vmcnt, one lane stores the flag,
-// consumer: relaxed poll -> one acquire -> __syncthreads -> loads); the consumer re-arms the flag (a slab has one reader).
-constexpr int SK_SLAB_FLOATS = BM * BN;
-constexpr unsigned SK_SPIN_LIMIT = 1u << 22;
-
-struct SkPiece { int nseg, tile, t0, n, role, g, s, j0, tot, nk; };
-
-// Piece ``sg`` (0 or 1) of this work-group: logical tile id, first K-tile, number of K-tiles (-1: the whole tile / split-K chunk),
-// role 0: whole tile, 1: owner of a tile whose head other work-groups computed, 2: publish a partial.  Pure scalar arithmetic
-// on blockIdx and kernel arguments.
-AFX_DEV SkPiece sk_piece(const GemmBatch& batch, int sg, int ES) {
-  SkPiece r{1, 0, 0, -1, 0, 0, 0, 0, 0, 0};
-  if (batch.sk_cus <= 0) {
-    r.tile = xcd_remap(blockIdx.x, gridDim.x);
-    return r;
-  }
-  const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3;
-  const int T = batch.sk_tiles_per_xcd, full = batch.sk_full, C = batch.sk_cus;
-  if (l < full) {
-    r.tile = xcd * T + l;
-    return r;
-  }
-  r.s = l - full;
-  r.g = xcd * C + r.s;
-  r.nk = batch.p[0].K * ES / (BK * 2);               // the launcher guarantees one K for every problem of a stream-K launch
-  r.tot = (T - full) * r.nk;
-  const int u0 = (int)((int64_t)r.s * r.tot / C), u1 = (int)((int64_t)(r.s + 1) * r.tot / C);
-  r.j0 = u0 / r.nk;
-  const int it0 = u0 - r.j0 * r.nk;
-  const int tile_end = (r.j0 + 1) * r.nk;
-  const int base = xcd * T + full;
-  if (u1 <= tile_end) {                              // one piece
-    r.tile = base + r.j0; r.t0 = it0; r.n = u1 - u0;
-    r.role = u1 == tile_end ? (it0 > 0 ? 1 : 0) : 2;
-  } else {                                           // head of the next tile FIRST (published), then the owned tail
-    r.nseg = 2;
-    if (sg == 0) {
-      r.tile = base + r.j0 + 1; r.t0 = 0; r.n = u1 - tile_end; r.role = 2;
-    } else {
-      r.tile = base + r.j0; r.t0 = it0; r.n = tile_end - u0; r.role = it0 > 0 ? 1 : 0;
-    }
-  }
-  return r;
-}
-
 template <bool FP8>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel_v2(const GemmBatch batch) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ES = FP8 ? 1 : 2;       // bytes per operand element
-
-  // ---- this work-group's pieces (decoded from blockIdx on demand: nothing but the piece index stays live across the main loop)
-  const int nseg = sk_piece(batch, 0, ES).nseg;
-
-#pragma unroll 1
-  for (int sg = 0; sg < nseg; ++sg) {
-  // Every lane constant is re-derived from an OPAQUE copy of threadIdx inside the piece loop: as loop invariants the compiler
-  // hoists ~60 of them (swizzle offsets, epilogue address pieces) in front of the loop and spills them around the main loop.
-  int tid_o = threadIdx.x;
-  asm volatile("" : "+v"(tid_o));
-  const int tid = tid_o;
+  const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const int frow = lane & 15, fq = lane >> 4;
   const int arow = wr * 64 + frow;      // + i*16
   const int brow = wc * 32 + frow;      // + j*16
-  int role, wg;
-  int t0 = 0, nk = -1;
-  {
-    const SkPiece pc = sk_piece(batch, sg, ES);
-    wg = pc.tile; role = pc.role;
-    if (pc.n >= 0) { t0 = pc.t0; nk = pc.n; }
-  }
+  int wg = xcd_remap(blockIdx.x, gridDim.x);
   int pi = 0;
 #pragma unroll
   for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
@@ -1123,14 +865,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel_v2(const GemmBatc
   const int tm = first_m + in_grp % gsz;
   const int tn = in_grp / gsz;
   const int m0 = tm * BM, n0 = tn * BN;
-  if (nk < 0) {                         // whole tile or split-K chunk (stream-K pieces come with their own range)
-    nk = P.K * ES / (BK * 2);
-    if (P.split_k > 1) {
-      const int per = (nk + P.split_k - 1) / P.split_k;
-      t0 = chunk * per;
-      nk = min(per, nk - t0);
-      if (nk <= 0) return;              // (the launcher's chunking leaves no empty chunk; uniform, before any barrier)
-    }
+  int t0 = 0, nk = P.K * ES / (BK * 2);
+  if (P.split_k > 1) {
+    const int per = (nk + P.split_k - 1) / P.split_k;
+    t0 = chunk * per;
+    nk = min(per, nk - t0);
+    if (nk <= 0) return;                // (the launcher's chunking leaves no empty chunk; uniform, before any barrier)
   }
 #ifdef AFX_GEMM_TRACE
   unsigned tr[24];
@@ -1263,47 +1003,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel_v2(const GemmBatc
   __syncthreads();
   AFX_TRC(20)
 
-  if (role == 2) {
-    // ---- publish the raw accumulators: slab[v][tid] 16-byte words, write-through, then this work-group's flag ----------
-    const int sk_g = sk_piece(batch, sg, ES).g;
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(batch.sk_slab + (int64_t)sk_g * SK_SLAB_FLOATS, 0,
-                                                                 SK_SLAB_FLOATS * 4, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[i][j]), rs, ((i * 4 + j) * GEMM_THREADS + tid) * 16, 0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its own stores
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(batch.sk_flags + sk_g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    continue;
-  }
-  if (role == 1) {
-    // ---- add the partials of the work-groups that computed this tile's head: s-1, s-2, ... while their range reaches into it
-    const SkPiece pc = sk_piece(batch, sg, ES);
-    const int tile_u0 = pc.j0 * pc.nk, sk_tot = pc.tot, sk_s = pc.s, sk_g = pc.g;
-    for (int sp = sk_s - 1; sp >= 0 && (int)((int64_t)(sp + 1) * sk_tot / batch.sk_cus) > tile_u0; --sp) {
-      const int g = sk_g - sk_s + sp;
-      if (tid == 0) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(batch.sk_flags + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && ++spins < SK_SPIN_LIMIT)
-          __builtin_amdgcn_s_sleep(8);
-        if (spins >= SK_SPIN_LIMIT) __hip_atomic_store(batch.sk_flags + 8 * 64, 0xdeadu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      __syncthreads();
-      __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(batch.sk_slab + (int64_t)g * SK_SLAB_FLOATS, 0, SK_SLAB_FLOATS * 4,
-                                                                   0x00020000);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] += __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, ((i * 4 + j) * GEMM_THREADS + tid) * 16, 0, 0));
-      __syncthreads();                                    // every wave has its slab words (the adds above waited for them)
-      if (tid == 0) __hip_atomic_store(batch.sk_flags + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
-    }
-  }
-
   // ---- epilogue: straight from the (transposed) accumulators ------------------------------------
   {   // lane constants of the epilogue from an OPAQUE copy of threadIdx: otherwise its column / row offsets are hoisted above the
       // main loop, where every register is spoken for (the fp8 instance spilled inside the loop: 158 -> 187 us at N = 9216)
@@ -1318,7 +1017,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel_v2(const GemmBatc
   if ((blockIdx.x == 0 || blockIdx.x == 300) && lane == 0)
     for (int i = 0; i < 24; ++i) g_gemm_trace[blockIdx.x ? 1 : 0][wave][i] = tr[i];
 #endif
-  }   // pieces
 }
 
 
@@ -1339,19 +1037,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel_v2(const GemmBatc
 //   * LDS = A x 2 slots + W x 3 slots: W(t+2) goes to the slot W(t-1) left at mid-tile t-1 (1.5 tiles ahead of its first read),
 //     A(t+2) to the slot A(t) leaves at mid-tile t (one tile ahead).
 //   * epilogue: epi_store_fast_any_acc on the asm-owned accumulator file (AccLit); round 6: the last K-tile's MFMAs are issued from inside it (TAIL, below).
-#ifndef V3_EXP
-#define V3_EXP 0
-#endif
-#ifndef V3F8_TAIL            // the same for the fp8 kernel (gemm_kernel_v3f8)
-#define V3F8_TAIL 1
-#endif
-#ifndef V3_TAIL              // 0: the last K-tile in front of the epilogue (round 5's schedule; A/B builds)
-#define V3_TAIL 1
-#endif
-#ifndef V3_EPI_SWAP          // 0: the 4-columns-per-lane epilogue without the permlane exchange (A/B builds; it has no masked residual add: gemm_dropres_available() is false there)
-#define V3_EPI_SWAP 1
-#endif
-#define V3_EPI_SWAP_DEFAULT V3_EPI_SWAP
 AFX_DEV uint64_t v3_uniform_u64(uint64_t v) {      // a wave-uniform 64-bit value, in an SGPR pair
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
@@ -1360,7 +1045,7 @@ AFX_DEV uint64_t v3_uniform_u64(uint64_t v) {      // a wave-uniform 64-bit valu
 // ASM-OWNED accumulators (round 6): gemm_kernel_v3's 4 MI NJ fp32 accumulators per lane are a[0 : 4 MI NJ) BY LITERAL NAME -- tile (i, j) = a[4 (i NJ + j) : + 3] --
 // in every MFMA and every epilogue read (AccLit), and `amdgpu_num_vgpr` confines hipcc's own allocation to the arch VGPRs: hipcc does not know the accumulator
 // file is in use.  (With "+a" operands hipcc owned the placement: fine for ONE MFMA chain in front of the epilogue, but once the last K-tile's MFMAs were issued
-// from inside the epilogue branches -- V3_TAIL -- it moved tiles between registers around every MFMA, parked them in arch VGPRs and spilled accumulators, also in
+// from inside the epilogue branches -- TAIL -- it moved tiles between registers around every MFMA, parked them in arch VGPRs and spilled accumulators, also in
 // the main loop.  Physical-register constraints "+{a[n:m]}" made it spill the tiles it could no longer move.)  What hipcc no longer does for us: the MFMA ->
 // accumulator-read wait states (explicit s_nop / program order below) and "parking" arch VGPRs in retired accumulator rows during the epilogue.
 // Which registers hipcc may still take: the arch VGPRs up to `amdgpu_num_vgpr`, and -- it allocates values that only move (copies, loads, stores) to either
@@ -1405,8 +1090,8 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
   // epilogue's preamble, then one MFMA of row tile i + 1 at each of the 4 NS points of row tile i's steps (TailHook above) -- so 2 MI NJ - 2 NJ of the tile's last
   // 2 MI NJ MFMAs run under the epilogue's VALU / store issue instead of in front of it.  Everything the last tile needs has landed at the mid-tile barrier of
   // tile nk - 2 (or at the very first barrier for nk = 1), so the tail has no barrier and no wait of its own; accumulation order per accumulator is unchanged
-  // (k-half 0, then k-half 1 of the last tile): the results are bit-identical to the plain schedule (-DV3_TAIL=0).
-  constexpr bool TAIL = V3_TAIL != 0 && !CONV && PERSIST == 0;
+  // (k-half 0, then k-half 1 of the last tile): the results are bit-identical to the plain schedule, which the convolution and persistent instances keep.
+  constexpr bool TAIL = !CONV && PERSIST == 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const smem_w = smem + 2 * A_SLOT;
   const int tid = threadIdx.x;
@@ -1568,11 +1253,10 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
         V3_FENCE();
         if ((m & 1) && (m >> 1) < MI + NJ) {
           const int r = m >> 1;               // b1[0..NJ), a1[0..MI)
-          if (V3_EXP == 2) {
-          } else if (r < NJ) b1[r] = lds_frag(sw, brow + r * 16, 4 + fq);
+          if (r < NJ) b1[r] = lds_frag(sw, brow + r * 16, 4 + fq);
           else a1[r - NJ] = lds_frag(sa, arow + (r - NJ) * 16, 4 + fq);
         }
-        if (m >= NM / 2 && (m - NM / 2) % W_SP == 1 && (m - NM / 2) / W_SP < NJ && V3_EXP != 1) {
+        if (m >= NM / 2 && (m - NM / 2) % W_SP == 1 && (m - NM / 2) / W_SP < NJ) {
           const int q = (m - NM / 2) / W_SP;
           const uint64_t src_ = wsrc_u;             // (locals: operands of an asm statement inside a generic lambda do not capture by themselves)
           const uint32_t off_ = woff[q];
@@ -1601,12 +1285,11 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
         V3_FENCE();
         if ((m & 1) && (m >> 1) < MI + NJ) {
           const int r = m >> 1;               // (past the last tile: re-reads a landed slot, unused)
-          if (V3_EXP == 2) {
-          } else if (TAIL && !more) {          // (the tail reads the last tile's fragments itself, a few MFMAs ahead of their use: nothing of them is live across the epilogue's preamble)
+          if (TAIL && !more) {          // (the tail reads the last tile's fragments itself, a few MFMAs ahead of their use: nothing of them is live across the epilogue's preamble)
           } else if (r < NJ) b0[r] = lds_frag(nw, brow + r * 16, fq);
           else a0[r - NJ] = lds_frag(na, arow + (r - NJ) * 16, fq);
         }
-        if (m >= NM / 2 && (m - NM / 2) % A_SP == 1 && (m - NM / 2) / A_SP < MI && V3_EXP != 1) {
+        if (m >= NM / 2 && (m - NM / 2) % A_SP == 1 && (m - NM / 2) / A_SP < MI) {
           const int q = (m - NM / 2) / A_SP;
           const uint64_t src_ = asrc_u;
           const uint32_t off_ = aoff[q];
@@ -1649,17 +1332,13 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
     if constexpr (CONV) {      // bias (+ residual) + re-zeroing of the border pixels: the output grid is the next layer's padded input
       if (P.epi == EPI_GATE_RES) epi_store_fast_acc<EPI_GATE_RES, MI, NJ, true, false, false, false, true, (NJ <= 4), false, NoHook>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, NoHook{});
       else epi_store_fast_acc<EPI_NONE, MI, NJ, true, false, false, false, true, (NJ <= 4), false, NoHook>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, NoHook{});
-    } else
-#ifdef V3_NO_EPI      // timing bound only (WRONG results: nothing is stored): what hiding the WHOLE epilogue behind matrix work could buy at most (profiles/r05b_gemm_no_epilogue_bound.txt)
-    asm volatile("" ::"v"(frow2), "v"(fq2), "s"(m0e), "s"(n0e));
-#else
-    if constexpr (TAIL) {
+    } else if constexpr (TAIL) {
       // tile nk - 1 is multiplied from here on: ALL of its fragments are read by the tail itself (the loop's second copy no longer pre-reads them), a few MFMAs
       // ahead of their use, out of the slots tile nk - 1 landed in
       const char* const sa_l = smem + ((nk - 1) & 1) * A_SLOT;
       const char* const sw_l = smem_w + ((nk - 1) % 3) * W_SLOT;
       constexpr int PER_ROW = 2 * NJ;                                  // MFMAs per row tile: k-half 0 then k-half 1, column tiles in order
-      constexpr int PTS = 4 * (V3_EPI_SWAP != 0 ? (NJ + 1) / 2 : NJ);  // hook points per row tile (>= PER_ROW)
+      constexpr int PTS = 4 * ((NJ + 1) / 2);                           // hook points per row tile (>= PER_ROW)
       static_assert(PTS >= PER_ROW, "one MFMA per hook point");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (nothing in flight for nk >= 2; nk = 1: the prologue's clamped re-fetches must not outlive the work-group's LDS)
       // Register budget: the epilogues' own state (bias, RMSNorm weights, cos / sin, residual and gate words: up to ~160 VGPRs) sits beside ALL 256 accumulators
@@ -1711,10 +1390,9 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
         __builtin_amdgcn_sched_barrier(0);
       };
       const TailHook<decltype(hook)> hk{hook};
-      epi_store_fast_any_acc<MI, NJ, V3_EPI_SWAP != 0, false, false, TailHook<decltype(hook)>>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, hk);
+      epi_store_fast_any_acc<MI, NJ, true, false, false, TailHook<decltype(hook)>>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, hk);
     } else
-    epi_store_fast_any_acc<MI, NJ, V3_EPI_SWAP != 0, false, false, NoHook>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, NoHook{});
-#endif
+    epi_store_fast_any_acc<MI, NJ, true, false, false, NoHook>(P, acc, m0e + wr2 * (16 * MI), n0e + wc2 * (16 * NJ), frow2, fq2, NoHook{});
 #ifdef AFX_GEMM_TRACE
     AFX_TRC(21)
     tr[23] = (unsigned)__builtin_amdgcn_s_memrealtime();
@@ -2067,9 +1745,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) __attribute__((amdgpu_num_vgpr(256))
   using F_ = std::false_type;
   // TAIL (round 6, as gemm_kernel_v3's): the LAST K-tile is not multiplied in front of the epilogue but from inside it, row tile by row tile (NJ MFMAs of 32
   // cycles each per row tile, one at every second hook point of the previous row tile's steps).  Everything tile nk - 1 needs has landed at the mid-tile
-  // barrier of tile nk - 2 (its wait is vmcnt(0)); per accumulator the order of the K-tiles is unchanged: bit-identical results (-DV3F8_TAIL=0).
-  constexpr bool TAIL = V3F8_TAIL != 0;
-  using TL = std::integral_constant<bool, TAIL>;
+  // barrier of tile nk - 2 (its wait is vmcnt(0)); per accumulator the order of the K-tiles is unchanged.
   int t = 0;
   if constexpr (MX) {
     // nk = 4 G tiles; the first group's scales were requested in front of the prologue's DMA
@@ -2090,15 +1766,12 @@ __global__ __launch_bounds__(V3_THREADS, 1) __attribute__((amdgpu_num_vgpr(256))
     }
     tile(T_{}, t, I0{}, F_{}, F_{});
     tile(T_{}, t + 1, I1{}, F_{}, F_{});
-    tile(F_{}, t + 2, I2{}, F_{}, TL{});
-    if constexpr (!TAIL) tile(F_{}, t + 3, I3{}, F_{}, F_{});
+    tile(F_{}, t + 2, I2{}, F_{}, T_{});
   } else {
 #pragma unroll 1
     for (; t < nk - 2; ++t) tile(T_{}, t, I0{}, F_{}, F_{});
-    tile(F_{}, t, I0{}, F_{}, TL{});                  // (nk >= 2: the launcher sends K >= 256 here)
-    if constexpr (!TAIL) tile(F_{}, t + 1, I0{}, F_{}, F_{});
+    tile(F_{}, t, I0{}, F_{}, T_{});                  // (nk >= 2: the launcher sends K >= 256 here)
   }
-  if constexpr (!TAIL) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");       // MFMA -> accumulator-read wait states (hipcc does not know the dependency)
   {
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));
@@ -2113,71 +1786,63 @@ __global__ __launch_bounds__(V3_THREADS, 1) __attribute__((amdgpu_num_vgpr(256))
       } else
         epi_store_fast_any_acc<MI, NJ, true, true, false, HK>(Q, acc, rb, cb, frow2, fq2, hk);
     };
-    if constexpr (TAIL) {
-      // tile nk - 1: every fragment is read here, out of the slots it landed in, a few MFMAs ahead of its use: W fragments (32 bytes per lane = two reads) through
-      // a ring of RING register sets -- every row tile re-reads its NJ W fragments: the epilogues' own state sits beside all accumulators --, A one row tile ahead
-      const int tl = nk - 1;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int arow2 = wr2 * (16 * MI) + frow2, brow2 = wc2 * (16 * NJ) + frow2;      // (from the opaque thread id: nothing of the tail's addressing is live across the main loop)
-      const uint32_t ta0_ = (uint32_t)(arow2 * 128 + (((0 + fq2) ^ ((arow2 >> 1) & 7)) << 4)), ta1_ = (uint32_t)(arow2 * 128 + (((4 + fq2) ^ ((arow2 >> 1) & 7)) << 4));
-      const uint32_t tb0_ = (uint32_t)(brow2 * 128 + (((0 + fq2) ^ ((brow2 >> 1) & 7)) << 4)), tb1_ = (uint32_t)(brow2 * 128 + (((4 + fq2) ^ ((brow2 >> 1) & 7)) << 4));
-      uint32_t pa[2], pw[2];
-      slot_bases(smem + (tl & 1) * A_SLOT, ta0_, ta1_, pa);
-      slot_bases(smem_w + (tl % 3) * W_SLOT, tb0_, tb1_, pw);
-      constexpr int RING = 2, PTS = 16, NA = 2;
-      constexpr int BT_LAST = 3;                           // MX: nk is a multiple of 4, the last tile is byte 3 of its scale dwords
-      i32x8_t tw[RING], ta[NA];
-      auto w_of = [&](i32x8_t& f, int g) { ld_at(f, 0, pw[0], g % NJ); ld_at(f, 1, pw[1], g % NJ); };      // W fragment of tail MFMA g = row * NJ + j
-      auto a_of = [&](i32x8_t& f, int row) { ld_at(f, 0, pa[0], row); ld_at(f, 1, pa[1], row); };
-      auto prime = [&]() {
+    // tile nk - 1: every fragment is read here, out of the slots it landed in, a few MFMAs ahead of its use: W fragments (32 bytes per lane = two reads) through
+    // a ring of RING register sets -- every row tile re-reads its NJ W fragments: the epilogues' own state sits beside all accumulators --, A one row tile ahead
+    const int tl = nk - 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int arow2 = wr2 * (16 * MI) + frow2, brow2 = wc2 * (16 * NJ) + frow2;      // (from the opaque thread id: nothing of the tail's addressing is live across the main loop)
+    const uint32_t ta0_ = (uint32_t)(arow2 * 128 + (((0 + fq2) ^ ((arow2 >> 1) & 7)) << 4)), ta1_ = (uint32_t)(arow2 * 128 + (((4 + fq2) ^ ((arow2 >> 1) & 7)) << 4));
+    const uint32_t tb0_ = (uint32_t)(brow2 * 128 + (((0 + fq2) ^ ((brow2 >> 1) & 7)) << 4)), tb1_ = (uint32_t)(brow2 * 128 + (((4 + fq2) ^ ((brow2 >> 1) & 7)) << 4));
+    uint32_t pa[2], pw[2];
+    slot_bases(smem + (tl & 1) * A_SLOT, ta0_, ta1_, pa);
+    slot_bases(smem_w + (tl % 3) * W_SLOT, tb0_, tb1_, pw);
+    constexpr int RING = 2, PTS = 16, NA = 2;
+    constexpr int BT_LAST = 3;                           // MX: nk is a multiple of 4, the last tile is byte 3 of its scale dwords
+    i32x8_t tw[RING], ta[NA];
+    auto w_of = [&](i32x8_t& f, int g) { ld_at(f, 0, pw[0], g % NJ); ld_at(f, 1, pw[1], g % NJ); };      // W fragment of tail MFMA g = row * NJ + j
+    auto a_of = [&](i32x8_t& f, int row) { ld_at(f, 0, pa[0], row); ld_at(f, 1, pa[1], row); };
+    auto prime = [&]() {
 #pragma unroll
-        for (int g = 0; g < RING; ++g) w_of(tw[g], g);
-        a_of(ta[0], 0);
-      };
-      auto tail_mfma = [&](auto row_c, auto j_c) AFX_INL {
-        constexpr int row = decltype(row_c)::value, j = decltype(j_c)::value, g = row * NJ + j;
-        {
-          const i32x8_t& wa_ = tw[g % RING];
-          const i32x8_t& xa_ = ta[row % NA];
-          const uint32_t sc_ = sc_cur[MX ? row : 0];
-          (void)sc_;
-          V3F8_MFMA(BT_LAST, row * NJ + j, wa_, xa_, sc_);
-        }
-        V3_FENCE();
-        if constexpr (g + RING < MI * NJ) w_of(tw[g % RING], g + RING);
-        if constexpr (j == (NA == 2 ? 2 : NJ - 1) && row + 1 < MI) a_of(ta[(row + 1) % NA], row + 1);
-        V3_FENCE();
-      };
-      auto hook = [&](auto code_c) AFX_INL {
-        constexpr int code = decltype(code_c)::value;
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (code == -1) {                                    // row tile 0, behind the epilogue's preamble
-          prime();
-          static_for<NJ>([&](auto j_c) AFX_INL { tail_mfma(std::integral_constant<int, 0>{}, j_c); });
-          asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-        } else if constexpr (code == -2) {                             // everything at once (an epilogue without hook points)
-          prime();
-          static_for<MI>([&](auto r_c) AFX_INL { static_for<NJ>([&](auto j_c) AFX_INL { tail_mfma(r_c, j_c); }); });
-          asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-        } else {
-          constexpr int row = code / PTS + 1, pt = code % PTS;         // one MFMA at every second point (NJ MFMAs, 16 points per row tile)
-          if constexpr (row < MI && pt % 2 == 0 && pt / 2 < NJ) tail_mfma(std::integral_constant<int, row>{}, std::integral_constant<int, pt / 2>{});
-          if constexpr (row < MI && pt == PTS - 1) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      const TailHook<decltype(hook)> hk{hook};
-      epilogue(hk);
-    } else {
-      epilogue(NoHook{});
-    }
+      for (int g = 0; g < RING; ++g) w_of(tw[g], g);
+      a_of(ta[0], 0);
+    };
+    auto tail_mfma = [&](auto row_c, auto j_c) AFX_INL {
+      constexpr int row = decltype(row_c)::value, j = decltype(j_c)::value, g = row * NJ + j;
+      {
+        const i32x8_t& wa_ = tw[g % RING];
+        const i32x8_t& xa_ = ta[row % NA];
+        const uint32_t sc_ = sc_cur[MX ? row : 0];
+        (void)sc_;
+        V3F8_MFMA(BT_LAST, row * NJ + j, wa_, xa_, sc_);
+      }
+      V3_FENCE();
+      if constexpr (g + RING < MI * NJ) w_of(tw[g % RING], g + RING);
+      if constexpr (j == (NA == 2 ? 2 : NJ - 1) && row + 1 < MI) a_of(ta[(row + 1) % NA], row + 1);
+      V3_FENCE();
+    };
+    auto hook = [&](auto code_c) AFX_INL {
+      constexpr int code = decltype(code_c)::value;
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (code == -1) {                                    // row tile 0, behind the epilogue's preamble
+        prime();
+        static_for<NJ>([&](auto j_c) AFX_INL { tail_mfma(std::integral_constant<int, 0>{}, j_c); });
+        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
+      } else if constexpr (code == -2) {                             // everything at once (an epilogue without hook points)
+        prime();
+        static_for<MI>([&](auto r_c) AFX_INL { static_for<NJ>([&](auto j_c) AFX_INL { tail_mfma(r_c, j_c); }); });
+        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
+      } else {
+        constexpr int row = code / PTS + 1, pt = code % PTS;         // one MFMA at every second point (NJ MFMAs, 16 points per row tile)
+        if constexpr (row < MI && pt % 2 == 0 && pt / 2 < NJ) tail_mfma(std::integral_constant<int, row>{}, std::integral_constant<int, pt / 2>{});
+        if constexpr (row < MI && pt == PTS - 1) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    const TailHook<decltype(hook)> hk{hook};
+    epilogue(hk);
   }
 }
 
-int& last_sk_cus() {           // CUs per XCD the last 8-phase launch split its tail over (0: plain launch) -- read by the stream-K tests
-  static thread_local int v = 0;
-  return v;
-}
 LaunchTimer& launch_timer() {
   static thread_local LaunchTimer t;
   return t;
@@ -2191,34 +1856,47 @@ template __global__ void gemm_kernel_v3f8<V3F8_ONLY>(const GemmBatch);
 #endif
 }  // namespace afx
 #else
-// ---- tile shape / kernel choice -------------------------------------------------------------------------------------------
-struct GemmMode { int impl = -1, tile = 0; };
-bool gemm_qk_fusion_available();
+// ---- settings / kernel choice ---------------------------------------------------------------------------------------------
+// The GEMM's environment settings, read ONCE (the launcher and the predicates below agree on every launch):
+//   AFX_GEMM_IMPL       2 = the 8-phase kernel only, 3 (default; any other value) = the one-wave-per-SIMD kernels for the launches they take
+//   AFX_GEMM_TILE       (impl 3) 0 = pick per launch, 1 ... 6 = force 256x256 / 288x192 / 320x192 / 128x128 / 256x224 / 224x256
+//   AFX_QK_FUSE=0       keep the separate kv_prep launch (A/B)
+//   AFX_FP8_V3=0        fp8 launches on the 8-phase kernel (A/B);  AFX_FP8_V3_MIN: fewest 256x256 tiles of a launch for the fp8 v3 kernel;
+//   AFX_FP8_TILE        1 / 2 force its 256x256 / 224x256 shape
+//   AFX_GEMM_GROUP_M    tile-order super-row height;  AFX_GEMM_PEN224 / AFX_GEMM_PEN_QK224: cost factors of the 256x224 / 224x256 shapes (1e9 = never)
+// afx_gemm_set_mode() overrides impl and tile (parity tests, A/B runs).
+struct GemmMode {
+  int impl = 3, tile = 0;
+  bool qk_fuse = true, fp8_v3 = true;
+  int fp8_v3_min = -1;            // < 0: half the CUs
+  int fp8_tile = 0, group_m = 0;  // group_m 0: the tile shape's own
+  double pen224 = 1.03, pen_qk224 = 1.03;
+};
 static GemmMode& gemm_mode() {
-  static GemmMode m;
+  static GemmMode m = [] {
+    GemmMode r;
+    if (const char* e = getenv("AFX_GEMM_IMPL")) r.impl = e[0] == '2' ? 2 : 3;
+    if (const char* e = getenv("AFX_GEMM_TILE")) r.tile = atoi(e);
+    if (const char* e = getenv("AFX_QK_FUSE")) r.qk_fuse = e[0] != '0';
+    if (const char* e = getenv("AFX_FP8_V3")) r.fp8_v3 = e[0] != '0';
+    if (const char* e = getenv("AFX_FP8_V3_MIN")) r.fp8_v3_min = atoi(e);
+    if (const char* e = getenv("AFX_FP8_TILE")) r.fp8_tile = atoi(e);
+    if (const char* e = getenv("AFX_GEMM_GROUP_M")) r.group_m = atoi(e) > 0 ? atoi(e) : 0;
+    if (const char* e = getenv("AFX_GEMM_PEN224")) r.pen224 = atof(e);
+    if (const char* e = getenv("AFX_GEMM_PEN_QK224")) r.pen_qk224 = atof(e);
+    return r;
+  }();
   return m;
 }
 bool gemm_conv_stats_available() {                      // convolution launches go to the kernel whose epilogue accumulates GroupNorm sums
-  if (gemm_mode().impl < 0) (void)gemm_qk_fusion_available();
   return gemm_mode().impl == 3 && gemm_mode().tile == 0;
 }
-bool gemm_qk_fusion_available() {
-  if (gemm_mode().impl < 0) {                           // same defaults as launch_gemm's first call
-    const char* e = getenv("AFX_GEMM_IMPL");
-    gemm_mode().impl = (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 3;
-    if (const char* t = getenv("AFX_GEMM_TILE")) gemm_mode().tile = atoi(t);
-  }
-  const char* k = getenv("AFX_GEMM_SK");
-  const char* f = getenv("AFX_QK_FUSE");                // AFX_QK_FUSE=0: keep the separate kv_prep launch (A/B)
-  return gemm_mode().impl == 3 && !(k && atoi(k) != 0) && !(f && f[0] == '0');
-}
+bool gemm_qk_fusion_available() { return gemm_mode().impl == 3 && gemm_mode().qk_fuse; }
 bool gemm_dropres_available() {                         // launch_gemm would take a problem with drop_on: the masked residual add exists in the one-wave-per-SIMD
-  if (gemm_mode().impl < 0) (void)gemm_qk_fusion_available();      // kernel's permlane-paired epilogue only (kernel mode 3, no stream-K request)
-  const char* k = getenv("AFX_GEMM_SK");
-  return V3_EPI_SWAP_DEFAULT != 0 && gemm_mode().impl == 3 && !(k && atoi(k) != 0);
+  return gemm_mode().impl == 3;                         // kernel's permlane-paired epilogue only
 }
 void gemm_set_mode(int impl, int tile) {
-  gemm_mode().impl = (impl >= 1 && impl <= 3) ? impl : 3;
+  gemm_mode().impl = impl == 2 ? 2 : 3;
   gemm_mode().tile = (tile >= 0 && tile <= 6) ? tile : 0;
 }
 struct TileCfg { int tm, tn, group_m; };
@@ -2296,40 +1974,22 @@ static hipError_t launch_v3(GemmBatch& batch, int total, hipStream_t stream) {
 
 bool gemm_fp8_mx_ok(int64_t rows_total, int N, int K) {
   (void)rows_total; (void)N;                       // a block-scaled launch always takes the one-wave-per-SIMD kernel, whatever its tile count
-  const char* e = getenv("AFX_FP8_V3");
-  const char* k = getenv("AFX_GEMM_SK");
-  if (gemm_mode().impl < 0) (void)gemm_qk_fusion_available();      // (reads AFX_GEMM_IMPL once, like launch_gemm's first call)
-  // the same predicate launch_gemm applies: the kernel choice may have been overridden by afx_gemm_set_mode() (parity tests, A/B runs), not only by the environment
-  return !(e && e[0] == '0') && !(k && atoi(k) != 0) && gemm_mode().impl == 3 && K % 512 == 0 && K >= 512;
+  return gemm_mode().fp8_v3 && gemm_mode().impl == 3 && K % 512 == 0 && K >= 512;      // the same predicate launch_gemm applies
 }
 
 hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
-  static int cus = 256, sk_env = 0;
-  static int group_m_env = 0;
+  static int cus = 256;
   static bool init = false;
-  int& impl = gemm_mode().impl;
-  int& tile_env = gemm_mode().tile;
+  const GemmMode& mode = gemm_mode();
+  const int impl = mode.impl, tile_env = mode.tile, group_m_env = mode.group_m;
   if (!init) {
     init = true;
-    if (const char* g = getenv("AFX_GEMM_GROUP_M")) group_m_env = atoi(g) > 0 ? atoi(g) : 0;
-    // AFX_GEMM_IMPL: 1 = simple 2-stage kernel (reference / A-B), 2 = 8-phase kernel only, 3 (default) = one-wave-per-SIMD kernel
-    // for the forward's bf16 epilogue modes (8-phase for everything else).  AFX_GEMM_TILE (impl 3): 0 = pick per launch,
-    // 1 ... 6 = force 256x256 / 288x192 / 320x192 / 128x128 / 256x224 / 224x256.  afx_gemm_set_mode() overrides both (parity tests, A/B runs).
-    if (impl < 0) {
-      const char* e = getenv("AFX_GEMM_IMPL");
-      impl = (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 3;
-      if (const char* t = getenv("AFX_GEMM_TILE")) tile_env = atoi(t);
-    }
-    if (const char* k = getenv("AFX_GEMM_SK")) sk_env = atoi(k);             // the stream-K tail lives in the 8-phase kernel
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
       cus = prop.multiProcessorCount;
-    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel),
+    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v2<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    if (r != hipSuccess) return r;
-    r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v2<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
     if (r != hipSuccess) return r;
     r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v2<true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
@@ -2337,7 +1997,7 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
   }
   // ---- one-wave-per-SIMD kernel: bf16 launches whose every problem is in a fast epilogue mode.  The tile shape is the one with
   // the least (rounds of `cus` tiles) x (tile area): the launch is as long as its fullest CU.
-  bool v3_ok = impl == 3 && sk_env == 0 && batch.sk_force == 0;
+  bool v3_ok = impl == 3;
   for (int i = 0; i < batch.nprob; ++i) {
     const GemmProblem& p = batch.p[i];
     const bool bf16_out = p.out_f32 == 0, f32_out = (p.out_f32 == 1 || p.out_f32 == 2) && p.epi == EPI_NONE;     // (3 = split-K slabs: 8-phase)
@@ -2362,7 +2022,6 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
     batch.total_tiles = total;
     if (total == 0) return hipSuccess;
     batch.group_m = group_m_env ? group_m_env : GROUP_M;
-    batch.sk_cus = 0;
     return narrow ? launch_v3<8, 4, true>(batch, total, stream) : launch_v3<8, 8, true>(batch, total, stream);
   }
   bool qk = false;
@@ -2393,23 +2052,13 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
       else if (tile_env == 0) {
         const int t0 = count_tiles(batch, 256, 256, false), t5 = count_tiles(batch, 224, 256, false);
         if (t0 == 0) return hipSuccess;
-        static double pen_qk224 = -1;
-        if (pen_qk224 < 0) {
-          const char* e = getenv("AFX_GEMM_PEN_QK224");   // A/B knob (1e9 = never)
-          pen_qk224 = e ? atof(e) : 1.03;
-        }
-        const double c0 = (double)((t0 + cus - 1) / cus) * 256, c5 = (double)((t5 + cus - 1) / cus) * 224 * pen_qk224;
+        const double c0 = (double)((t0 + cus - 1) / cus) * 256, c5 = (double)((t5 + cus - 1) / cus) * 224 * mode.pen_qk224;
         if (c5 < c0) best = 5;
       }
     } else if (tile_env >= 1 && tile_env <= 6) best = (tile_env == 5 && f32_any) ? 0 : tile_env - 1;
     else {
       double best_cost = 0;
       int tiles256 = 0;
-      static double pen_224 = -1;
-      if (pen_224 < 0) {
-        const char* e = getenv("AFX_GEMM_PEN224");       // A/B knob: cost factor of the 256x224 shape (1e9 = never pick it)
-        pen_224 = e ? atof(e) : 1.03;
-      }
       for (int c = 0; c < 5; ++c) {
         const int tiles = count_tiles(batch, kTileCfg[c].tm, kTileCfg[c].tn, false);
         if (tiles == 0) return hipSuccess;
@@ -2426,7 +2075,7 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
         if (c == 1) pen = batch.p[0].K <= 8192 ? 1.05 : 1.5;
         if (c == 2) pen = 1.10;
         if (c == 3) pen = 2.0;          // 16 MFMAs per 8 fragment reads and 4 DMA issues per k-half: the loop runs at about half rate
-        if (c == 4) pen = f32_any ? 1e9 : pen_224;   // 56 MFMAs per 15 fragment reads (256x256: 64 per 16); bf16 epilogues only
+        if (c == 4) pen = f32_any ? 1e9 : mode.pen224;   // 56 MFMAs per 15 fragment reads (256x256: 64 per 16); bf16 epilogues only
         const double cost = (double)rounds * kTileCfg[c].tm * kTileCfg[c].tn * pen;
         if (c == 0 || cost < best_cost) { best = c; best_cost = cost; }
       }
@@ -2435,19 +2084,13 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
     batch.total_tiles = total;
     if (total == 0) return hipSuccess;
     batch.group_m = group_m_env ? group_m_env : kTileCfg[best].group_m;
-    batch.sk_cus = 0;
     return best == 0 ? launch_v3<8, 8>(batch, total, stream) : best == 1 ? launch_v3<9, 6>(batch, total, stream)
          : best == 2 ? launch_v3<10, 6>(batch, total, stream) : best == 3 ? launch_v3<4, 4>(batch, total, stream)
          : best == 4 ? launch_v3<8, 7>(batch, total, stream) : launch_v3<7, 8>(batch, total, stream);
   }
   // ---- fp8 launches with at least one full round of 256x256 tiles: the one-wave-per-SIMD fp8 kernel (AFX_FP8_V3=0: 8-phase kernel, A/B)
   {
-    static int f8v3 = -1;
-    if (f8v3 < 0) {
-      const char* e = getenv("AFX_FP8_V3");
-      f8v3 = (e && e[0] == '0') ? 0 : 1;
-    }
-    bool ok = f8v3 != 0 && impl == 3 && sk_env == 0 && batch.sk_force == 0 && batch.nprob >= 1;
+    bool ok = mode.fp8_v3 && impl == 3 && batch.nprob >= 1;
     bool mx_any = false, mx_all = true, c8_any = false, qk_any = false;
     for (int i = 0; i < batch.nprob; ++i) {
       const GemmProblem& p = batch.p[i];
@@ -2459,11 +2102,9 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
       c8_any = c8_any || p.c8 != nullptr;
       mx_all = mx_all && p.a_mx != nullptr && p.K % 512 == 0 && p.ld_mx % 4 == 0;
     }
-    static int min_tiles = -1;
-    if (min_tiles < 0) {
-      const char* e = getenv("AFX_FP8_V3_MIN");      // fewest 256x256 tiles of a launch that takes this kernel
-      min_tiles = e ? atoi(e) : cus / 2;         // 216-tile launches (N = 3072): 2.1-2.2 -> 2.7 PF; below half a round the 8-phase kernel's 2 waves per SIMD win
-    }
+    // fewest 256x256 tiles of a launch that takes this kernel: by default half a round -- 216-tile launches (N = 3072): 2.1-2.2 -> 2.7 PF; below half a
+    // round the 8-phase kernel's 2 waves per SIMD win
+    const int min_tiles = mode.fp8_v3_min >= 0 ? mode.fp8_v3_min : cus / 2;
     if (mx_any && !(ok && mx_all)) return hipErrorInvalidValue;      // block scales are this kernel's format only (callers ask gemm_fp8_mx_ok() first)
     if ((c8_any || qk_any) && !ok) return hipErrorInvalidValue;     // (the fused q / k epilogue: this kernel only; the engine asks for it with block scales only)
     if (ok && (mx_any || c8_any || qk_any || count_tiles(batch, 256, 256, false) >= min_tiles)) {
@@ -2472,11 +2113,7 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
       // 960 = 3.75 -> 4, 720 = 2.8 -> 3 rounds of tiles 7/8 the size); FLUX's joint 4608 rows of the single blocks likewise (out-projection: 252 tiles).
       // AFX_FP8_TILE=1 / 2 force 256x256 / 224x256 (A/B).  The fused q / k epilogue keeps 256x256 (one head = one wave's 128 columns either way, but its
       // row-tile loop is written for 8).
-      static int tile_env8 = -1;
-      if (tile_env8 < 0) {
-        const char* e = getenv("AFX_FP8_TILE");
-        tile_env8 = e ? atoi(e) : 0;
-      }
+      const int tile_env8 = mode.fp8_tile;
       const int t8 = count_tiles(batch, 256, 256, false), t7 = count_tiles(batch, 224, 256, false);
       const int r8 = (t8 + cus - 1) / cus, r7 = (t7 + cus - 1) / cus;
       bool use7 = !qk_any && (tile_env8 == 2 || (tile_env8 == 0 && (double)r7 * 224 * 1.02 < (double)r8 * 256));
@@ -2484,8 +2121,7 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
       batch.total_tiles = total;
       if (total == 0) return hipSuccess;
       batch.group_m = group_m_env ? group_m_env : GROUP_M;
-      batch.sk_cus = 0;
-      static bool attr = false;
+        static bool attr = false;
       if (!attr) {
         hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v3f8<8, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(8, 8));
         if (r != hipSuccess) return r;
@@ -2518,61 +2154,17 @@ hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
       return hipGetLastError();
     }
   }
-  int total = count_tiles(batch, BM, BN, true);
+  const int total = count_tiles(batch, BM, BN, true);
   batch.total_tiles = total;
   if (total == 0) return hipSuccess;
-  const int group_m = group_m_env ? group_m_env : GROUP_M;
-  batch.group_m = group_m;
-  batch.sk_cus = 0;
-  int use = impl == 1 ? 1 : 2;
-  bool conv = false;
-  for (int i = 0; i < batch.nprob; ++i) conv = conv || batch.p[i].conv_cin_tiles > 0;
-  if (conv) use = 2;                                 // the implicit-conv addressing lives in the 8-phase kernel
-  for (int i = 0; i < batch.nprob; ++i)
-    if (batch.p[i].out_f32 == 3) use = 2;            // ... and so do split-K and the atomic epilogue
+  batch.group_m = group_m_env ? group_m_env : GROUP_M;
   bool fp8 = false;
   for (int i = 0; i < batch.nprob; ++i) fp8 = fp8 || batch.p[i].fp8 != 0;     // a launch is all-bf16 or all-fp8
-  // ---- stream-K tail: only with a caller-provided slab / flag workspace (the engine's), one K, plain bf16 / fp8 output tiles
-  static int sk_mode = -1, cus_per_xcd = 32;
-  if (sk_mode < 0) {
-    // 0 (default): off, 1: launches with >= 1 full round in front of the tail, 2: every eligible launch.  OFF by default: in the
-    // FLUX forward the tail costs more than it wins (r02p, same box, 3 interleaved runs: 7.06 / 7.02 / 6.93 images/s for 0 / 1 / 2)
-    // although the isolated qkv GEMM gains 6-9 % -- the 64 MB of write-through partial slabs per launch compete with the next
-    // launches' operands for the L2 / Infinity Cache.  Kept (and tested through afx_linear_bf16_sk) as the measured negative result.
-    const char* e = getenv("AFX_GEMM_SK");
-    sk_mode = e ? atoi(e) : 0;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8)
-      cus_per_xcd = prop.multiProcessorCount / 8;
-  }
-  // (the gate used to read sk_mode only, so afx_linear_bf16_sk -- sk_force -- compared the plain kernel with itself)
-  if ((sk_mode || batch.sk_force) && use == 2 && !conv && batch.sk_slab != nullptr && batch.sk_flags != nullptr && total % 8 == 0 && cus_per_xcd <= 32) {
-    bool ok = true;
-    for (int i = 0; i < batch.nprob; ++i)
-      ok = ok && batch.p[i].out_f32 == 0 && batch.p[i].split_k == 1 && batch.p[i].K == batch.p[0].K && batch.p[i].fp8 == batch.p[0].fp8;
-    const int T = total / 8, C = cus_per_xcd;
-    const int full = T / C * C, rem = T - full;
-    const int nk = batch.p[0].K * (fp8 ? 1 : 2) / (BK * 2);
-    // Worth it when the tail round is visibly under-filled and a piece keeps a useful number of K-tiles.  Launches that are ONE
-    // under-filled round (216 tiles: full == 0) split EVERY tile: 256 partial slabs = 64 MB written through + read back per
-    // launch, which costs what the 16 % tail would win (r02d: 4608x3072xK, K = 3072 / 12288 / 15360: -10 % / -3 % / -1.5 %);
-    // launches with full rounds in front split only the remainder tiles (N = 9216: +6 %, N = 12288: +3 %).
-    if (ok && rem > 0 && rem * 8 <= C * 7 && (int64_t)rem * nk / C >= 6 && (full > 0 || sk_mode >= 2 || batch.sk_force)) {
-      batch.sk_cus = C;
-      batch.sk_tiles_per_xcd = T;
-      batch.sk_full = full;
-      total = 8 * (full + C);
-    }
-  }
-  last_sk_cus() = batch.sk_cus;
   if (fp8 && launch_timer().start != nullptr && launch_timer().stop != nullptr)
     hipExtLaunchKernelGGL(gemm_kernel_v2<true>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, launch_timer().start,
                           launch_timer().stop, 0, batch);
   else if (fp8)
     hipLaunchKernelGGL(gemm_kernel_v2<true>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, batch);
-  else if (use == 1)
-    hipLaunchKernelGGL(gemm_bf16_kernel, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, batch);
   else if (launch_timer().start != nullptr && launch_timer().stop != nullptr)
     hipExtLaunchKernelGGL(gemm_kernel_v2<false>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, launch_timer().start,
                           launch_timer().stop, 0, batch);

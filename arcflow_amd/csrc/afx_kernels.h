@@ -80,12 +80,6 @@ struct GemmBatch {
   int32_t nprob;
   int32_t total_tiles;
   int32_t group_m;     // tile-order super-row height (set by the launcher)
-  // stream-K tail (afx_gemm.hip): the caller lends a workspace -- sk_flags: 1024 zero-initialised uint32 (re-armed by the
-  // kernel), sk_slab: 256 x 256 KiB fp32 accumulator slabs; the launcher fills the three ints (sk_cus == 0: plain launch)
-  float* sk_slab;
-  uint32_t* sk_flags;
-  int32_t sk_cus, sk_tiles_per_xcd, sk_full;
-  int32_t sk_force;    // caller asks for the stream-K tail on every eligible launch (parity tests / micro benches), not only where it pays
   GemmProblem p[GEMM_MAX_PROBLEMS];
 };
 
@@ -96,19 +90,16 @@ hipError_t launch_gemm_tn_f32(const uint16_t* X, int64_t ldx, const uint16_t* Y,
 int gemm_tn_ksplit(int M, int N1, int N2);
 int64_t gemm_tn_ws_bytes(int M, int N1, int N2);
 bool gemm_conv_stats_available();           // GemmProblem::gn_stats is honoured (kernel mode 3, no forced tile shape)
-bool gemm_qk_fusion_available();            // the launcher would take a problem with qk_D > 0 (kernel mode 3, no stream-K request)
+bool gemm_qk_fusion_available();            // the launcher would take a problem with qk_D > 0 (kernel mode 3, AFX_QK_FUSE not 0)
 bool gemm_dropres_available();              // ... a problem with drop_on (the LoRA branch's masked residual add in the epilogue)
 void gemm_set_mode(int impl, int tile);      // kernel / tile-shape override of AFX_GEMM_IMPL / AFX_GEMM_TILE (see launch_gemm)
 constexpr int GN_SLOTS = 64;
-constexpr int64_t GEMM_SK_FLAG_BYTES = 4096;                       // 1024 flag words
-constexpr int64_t GEMM_SK_SLAB_BYTES = 256ll * 256 * 256 * 4;      // 256 work-groups x one fp32 256x256 tile
 
 // Optional per-launch timing without extra queue packets: when both are non-null, the NEXT launch_gemm / launch_attention issues
 // its kernel with hipExtLaunchKernelGGL(start, stop), which stamps the kernel's own begin / end on the events (the engine's
 // ProfScope sets and clears them; a plain hipEventRecord pair costs a barrier packet each: ~2 % of the forward).
 struct LaunchTimer { hipEvent_t start = nullptr, stop = nullptr; };
 LaunchTimer& launch_timer();
-int& last_sk_cus();
 
 // ---- attention ------------------------------------------------------------------------------
 // vt: [B, H, 128, S_pad] transposed + key-permuted V (see afx_attn.hip); S_pad = roundup(S, 64)
@@ -125,7 +116,7 @@ hipError_t launch_attention(const uint16_t* q, int64_t ldq, const uint16_t* k, i
 bool attention_v3_eligible(int S);
 hipError_t launch_attention_v3(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* vt, uint16_t* o,
                                int64_t ldo, int B, int H, int S, hipStream_t stream, float* lse, const AttnMx8* mx8 = nullptr, bool split = true);
-void attn_set_impl(int impl);               // 0 = default (v3 where eligible, under-filled last round KV-split), 1 = 4-wave kernel, 2 = 8-wave ping-pong (experimental), 3 = v3 on the plain grid
+void attn_set_impl(int impl);               // 0 = default (v3 where eligible, under-filled last round KV-split), 1 = 4-wave kernel, 3 = v3 on the plain grid
 // K, Q <- RoPE(RMSNorm(.) w) in place (same row stride) and V -> V^T (key-permuted), one launch
 hipError_t launch_kv_prep(uint16_t* k, uint16_t* q, int64_t ldk, const float* wk_txt, const float* wk_img, const float* wq_txt,
                           const float* wq_img, const float* cos_t, const float* sin_t, int n_txt, const uint16_t* v, int64_t ldv,

@@ -355,7 +355,7 @@ int afx_linear_fp8_mx(const void* Aq, int64_t lda, const void* a_mx, int64_t ld_
   if (M < 0 || N < 0 || K < 512 || K % 512 || N % 8 || lda % 16 || ldw % 16 || ldc % 8 || ld_mx % 4 || ld_mx < K / 128 || epi < 0 || epi > 2)
     return fail(AFX_E_INVALID, "afx_linear_fp8_mx: need K%%512==0, N%%8==0, lda/ldw%%16==0, ldc%%8==0, ld_mx%%4==0");
   if (epi == EPI_GATE_RES && (!res || ldr % 8 || (gate && rows_per_batch < 1))) return fail(AFX_E_INVALID, "gated residual epilogue needs res");
-  if (!gemm_fp8_mx_ok(M, N, K)) return fail(AFX_E_INVALID, "afx_linear_fp8_mx: the block-scaled kernel is switched off (AFX_FP8_V3 / AFX_GEMM_IMPL / AFX_GEMM_SK)");
+  if (!gemm_fp8_mx_ok(M, N, K)) return fail(AFX_E_INVALID, "afx_linear_fp8_mx: the block-scaled kernel is switched off (AFX_FP8_V3 / AFX_GEMM_IMPL)");
   GemmBatch gb{};
   gb.nprob = 1;
   GemmProblem& p = gb.p[0];

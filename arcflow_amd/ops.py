@@ -71,12 +71,10 @@ def _rows_f32(v: torch.Tensor, R: int, C: int, rows_per_batch: int, name: str) -
 
 def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: str = 'none',
            gelu_col0: int = 0, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-           rows_per_batch: int = 0, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None,
-           sk_ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+           rows_per_batch: int = 0, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = epi(a @ w.T + bias + pre); a [M,K] (last-dim contiguous, may be a strided view), w [N,K] bf16.
     epilogue: 'none' | 'gelu' (tanh, on columns >= gelu_col0) | 'gate_res' (residual + gate[b] * (.)).
-    pre [M,N] bf16 is added before the activation / gate (LoRA-dropout correction).
-    sk_ws: a ``stream_k_workspace()`` buffer -> the launch may split its under-filled last round stream-K style."""
+    pre [M,N] bf16 is added before the activation / gate (LoRA-dropout correction)."""
     lib = _lib.load()
     assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a.stride(-1) == 1 and w.stride(-1) == 1
     M, K = a.shape
@@ -89,12 +87,6 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         if gate.dim() == 1:
             gate = gate[None]
     rpb = rows_per_batch if rows_per_batch > 0 else max(M, 1)
-    if sk_ws is not None:
-        assert pre is None
-        _lib.check(lib.afx_linear_bf16_sk(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K,
-                                          epi, gelu_col0, _p(gate), 0 if gate is None else gate.stride(0), rpb,
-                                          _p(residual), 0 if residual is None else residual.stride(0), _p(sk_ws), _s()))
-        return out
     _lib.check(lib.afx_linear_bf16_pre(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K,
                                        epi, gelu_col0, _p(gate), 0 if gate is None else gate.stride(0), rpb,
                                        _p(residual), 0 if residual is None else residual.stride(0),
@@ -104,13 +96,13 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 
 def set_gemm_mode(impl: int = 3, tile: int = 0) -> None:
     """Kernel / tile-shape override of every bf16 GEMM (``afx_gemm_set_mode``): impl 3 = one-wave-per-SIMD kernel with tile 0 = picked
-    per launch, 1 ... 6 = 256x256 / 288x192 / 320x192 / 128x128 / 256x224 / 224x256; impl 2 = 8-phase 256x256 kernel; impl 1 = simple reference kernel."""
+    per launch, 1 ... 6 = 256x256 / 288x192 / 320x192 / 128x128 / 256x224 / 224x256; impl 2 = 8-phase 256x256 kernel (any other impl: 3)."""
     _lib.check(_lib.load().afx_gemm_set_mode(impl, tile))
 
 
 def set_attn_impl(impl: int = 0) -> None:
     """Kernel choice of the joint attention (``afx_attn_set_impl``): 0 = one-wave-per-SIMD kernel where eligible, the blocks of an under-filled
-    last round KV-split (default), 1 = 4-wave kernel always, 2 = 8-wave ping-pong kernel (experimental), 3 = as 0 on the plain grid."""
+    last round KV-split (default), 1 = 4-wave kernel always, 3 = as 0 on the plain grid (any other value: 0)."""
     _lib.check(_lib.load().afx_attn_set_impl(impl))
 
 
@@ -118,12 +110,6 @@ def set_attn_bwd_impl(impl: int = 3) -> None:
     """Kernel generation of ``attention_bwd`` (``afx_attn_bwd_set_impl``): 3 = generated dK / dV + dQ streams in one launch (default), 4 = as two launches,
     1 = generated dK / dV + round-4 dQ, 2 = the round-4 kernels."""
     _lib.check(_lib.load().afx_attn_bwd_set_impl(impl))
-
-
-def stream_k_workspace(device='cuda') -> torch.Tensor:
-    """Zero-initialised workspace for ``linear(..., sk_ws=)`` (hand-off flags + fp32 accumulator slabs of the stream-K tail)."""
-    lib = _lib.load()
-    return torch.zeros(lib.afx_linear_sk_ws_bytes(), dtype=torch.uint8, device=device)
 
 
 def lora_dropout(src: torch.Tensor, p: float, seed: int, row0: int = 0, mode: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -360,8 +346,9 @@ def linear_dropres(a, w, residual, p: float, seed: int, row0: int = 0, out=None)
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     if not lib.afx_gemm_dropres_available():
-        # the masked residual add lives in the one-wave-per-SIMD kernel's epilogue only (set_gemm_mode(1 / 2), AFX_GEMM_IMPL, AFX_GEMM_SK select
-        # other kernels in A/B runs and parity tests): the product to memory, then the mask-and-add pass -- the same bits
+        # the masked residual add lives in the one-wave-per-SIMD kernel's epilogue only (set_gemm_mode(2) / AFX_GEMM_IMPL=2 select the 8-phase
+        # kernel in A/B runs and parity tests): the product to memory, then the mask-and-add pass.  NOT the same bits: the fused epilogue masks
+        # the fp32 product and rounds once, this path rounds the product to bf16 and rounds again after the add
         if out.data_ptr() != residual.data_ptr():
             out.copy_(residual)
         return lora_dropout(linear(a, w), p, seed, row0, mode=3, out=out)

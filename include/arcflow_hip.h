@@ -314,7 +314,7 @@ int afx_groupnorm_nhwc(const void* x, void* y, double* stats_ws, int32_t H, int3
  * grids are the largest), Cout / groups = 4, 8 or a multiple of 8.  afx_groupnorm_nhwc_from_stats
  * then normalises y without a statistics pass of its own (diffusers' ResnetBlock2D order norm -> act -> conv: every GroupNorm input of the
  * decoder except the attention output is a convolution output).  afx_conv_stats_available(): 0 when the GEMM kernel override in force has no
- * such epilogue (AFX_GEMM_IMPL=1). */
+ * such epilogue (AFX_GEMM_IMPL=2 or a forced tile shape). */
 int afx_conv3x3_bf16_stats(const void* x, const void* w, const void* bias, void* y, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                            const void* res, double* gn_stats, int32_t groups, void* stream);
 int afx_groupnorm_nhwc_from_stats(const void* x, void* y, const double* gn_stats, double* stats_ws, int32_t H, int32_t W, int32_t C,
@@ -412,32 +412,20 @@ int afx_linear_bf16_pre(const void* A, int64_t lda, const void* W, int64_t ldw, 
                         void* C, int64_t ldc, int32_t M, int32_t N, int32_t K,
                         int32_t epi, int32_t gelu_col0, const float* gate, int64_t ldg,
                         int32_t rows_per_batch, const void* res, int64_t ldr, const void* pre, int64_t ldp, void* stream);
-/* afx_linear_bf16 with a caller-lent workspace for the stream-K tail of the 8-phase GEMM (the MMDiT engine lends a region of its
- * own workspace to every block GEMM; this entry point exists for the parity tests and micro benches): sk_ws holds
- * afx_linear_sk_ws_bytes() bytes, 256-byte aligned, whose first 4096 bytes were zeroed ONCE by the caller (hand-off flags; the
- * kernel re-arms them).  When the launch's tile count does not leave an under-filled last round the call is a plain GEMM. */
-int64_t afx_linear_sk_ws_bytes(void);
-/* CUs per XCD over which the calling thread's last afx_linear_bf16_sk launch split its under-filled last round (0: it ran as a plain
- * GEMM) -- lets a test assert that the stream-K path really executed. */
-int afx_linear_sk_last_split(void);
 /* Tuning / test knob of every bf16 GEMM in the library (process-wide, not thread-safe against running launches): impl 3 (default) =
  * one-wave-per-SIMD kernel for the bf16 epilogue modes with the tile shape picked per launch (tile 0) or forced (1: 256x256,
- * 2: 288x192, 3: 320x192, 4: 128x128, 5: 256x224); impl 2 = 8-phase 256x256 kernel for everything; impl 1 = simple reference kernel.  Same meaning as the
- * AFX_GEMM_IMPL / AFX_GEMM_TILE environment variables, which it overrides.  Returns 0. */
+ * 2: 288x192, 3: 320x192, 4: 128x128, 5: 256x224, 6: 224x256); impl 2 = 8-phase 256x256 kernel for everything; any other impl selects 3.  Same meaning
+ * as the AFX_GEMM_IMPL / AFX_GEMM_TILE environment variables (read once, on first use), which it overrides.  Returns 0. */
 int afx_gemm_set_mode(int32_t impl, int32_t tile);
 /* 1 when afx_linear_bf16_dropres can run under the current kernel choice (its masked residual add lives in the one-wave-per-SIMD kernel's epilogue: kernel
- * mode 3, no stream-K request), 0 otherwise -- the caller then computes the product with afx_linear_bf16 and masks + adds it with afx_lora_dropout_bf16 mode 3
+ * mode 3), 0 otherwise -- the caller then computes the product with afx_linear_bf16 and masks + adds it with afx_lora_dropout_bf16 mode 3
  * (arcflow_amd/ops.py linear_dropres does).  Host-side, no GPU needed. */
 int afx_gemm_dropres_available(void);
 /* Kernel choice of every joint attention launch (process-wide; same meaning as AFX_ATTN_IMPL, which it overrides): 0 (default) = the
  * one-wave-per-SIMD kernel (afx_attn3.hip: 64 queries per wave, any S > 64: ragged tails handled) where eligible, else the 4-wave kernel; 1 = 4-wave kernel
- * always; 2 = 8-wave ping-pong kernel (experimental); 3 = the one-wave-per-SIMD kernel on its plain grid (0 cuts the 256-query blocks of an under-filled
- * last round into one run of key tiles per CU and merges the partial results: afx_attn3.hip).  For A/B runs and the parity tests.  Returns 0. */
+ * always; 3 = the one-wave-per-SIMD kernel on its plain grid (0 cuts the 256-query blocks of an under-filled last round into one run of key tiles per
+ * CU and merges the partial results: afx_attn3.hip); any other value selects 0.  For A/B runs and the parity tests.  Returns 0. */
 int afx_attn_set_impl(int32_t impl);
-int afx_linear_bf16_sk(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias,
-                       void* C, int64_t ldc, int32_t M, int32_t N, int32_t K,
-                       int32_t epi, int32_t gelu_col0, const float* gate, int64_t ldg,
-                       int32_t rows_per_batch, const void* res, int64_t ldr, void* sk_ws, void* stream);
 /* LoRA input dropout masks from a counter-based hash of (seed, row0 + row, col), keep probability 1 - p, delta = keep/(1-p) - 1:
  * mode 0: dst = src * delta;  1: dst = src * (1 + delta) (= dropout(src));  2: dst += src * delta;  3: dst += src * (1 + delta) */
 int afx_lora_dropout_bf16(const void* src, int64_t lds_, void* dst, int64_t ldd, int64_t M, int32_t N, int64_t row0, float p,

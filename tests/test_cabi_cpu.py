@@ -63,10 +63,12 @@ def test_argument_validation_no_gpu(lib):
     assert lib.afx_linear_tn_f32out_ws(None, 8, None, 8, None, 8, 64, 8, 8, 0, None, None) == -1
     assert lib.afx_linear_tn_f32out_ws(C.c_void_p(4096), 8, C.c_void_p(8192), 8, C.c_void_p(16384), 8, 64, 8, 8, 0, C.c_void_p(4096 + 4), None) == -1   # misaligned workspace
     # round-6: the capability query behind ops.linear_dropres' fallback follows the kernel choice (host-side state only)
-    if os.environ.get('AFX_GEMM_IMPL', '3') == '3' and os.environ.get('AFX_GEMM_SK', '0') == '0':
+    if os.environ.get('AFX_GEMM_IMPL', '3') == '3':
         assert lib.afx_gemm_dropres_available() == 1
         assert lib.afx_gemm_set_mode(2, 0) == 0 and lib.afx_gemm_dropres_available() == 0
         assert lib.afx_gemm_set_mode(3, 0) == 0 and lib.afx_gemm_dropres_available() == 1
+        assert lib.afx_gemm_set_mode(1, 0) == 0 and lib.afx_gemm_dropres_available() == 1      # no kernel 1 any more: the default stays in force
+        assert lib.afx_gemm_set_mode(3, 0) == 0
     assert lib.afx_destroy(ctx) == 0
 
 

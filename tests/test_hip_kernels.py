@@ -88,10 +88,15 @@ def test_linear_strided_gelu_cols(ops, gemm_mode):
     assert outbuf[:, N:].abs().max().item() == 0           # nothing written past N
 
 
-@all_gemm_modes
-def test_linear_gate_residual_inplace(ops, gemm_mode):
+# (B, S, K, N): two samples with their own gate rows, and the mlp2 / proj_out shape of the FLUX forward (one gate row, long K)
+GATE_RES_SIZES = [(2, 150, 512, 256), (1, 4608, 12288, 3072)]
+
+
+@pytest.mark.parametrize('gemm_mode,size', [pytest.param(m, z, id=i if j == 0 else f'{i}-{z[1]}x{z[3]}x{z[2]}')
+                                            for j, z in enumerate(GATE_RES_SIZES) for m, i in zip(GEMM_MODES, GEMM_MODE_IDS)], indirect=['gemm_mode'])
+def test_linear_gate_residual_inplace(ops, gemm_mode, size):
     g = torch.Generator().manual_seed(6)
-    B, S, K, N = 2, 150, 512, 256
+    B, S, K, N = size
     a = bf(torch.randn(B * S, K, generator=g)).to(dev())
     w = bf(torch.randn(N, K, generator=g) * 0.05).to(dev())
     b = bf(torch.randn(N, generator=g)).to(dev())
@@ -459,18 +464,24 @@ def test_arcflow_step_full_size_properties(ops):
     assert torch.allclose(a, b, rtol=1e-4, atol=1e-4)
 
 
+FULL_SIZE_SHAPES = [(4608, 3072, 3072), (4096, 1152, 3072), (512, 9216, 3072), (4608, 3072, 15360), (2304, 21504, 3072), (4608, 9216, 3072), (4608, 12288, 3072)]
+
+
 @all_gemm_modes
-@pytest.mark.parametrize('M,N,K', [(4608, 3072, 3072), (4096, 1152, 3072), (512, 9216, 3072), (4608, 3072, 15360), (2304, 21504, 3072)])
-def test_linear_full_size_vs_device_reference(ops, gemm_mode, M, N, K):
-    """Full-size shapes of the FLUX forward, checked on-device against torch's (hipBLASLt) bf16 linear,
-    three launches each so a rare pipeline race (DMA landing late / restaged early) shows up."""
+@pytest.mark.parametrize('M,N,K,epilogue', [pytest.param(M, N, K, e, id=f'{M}-{N}-{K}' if e == 'none' else f'{M}-{N}-{K}-{e}')
+                                            for M, N, K in FULL_SIZE_SHAPES for e in ('none', 'gelu')])
+def test_linear_full_size_vs_device_reference(ops, gemm_mode, M, N, K, epilogue):
+    """Full-size shapes of the FLUX forward, checked on-device against fp32 math on the same bf16 inputs (epilogue 'gelu': tanh GELU on the
+    right half of the columns), three launches each so a rare pipeline race (DMA landing late / restaged early) shows up."""
     g = torch.Generator(device='cuda').manual_seed(K + N)
     a = torch.randn(M, K, generator=g, device='cuda').bfloat16()
     w = (torch.randn(N, K, generator=g, device='cuda') * 0.03).bfloat16()
     b = torch.randn(N, generator=g, device='cuda').bfloat16()
     ref = torch.nn.functional.linear(a.float(), w.float(), b.float())
+    if epilogue == 'gelu':
+        ref[:, N // 2:] = torch.nn.functional.gelu(ref[:, N // 2:], approximate='tanh')
     for _ in range(3):
-        out = ops.linear(a, w, b)
+        out = ops.linear(a, w, b, epilogue=epilogue, gelu_col0=N // 2)
         assert rel_l2(out, ref) < 4e-3
         assert (out.float() - ref).abs().max().item() < 0.02 * ref.abs().max().item() + 0.05
 
@@ -667,55 +678,6 @@ def test_attention_writes_block_scaled_operand(B, S, H):
     assert (deq - o.float()).abs().max().item() <= 0.0625 * o.float().abs().max().item() + 1e-3
     same = mx == rmx
     assert (o8.view(B * S, H, 128)[same] != rq.view(B * S, H, 128)[same]).float().mean().item() < 0.08     # the bf16 detour moves a value across an e4m3 rounding boundary now and then
-
-
-# ------------------------------------------------------------------------------------------ stream-K tail of the GEMM
-@pytest.mark.parametrize('M,N,K', [(4608, 3072, 3072), (4608, 3072, 15360), (4608, 9216, 3072), (4608, 12288, 3072),
-                                   (2048, 1024, 512), (4608, 21504, 3072)])
-def test_linear_stream_k_tail(ops, M, N, K):
-    """The FLUX block GEMM shapes whose last round is under-filled (216 / 648 / 864 tiles on 256 CUs) with the stream-K tail
-    on: against fp32 math on the device AND against the plain launch (same products, only the order of the fp32 partial sums
-    differs).  Run twice on one workspace: the hand-off flags must be re-armed by the kernel."""
-    g = torch.Generator(device='cuda').manual_seed(M + N + K)
-    a = torch.randn(M, K, generator=g, device='cuda').bfloat16()
-    w = (torch.randn(N, K, generator=g, device='cuda') * 0.03).bfloat16()
-    b = torch.randn(N, generator=g, device='cuda').bfloat16()
-    ws = ops.stream_k_workspace()
-    plain = ops.linear(a, w, b, epilogue='gelu', gelu_col0=N // 2)
-    ref = a.float() @ w.float().t() + b.float()
-    ref[:, N // 2:] = torch.nn.functional.gelu(ref[:, N // 2:], approximate='tanh')
-    from arcflow_amd import _lib
-    # 32 tiles / 1512 tiles (last round 29 of 32 CUs per XCD busy): no under-filled last round worth splitting -> plain launch
-    split_expected = (M, N, K) not in ((2048, 1024, 512), (4608, 21504, 3072))
-    for rep in range(2):
-        out = ops.linear(a, w, b, epilogue='gelu', gelu_col0=N // 2, sk_ws=ws)
-        torch.cuda.synchronize()
-        # ADVICE r2: the split path must really have run (the launcher used to ignore sk_force and these tests compared the plain
-        # kernel with itself); afx_linear_sk_last_split = CUs per XCD the tail was split over, 0 = plain launch
-        assert (_lib.load().afx_linear_sk_last_split() > 0) == split_expected
-        assert rel_l2(out, ref) < 4e-3, rep
-        assert rel_l2(out, plain) < 1e-3, rep
-        assert (out.float() - plain.float()).abs().max().item() < 0.05 * plain.float().abs().max().item()
-    flags = ws[:4096].view(torch.int32)
-    assert int(flags.abs().sum()) == 0, 'hand-off flags not re-armed / timeout word set'
-
-
-def test_linear_stream_k_gate_residual_inplace(ops):
-    """mlp2 / proj_out form: C = res + gate * (A W^T + b) written over the residual, long K (the owner adds 1-2 partial slabs)."""
-    g = torch.Generator(device='cuda').manual_seed(77)
-    M, N, K = 4608, 3072, 12288
-    a = torch.randn(M, K, generator=g, device='cuda').bfloat16()
-    w = (torch.randn(N, K, generator=g, device='cuda') * 0.02).bfloat16()
-    b = torch.randn(N, generator=g, device='cuda').bfloat16()
-    gate = torch.randn(1, N, generator=g, device='cuda')
-    x = torch.randn(M, N, generator=g, device='cuda').bfloat16()
-    ref = x.float() + gate * (a.float() @ w.float().t() + b.float())
-    ws = ops.stream_k_workspace()
-    out = ops.linear(a, w, b, epilogue='gate_res', gate=gate, residual=x, rows_per_batch=M, out=x, sk_ws=ws)
-    from arcflow_amd import _lib
-    assert _lib.load().afx_linear_sk_last_split() > 0
-    assert rel_l2(out, ref) < 4e-3
-
 
 
 @pytest.mark.parametrize('out_f,in_f,r', [(384, 256, 32), (3072, 3072, 256), (200, 136, 8)])

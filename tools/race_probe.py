@@ -35,9 +35,7 @@ def main():
         w = (torch.randn(N, K, generator=g, device='cuda') * 0.02).bfloat16()
         b = torch.randn(N, generator=g, device='cuda').bfloat16()
         out = torch.empty(M, N, dtype=torch.bfloat16, device='cuda')
-        print(f'gemm {M}x{N}x{K} plain   :', count(lambda: ops.linear(a, w, b, out=out), disturb=disturb), flush=True)
-        ws = ops.stream_k_workspace()
-        print(f'gemm {M}x{N}x{K} stream-K:', count(lambda: ops.linear(a, w, b, out=out, sk_ws=ws), disturb=disturb), flush=True)
+        print(f'gemm {M}x{N}x{K}:', count(lambda: ops.linear(a, w, b, out=out), disturb=disturb), flush=True)
     for S in (4608, 4173):
         q, k, v = (torch.randn(1, S, 24, 128, generator=g, device='cuda').bfloat16() for _ in range(3))
         print(f'attention S={S}:', count(lambda: ops.attention(q, k, v), reps=REPS // 2, disturb=disturb), flush=True)
