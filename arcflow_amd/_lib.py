@@ -31,7 +31,11 @@ EXPORTS = [
     'afx_arcflow_step_dropout', 'afx_arcflow_backward', 'afx_mse_loss', 'afx_euler_roll', 'afx_axpby_rows', 'afx_cfg_combine',
     'afx_head_grad', 'afx_linear_bf16_f32out', 'afx_linear_tn_f32out', 'afx_linear_tn_f32out_ws', 'afx_linear_tn_ws_bytes', 'afx_linear_bf16_dropres', 'afx_transpose_bf16', 'afx_colsum_bf16', 'afx_normout_backward', 'afx_normout_backward_split',
     'afx_outer_accum', 'afx_mmdit_export', 'afx_sumsq', 'afx_adamw_step', 'afx_adamw8bit_step', 'afx_ema_lerp', 'afx_cast_f32_bf16',
+    'afx_qkv_operands', 'afx_norm_modulate_joint_bf16', 'afx_norm_modulate_mx8',
 ]
+
+AFX_BLOCK_DOUBLE, AFX_BLOCK_SINGLE = 0, 1
+AFX_QKV_PATHS = {'auto': 0, 'vt_proj': 1, 'qk_epi': 2, 'kv_prep': 3}
 
 
 class ModelDesc(C.Structure):
@@ -165,6 +169,9 @@ def load() -> C.CDLL:
     lib.afx_adamw8bit_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, i32, f32, i64, vp]
     lib.afx_ema_lerp.argtypes = [vp, vp, f32, i64, vp]
     lib.afx_cast_f32_bf16.argtypes = [vp, vp, i64, vp]
+    lib.afx_qkv_operands.argtypes = [i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp]
+    lib.afx_norm_modulate_joint_bf16.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, i32, i32, vp]
+    lib.afx_norm_modulate_mx8.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, C.POINTER(i32), vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:       # default restype: status code

@@ -214,6 +214,132 @@ double gemm_flops(const GemmBatch& gb) {
   return f;
 }
 
+// ---- the attention operands of one block: the k|v|q(|mlp) projection and the q / k / V^T preparation -----------------------------
+// Three ways (AFX_QKV_* in arcflow_hip.h), picked per shape by qkv_path():
+//   VT_PROJ  V^T straight out of the projection: k and q as problems of their own with the q / k epilogue (GemmProblem::qk_D), the V third
+//            computed transposed (A = the V rows of the weight, W = the tokens; w_perm16 / bias_rows) into Vt at the rows' key offset.  Needs
+//            16-key groups that do not straddle the text / image boundary and no key padding (T % 16 == 0, S % 64 == 0);
+//   QK_EPI   RMSNorm + RoPE of q / k in the epilogue of the whole projection, then launch_v_transpose;
+//   KV_PREP  the plain projection, then launch_kv_prep (norm, RoPE and transpose of the bf16-rounded projection in one launch).
+// The forward and afx_qkv_operands build their launches with the functions below.
+struct BlockShape {
+  int64_t D;
+  int H, B, N, T, S, S_pad;                    // S = N + T joint rows per sample: [text T | image N]
+  const float* rope_cos;                       // [S, 64] f32 tables of the joint positions
+  const float* rope_sin;
+  uint16_t* Vt;                                // [B][H][128][S_pad] key-permuted V^T (afx_attn.hip key_of_pos)
+};
+
+BlockShape block_shape(int H, int B, int N, int T, const float* rope_cos, const float* rope_sin, uint16_t* Vt) {
+  BlockShape q;
+  q.D = (int64_t)H * 128; q.H = H; q.B = B; q.N = N; q.T = T; q.S = N + T; q.S_pad = (int)attn_spad(N + T);
+  q.rope_cos = rope_cos; q.rope_sin = rope_sin; q.Vt = Vt;
+  return q;
+}
+
+bool vt_proj_shape_ok(const BlockShape& q, bool single) {
+  return q.T % 16 == 0 && q.S % 64 == 0 && (!single || q.B + 3 <= GEMM_MAX_PROBLEMS);
+}
+
+// the forward's choice (fp8: the block linears run on the fp8 MFMA; qk_fuse_fp8: its q / k epilogue is switched on)
+int qkv_path(const BlockShape& q, bool single, bool fp8, bool qk_fuse_fp8) {
+  const bool qk_fuse = gemm_qk_fusion_available() && (!fp8 || qk_fuse_fp8);
+  const bool vt_fuse = qk_fuse && !fp8 && getenv("AFX_VT_FUSE_OFF") == nullptr && vt_proj_shape_ok(q, single);
+  return vt_fuse ? AFX_QKV_VT_PROJ : qk_fuse ? AFX_QKV_QK_EPI : AFX_QKV_KV_PREP;
+}
+
+// q / k RMSNorm + RoPE in the epilogue of problem p: its row r sits at joint position (row0 + r) % period
+void set_qk_epilogue(GemmProblem& p, const BlockShape& q, const float* wq, const float* wk, int row0, int period) {
+  p.qk_D = (int)q.D; p.qk_wq = wq; p.qk_wk = wk;
+  p.rope_cos = q.rope_cos; p.rope_sin = q.rope_sin; p.rope_row0 = row0; p.rope_period = period; p.rope_rows = q.S;
+}
+
+// ... of the image (s = 0) or text (s = 1) rows of a double block: qkn = [img_q, img_k, txt_q, txt_k][128]
+void stream_qk_epilogue(GemmProblem& p, const BlockShape& q, const float* qkn, int s) {
+  set_qk_epilogue(p, q, qkn + (s == 0 ? 0 : 2) * 128, qkn + (s == 0 ? 1 : 3) * 128, s == 0 ? q.T : 0, 1 << 30);
+}
+
+// the image (s = 0) or text (s = 1) rows of sample b in a per-stream linear over the joint token matrix
+void stream_problem(GemmProblem& p, const BlockShape& q, const uint16_t* A, int64_t lda, int K, const LinW& lw, uint16_t* C, int64_t ldc,
+                    int Nout, int b, int s) {
+  p = GemmProblem{};
+  const int64_t row0 = (int64_t)b * q.S + (s == 0 ? q.T : 0);
+  p.A = A + row0 * lda; p.lda = lda;
+  p.W = lw.w; p.ldw = K; p.bias = lw.b;
+  p.C = C + row0 * ldc; p.ldc = ldc;
+  p.M = (s == 0 ? q.N : q.T); p.N = Nout; p.K = K;
+}
+
+// VT_PROJ: the k, q and transposed-v problems of one k|v|q(|mlp) projection over `rows` joint rows starting at joint row `row0g` of sample b
+void kqv_problems(GemmBatch& gb, const BlockShape& q, const uint16_t* A, int64_t lda, const LinW& lw, uint16_t* C, int64_t ldc, int64_t row0g,
+                  int rows, int b, int pos0, int period, const float* wq, const float* wk, bool with_v) {
+  const int64_t D = q.D;
+  for (int part = 0; part < (with_v ? 3 : 2); ++part) {        // 0: k (weight rows 0..D), 1: q (2D..3D), 2: v^T (D..2D)
+    GemmProblem& p = gb.p[gb.nprob++];
+    p = GemmProblem{};
+    p.K = (int)D; p.epi = EPI_NONE;
+    if (part < 2) {
+      const int64_t wrow = part == 0 ? 0 : 2 * D;
+      p.A = A + row0g * lda; p.lda = lda;
+      p.W = lw.w + wrow * D; p.ldw = D; p.bias = lw.b ? lw.b + wrow : nullptr;
+      p.C = C + row0g * ldc + wrow; p.ldc = ldc; p.M = rows; p.N = (int)D;
+      set_qk_epilogue(p, q, part == 0 ? wk : wq, part == 0 ? wk : wq, pos0, period);     // a problem of its own: its columns are "region 0"
+    } else {
+      p.A = lw.w + D * D; p.lda = D; p.bias = lw.b ? lw.b + D : nullptr; p.bias_rows = 1;
+      p.W = A + row0g * lda; p.ldw = lda; p.w_perm16 = 1;
+      p.C = q.Vt + (int64_t)b * q.H * 128 * q.S_pad + pos0; p.ldc = q.S_pad; p.M = (int)D; p.N = rows;
+    }
+  }
+}
+
+// VT_PROJ, double block: sample b's image k, q, v^T + text k, q, v^T = 6 problems of one launch
+void double_vt_batch(GemmBatch& gb, const BlockShape& q, const uint16_t* A, int64_t lda, const LinW (&lw)[2], uint16_t* QKV, int64_t ldq,
+                     const float* qkn, int b) {
+  for (int s = 0; s < 2; ++s)
+    kqv_problems(gb, q, A, lda, lw[s], QKV, ldq, (int64_t)b * q.S + (s == 0 ? q.T : 0), s == 0 ? q.N : q.T, b, s == 0 ? q.T : 0, 1 << 30,
+                 qkn + (s == 0 ? 0 : 2) * 128, qkn + (s == 0 ? 1 : 3) * 128, true);
+}
+
+// Single block: the fused [k | v | q | mlp] projection over all B S joint rows (position = row % S, qkn = [q, k][128]), mlp columns through
+// GELU.  QK_EPI / KV_PREP: one problem (with / without the q / k epilogue); VT_PROJ: k, q, the mlp columns and one transposed v per sample.
+void single_qkv_batch(GemmBatch& gb, int path, const BlockShape& q, const uint16_t* A, int64_t lda, const LinW& lw, uint16_t* F, int64_t ldf,
+                      const float* qkn) {
+  const int64_t D = q.D;
+  const int R = q.B * q.S;
+  gb.nprob = 1;
+  GemmProblem& f = gb.p[0];
+  f = GemmProblem{};
+  f.A = A; f.lda = lda; f.W = lw.w; f.ldw = D; f.bias = lw.b;
+  f.C = F; f.ldc = ldf; f.M = R; f.N = (int)(7 * D); f.K = (int)D; f.epi = EPI_GELU; f.gelu_col0 = (int)(3 * D);
+  if (path == AFX_QKV_VT_PROJ) {
+    gb.nprob = 0;
+    kqv_problems(gb, q, A, lda, lw, F, ldf, 0, R, 0, 0, q.S, qkn, qkn + 128, false);
+    GemmProblem& m = gb.p[gb.nprob++];
+    m = GemmProblem{};
+    m.A = A; m.lda = lda; m.W = lw.w + 3 * D * D; m.ldw = D; m.bias = lw.b ? lw.b + 3 * D : nullptr;
+    m.C = F + 3 * D; m.ldc = ldf; m.M = R; m.N = (int)(4 * D); m.K = (int)D; m.epi = EPI_GELU; m.gelu_col0 = 0;
+    for (int b = 0; b < q.B; ++b) {
+      GemmProblem& v = gb.p[gb.nprob++];
+      v = GemmProblem{};
+      v.A = lw.w + D * D; v.lda = D; v.bias = lw.b ? lw.b + D : nullptr; v.bias_rows = 1;
+      v.W = A + (int64_t)b * q.S * lda; v.ldw = lda; v.w_perm16 = 1;
+      v.C = q.Vt + (int64_t)b * q.H * 128 * q.S_pad; v.ldc = q.S_pad; v.M = (int)D; v.N = q.S; v.K = (int)D; v.epi = EPI_NONE;
+    }
+  } else if (path == AFX_QKV_QK_EPI) {
+    set_qk_epilogue(f, q, qkn, qkn + 128, 0, q.S);
+  }
+}
+
+// what is left behind the projection [k | v | q ...] (row stride ldf): QK_EPI transposes V, KV_PREP normalises and rotates k and q in place
+// (joint rows < T with the text weights) and transposes V
+hipError_t qkv_finish(int path, const BlockShape& q, uint16_t* F, int64_t ldf, const float* wk_txt, const float* wk_img, const float* wq_txt,
+                      const float* wq_img, hipStream_t st) {
+  if (path == AFX_QKV_QK_EPI) return launch_v_transpose(F + q.D, ldf, q.Vt, q.B, q.H, q.S, st);
+  if (path == AFX_QKV_KV_PREP)
+    return launch_kv_prep(F, F + 2 * q.D, ldf, wk_txt, wk_img, wq_txt, wq_img, q.rope_cos, q.rope_sin, q.T, F + q.D, ldf, q.Vt, q.B, q.H, q.S, st);
+  return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -480,37 +606,11 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   const bool attn_mx = mx && H * 128 == D && getenv("AFX_FP8_ATTN_MX_OFF") == nullptr;      // the attention epilogue as the last producer of the format
   const char* qkf8 = getenv("AFX_FP8_QK_FUSE");
   const bool qk_fuse_fp8 = mx && qkf8 != nullptr && qkf8[0] == '1';
-  // helper: one grouped GEMM over the image and text row ranges of every sample
-  // q / k RMSNorm + RoPE inside the epilogue of the k|v|q projections (GemmProblem::qk_D) when the GEMM kernel in use offers it:
-  // the separate launch then only transposes V.  Not in fp8 mode (that kernel has no such epilogue).
-  const bool qk_fuse = gemm_qk_fusion_available() && (!c->fp8 || qk_fuse_fp8);
-  // ... and V^T straight out of the projection (GemmProblem::w_perm16 / bias_rows: the V third computed transposed, A = the V rows
-  // of the weight, W = the tokens) when the 16-key groups of the joint sequence do not straddle the text / image boundary and no
-  // key padding is needed: then no preparation launch is left between the projection and the attention.
-  const int S_pad_ = (int)attn_spad(S);
-  const bool vt_fuse = qk_fuse && !c->fp8 && T % 16 == 0 && S % 64 == 0 && getenv("AFX_VT_FUSE_OFF") == nullptr;
-  const int64_t vt_sample = (int64_t)H * 128 * S_pad_;           // elements of one sample's V^T
-  // the k, q and transposed-v problems of one k|v|q(|mlp) projection over `rows` joint rows starting at joint row `row0` of sample b
-  auto kqv_problems = [&](GemmBatch& gb, const uint16_t* A, int64_t lda, const LinW& lw, uint16_t* C, int64_t ldc, int64_t row0g,
-                          int rows, int b, int pos0, int period, const float* wq, const float* wk, bool with_v) {
-    for (int part = 0; part < (with_v ? 3 : 2); ++part) {        // 0: k (weight rows 0..D), 1: q (2D..3D), 2: v^T (D..2D)
-      GemmProblem& p = gb.p[gb.nprob++];
-      p = GemmProblem{};
-      p.K = (int)D; p.epi = EPI_NONE;
-      if (part < 2) {
-        const int64_t wrow = part == 0 ? 0 : 2 * D;
-        p.A = A + row0g * lda; p.lda = lda;
-        p.W = lw.w + wrow * D; p.ldw = D; p.bias = lw.b ? lw.b + wrow : nullptr;
-        p.C = C + row0g * ldc + wrow; p.ldc = ldc; p.M = rows; p.N = (int)D;
-        p.qk_D = (int)D; p.qk_wk = part == 0 ? wk : wq; p.qk_wq = p.qk_wk;       // a problem of its own: its columns are "region 0"
-        p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_row0 = pos0; p.rope_period = period; p.rope_rows = (int)S;
-      } else {
-        p.A = lw.w + D * D; p.lda = D; p.bias = lw.b ? lw.b + D : nullptr; p.bias_rows = 1;
-        p.W = A + row0g * lda; p.ldw = lda; p.w_perm16 = 1;
-        p.C = ws.Vt + (int64_t)b * vt_sample + pos0; p.ldc = S_pad_; p.M = (int)D; p.N = rows;
-      }
-    }
-  };
+  // how each block prepares its attention operands (see qkv_path): q / k RMSNorm + RoPE in the epilogue of the k|v|q projections when
+  // the GEMM kernel in use offers it (not in fp8 mode unless AFX_FP8_QK_FUSE), and V^T straight out of the projection where the shape
+  // allows: then no preparation launch is left between the projection and the attention
+  const BlockShape bs = block_shape(H, B, N, T, rope_cos, rope_sin, ws.Vt);
+  const int dpath = qkv_path(bs, false, c->fp8, qk_fuse_fp8), spath = qkv_path(bs, true, c->fp8, qk_fuse_fp8);
   // mx_in: 0 = quantise A here; 1 = A is the wide operand a previous epilogue left in q8 / mxw; 2 = the LayerNorm kernel left it in q8n (+ qs: one scale
   // per row, or + mxn with AFX_FP8_NORM_MX); 3 = the attention kernel left it in q8n / mxn.
   // mx_out: this GEMM's epilogue writes the wide operand.
@@ -523,10 +623,8 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
     for (int b = 0; b < B; ++b)
       for (int s = 0; s < 2; ++s) {   // 0 image rows, 1 text rows
         GemmProblem& p = gb.p[gb.nprob++];
-        p = GemmProblem{};
+        stream_problem(p, bs, A, lda, K, lw[s], C, ldc, Nout, b, s);
         const int64_t row0 = (int64_t)b * S + (s == 0 ? T : 0);
-        p.A = A + row0 * lda; p.lda = lda;
-        p.W = lw[s].w; p.ldw = K; p.bias = lw[s].b;
         if (mx) {
           p.W = (const uint16_t*)lw[s].wq; p.fp8 = 1; p.a_scale = ws.ones + row0; p.w_scale = lw[s].wscale; p.lda = K;
           if (mx_in == 2 && norm_rows) { p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.qs + row0; }      // LayerNorm rows: one scale per row, the plain fp8 MFMA
@@ -537,13 +635,8 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
           p.A = (const uint16_t*)(ws.q8 + row0 * K); p.lda = K;
           p.W = (const uint16_t*)lw[s].wq; p.fp8 = 1; p.a_scale = ws.qs + row0; p.w_scale = lw[s].wscale;
         }
-        p.C = C + row0 * ldc; p.ldc = ldc;
-        p.M = (s == 0 ? N : T); p.N = Nout; p.K = K;
         p.epi = epi; p.gelu_col0 = 0;
-        if (qkn != nullptr) {           // [img_q, img_k, txt_q, txt_k][128]
-          p.qk_D = (int)D; p.qk_wq = qkn + (s == 0 ? 0 : 2) * 128; p.qk_wk = qkn + (s == 0 ? 1 : 3) * 128;
-          p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_row0 = (s == 0 ? T : 0); p.rope_period = 1 << 30; p.rope_rows = (int)S;
-        }
+        if (qkn != nullptr) stream_qk_epilogue(p, bs, qkn, s);          // [img_q, img_k, txt_q, txt_k][128]
         if (epi == EPI_GATE_RES) {
           p.gate = ws.mod + (int64_t)b * ldm + ml.dbl(blk, s, gate_chunk); p.ldg = 0; p.rows_per_batch = 1 << 30;
           p.res = C + row0 * ldc; p.ldr = ldc;
@@ -594,23 +687,17 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
     const float* qkn = bw.qkn;          // [img_q, img_k, txt_q, txt_k][128]
     if (c->ckpt) HIP_TRY(hipMemcpyAsync(c->ckpt + (int64_t)i * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, st));
     if ((rc = stream_norm(i, 0, 1))) return rc;
-    if (vt_fuse) {                        // per sample: img k, q, v^T + txt k, q, v^T = 6 problems in one launch
+    if (dpath == AFX_QKV_VT_PROJ) {       // per sample: img k, q, v^T + txt k, q, v^T = 6 problems in one launch
       for (int b = 0; b < B; ++b) {
         GemmBatch gb{};
-        for (int s = 0; s < 2; ++s)
-          kqv_problems(gb, ws.Xn, D, bw.qkv[s], QKV, 3 * D, (int64_t)b * S + (s == 0 ? T : 0), s == 0 ? N : T, b, s == 0 ? T : 0, 1 << 30,
-                       qkn + (s == 0 ? 0 : 2) * 128, qkn + (s == 0 ? 1 : 3) * 128, true);
+        double_vt_batch(gb, bs, ws.Xn, D, bw.qkv, QKV, 3 * D, qkn, b);
         { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
       }
     } else
-    if ((rc = stream_gemm(ws.Xn, D, (int)D, bw.qkv, QKV, 3 * D, (int)(3 * D), EPI_NONE, i, 0, qk_fuse ? qkn : nullptr, norm_fused ? 2 : 0, false, 1))) return rc;
-    // k, q: RMSNorm + RoPE in place, v -> V^T: one launch
-    if (vt_fuse) {
-    } else if (qk_fuse)
-      HIP_TRY(launch_v_transpose(QKV + D, 3 * D, ws.Vt, B, H, S, st));
-    else
-    HIP_TRY(launch_kv_prep(QKV, QKV + 2 * D, 3 * D, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, rope_cos, rope_sin, T, QKV + D,
-                           3 * D, ws.Vt, B, H, S, st));
+    if ((rc = stream_gemm(ws.Xn, D, (int)D, bw.qkv, QKV, 3 * D, (int)(3 * D), EPI_NONE, i, 0, dpath == AFX_QKV_QK_EPI ? qkn : nullptr,
+                          norm_fused ? 2 : 0, false, 1))) return rc;
+    // V -> V^T (QK_EPI), or k, q: RMSNorm + RoPE in place and V -> V^T in one launch (KV_PREP)
+    HIP_TRY(qkv_finish(dpath, bs, QKV, 3 * D, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, st));
     bool o_fused = false;            // mx: the attention kernel wrote the out-projection's operand itself (q8n / mxn)
     const AttnMx8 omx_d{ws.q8n, D, ws.mxn, ws.ld_mxn};
     { ProfScope ps_(c, st, 1, 4.0 * B * H * (double)S * S * 128);
@@ -632,11 +719,8 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
                                              nullptr, nullptr, ldm, (int)S, 0, st, &sgl_fused, norm_rows ? ws.qs : nullptr));
     if (!sgl_fused) HIP_TRY(launch_norm_modulate(ws.X, D, ws.Xn, D, (int)R, (int)D, ws.mod + ml.sgl(i, 1), ws.mod + ml.sgl(i, 0), ldm, S, 0, st));
     GemmBatch gb{};
-    gb.nprob = 1;
+    single_qkv_batch(gb, spath, bs, ws.Xn, D, bw.fused, ws.F, 7 * D, qkn);      // (VT_PROJ is never taken in fp8 mode)
     GemmProblem& f = gb.p[0];
-    f = GemmProblem{};
-    f.A = ws.Xn; f.lda = D; f.W = bw.fused.w; f.ldw = D; f.bias = bw.fused.b;
-    f.C = ws.F; f.ldc = 7 * D; f.M = (int)R; f.N = (int)(7 * D); f.K = (int)D; f.epi = EPI_GELU; f.gelu_col0 = (int)(3 * D);
     if (mx) {             // A: the LayerNorm rows, block-scaled; the mlp columns leave as columns [D, 5D) of the proj_out operand
       if (!sgl_fused) HIP_TRY(launch_quant_rows_mx8(ws.Xn, D, ws.q8n, D, ws.mxn, ws.ld_mxn, (int)R, (int)D, st));
       f.A = (const uint16_t*)ws.q8n; f.W = (const uint16_t*)bw.fused.wq; f.fp8 = 1; f.a_scale = ws.ones; f.w_scale = bw.fused.wscale;
@@ -647,32 +731,8 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
       HIP_TRY(launch_quant_rows_fp8(ws.Xn, D, ws.q8, D, ws.qs, (int)R, (int)D, st));
       f.A = (const uint16_t*)ws.q8; f.W = (const uint16_t*)bw.fused.wq; f.fp8 = 1; f.a_scale = ws.qs; f.w_scale = bw.fused.wscale;
     }
-    if (vt_fuse && B + 3 <= GEMM_MAX_PROBLEMS) {
-      // k and q over the joint rows of every sample (position = row % S), the mlp columns, one transposed v per sample
-      gb.nprob = 0;
-      kqv_problems(gb, ws.Xn, D, bw.fused, ws.F, 7 * D, 0, (int)R, 0, 0, (int)S, qkn, qkn + 128, false);
-      GemmProblem& m = gb.p[gb.nprob++];
-      m = GemmProblem{};
-      m.A = ws.Xn; m.lda = D; m.W = bw.fused.w + 3 * D * D; m.ldw = D; m.bias = bw.fused.b ? bw.fused.b + 3 * D : nullptr;
-      m.C = ws.F + 3 * D; m.ldc = 7 * D; m.M = (int)R; m.N = (int)(4 * D); m.K = (int)D; m.epi = EPI_GELU; m.gelu_col0 = 0;
-      for (int b = 0; b < B; ++b) {
-        GemmProblem& v = gb.p[gb.nprob++];
-        v = GemmProblem{};
-        v.A = bw.fused.w + D * D; v.lda = D; v.bias = bw.fused.b ? bw.fused.b + D : nullptr; v.bias_rows = 1;
-        v.W = ws.Xn + (int64_t)b * S * D; v.ldw = D; v.w_perm16 = 1;
-        v.C = ws.Vt + (int64_t)b * vt_sample; v.ldc = S_pad_; v.M = (int)D; v.N = (int)S; v.K = (int)D; v.epi = EPI_NONE;
-      }
-    } else if (qk_fuse) {               // [q, k][128]; the joint rows of every sample: position = row % S
-      f.qk_D = (int)D; f.qk_wq = qkn; f.qk_wk = qkn + 128;
-      f.rope_cos = rope_cos; f.rope_sin = rope_sin; f.rope_row0 = 0; f.rope_period = (int)S; f.rope_rows = (int)S;
-    }
     { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-    if (vt_fuse && B + 3 <= GEMM_MAX_PROBLEMS) {
-    } else if (qk_fuse)
-      HIP_TRY(launch_v_transpose(ws.F + D, 7 * D, ws.Vt, B, H, S, st));
-    else
-    HIP_TRY(launch_kv_prep(ws.F, ws.F + 2 * D, 7 * D, qkn + 128, qkn + 128, qkn, qkn, rope_cos, rope_sin, T, ws.F + D, 7 * D, ws.Vt, B,
-                           H, S, st));
+    HIP_TRY(qkv_finish(spath, bs, ws.F, 7 * D, qkn + 128, qkn + 128, qkn, qkn, st));
     bool o_fused = false;            // mx: ... columns [0, D) of the [O | mlp] operand (q8 / mxw)
     const AttnMx8 omx_s{ws.q8, 5 * D, ws.mxw, ws.ld_mxw};
     { ProfScope ps_(c, st, 1, 4.0 * B * H * (double)S * S * 128);
@@ -1133,6 +1193,100 @@ int afx_gemv_bf16(const float* x, const void* W, const void* bias, float* y, int
   if (!x || !W || !y) return fail(AFX_E_INVALID, "null argument to afx_gemv_bf16");
   if (B < 1 || B > 8 || N < 1 || K < 8 || K % 8) return fail(AFX_E_INVALID, "bad gemv shape (B<=8, K%%8==0)");
   HIP_TRY(launch_gemv(x, (const uint16_t*)W, (const uint16_t*)bias, y, B, N, K, act, accumulate, (hipStream_t)stream));
+  return AFX_OK;
+}
+
+int afx_qkv_operands(int32_t kind, const void* A, int64_t lda, const void* w_img, const void* b_img, const void* w_txt, const void* b_txt,
+                     const float* qkn, const float* rope_cos, const float* rope_sin, int32_t B, int32_t N, int32_t T, int32_t heads,
+                     int32_t path, void* F, int64_t ldf, void* Vt, void* stream) {
+  if (kind != AFX_BLOCK_DOUBLE && kind != AFX_BLOCK_SINGLE) return fail(AFX_E_INVALID, "afx_qkv_operands: kind must be AFX_BLOCK_DOUBLE or AFX_BLOCK_SINGLE");
+  const bool single = kind == AFX_BLOCK_SINGLE;
+  if (!A || !w_img || !qkn || !rope_cos || !rope_sin || !F || !Vt || (!single && !w_txt) || (!single && (!b_img) != (!b_txt)))
+    return fail(AFX_E_INVALID, "null argument to afx_qkv_operands");
+  if (B < 1 || B > AFX_MAX_MICRO_BATCH || N < 1 || T < 1 || heads < 1 || path < AFX_QKV_AUTO || path > AFX_QKV_KV_PREP)
+    return fail(AFX_E_INVALID, "afx_qkv_operands: need 1 <= batch <= %d, n_img, n_txt, heads >= 1 and a path AFX_QKV_*", AFX_MAX_MICRO_BATCH);
+  const int64_t D = (int64_t)heads * 128, width = (single ? 7 : 3) * D;
+  if (lda < D || ldf < width || lda % 8 || ldf % 8)
+    return fail(AFX_E_INVALID, "afx_qkv_operands: need lda >= %lld, ldf >= %lld, both multiples of 8", (long long)D, (long long)width);
+  if (((uintptr_t)A | (uintptr_t)w_img | (uintptr_t)b_img | (uintptr_t)w_txt | (uintptr_t)b_txt | (uintptr_t)qkn | (uintptr_t)rope_cos |
+       (uintptr_t)rope_sin | (uintptr_t)F | (uintptr_t)Vt) & 15)
+    return fail(AFX_E_INVALID, "afx_qkv_operands: operands must be 16-byte aligned");
+  const BlockShape bs = block_shape(heads, B, N, T, rope_cos, rope_sin, (uint16_t*)Vt);
+  const int p = path == AFX_QKV_AUTO ? qkv_path(bs, single, false, false) : path;
+  if (p != AFX_QKV_KV_PREP && !gemm_qk_fusion_available())
+    return fail(AFX_E_INVALID, "afx_qkv_operands: the GEMM kernel in use has no q / k epilogue (afx_gemm_set_mode / AFX_QK_FUSE)");
+  if (p == AFX_QKV_VT_PROJ && !vt_proj_shape_ok(bs, single))
+    return fail(AFX_E_INVALID, "afx_qkv_operands: V^T from the projection needs n_txt %% 16 == 0 and (n_img + n_txt) %% 64 == 0");
+  hipStream_t st = (hipStream_t)stream;
+  const uint16_t* a = (const uint16_t*)A;
+  uint16_t* f = (uint16_t*)F;
+  if (single) {
+    LinW lw;
+    lw.w = (const uint16_t*)w_img; lw.b = (const uint16_t*)b_img;
+    GemmBatch gb{};
+    single_qkv_batch(gb, p, bs, a, lda, lw, f, ldf, qkn);
+    HIP_TRY(launch_gemm(gb, st));
+    HIP_TRY(qkv_finish(p, bs, f, ldf, qkn + 128, qkn + 128, qkn, qkn, st));
+    return AFX_OK;
+  }
+  LinW lw[2];
+  lw[0].w = (const uint16_t*)w_img; lw[0].b = (const uint16_t*)b_img;
+  lw[1].w = (const uint16_t*)w_txt; lw[1].b = (const uint16_t*)b_txt;
+  if (p == AFX_QKV_VT_PROJ) {
+    for (int b = 0; b < B; ++b) {
+      GemmBatch gb{};
+      double_vt_batch(gb, bs, a, lda, lw, f, ldf, qkn, b);
+      HIP_TRY(launch_gemm(gb, st));
+    }
+    return AFX_OK;
+  }
+  GemmBatch gb{};
+  for (int b = 0; b < B; ++b)
+    for (int s = 0; s < 2; ++s) {
+      GemmProblem& pr = gb.p[gb.nprob++];
+      stream_problem(pr, bs, a, lda, (int)D, lw[s], f, ldf, (int)width, b, s);
+      if (p == AFX_QKV_QK_EPI) stream_qk_epilogue(pr, bs, qkn, s);
+    }
+  HIP_TRY(launch_gemm(gb, st));
+  HIP_TRY(qkv_finish(p, bs, f, ldf, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, st));
+  return AFX_OK;
+}
+
+// shared argument checks of the two AdaLN entry points below
+static int norm_joint_args(const char* fn, const void* x, int64_t ldx, int64_t ldo, int32_t rows, int32_t D, const float* scale, const float* shift,
+                           const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S, int32_t n_txt) {
+  if (!x || !scale || !shift || (!scale_txt) != (!shift_txt)) return fail(AFX_E_INVALID, "null argument to %s", fn);
+  if (rows < 0 || D < 8 || D % 8 || D > 4096 || ldx < D || ldx % 8 || ldo < D || ldo % 8 || ldmod < 0 || ldmod % 4 || S < 1 || n_txt < 0 ||
+      n_txt > S || (!scale_txt && n_txt != 0))
+    return fail(AFX_E_INVALID, "%s: need D %% 8 == 0, D <= 4096, ldx / ldo >= D and multiples of 8, ldmod %% 4 == 0, 0 <= n_txt <= S "
+                "(n_txt 0 without text vectors)", fn);
+  if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)scale_txt | (uintptr_t)shift_txt) & 15)
+    return fail(AFX_E_INVALID, "%s: operands must be 16-byte aligned", fn);
+  return AFX_OK;
+}
+
+int afx_norm_modulate_joint_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t rows, int32_t D, const float* scale,
+                                 const float* shift, const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S,
+                                 int32_t n_txt, void* stream) {
+  int r = norm_joint_args("afx_norm_modulate_joint_bf16", x, ldx, ldo, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt);
+  if (r != AFX_OK) return r;
+  if (!out || ((uintptr_t)out & 15)) return fail(AFX_E_INVALID, "afx_norm_modulate_joint_bf16: out null or not 16-byte aligned");
+  HIP_TRY(launch_norm_modulate_joint((const uint16_t*)x, ldx, (uint16_t*)out, ldo, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt,
+                                     (hipStream_t)stream));
+  return AFX_OK;
+}
+
+int afx_norm_modulate_mx8(const void* x, int64_t ldx, void* q8, int64_t ldq, void* mx, int64_t ld_mx, float* rowscale, int32_t rows, int32_t D,
+                          const float* scale, const float* shift, const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S,
+                          int32_t n_txt, int32_t* fused, void* stream) {
+  int r = norm_joint_args("afx_norm_modulate_mx8", x, ldx, ldq, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt);
+  if (r != AFX_OK) return r;
+  if (!q8 || !fused || ((uintptr_t)q8 & 7) || (!rowscale && (!mx || ld_mx < (D + 127) / 128 || ld_mx % 4)) || ((uintptr_t)rowscale & 3))
+    return fail(AFX_E_INVALID, "afx_norm_modulate_mx8: need q8 (8-byte aligned), fused, and rowscale or mx with ld_mx >= D / 128, ld_mx %% 4 == 0");
+  bool f = false;
+  HIP_TRY(launch_norm_modulate_mx8((const uint16_t*)x, ldx, (uint8_t*)q8, ldq, (uint8_t*)mx, ld_mx, rows, D, scale, shift, scale_txt, shift_txt,
+                                   ldmod, S, n_txt, (hipStream_t)stream, &f, rowscale));
+  *fused = f ? 1 : 0;
   return AFX_OK;
 }
 

@@ -176,6 +176,112 @@ def qk_norm_rope_(x: torch.Tensor, w_txt: torch.Tensor, w_img: torch.Tensor, cos
     return x
 
 
+def _joint_vectors(vecs, B: int, D: int, name: str) -> int:
+    """The AdaLN vectors of a joint launch: each [B, D] fp32 (or [D] when B == 1), unit inner stride, 16-byte aligned rows, all with the
+    same row stride (the kernels take one ldmod).  Returns that stride."""
+    ld = None
+    for v, n in vecs:
+        if v.device.type != 'cuda':
+            raise _lib.ArcflowHipError(f'{name} {n}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+        v2 = v[None] if v.dim() == 1 else v
+        if v2.dim() != 2 or tuple(v2.shape) != (B, D) or v2.dtype != torch.float32 or v2.stride(1) != 1 or v2.data_ptr() % 16:
+            raise ValueError(f'{name} {n}: need a [{B}, {D}] float32 tensor with unit inner stride and 16-byte aligned rows, got '
+                             f'{tuple(v.shape)} {v.dtype} strides {v.stride()}')
+        s = v2.stride(0) if B > 1 else 0
+        if s % 4 or (ld is not None and s != ld):
+            raise ValueError(f'{name} {n}: every modulation vector needs the same row stride (a multiple of 4), got {v2.stride(0)}')
+        ld = s
+    return ld
+
+
+def _joint_norm_args(x, scale, shift, S, scale_txt, shift_txt, n_txt, name):
+    _mat(x, torch.bfloat16, f'{name} x')
+    R, D = x.shape
+    if S < 1 or R % S:
+        raise ValueError(f'{name}: {R} rows are not a whole number of samples of S = {S}')
+    if (scale_txt is None) != (shift_txt is None) or not 0 <= n_txt <= S or (scale_txt is None and n_txt):
+        raise ValueError(f'{name}: text vectors need both scale_txt and shift_txt and 0 <= n_txt <= S (n_txt 0 without them)')
+    vecs = [(scale, 'scale'), (shift, 'shift')] + ([] if scale_txt is None else [(scale_txt, 'scale_txt'), (shift_txt, 'shift_txt')])
+    return R, D, _joint_vectors(vecs, R // S, D, name)
+
+
+def norm_modulate_joint(x, scale, shift, S: int, scale_txt=None, shift_txt=None, n_txt: int = 0, out=None):
+    """AdaLN of the joint token matrix x [B*S, D] bf16 in one launch (the forward's double blocks): LayerNorm(x) * (1 + scale[b]) + shift[b],
+    the first n_txt rows of every sample with (scale_txt, shift_txt).  Vectors [B, D] fp32 views with one common row stride."""
+    lib = _lib.load()
+    R, D, ldm = _joint_norm_args(x, scale, shift, S, scale_txt, shift_txt, n_txt, 'norm_modulate_joint')
+    if out is None:
+        out = torch.empty(R, D, dtype=torch.bfloat16, device=x.device)
+    _mat(out, torch.bfloat16, 'norm_modulate_joint out', (R, D))
+    _lib.check(lib.afx_norm_modulate_joint_bf16(_p(x), x.stride(0), _p(out), out.stride(0), R, D, _p(scale), _p(shift), _p(scale_txt),
+                                                _p(shift_txt), ldm, S, n_txt, _s()))
+    return out
+
+
+def norm_modulate_mx8(x, scale, shift, S: int, scale_txt=None, shift_txt=None, n_txt: int = 0, row_scale: bool = False):
+    """``norm_modulate_joint`` straight into the next fp8 GEMM's operand: returns (q uint8 [R, D] e4m3, scales, fused) with scales = uint8
+    [R, D / 128] E8M0 bytes (block-scaled) or, row_scale=True, fp32 [R] (absmax / 448 per row).  fused False: this shape has no fused
+    kernel and nothing was launched (q and scales are uninitialised)."""
+    lib = _lib.load()
+    R, D, ldm = _joint_norm_args(x, scale, shift, S, scale_txt, shift_txt, n_txt, 'norm_modulate_mx8')
+    q = torch.empty(R, D, dtype=torch.uint8, device=x.device)
+    nb = (D + 127) // 128
+    mx = None if row_scale else torch.empty(R, (nb + 3) // 4 * 4, dtype=torch.uint8, device=x.device)
+    rs = torch.empty(R, dtype=torch.float32, device=x.device) if row_scale else None
+    fused = C.c_int32(0)
+    _lib.check(lib.afx_norm_modulate_mx8(_p(x), x.stride(0), _p(q), D, _p(mx), 0 if mx is None else mx.stride(0), _p(rs), R, D, _p(scale),
+                                         _p(shift), _p(scale_txt), _p(shift_txt), ldm, S, n_txt, C.byref(fused), _s()))
+    return q, (rs if row_scale else mx[:, :nb]), bool(fused.value)
+
+
+def qkv_operands(kind: str, a, w, bias, qkn, cos, sin, B: int, N: int, T: int, path: str = 'auto', out=None, vt=None):
+    """The attention operands of one block as the forward builds them (``afx_qkv_operands``).  a [B*(N+T), D] bf16 AdaLN rows (joint layout,
+    row-strided view allowed); kind 'double': w = (w_img, w_txt) [3D, D], bias = (b_img, b_txt) [3D] or None, qkn [4, 128]
+    (img_q, img_k, txt_q, txt_k); kind 'single': w [7D, D], bias [7D] or None, qkn [2, 128] (q, k).  cos / sin [N+T, 64] fp32.
+    path: 'auto' (the forward's choice) | 'vt_proj' | 'qk_epi' | 'kv_prep'.  Returns (out [B*(N+T), 3D or 7D] bf16, which may be a
+    column view of a wider buffer, vt [B, H, 128, roundup(N+T, 64)] bf16)."""
+    lib = _lib.load()
+    if kind not in ('double', 'single') or path not in _lib.AFX_QKV_PATHS:
+        raise ValueError(f'qkv_operands: kind {kind!r} / path {path!r}')
+    single = kind == 'single'
+    S = N + T
+    _mat(a, torch.bfloat16, 'qkv_operands a')
+    R, D = a.shape
+    if D % 128 or R != B * S:
+        raise ValueError(f'qkv_operands a: need [{B} x {S}, heads x 128], got {tuple(a.shape)}')
+    H, width = D // 128, (7 if single else 3) * D
+    ws = (w,) if single else tuple(w)
+    bs = (bias,) if single else ((None, None) if bias is None else tuple(bias))
+    if len(ws) != (1 if single else 2) or len(bs) != len(ws):
+        raise ValueError('qkv_operands: a double block takes (w_img, w_txt) and (b_img, b_txt) or None')
+    for i, t in enumerate(ws):
+        _mat(t, torch.bfloat16, f'qkv_operands w[{i}]', ((width, D)))
+        if not t.is_contiguous():
+            raise ValueError(f'qkv_operands w[{i}]: the weight rows must be contiguous (row stride D)')
+    for i, t in enumerate(bs):
+        if t is not None and (t.device.type != 'cuda' or t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != (width,)):
+            raise ValueError(f'qkv_operands bias[{i}]: need a contiguous bf16 [{width}] tensor')
+    if sum(t is None for t in bs) not in (0, len(bs)):
+        raise ValueError('qkv_operands: both streams with a bias or neither')
+    for t, n, shp in ((qkn, 'qkn', (2 if single else 4, 128)), (cos, 'cos', (S, 64)), (sin, 'sin', (S, 64))):
+        if t.device.type != 'cuda' or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f'qkv_operands {n}: need a contiguous float32 {list(shp)} tensor, got {tuple(t.shape)} {t.dtype}')
+    S_pad = (S + 63) // 64 * 64
+    if out is None:
+        out = torch.empty(R, width, dtype=torch.bfloat16, device=a.device)
+    _mat(out, torch.bfloat16, 'qkv_operands out', (R, width))
+    if vt is None:
+        vt = torch.empty(B, H, 128, S_pad, dtype=torch.bfloat16, device=a.device)
+    if vt.device.type != 'cuda' or vt.dtype != torch.bfloat16 or not vt.is_contiguous() or tuple(vt.shape) != (B, H, 128, S_pad):
+        raise ValueError(f'qkv_operands vt: need a contiguous bf16 [{B}, {H}, 128, {S_pad}] workspace, got {tuple(vt.shape)} {vt.dtype}')
+    w_img, w_txt = ws[0], (None if single else ws[1])
+    b_img, b_txt = bs[0], (None if single else bs[1])
+    _lib.check(lib.afx_qkv_operands(_lib.AFX_BLOCK_SINGLE if single else _lib.AFX_BLOCK_DOUBLE, _p(a), a.stride(0), _p(w_img), _p(b_img),
+                                    _p(w_txt), _p(b_txt), _p(qkn), _p(cos), _p(sin), B, N, T, H, _lib.AFX_QKV_PATHS[path], _p(out),
+                                    out.stride(0), _p(vt), _s()))
+    return out, vt
+
+
 def gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: str = 'none',
          out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     lib = _lib.load()

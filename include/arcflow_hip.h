@@ -475,6 +475,38 @@ int afx_qk_norm_rope_bf16(void* x, int64_t ldx, const float* w_txt, const float*
 int afx_gemv_bf16(const float* x, const void* W, const void* bias, float* y, int32_t B, int32_t N,
                   int32_t K, int32_t act, int32_t accumulate, void* stream);
 
+/* The attention operands of ONE block exactly as afx_mmdit_forward builds them (bf16 linears), for parity tests.
+ * A: the AdaLN output [B*S, D] bf16 (row stride lda), the joint layout [text T | image N] per sample, S = N + T, D = heads * 128.
+ * kind AFX_BLOCK_DOUBLE: per-stream k|v|q weights w_img / w_txt [3D, D] (+ biases [3D] or both null), qkn [img_q, img_k, txt_q, txt_k][128];
+ *   F [B*S, 3D] (row stride ldf) receives k | v | q.
+ * kind AFX_BLOCK_SINGLE: the fused weight w_img [7D, D] (+ b_img [7D]; w_txt / b_txt unused), qkn [q, k][128]; F [B*S, 7D] receives
+ *   k | v | q | gelu_tanh(mlp).
+ * k and q leave as RoPE(RMSNorm_128(.) * w) per head at the row's joint position (the single block: row % S) of rope_cos / rope_sin
+ * [S, 64] f32; Vt [B][heads][128][roundup(S, 64)] bf16 receives V^T with the keys of every 16-group in the attention kernel's order and
+ * zeros for keys >= S (V itself stays in F for every path but AFX_QKV_VT_PROJ, which leaves F's V columns unwritten).
+ * path: AFX_QKV_AUTO = the forward's choice for this shape, or one of the three forced; AFX_E_INVALID when it cannot run on the shape
+ * or with the GEMM kernel in use.  batch <= AFX_MAX_MICRO_BATCH. */
+#define AFX_BLOCK_DOUBLE 0
+#define AFX_BLOCK_SINGLE 1
+#define AFX_QKV_AUTO 0
+#define AFX_QKV_VT_PROJ 1   /* V^T out of the projection GEMM, q / k epilogue on separate k and q problems: T % 16 == 0, S % 64 == 0 */
+#define AFX_QKV_QK_EPI 2    /* q / k RMSNorm + RoPE in the projection's fp32 epilogue, then a V transpose launch */
+#define AFX_QKV_KV_PREP 3   /* the plain projection, then norm + RoPE of the bf16 k / q and the V transpose in one launch */
+int afx_qkv_operands(int32_t kind, const void* A, int64_t lda, const void* w_img, const void* b_img, const void* w_txt, const void* b_txt,
+                     const float* qkn, const float* rope_cos, const float* rope_sin, int32_t batch, int32_t n_img, int32_t n_txt,
+                     int32_t heads, int32_t path, void* F, int64_t ldf, void* Vt, void* stream);
+/* AdaLN of a joint token matrix in one launch (the forward's double blocks): out = LayerNorm(x) * (1 + scale) + shift, rows of sample
+ * b = row / S at scale + b * ldmod, the first n_txt rows of each sample with scale_txt / shift_txt (both null: one stream, n_txt 0). */
+int afx_norm_modulate_joint_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t rows, int32_t D, const float* scale,
+                                 const float* shift, const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S,
+                                 int32_t n_txt, void* stream);
+/* ... straight into the next fp8 GEMM's operand: e4m3 bytes q8 [rows, ldq] with one E8M0 byte per row and 128 columns in mx [rows, ld_mx]
+ * or, with rowscale != null, one f32 scale per row (absmax / 448).  *fused = 0: no fused kernel for this shape and nothing was
+ * launched (the forward then runs the bf16 kernel and a quantisation pass). */
+int afx_norm_modulate_mx8(const void* x, int64_t ldx, void* q8, int64_t ldq, void* mx, int64_t ld_mx, float* rowscale, int32_t rows,
+                          int32_t D, const float* scale, const float* shift, const float* scale_txt, const float* shift_txt,
+                          int64_t ldmod, int32_t S, int32_t n_txt, int32_t* fused, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,57 @@ def test_argument_validation_no_gpu(lib):
     assert lib.afx_destroy(ctx) == 0
 
 
+def test_forward_operand_entry_points_validate_before_launch(lib):
+    """afx_qkv_operands / afx_norm_modulate_joint_bf16 / afx_norm_modulate_mx8 refuse bad arguments with AFX_E_INVALID before anything
+    touches the device (fake but aligned pointers: a launch would fault)."""
+    p = lambda off=0: C.c_void_p(1 << 20 | off)         # noqa: E731
+    D, H = 3072, 24
+    qkv = lib.afx_qkv_operands
+    ok = dict(A=p(), lda=D, wi=p(), bi=p(), wt=p(), bt=p(), qkn=p(), cos=p(), sin=p(), B=1, N=4096, T=512, H=H, path=0, F=p(), ldf=3 * D, Vt=p())
+
+    def call(kind=0, **kw):
+        a = dict(ok, **kw)
+        return qkv(kind, a['A'], a['lda'], a['wi'], a['bi'], a['wt'], a['bt'], a['qkn'], a['cos'], a['sin'], a['B'], a['N'], a['T'], a['H'],
+                   a['path'], a['F'], a['ldf'], a['Vt'], None)
+    assert call(kind=2) == -1 and b'kind' in lib.afx_last_error()
+    assert call(A=None) == -1 and b'null' in lib.afx_last_error()
+    assert call(wt=None) == -1                                            # a double block needs the text weights
+    assert call(bt=None) == -1                                            # ... and a bias for both streams or neither
+    assert call(B=5) == -1 and call(B=0) == -1 and call(T=0) == -1 and call(path=4) == -1 and call(path=-1) == -1
+    assert call(lda=D - 8) == -1 and call(ldf=3 * D - 8) == -1 and call(ldf=3 * D + 4) == -1
+    assert call(kind=1, ldf=3 * D) == -1 and b'ldf' in lib.afx_last_error()       # a single block writes 7D columns
+    assert call(A=p(8)) == -1 and call(Vt=p(2)) == -1 and call(qkn=p(4)) == -1 and b'aligned' in lib.afx_last_error()
+    if os.environ.get('AFX_GEMM_IMPL', '3') == '3' and os.environ.get('AFX_QK_FUSE') is None:
+        assert call(path=1, T=77) == -1 and b'% 16' in lib.afx_last_error()      # V^T from the projection: 16-key groups, no key padding
+        assert call(path=1, N=4100, T=496) == -1                                  # S % 64 != 0
+        assert lib.afx_gemm_set_mode(2, 0) == 0
+        try:
+            for path in (1, 2):
+                assert call(path=path) == -1 and b'q / k epilogue' in lib.afx_last_error()
+        finally:
+            assert lib.afx_gemm_set_mode(3, 0) == 0
+    # the AdaLN entry points
+    nmj = lib.afx_norm_modulate_joint_bf16
+    assert nmj(None, D, p(), D, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, None) == -1
+    assert nmj(p(), D, p(), D, 4608, D, p(), p(), p(), None, 98304, 4608, 512, None) == -1            # shift_txt missing
+    assert nmj(p(), D, p(), D, 4608, D, p(), p(), None, None, 98304, 4608, 512, None) == -1            # n_txt without text vectors
+    assert nmj(p(), D, p(), D, 4608, D, p(), p(), p(), p(), 98304, 4608, 4609, None) == -1             # n_txt > S
+    assert nmj(p(), D, p(), D, 4608, D + 4, p(), p(), p(), p(), 98304, 4608, 512, None) == -1          # D % 8
+    assert nmj(p(), D - 8, p(), D, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, None) == -1          # ldx < D
+    assert nmj(p(), D, p(), D, 4608, D, p(), p(), p(), p(), 98306, 4608, 512, None) == -1              # ldmod % 4
+    assert nmj(p(), D, p(8), D, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, None) == -1             # out misaligned
+    assert b'afx_norm_modulate_joint_bf16' in lib.afx_last_error()
+    mx8 = lib.afx_norm_modulate_mx8
+    fused = C.c_int32(7)
+    assert mx8(p(), D, p(), D, p(), 24, None, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, None, None) == -1     # no fused flag
+    assert mx8(p(), D, p(), D, None, 24, None, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, C.byref(fused), None) == -1   # no scales
+    assert mx8(p(), D, p(), D, p(), 20, None, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, C.byref(fused), None) == -1   # ld_mx < D / 128
+    assert mx8(p(), D, p(), D, p(), 26, None, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, C.byref(fused), None) == -1   # ld_mx % 4
+    assert mx8(p(), D, p(4), D, p(), 24, None, 4608, D, p(), p(), p(), p(), 98304, 4608, 512, C.byref(fused), None) == -1  # q8 alignment
+    assert mx8(p(), D, p(), D, None, 0, p(2), 4608, D, p(), p(), p(), p(), 98304, 4608, 512, C.byref(fused), None) == -1   # rowscale alignment
+    assert fused.value == 7 and b'afx_norm_modulate_mx8' in lib.afx_last_error()
+
+
 def test_schedule_matches_oracle_and_golden(golden):
     from arcflow_amd.schedule import FlowMatchEulerDiscreteScheduler, retrieve_raw_timesteps
     from oracle import arcflow_ref as R
