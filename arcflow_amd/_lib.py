@@ -17,7 +17,7 @@ AFX_DT_FP8 = 3
 
 EXPORTS = [
     'afx_last_error', 'afx_version', 'afx_create', 'afx_destroy', 'afx_bind_weight', 'afx_finalize',
-    'afx_workspace_bytes', 'afx_set_workspace', 'afx_mmdit_forward', 'afx_profile_enable', 'afx_profile_read', 'afx_set_checkpoint_buffer', 'afx_arcflow_step',
+    'afx_workspace_bytes', 'afx_head_width', 'afx_set_workspace', 'afx_mmdit_forward', 'afx_profile_enable', 'afx_profile_read', 'afx_set_checkpoint_buffer', 'afx_arcflow_step',
     'afx_arcflow_velocity', 'afx_linear_bf16', 'afx_attention_ws_bytes', 'afx_attention_bf16', 'afx_attention_to_mx8',
     'afx_norm_modulate_bf16', 'afx_qk_norm_rope_bf16', 'afx_gemv_bf16',
     'afx_attention_fwd_lse_bf16', 'afx_attention_bwd_ws_bytes', 'afx_attention_bwd_bf16',
@@ -26,7 +26,7 @@ EXPORTS = [
     'afx_latent_to_nhwc', 'afx_nhwc_to_image', 'afx_latent_to_nhwc_affine', 'afx_rmsnorm_nhwc',
     'afx_embed_rows_bf16', 'afx_norm_rows_bf16', 'afx_act_mul_bf16', 'afx_rope_half_bf16', 'afx_attention_ext_ws_bytes',
     'afx_attention_ext_bf16', 'afx_linear_bf16_splitk', 'afx_finish_f32_bf16', 'afx_linear_splitk_chunks', 'afx_quant_rows_fp8', 'afx_linear_fp8', 'afx_quant_rows_mx8', 'afx_linear_fp8_mx', 'afx_linear_fp8_to_mx8',
-    'afx_linear_bf16_pre', 'afx_gemm_set_mode', 'afx_gemm_dropres_available', 'afx_attn_set_impl', 'afx_attn_bwd_set_impl', 'afx_mmdit_prepare_steps', 'afx_mmdit_use_prepared_step', 'afx_lora_dropout_bf16', 'afx_mmdit_forward_stage', 'afx_mmdit_import_tokens',
+    'afx_linear_bf16_pre', 'afx_gemm_set_mode', 'afx_gemm_set_fp8_tile', 'afx_gemm_dropres_available', 'afx_attn_set_impl', 'afx_attn_bwd_set_impl', 'afx_mmdit_prepare_steps', 'afx_mmdit_use_prepared_step', 'afx_lora_dropout_bf16', 'afx_mmdit_forward_stage', 'afx_mmdit_import_tokens',
     'afx_coldot_bf16', 'afx_gate_residual_bf16', 'afx_gemv_t_bf16', 'afx_set_temb_override', 'afx_set_fp8_linear',
     'afx_arcflow_step_dropout', 'afx_arcflow_backward', 'afx_mse_loss', 'afx_euler_roll', 'afx_axpby_rows', 'afx_cfg_combine',
     'afx_head_grad', 'afx_linear_bf16_f32out', 'afx_linear_tn_f32out', 'afx_linear_tn_f32out_ws', 'afx_linear_tn_ws_bytes', 'afx_linear_bf16_dropres', 'afx_transpose_bf16', 'afx_colsum_bf16', 'afx_normout_backward', 'afx_normout_backward_split',
@@ -71,6 +71,8 @@ def load() -> C.CDLL:
     lib.afx_finalize.argtypes = [vp]
     lib.afx_workspace_bytes.argtypes = [vp, i32, i32, i32]
     lib.afx_workspace_bytes.restype = i64
+    lib.afx_head_width.argtypes = [vp]
+    lib.afx_head_width.restype = i32
     lib.afx_set_workspace.argtypes = [vp, vp, i64]
     lib.afx_mmdit_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.afx_set_checkpoint_buffer.argtypes = [vp, vp]
@@ -126,6 +128,8 @@ def load() -> C.CDLL:
     lib.afx_mmdit_use_prepared_step.argtypes = [vp, i32]
     lib.afx_gemm_set_mode.argtypes = [i32, i32]
     lib.afx_gemm_set_mode.restype = i32
+    lib.afx_gemm_set_fp8_tile.argtypes = [i32]
+    lib.afx_gemm_set_fp8_tile.restype = i32
     lib.afx_gemm_dropres_available.argtypes = []
     lib.afx_gemm_dropres_available.restype = i32
     lib.afx_attn_set_impl.argtypes = [i32]

@@ -459,6 +459,11 @@ int64_t afx_workspace_bytes(const afx_ctx* ctx, int32_t batch, int32_t n_img, in
   return carve(ctx, nullptr, batch, n_img, n_txt).total;
 }
 
+int afx_head_width(const afx_ctx* ctx) {
+  if (!ctx) return fail(AFX_E_INVALID, "afx_head_width: null ctx");
+  return ctx->head_n;
+}
+
 int afx_set_workspace(afx_ctx* ctx, void* dptr, int64_t bytes) {
   if (!ctx || !dptr || bytes <= 0) return fail(AFX_E_INVALID, "bad workspace");
   if (((uintptr_t)dptr & 255) != 0) return fail(AFX_E_INVALID, "workspace must be 256-byte aligned");
@@ -1063,6 +1068,7 @@ int afx_gemm_set_mode(int32_t impl, int32_t tile) {
   gemm_set_mode(impl, tile);
   return 0;
 }
+int afx_gemm_set_fp8_tile(int32_t tile) { return gemm_set_fp8_tile(tile); }
 int afx_attn_set_impl(int32_t impl) {
   attn_set_impl(impl);
   return 0;

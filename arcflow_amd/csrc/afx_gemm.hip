@@ -1864,7 +1864,7 @@ template __global__ void gemm_kernel_v3f8<V3F8_ONLY>(const GemmBatch);
 //   AFX_FP8_V3=0        fp8 launches on the 8-phase kernel (A/B);  AFX_FP8_V3_MIN: fewest 256x256 tiles of a launch for the fp8 v3 kernel;
 //   AFX_FP8_TILE        1 / 2 force its 256x256 / 224x256 shape
 //   AFX_GEMM_GROUP_M    tile-order super-row height;  AFX_GEMM_PEN224 / AFX_GEMM_PEN_QK224: cost factors of the 256x224 / 224x256 shapes (1e9 = never)
-// afx_gemm_set_mode() overrides impl and tile (parity tests, A/B runs).
+// afx_gemm_set_mode() overrides impl and tile, afx_gemm_set_fp8_tile() fp8_tile (parity tests, A/B runs).
 struct GemmMode {
   int impl = 3, tile = 0;
   bool qk_fuse = true, fp8_v3 = true;
@@ -1898,6 +1898,10 @@ bool gemm_dropres_available() {                         // launch_gemm would tak
 void gemm_set_mode(int impl, int tile) {
   gemm_mode().impl = impl == 2 ? 2 : 3;
   gemm_mode().tile = (tile >= 0 && tile <= 6) ? tile : 0;
+}
+int gemm_set_fp8_tile(int tile) {
+  gemm_mode().fp8_tile = (tile >= 0 && tile <= 2) ? tile : 0;
+  return gemm_mode().fp8_tile;
 }
 struct TileCfg { int tm, tn, group_m; };
 // {4,4} = 128x128: 64 accumulators and 80 KiB of LDS, TWO work-groups per CU -- for launches that would leave most CUs without a

@@ -93,6 +93,7 @@ bool gemm_conv_stats_available();           // GemmProblem::gn_stats is honoured
 bool gemm_qk_fusion_available();            // the launcher would take a problem with qk_D > 0 (kernel mode 3, AFX_QK_FUSE not 0)
 bool gemm_dropres_available();              // ... a problem with drop_on (the LoRA branch's masked residual add in the epilogue)
 void gemm_set_mode(int impl, int tile);      // kernel / tile-shape override of AFX_GEMM_IMPL / AFX_GEMM_TILE (see launch_gemm)
+int gemm_set_fp8_tile(int tile);             // ... of AFX_FP8_TILE (0 = per launch, 1 = 256x256, 2 = 224x256; else 0); returns the value in force
 constexpr int GN_SLOTS = 64;
 
 // Optional per-launch timing without extra queue packets: when both are non-null, the NEXT launch_gemm / launch_attention issues

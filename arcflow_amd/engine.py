@@ -135,6 +135,14 @@ class MMDiTEngine:
         _lib.check(self.lib.afx_set_checkpoint_buffer(self._ctx, _ptr(buf)))
 
     @property
+    def head_n(self) -> int:
+        """N of the head GEMM (afx_head_width): the stacked ArcFlow heads padded to a multiple of 8."""
+        n = self.lib.afx_head_width(self._ctx)
+        if n < 0:
+            _lib.check(n)
+        return n
+
+    @property
     def n_mod(self) -> int:
         return (self.num_double * 12 + self.num_single * 3 + 2) * self.dim
 

@@ -100,6 +100,12 @@ def set_gemm_mode(impl: int = 3, tile: int = 0) -> None:
     _lib.check(_lib.load().afx_gemm_set_mode(impl, tile))
 
 
+def set_fp8_tile(tile: int = 0) -> int:
+    """Tile shape of the one-wave-per-SIMD fp8 GEMM (``afx_gemm_set_fp8_tile``): 0 = picked per launch, 1 = 256x256, 2 = 224x256 (any other
+    value: 0).  Returns the setting now in force."""
+    return _lib.load().afx_gemm_set_fp8_tile(tile)
+
+
 def set_attn_impl(impl: int = 0) -> None:
     """Kernel choice of the joint attention (``afx_attn_set_impl``): 0 = one-wave-per-SIMD kernel where eligible, the blocks of an under-filled
     last round KV-split (default), 1 = 4-wave kernel always, 3 = as 0 on the plain grid (any other value: 0)."""
@@ -136,16 +142,22 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor
     return o.reshape(B, S, H * Dh)
 
 
-def attention_to_mx8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
-    """``attention`` with the output as a block-scaled fp8 operand: (uint8 [B*S, H*128] e4m3, uint8 [B*S, H] E8M0 -- one scale per token and head)."""
+def attention_to_mx8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out=None):
+    """``attention`` with the output as a block-scaled fp8 operand: (uint8 [B*S, H*128] e4m3, uint8 [B*S, H] E8M0 -- one scale per token and head).
+    out: (o8, mx) row-strided views to write into (row strides multiples of 16 / 4)."""
     lib = _lib.load()
     B, S, H, Dh = q.shape
     assert Dh == 128 and q.dtype == torch.bfloat16
     q2, k2, v2 = (t.reshape(B * S, H * Dh) for t in (q.contiguous(), k.contiguous(), v.contiguous()))
-    o8 = torch.empty(B * S, H * Dh, dtype=torch.uint8, device=q.device)
-    mx = torch.empty(B * S, (H + 3) // 4 * 4, dtype=torch.uint8, device=q.device)
+    if out is None:
+        o8 = torch.empty(B * S, H * Dh, dtype=torch.uint8, device=q.device)
+        mx = torch.empty(B * S, (H + 3) // 4 * 4, dtype=torch.uint8, device=q.device)
+    else:
+        o8, mx = out
+        assert o8.shape == (B * S, H * Dh) and mx.shape[0] == B * S and mx.shape[1] >= H and o8.dtype == mx.dtype == torch.uint8
+        assert o8.stride(1) == 1 and mx.stride(1) == 1 and o8.stride(0) % 16 == 0 and mx.stride(0) % 4 == 0
     ws = torch.empty(lib.afx_attention_ws_bytes(B, H, S), dtype=torch.uint8, device=q.device)
-    _lib.check(lib.afx_attention_to_mx8(_p(q2), H * Dh, _p(k2), H * Dh, _p(v2), H * Dh, _p(o8), H * Dh, _p(mx), mx.stride(0), _p(ws), B, H, S, _s()))
+    _lib.check(lib.afx_attention_to_mx8(_p(q2), H * Dh, _p(k2), H * Dh, _p(v2), H * Dh, _p(o8), o8.stride(0), _p(mx), mx.stride(0), _p(ws), B, H, S, _s()))
     return o8, mx[:, :H]
 
 
@@ -543,21 +555,29 @@ def linear_fp8_mx(aq, a_mx, wq, w_scale, bias=None, epilogue: str = 'none', gelu
     return out
 
 
-def linear_fp8_to_mx8(aq, a_mx, wq, w_scale, bias=None, gelu: bool = False, c8_col0: int = 0, a_scale=None):
+def linear_fp8_to_mx8(aq, a_mx, wq, w_scale, bias=None, gelu: bool = False, c8_col0: int = 0, a_scale=None, out=None):
     """The fp8 GEMM whose epilogue writes the next GEMM's block-scaled operand: returns (bf16 [M, c8_col0] or None, q uint8 [M, N - c8_col0],
-    mx uint8 [M, (N - c8_col0) / 128]).  a_mx None: per-row ``a_scale`` only."""
+    mx uint8 [M, (N - c8_col0) / 128]).  a_mx None: per-row ``a_scale`` only.  out: (head or None, q, mx) row-strided views to write into
+    (q's row stride a multiple of 8, mx's of 4)."""
     lib = _lib.load()
     M, K = aq.shape
     N = wq.shape[0]
     n8 = N - c8_col0
     nb = (n8 + 127) // 128
-    head = torch.empty(M, c8_col0, dtype=torch.bfloat16, device=aq.device) if c8_col0 > 0 else None
-    q = torch.empty(M, n8, dtype=torch.uint8, device=aq.device)
-    mx = torch.empty(M, (nb + 3) // 4 * 4, dtype=torch.uint8, device=aq.device)
+    if out is None:
+        head = torch.empty(M, c8_col0, dtype=torch.bfloat16, device=aq.device) if c8_col0 > 0 else None
+        q = torch.empty(M, n8, dtype=torch.uint8, device=aq.device)
+        mx = torch.empty(M, (nb + 3) // 4 * 4, dtype=torch.uint8, device=aq.device)
+    else:
+        head, q, mx = out
+        assert (head is None) == (c8_col0 == 0) and (head is None or (head.shape == (M, c8_col0) and head.dtype == torch.bfloat16))
+        assert q.shape == (M, n8) and q.dtype == torch.uint8 and mx.shape[0] == M and mx.shape[1] >= nb and mx.dtype == torch.uint8
+        assert q.stride(1) == 1 and mx.stride(1) == 1 and q.stride(0) % 8 == 0 and mx.stride(0) % 4 == 0
+        assert head is None or (head.stride(1) == 1 and head.stride(0) % 8 == 0)
     if a_scale is None:
         a_scale = torch.ones(M, dtype=torch.float32, device=aq.device)
     _lib.check(lib.afx_linear_fp8_to_mx8(_p(aq), aq.stride(0), _p(a_mx), 0 if a_mx is None else a_mx.stride(0), _p(a_scale), _p(wq), wq.stride(0),
-                                         _p(w_scale), _p(bias), _p(head), c8_col0 if head is not None else 8, _p(q), n8, _p(mx), mx.stride(0),
+                                         _p(w_scale), _p(bias), _p(head), head.stride(0) if head is not None else 8, _p(q), q.stride(0), _p(mx), mx.stride(0),
                                          c8_col0, M, N, K, int(gelu), _s()))
     return head, q, mx[:, :nb]
 

@@ -86,6 +86,9 @@ int afx_bind_weight(afx_ctx* ctx, const char* name, const void* dptr, int32_t dt
 /* Verify every weight the description requires is bound with the right shape. */
 int afx_finalize(afx_ctx* ctx);
 
+/* Output width of the head GEMM (the stacked ArcFlow heads, padded to a multiple of 8): the N of its launch and the rows of "head.weight". */
+int afx_head_width(const afx_ctx* ctx);
+
 /* Scratch memory: size for the largest (batch, image tokens, text tokens) the ctx will see. */
 int64_t afx_workspace_bytes(const afx_ctx* ctx, int32_t batch, int32_t n_img, int32_t n_txt);
 int afx_set_workspace(afx_ctx* ctx, void* dptr, int64_t bytes);
@@ -417,6 +420,10 @@ int afx_linear_bf16_pre(const void* A, int64_t lda, const void* W, int64_t ldw, 
  * 2: 288x192, 3: 320x192, 4: 128x128, 5: 256x224, 6: 224x256); impl 2 = 8-phase 256x256 kernel for everything; any other impl selects 3.  Same meaning
  * as the AFX_GEMM_IMPL / AFX_GEMM_TILE environment variables (read once, on first use), which it overrides.  Returns 0. */
 int afx_gemm_set_mode(int32_t impl, int32_t tile);
+/* Tile shape of the one-wave-per-SIMD fp8 GEMM kernel (process-wide, like afx_gemm_set_mode): 0 (default) = picked per launch, 1 = 256x256,
+ * 2 = 224x256 (launches with the fused q / k epilogue keep 256x256); any other value selects 0.  Same meaning as the AFX_FP8_TILE environment
+ * variable, which it overrides.  Returns the setting now in force (0, 1 or 2).  Host-side, no GPU needed. */
+int afx_gemm_set_fp8_tile(int32_t tile);
 /* 1 when afx_linear_bf16_dropres can run under the current kernel choice (its masked residual add lives in the one-wave-per-SIMD kernel's epilogue: kernel
  * mode 3), 0 otherwise -- the caller then computes the product with afx_linear_bf16 and masks + adds it with afx_lora_dropout_bf16 mode 3
  * (arcflow_amd/ops.py linear_dropres does).  Host-side, no GPU needed. */

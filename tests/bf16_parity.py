@@ -1,4 +1,7 @@
-"""Shared checks of the fp64 parity tests (test_hip_train_kernels.py, test_text_encoders.py): bf16 outputs against an fp64 reference."""
+"""Shared checks of the fp64 parity tests (test_hip_train_kernels.py, test_text_encoders.py, test_hip_forward_operands.py, test_hip_gemm_fp64.py,
+test_hip_attention_fp64.py): bf16 / fp32 outputs against an fp64 reference, and the fp64 GEMM reference with its fp32 summation bound."""
+import math
+
 import torch
 
 U32 = 2.0 ** -24
@@ -20,3 +23,31 @@ def check_bf16(out, ref, floor=0.0, min_equal=0.99, what=''):
                              f'ref {ref.flatten()[i].item()} tol {torch.as_tensor(tol).expand_as(err).flatten()[i].item():.3e}')
     eq = (out == ref.float().bfloat16()).double().mean().item()
     assert eq >= min_equal, f'{what}: only {eq:.4f} of the elements equal the fp64 reference rounded to nearest even (need {min_equal})'
+
+
+def check_f32(out, ref, bound, what=''):
+    """out (fp32) against ref (fp64): per-element |out - ref| <= bound."""
+    ref = ref.double()
+    err = (out.double() - ref).abs()
+    bound = torch.as_tensor(bound, dtype=torch.float64, device=err.device).expand_as(err)
+    bad = err > bound
+    if bool(bad.any()):
+        i = int((err - bound).flatten().argmax())
+        raise AssertionError(f'{what}: {int(bad.sum())} of {err.numel()} elements beyond the bound; worst out {out.flatten()[i].item()} '
+                             f'ref {ref.flatten()[i].item()} bound {bound.flatten()[i].item():.3e}')
+
+
+def proj64(a, w, b, kstep=32):
+    """a @ w.T + b in fp64 and the fp32 summation bound of the GEMM's accumulation: one rounding per MFMA K-step into the accumulator plus a
+    serial chain over one instruction's kstep products, + 1 for the bias (depth K / kstep + kstep + 1).  kstep 32: the bf16 kernels
+    (v_mfma_f32_16x16x32_bf16); 128: the fp8 kernels (v_mfma_f32_16x16x128_f8f6f4)."""
+    ad, wd = a.double(), w.double()
+    y, mag = ad @ wd.T, ad.abs() @ wd.abs().T
+    if b is not None:
+        y += b.double()
+        mag += b.double().abs()
+    return y, (a.shape[1] // kstep + kstep + 1) * U32 * mag
+
+
+def gelu64(x):
+    return x * torch.sigmoid(2 * math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3))

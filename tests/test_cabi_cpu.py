@@ -72,6 +72,36 @@ def test_argument_validation_no_gpu(lib):
     assert lib.afx_destroy(ctx) == 0
 
 
+def test_head_width_query(lib):
+    """afx_head_width: K C + K L + (K - 1) L rounded up to 8 -- the N of the head GEMM (host-side, no GPU needed)."""
+    from arcflow_amd import _lib
+    desc = _lib.ModelDesc(0, 1, 1, 2, 128, 64, 128, 64, 1, 16, 4, 0)
+    ctx = C.c_void_p()
+    assert lib.afx_create(C.byref(desc), C.byref(ctx)) == 0
+    try:
+        assert lib.afx_head_width(ctx) == (16 * 64 + 16 * 4 + 15 * 4 + 7) // 8 * 8 == 1152
+    finally:
+        assert lib.afx_destroy(ctx) == 0
+    desc = _lib.ModelDesc(0, 1, 1, 2, 128, 128, 128, 64, 1, 5, 3, 0)
+    assert lib.afx_create(C.byref(desc), C.byref(ctx)) == 0
+    try:
+        assert lib.afx_head_width(ctx) == (5 * 128 + 5 * 3 + 4 * 3 + 7) // 8 * 8 == 672
+    finally:
+        assert lib.afx_destroy(ctx) == 0
+    assert lib.afx_head_width(None) == -1
+
+
+def test_fp8_tile_setter_clamps_to_per_launch_choice(lib):
+    """afx_gemm_set_fp8_tile: 0 / 1 / 2 are taken as given, any other value selects 0 (picked per launch); host-side state only."""
+    from arcflow_amd import ops
+    try:
+        for want, got in ((1, 1), (2, 2), (0, 0), (3, 0), (-1, 0), (2, 2), (7, 0), (1 << 20, 0)):
+            assert lib.afx_gemm_set_fp8_tile(want) == got, want
+        assert ops.set_fp8_tile(2) == 2 and ops.set_fp8_tile(5) == 0
+    finally:
+        lib.afx_gemm_set_fp8_tile(0)
+
+
 def test_forward_operand_entry_points_validate_before_launch(lib):
     """afx_qkv_operands / afx_norm_modulate_joint_bf16 / afx_norm_modulate_mx8 refuse bad arguments with AFX_E_INVALID before anything
     touches the device (fake but aligned pointers: a launch would fault)."""

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import pytest
 import torch
-from bf16_parity import U32, bf16_ulp, check_bf16
+from bf16_parity import U32, bf16_ulp, check_bf16, gelu64 as _gelu64, proj64 as _proj64
 
 pytestmark = pytest.mark.gpu
 
@@ -42,16 +42,6 @@ def _key_of_pos(n):
     return (p & ~15) + 4 * (j >> 3) + (j & 3) + 8 * ((j >> 2) & 1)
 
 
-def _proj64(a, w, b):
-    """a @ w.T + b in fp64 and the fp32 summation bound of the GEMM's accumulation."""
-    ad, wd = a.double(), w.double()
-    y, mag = ad @ wd.T, ad.abs() @ wd.abs().T
-    if b is not None:
-        y += b.double()
-        mag += b.double().abs()
-    return y, (a.shape[1] // 32 + 33) * U32 * mag
-
-
 def _qk64(y, e, w_rows, pos, cos, sin, round_first):
     """RoPE(RMSNorm_128(y) * w) per head in fp64 and its floor.  round_first (kv_prep): the kernel normalises its bf16-rounded projection,
     which may sit one bf16 ulp from RNE of the exact one: that ulp joins the input error."""
@@ -68,10 +58,6 @@ def _qk64(y, e, w_rows, pos, cos, sin, round_first):
     out = torch.stack([a_ * c - b_ * s, a_ * s + b_ * c], -1).flatten(-2)
     floor = 4 * rstd * wr.abs().amax(-1, keepdim=True) * eh.amax(-1, keepdim=True) + U32 * 128 * n.abs().amax(-1, keepdim=True)
     return out.reshape(R, D), floor.expand(R, H, 128).reshape(R, D)
-
-
-def _gelu64(x):
-    return x * torch.sigmoid(2 * math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3))
 
 
 def _vt_ref(v, B, S):
