@@ -24,6 +24,7 @@ EXPORTS = [
     'afx_ln_modulate_backward', 'afx_qk_norm_rope_oop_bf16', 'afx_gelu_bf16', 'afx_add_scale_bf16',
     'afx_conv3x3_bf16', 'afx_conv3x3_bf16_stats', 'afx_groupnorm_nhwc_from_stats', 'afx_conv_stats_available', 'afx_upconv3x3_bf16', 'afx_groupnorm_nhwc', 'afx_groupnorm_ws_bytes', 'afx_upsample2x_nhwc', 'afx_interior_nhwc', 'afx_softmax_rows_f32',
     'afx_latent_to_nhwc', 'afx_nhwc_to_image', 'afx_latent_to_nhwc_affine', 'afx_rmsnorm_nhwc',
+    'afx_conv3x3s2_bf16', 'afx_image_to_cols27', 'afx_posterior_latents',
     'afx_embed_rows_bf16', 'afx_norm_rows_bf16', 'afx_act_mul_bf16', 'afx_rope_half_bf16', 'afx_attention_ext_ws_bytes',
     'afx_attention_ext_bf16', 'afx_linear_bf16_splitk', 'afx_finish_f32_bf16', 'afx_linear_splitk_chunks', 'afx_quant_rows_fp8', 'afx_linear_fp8', 'afx_quant_rows_mx8', 'afx_linear_fp8_mx', 'afx_linear_fp8_to_mx8',
     'afx_linear_bf16_pre', 'afx_gemm_set_mode', 'afx_gemm_set_fp8_tile', 'afx_gemm_dropres_available', 'afx_attn_set_impl', 'afx_attn_bwd_set_impl', 'afx_mmdit_prepare_steps', 'afx_mmdit_use_prepared_step', 'afx_lora_dropout_bf16', 'afx_mmdit_forward_stage', 'afx_mmdit_import_tokens',
@@ -111,6 +112,9 @@ def load() -> C.CDLL:
     lib.afx_nhwc_to_image.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.afx_latent_to_nhwc_affine.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.afx_rmsnorm_nhwc.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp]
+    lib.afx_conv3x3s2_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]
+    lib.afx_image_to_cols27.argtypes = [vp, i32, vp, i32, i32, i32, vp]
+    lib.afx_posterior_latents.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp]
     lib.afx_embed_rows_bf16.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     lib.afx_norm_rows_bf16.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp, f32, i32, vp]
     lib.afx_act_mul_bf16.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, vp]

@@ -325,6 +325,95 @@ __global__ __launch_bounds__(256) void nhwc_to_image_kernel(const bf16_t* __rest
   img[g] = bf16_to_f32(x[((int64_t)(h + 1) * (W + 2) + (w + 1)) * C + ch]);
 }
 
+// ---- encoder side (images -> latents) ----------------------------------------------------------------------------------
+// space to depth between zero-bordered grids: y[(Y+1), (X+1)][(2 py + px) * C + c] = x[(2Y + py + 1), (2X + px + 1)][c], border of y zero.
+// One 16-byte chunk per thread.  The stride-2 convolution reads y with stride 1 (afx_conv3x3s2_bf16).
+__global__ __launch_bounds__(256) void space_to_depth_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int H, int W, int C) {
+  const int cpr = C >> 3;
+  const int Ho = H / 2 + 2, Wo = W / 2 + 2;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)Ho * Wo * 4 * cpr) return;
+  const int c = (int)(g % cpr);
+  const int ph = (int)((g / cpr) & 3);
+  const int64_t p = g / (4 * cpr);
+  const int yo = (int)(p / Wo), xo = (int)(p % Wo);
+  u32x4_t v = (u32x4_t){0u, 0u, 0u, 0u};
+  if (yo >= 1 && yo <= H / 2 && xo >= 1 && xo <= W / 2) {
+    const int yi = 2 * (yo - 1) + (ph >> 1) + 1, xi = 2 * (xo - 1) + (ph & 1) + 1;
+    v = *reinterpret_cast<const u32x4_t*>(x + ((int64_t)yi * (W + 2) + xi) * C + c * 8);
+  }
+  *reinterpret_cast<u32x4_t*>(y + (p * 4 + ph) * C + c * 8) = v;
+}
+
+// image [3][H][W] (fp32 or bf16; from01: values in [0, 1], mapped to 2 v - 1 first) -> zero-bordered grid [(H+2)*(W+2), 64] bf16 whose interior
+// rows hold the pixel's 3x3x3 neighbourhood, k = (3 dy + dx) * 3 + channel (zero outside the image), k = 27 a constant 1 (multiplies the bias
+// column of the re-laid conv_in weight), k > 27 zero.  Border rows are all zero, so the K = 64 GEMM that follows writes a zero border.
+template <typename T>
+__global__ __launch_bounds__(256) void image_to_cols27_kernel(const T* __restrict__ img, bf16_t* __restrict__ y, int H, int W, int from01) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)(H + 2) * (W + 2) * 8) return;
+  const int j = (int)(g & 7);
+  const int64_t p = g >> 3;
+  const int yy = (int)(p / (W + 2)), xx = (int)(p % (W + 2));
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  if (yy >= 1 && yy <= H && xx >= 1 && xx <= W) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int k = j * 8 + e;
+      if (k < 27) {
+        const int tap = k / 3, ch = k - 3 * tap;
+        const int sy = yy - 1 + tap / 3 - 1, sx = xx - 1 + tap % 3 - 1;
+        if (sy >= 0 && sy < H && sx >= 0 && sx < W) {
+          float v;
+          if constexpr (sizeof(T) == 2) v = bf16_to_f32(img[((int64_t)ch * H + sy) * W + sx]);
+          else v = img[((int64_t)ch * H + sy) * W + sx];
+          o[e] = from01 ? v * 2.0f - 1.0f : v;
+        }
+      } else if (k == 27) {
+        o[e] = 1.0f;
+      }
+    }
+  }
+  *reinterpret_cast<u32x4_t*>(y + p * 64 + j * 8) = pack8(o);
+}
+
+// Posterior of the encoder -> latents.  g: zero-bordered grid [(h+2)*(w+2), Cpad] bf16 whose first 32 channels are conv_out's output;
+// A / b (optional): the 1x1 quant_conv as an fp32 affine map [32][32] / [32] on them.  Moments (mean | logvar clamped to [-30, 20]) go to
+// mom [32][h][w]; z = mean + exp(logvar / 2) * eps (eps [16][h][w], null: z = mean); out = (z - sub[c]) * fac[c] or / fac[c], written as
+// [16][h][w] or as packed tokens [(h/2)*(w/2)][64], channel c * 4 + (y & 1) * 2 + (x & 1) (the inverse of latent_to_nhwc_kernel).
+__global__ __launch_bounds__(256) void posterior_kernel(const bf16_t* __restrict__ g, int Cpad, int h, int w, const float* __restrict__ A,
+                                                        const float* __restrict__ b, const float* __restrict__ eps,
+                                                        const float* __restrict__ sub, const float* __restrict__ fac, int divide,
+                                                        float* __restrict__ out, int packed, float* __restrict__ mom) {
+  const int hw = h * w;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= 16 * hw) return;
+  const int c = idx / hw, p = idx - c * hw;
+  const int y = p / w, x = p - y * w;
+  const bf16_t* row = g + ((int64_t)(y + 1) * (w + 2) + (x + 1)) * Cpad;
+  float mean, lv;
+  if (A != nullptr) {
+    mean = b[c]; lv = b[16 + c];
+    for (int k = 0; k < 32; ++k) {
+      const float v = bf16_to_f32(row[k]);
+      mean += A[c * 32 + k] * v;
+      lv += A[(16 + c) * 32 + k] * v;
+    }
+  } else {
+    mean = bf16_to_f32(row[c]); lv = bf16_to_f32(row[16 + c]);
+  }
+  lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+  mom[idx] = mean;
+  mom[16 * hw + idx] = lv;
+  float z = mean;
+  if (eps != nullptr) z = mean + expf(0.5f * lv) * eps[idx];
+  const float o = divide ? (z - sub[c]) / fac[c] : (z - sub[c]) * fac[c];
+  if (packed) out[((int64_t)(y >> 1) * (w >> 1) + (x >> 1)) * 64 + c * 4 + (y & 1) * 2 + (x & 1)] = o;
+  else out[idx] = o;
+}
+
 }  // namespace afx
 
 using namespace afx;
@@ -396,6 +485,40 @@ int afx_upconv3x3_bf16(const void* x, const void* w4, const void* bias, void* y,
 }
 
 int afx_conv_stats_available(void) { return gemm_conv_stats_available() ? 1 : 0; }
+
+int afx_conv3x3s2_bf16(const void* x, const void* w, const void* bias, void* y, void* ws, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                       double* gn_stats, int32_t groups, void* stream) {
+  // y = conv3x3(pad(x, right and bottom by 1), stride 2) + bias: space-to-depth of x into ws (a zero-bordered [(H/2+2)*(W/2+2), 4 Cin] grid with the
+  // guard rows of afx_conv3x3_bf16), then the stride-1 implicit GEMM on ws with the weight re-laid by arcflow_amd.vae.s2d_weights
+  // ([Cout][9][4 Cin]: source rows 2y, 2y+1 are phases 0, 1 of cell y, row 2y+2 phase 0 of cell y+1; the pad row / column is ws's zero border).
+  if (!x || !w || !y || !ws || H < 2 || W < 2 || (H & 1) || (W & 1) || Cin < 64 || Cin % 64 || Cout < 8 || Cout % 8)
+    return fail(AFX_E_INVALID, "afx_conv3x3s2_bf16: need even H, W >= 2, Cin %% 64 == 0, Cout %% 8 == 0 and a workspace grid");
+  if ((int64_t)(H / 2 + 2) * (W / 2 + 2) * 4 * Cin * 2 >= (1ll << 31)) return fail(AFX_E_INVALID, "afx_conv3x3s2_bf16: workspace grid >= 2 GiB");
+  hipLaunchKernelGGL(space_to_depth_kernel, dim3(vblocks((int64_t)(H / 2 + 2) * (W / 2 + 2) * 4 * (Cin >> 3))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)ws, H, W, Cin);
+  HIP_TRY(hipGetLastError());
+  return conv3x3_impl(ws, w, bias, y, H / 2, W / 2, 4 * Cin, Cout, nullptr, gn_stats, groups, stream);
+}
+
+int afx_image_to_cols27(const void* img, int32_t img_bf16, void* y, int32_t H, int32_t W, int32_t from01, void* stream) {
+  if (!img || !y || H < 1 || W < 1 || (int64_t)(H + 2) * (W + 2) * 64 * 2 >= (1ll << 31)) return fail(AFX_E_INVALID, "bad argument to afx_image_to_cols27");
+  const dim3 grid(vblocks((int64_t)(H + 2) * (W + 2) * 8)), blk(256);
+  if (img_bf16) hipLaunchKernelGGL(image_to_cols27_kernel<bf16_t>, grid, blk, 0, (hipStream_t)stream, (const bf16_t*)img, (bf16_t*)y, H, W, from01);
+  else hipLaunchKernelGGL(image_to_cols27_kernel<float>, grid, blk, 0, (hipStream_t)stream, (const float*)img, (bf16_t*)y, H, W, from01);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_posterior_latents(const void* grid, int32_t Cpad, int32_t h, int32_t w, const float* A, const float* b, const float* eps, const float* sub,
+                          const float* fac, int32_t divide, float* out, int32_t packed, float* moments, void* stream) {
+  if (!grid || !sub || !fac || !out || !moments || Cpad < 32 || h < 1 || w < 1 || (A == nullptr) != (b == nullptr) || (packed && ((h & 1) || (w & 1))) ||
+      (int64_t)h * w * 32 >= (1ll << 31))
+    return fail(AFX_E_INVALID, "afx_posterior_latents: need Cpad >= 32, A and b together, even h, w for the packed layout");
+  hipLaunchKernelGGL(posterior_kernel, dim3(vblocks((int64_t)16 * h * w)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)grid, Cpad, h, w, A, b, eps,
+                     sub, fac, divide, out, packed, moments);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
 
 
 int64_t afx_groupnorm_ws_bytes(int32_t C, int32_t groups) {

@@ -206,6 +206,11 @@ class ArcFluxPipeline(_PipelineBase):
             pipe.vae = AutoencoderKLDecoder(vsd, tuple(vcfg.get('block_out_channels', (128, 256, 512, 512))),
                                             vcfg.get('norm_num_groups', 32), vcfg.get('layers_per_block', 2),
                                             vcfg.get('scaling_factor', 0.3611), vcfg.get('shift_factor', 0.1159))
+            if any(k.startswith('encoder.') for k in vsd):     # full VAE snapshot: pipe.vae.encode(...) as on the reference's PretrainedVAE
+                from ..vae import AutoencoderKLEncoder
+                pipe.vae.encoder = AutoencoderKLEncoder(vsd, tuple(vcfg.get('block_out_channels', (128, 256, 512, 512))),
+                                                        vcfg.get('norm_num_groups', 32), vcfg.get('layers_per_block', 2),
+                                                        vcfg.get('scaling_factor', 0.3611), vcfg.get('shift_factor', 0.1159))
         if os.path.isdir(os.path.join(root, 'text_encoder')) and os.path.isdir(os.path.join(root, 'text_encoder_2')):
             from ..text_encoders import load_clip_text_encoder, load_t5_encoder       # prompt encoders on the HIP engine
             pipe.text_encoder = load_clip_text_encoder(os.path.join(root, 'text_encoder'))

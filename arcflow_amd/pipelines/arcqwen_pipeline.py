@@ -55,6 +55,11 @@ class ArcQwenImagePipeline(_PipelineBase):
             pipe.vae = AutoencoderKLQwenImageDecoder(vsd, vcfg['latents_mean'], vcfg['latents_std'],
                                                      tuple(vcfg.get('dim_mult', (1, 2, 4, 4))), vcfg.get('num_res_blocks', 2),
                                                      vcfg.get('z_dim', 16))
+            if any(k.startswith('encoder.') for k in vsd):     # full VAE snapshot: pipe.vae.encode(...) as on the reference's PretrainedVAEQwenImage
+                from ..vae import AutoencoderKLQwenImageEncoder
+                pipe.vae.encoder = AutoencoderKLQwenImageEncoder(vsd, vcfg['latents_mean'], vcfg['latents_std'], vcfg.get('base_dim'),
+                                                                 tuple(vcfg.get('dim_mult', (1, 2, 4, 4))), vcfg.get('num_res_blocks', 2),
+                                                                 tuple(vcfg.get('temperal_downsample', (False, True, True))), vcfg.get('z_dim', 16))
         if os.path.isdir(os.path.join(root, 'text_encoder')) and os.path.isdir(os.path.join(root, 'tokenizer')):
             from ..text_encoders import load_qwen25_text_encoder
             pipe.text_encoder = load_qwen25_text_encoder(os.path.join(root, 'text_encoder'))

@@ -128,14 +128,18 @@ class PromptEmbedCache:
 
     def __init__(self, cache_dir: str, datalist: Optional[Sequence[str]] = None, pad_seq_len: Optional[int] = None,
                  latent_size=(16, 128, 128), bucketize: bool = False, negative_prompt_embeds_path: Optional[str] = None,
-                 size_index: Optional[str] = None):
-        """negative_prompt_embeds_path: a torch.load-able dict of the NEGATIVE prompt's embeddings (same keys / legacy keys as an
+                 size_index: Optional[str] = None, load_latents: bool = False):
+        """load_latents (default off: items are unchanged): an item whose record carries ``latents`` (tools/cache_latents.py, or the
+        reference's own caches) also returns them as fp32 ``latents``, times ``latents_scale`` when the record has one
+        (image_prompts.py:373-383); a record without them raises.
+        negative_prompt_embeds_path: a torch.load-able dict of the NEGATIVE prompt's embeddings (same keys / legacy keys as an
         item), attached to every item as ``negative_prompt_embed_kwargs`` -- the reference's option of the same name
         (image_prompts.py:57-60,158-163,432), needed whenever the teacher runs true classifier-free guidance (Qwen config).
         size_index: JSON file {file name: [C, H, W]} with the latent size of every item.  ``bucketize`` needs the sizes up front;
         without an index it unpickles every cache file once (fine for thousands of items, hours for the reference's 3 M) and
         writes ``latent_sizes.json`` next to the cache so the next start is instant."""
         self.cache_dir, self.pad_seq_len, self.latent_size = cache_dir, pad_seq_len, tuple(latent_size)
+        self.load_latents = load_latents
         if datalist is None:
             datalist = sorted(f for f in os.listdir(cache_dir) if f.endswith(('.zst', '.pkl', '.pt')))
         self.files = list(datalist)
@@ -213,6 +217,12 @@ class PromptEmbedCache:
                                f'{tuple(known[i])} -- the cache changed after the index was written: delete the index and restart')
         if self.negative_prompt_embed_kwargs is not None:
             item['negative_prompt_embed_kwargs'] = self.negative_prompt_embed_kwargs
+        if self.load_latents:
+            if 'latents' not in raw:
+                raise KeyError(f'{self.files[i]}: load_latents=True but the record has no latents (write them with tools/cache_latents.py)')
+            lat = raw['latents'].float()
+            scale = raw.get('latents_scale', None)
+            item['latents'] = lat * scale if scale is not None else lat
         return item
 
 

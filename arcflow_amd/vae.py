@@ -111,21 +111,32 @@ def _single_head_attention(lib, xn: _Grid, x: _Grid, w_qkv, b_qkv, w_out, b_out,
     return y
 
 
-class AutoencoderKLDecoder:
-    def __init__(self, state_dict: Dict[str, torch.Tensor], block_out_channels: Sequence[int] = (128, 256, 512, 512),
-                 norm_num_groups: int = 32, layers_per_block: int = 2, scaling_factor: float = 0.3611,
-                 shift_factor: float = 0.1159, device='cuda'):
+class _VAEFacade:
+    """``pipe.vae`` stays the decoder object; when the snapshot's ``vae/`` also holds ``encoder.*`` weights the pipeline attaches the encoder
+    here, so ``pipe.vae.encode(...)`` works as on the reference's ``PretrainedVAE`` wrappers."""
+    encoder = None
+
+    def encode(self, images: torch.Tensor, **kw):
+        if self.encoder is None:
+            raise RuntimeError('this VAE was loaded without encoder.* weights (decoder-only snapshot): encode() needs a snapshot whose vae/ holds them')
+        return self.encoder.encode(images, **kw)
+
+
+class _KLBlocks:
+    """What the AutoencoderKL decoder and encoder share: the weight re-layout at load time and the layer primitives on grids
+    (3x3 convolution with GroupNorm sums from its epilogue, GroupNorm(+SiLU), ResnetBlock2D, the single-head mid-block attention)."""
+
+    def _setup(self, state_dict: Dict[str, torch.Tensor], prefix: str, norm_num_groups: int, device):
         self.lib = _lib.load()
         self.dev = torch.device(device)
-        self.groups, self.lpb = norm_num_groups, layers_per_block
-        self.rev = list(reversed(block_out_channels))
-        self.scaling_factor, self.shift_factor = scaling_factor, shift_factor
-        self.config = type('cfg', (), dict(scaling_factor=scaling_factor, shift_factor=shift_factor))()
+        self.groups = norm_num_groups
         self.w: Dict[str, torch.Tensor] = {}
         sd = state_dict
-        for k in [k for k in sd if k.startswith('decoder.') and k.endswith('.weight')]:
+        for k in [k for k in sd if k.startswith(prefix) and k.endswith('.weight')]:
             name = k[:-len('.weight')]
             wt, b = sd[k], sd.get(name + '.bias')
+            if self._relay(name, wt, b):                                  # a layer with a layout of its own (the encoder's conv_in / downsamplers)
+                continue
             if wt.dim() == 4 and wt.shape[-1] == 3:                       # 3x3 conv -> [Cout][tap][Cin], K-contiguous
                 co, ci = wt.shape[:2]
                 cip, cop = max(64, (ci + 63) // 64 * 64), (co + 7) // 8 * 8
@@ -143,14 +154,9 @@ class AutoencoderKLDecoder:
             else:                                                         # GroupNorm affine
                 self.w[name + '.weight'] = wt.to(self.dev, torch.float32)
                 self.w[name + '.bias'] = b.to(self.dev, torch.float32)
-        a = 'decoder.mid_block.attentions.0.'
+        a = prefix + 'mid_block.attentions.0.'
         self.w[a + 'qkv.weight'] = torch.cat([self.w[a + n + '.weight'] for n in ('to_q', 'to_k', 'to_v')]).contiguous()
         self.w[a + 'qkv.bias'] = torch.cat([self.w[a + n + '.bias'] for n in ('to_q', 'to_k', 'to_v')]).contiguous()
-        # nearest-2x upsample folded into the upsamplers' convolutions (four 2x2 phase kernels on the low-resolution grid)
-        self._fold_up = bool(self.lib.afx_conv_stats_available()) and os.environ.get('AFX_VAE_FOLD_UPSAMPLE', '1') != '0'     # (0: A/B runs)
-        if self._fold_up:
-            for k in [k for k in self.w if '.upsamplers.0.conv.weight' in k]:
-                self.w[k[:-len('.weight')] + '.weight4'] = phase_weights(self.w[k], self.w[k].shape[1] // 9)
         self._stats = torch.zeros(int(self.lib.afx_groupnorm_ws_bytes(2048, self.groups)) // 8, dtype=torch.float64, device=self.dev)   # afx_groupnorm_nhwc's scratch, sized by the library
         self._pool = _GridPool(self.dev)
         # GroupNorm sums out of the producing convolution's epilogue: a ring of slotted buffers (a grid's sums live until its norm ran:
@@ -159,16 +165,26 @@ class AutoencoderKLDecoder:
         self._stat_ring = [torch.zeros(64 * 2 * self.groups, dtype=torch.float64, device=self.dev) for _ in range(4)]
         self._stat_i = 0
 
+    def _relay(self, name: str, wt: torch.Tensor, b: torch.Tensor) -> bool:
+        return False
+
+    def _stat_slot(self, co: int):
+        """The statistics buffer for a convolution output of co channels that feeds a GroupNorm, or None when the epilogue cannot take it."""
+        gs = co // self.groups if co % self.groups == 0 else 0
+        if not (self._conv_stats and co <= 128 and gs >= 4 and gs % 4 == 0 and (gs <= 8 or gs % 8 == 0)):
+            return None
+        st = self._stat_ring[self._stat_i % len(self._stat_ring)]
+        self._stat_i += 1
+        return st
+
     # ------------------------------------------------------------------ primitives on grids
     def _conv(self, name: str, x: _Grid, cout: int, res: _Grid = None, stats: bool = True) -> _Grid:
         """stats: the output feeds a GroupNorm -> its sums come out of the GEMM epilogue (no statistics pass over the grid later)."""
         w, b = self.w[name + '.weight'], self.w[name + '.bias']
         co = w.shape[0]
         y = self._pool.grid(x.H, x.W, co)
-        gs = co // self.groups if co % self.groups == 0 else 0
-        if stats and self._conv_stats and co <= 128 and gs >= 4 and gs % 4 == 0 and (gs <= 8 or gs % 8 == 0):
-            y.stats = self._stat_ring[self._stat_i % len(self._stat_ring)]
-            self._stat_i += 1
+        y.stats = self._stat_slot(co) if stats else None
+        if y.stats is not None:
             _lib.check(self.lib.afx_conv3x3_bf16_stats(_p(x.t), _p(w), _p(b), _p(y.t), x.H, x.W, x.C, co, None if res is None else _p(res.t),
                                                        _p(y.stats), self.groups, _s()))
         else:
@@ -197,6 +213,22 @@ class AutoencoderKLDecoder:
         xn = self._gn(p + 'group_norm', x, False)
         return _single_head_attention(self.lib, xn, x, self.w[p + 'qkv.weight'], self.w[p + 'qkv.bias'],
                                       self.w[p + 'to_out.0.weight'], self.w[p + 'to_out.0.bias'], x.C ** -0.5)
+
+
+class AutoencoderKLDecoder(_KLBlocks, _VAEFacade):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], block_out_channels: Sequence[int] = (128, 256, 512, 512),
+                 norm_num_groups: int = 32, layers_per_block: int = 2, scaling_factor: float = 0.3611,
+                 shift_factor: float = 0.1159, device='cuda'):
+        self._setup(state_dict, 'decoder.', norm_num_groups, device)
+        self.lpb = layers_per_block
+        self.rev = list(reversed(block_out_channels))
+        self.scaling_factor, self.shift_factor = scaling_factor, shift_factor
+        self.config = type('cfg', (), dict(scaling_factor=scaling_factor, shift_factor=shift_factor))()
+        # nearest-2x upsample folded into the upsamplers' convolutions (four 2x2 phase kernels on the low-resolution grid)
+        self._fold_up = bool(self.lib.afx_conv_stats_available()) and os.environ.get('AFX_VAE_FOLD_UPSAMPLE', '1') != '0'     # (0: A/B runs)
+        if self._fold_up:
+            for k in [k for k in self.w if '.upsamplers.0.conv.weight' in k]:
+                self.w[k[:-len('.weight')] + '.weight4'] = phase_weights(self.w[k], self.w[k].shape[1] // 9)
 
     # ------------------------------------------------------------------ decode
     @torch.no_grad()
@@ -235,35 +267,30 @@ def _c64(c: int) -> int:
     return (c + 63) // 64 * 64
 
 
-class AutoencoderKLQwenImageDecoder:
-    """Decoder of AutoencoderKLQwenImage for single images (reference arcqwen_pipeline.py:470-481 and
-    lakonlab/models/architecture/diffusers/pretrained.py:142-149).  With one latent frame the causal 3-D convolutions
-    see two zero frames in front, so each reduces to its LAST temporal tap as a 2-D kernel and the temporal ``time_conv``
-    of the 3-D upsamplers is never reached; those 2-D kernels run as implicit GEMMs like the FLUX decoder's.  Channel
-    counts that are not multiples of 64 (96) live on grids padded to the next multiple (zero weights / gamma there).
-    The per-channel latent un-normalisation and the 1x1x1 ``post_quant_conv`` are folded into the unpack kernel."""
+class _QwenBlocks:
+    """What the AutoencoderKLQwenImage decoder and encoder share on ONE frame: every causal 3-D convolution reduced to its last temporal tap
+    and re-laid as a 2-D kernel on grids padded to multiples of 64 channels, the per-pixel RMS norm, the residual block and the attention."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], latents_mean: Sequence[float], latents_std: Sequence[float],
-                 dim_mult: Sequence[int] = (1, 2, 4, 4), num_res_blocks: int = 2, z_dim: int = 16, device='cuda'):
-        assert z_dim == 16, 'the packed-latent layout of the pipelines has 16 latent channels'
+    def _setup(self, state_dict: Dict[str, torch.Tensor], prefix: str, narrow: Dict[str, int], device):
+        """narrow: layer name -> padded output width for the layers whose output is not a grid the next convolution reads."""
         self.lib = _lib.load()
         self.dev = torch.device(device)
-        self.n_up, self.nrb = len(dim_mult), num_res_blocks
-        self.latents_mean, self.latents_std = list(latents_mean), list(latents_std)
-        self.config = type('cfg', (), dict(latents_mean=self.latents_mean, latents_std=self.latents_std, z_dim=z_dim))()
         self.w: Dict[str, torch.Tensor] = {}
         self.creal: Dict[str, int] = {}
         sd = {k: v.detach().cpu() for k, v in state_dict.items()}          # repacked on the host (a few hundred MB, once), then uploaded
-        for k in [k for k in sd if k.startswith('decoder.') and k.endswith('.weight') and 'time_conv' not in k]:
+        for k in [k for k in sd if k.startswith(prefix) and k.endswith('.weight') and 'time_conv' not in k]:
             name = k[:-len('.weight')]
             wt, b = sd[k].float(), sd[name + '.bias'].float()
             if wt.dim() == 5:
                 wt = wt[:, :, -1]                                         # causal: only the last temporal tap sees the frame
             co, ci = wt.shape[:2]
-            cop = 8 if name == 'decoder.conv_out' else _c64(co)
+            cop = narrow.get(name, _c64(co))
             cip = _c64(ci)
             bp = torch.zeros(cop, dtype=torch.bfloat16)
             bp[:co] = b.to(torch.bfloat16)
+            self.creal[name] = co
+            if self._relay(name, wt, b, cop):                             # a layer with a layout of its own (the encoder's conv_in / downsamplers)
+                continue
             if wt.shape[-1] == 3:                                         # 3x3 -> [Cout][tap][Cin], K-contiguous
                 wp = torch.zeros(cop, 9, cip, dtype=torch.bfloat16)
                 wp[:co, :, :ci] = wt.permute(0, 2, 3, 1).reshape(co, 9, ci).to(torch.bfloat16)
@@ -273,22 +300,16 @@ class AutoencoderKLQwenImageDecoder:
                 wp[:co, :ci] = wt.reshape(co, ci).to(torch.bfloat16)
                 self.w[name + '.weight'] = wp.to(self.dev)
             self.w[name + '.bias'] = bp.to(self.dev)
-            self.creal[name] = co
-        for k in [k for k in sd if k.startswith('decoder.') and k.endswith('.gamma')]:
+        for k in [k for k in sd if k.startswith(prefix) and k.endswith('.gamma')]:
             gm = sd[k].float().flatten()
             gp = torch.zeros(_c64(gm.numel()), dtype=torch.float32)
             gp[:gm.numel()] = gm
             self.w[k], self.creal[k] = gp.to(self.dev), gm.numel()
-        # v = post_quant_conv(lat * std + mean) = (Wq diag(std)) lat + (Wq mean + bq)
-        wq = sd['post_quant_conv.weight'].float().reshape(16, 16)
-        std, mean = torch.tensor(self.latents_std, dtype=torch.float32), torch.tensor(self.latents_mean, dtype=torch.float32)
         self._pool = _GridPool(self.dev)
-        self._fold_up = bool(self.lib.afx_conv_stats_available()) and os.environ.get('AFX_VAE_FOLD_UPSAMPLE', '1') != '0'
-        if self._fold_up:
-            for k in [k for k in self.w if '.upsamplers.0.resample.1.weight' in k]:
-                self.w[k[:-len('.weight')] + '.weight4'] = phase_weights(self.w[k], self.w[k].shape[1] // 9)
-        self._A = (wq * std[None, :]).contiguous().to(self.dev)
-        self._b = (wq @ mean + sd['post_quant_conv.bias'].float()).contiguous().to(self.dev)
+        return sd
+
+    def _relay(self, name: str, wt: torch.Tensor, b: torch.Tensor, cop: int) -> bool:
+        return False
 
     def _conv(self, name: str, x: _Grid, res: _Grid = None) -> _Grid:
         w, b = self.w[name + '.weight'], self.w[name + '.bias']
@@ -303,6 +324,10 @@ class AutoencoderKLQwenImageDecoder:
                                              _p(self.w[name + '.gamma']), int(act), _s()))
         return y
 
+    def _mid_attention(self, a: str, x: _Grid) -> _Grid:
+        return _single_head_attention(self.lib, self._norm(a + 'norm', x, False), x, self.w[a + 'to_qkv.weight'], self.w[a + 'to_qkv.bias'],
+                                      self.w[a + 'proj.weight'], self.w[a + 'proj.bias'], self.creal[a + 'norm.gamma'] ** -0.5)
+
     def _resnet(self, p: str, x: _Grid) -> _Grid:
         skip = x
         if p + 'conv_shortcut.weight' in self.w:
@@ -310,6 +335,32 @@ class AutoencoderKLQwenImageDecoder:
             ops.linear(x.t, self.w[p + 'conv_shortcut.weight'], self.w[p + 'conv_shortcut.bias'], out=skip.t)
         h = self._conv(p + 'conv1', self._norm(p + 'norm1', x, True))
         return self._conv(p + 'conv2', self._norm(p + 'norm2', h, True), res=skip)
+
+
+class AutoencoderKLQwenImageDecoder(_QwenBlocks, _VAEFacade):
+    """Decoder of AutoencoderKLQwenImage for single images (reference arcqwen_pipeline.py:470-481 and
+    lakonlab/models/architecture/diffusers/pretrained.py:142-149).  With one latent frame the causal 3-D convolutions
+    see two zero frames in front, so each reduces to its LAST temporal tap as a 2-D kernel and the temporal ``time_conv``
+    of the 3-D upsamplers is never reached; those 2-D kernels run as implicit GEMMs like the FLUX decoder's.  Channel
+    counts that are not multiples of 64 (96) live on grids padded to the next multiple (zero weights / gamma there).
+    The per-channel latent un-normalisation and the 1x1x1 ``post_quant_conv`` are folded into the unpack kernel."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], latents_mean: Sequence[float], latents_std: Sequence[float],
+                 dim_mult: Sequence[int] = (1, 2, 4, 4), num_res_blocks: int = 2, z_dim: int = 16, device='cuda'):
+        assert z_dim == 16, 'the packed-latent layout of the pipelines has 16 latent channels'
+        sd = self._setup(state_dict, 'decoder.', {'decoder.conv_out': 8}, device)
+        self.n_up, self.nrb = len(dim_mult), num_res_blocks
+        self.latents_mean, self.latents_std = list(latents_mean), list(latents_std)
+        self.config = type('cfg', (), dict(latents_mean=self.latents_mean, latents_std=self.latents_std, z_dim=z_dim))()
+        # v = post_quant_conv(lat * std + mean) = (Wq diag(std)) lat + (Wq mean + bq)
+        wq = sd['post_quant_conv.weight'].float().reshape(16, 16)
+        std, mean = torch.tensor(self.latents_std, dtype=torch.float32), torch.tensor(self.latents_mean, dtype=torch.float32)
+        self._fold_up = bool(self.lib.afx_conv_stats_available()) and os.environ.get('AFX_VAE_FOLD_UPSAMPLE', '1') != '0'
+        if self._fold_up:
+            for k in [k for k in self.w if '.upsamplers.0.resample.1.weight' in k]:
+                self.w[k[:-len('.weight')] + '.weight4'] = phase_weights(self.w[k], self.w[k].shape[1] // 9)
+        self._A = (wq * std[None, :]).contiguous().to(self.dev)
+        self._b = (wq @ mean + sd['post_quant_conv.bias'].float()).contiguous().to(self.dev)
 
     @torch.no_grad()
     def decode_tokens(self, tokens: torch.Tensor, hp: int, wp: int) -> torch.Tensor:
@@ -319,9 +370,7 @@ class AutoencoderKLQwenImageDecoder:
                                                       _p(self._A), _p(self._b), _s()))
         x = self._conv('decoder.conv_in', x)
         x = self._resnet('decoder.mid_block.resnets.0.', x)
-        a = 'decoder.mid_block.attentions.0.'
-        x = _single_head_attention(self.lib, self._norm(a + 'norm', x, False), x, self.w[a + 'to_qkv.weight'], self.w[a + 'to_qkv.bias'],
-                                   self.w[a + 'proj.weight'], self.w[a + 'proj.bias'], self.creal[a + 'norm.gamma'] ** -0.5)
+        x = self._mid_attention('decoder.mid_block.attentions.0.', x)
         x = self._resnet('decoder.mid_block.resnets.1.', x)
         for i in range(self.n_up):
             for j in range(self.nrb + 1):
@@ -341,3 +390,273 @@ class AutoencoderKLQwenImageDecoder:
 
     def decode_packed(self, latents: torch.Tensor, hp: int, wp: int) -> torch.Tensor:
         return torch.stack([self.decode_tokens(latents[b], hp, wp) for b in range(latents.shape[0])])
+
+
+# ====================================================================================================== encoders: images -> latents
+def s2d_weights(wt: torch.Tensor, cip: int, cop: int) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] kernel of the stride-2 convolution on pad(x, (0, 1, 0, 1)) -> [cop, 9 * 4 * cip] bf16: the stride-1 3x3 kernel on the
+    space-to-depth grid (cell (Y, X), channel (2 py + px) * cip + c = x[2Y + py][2X + px][c]) that afx_conv3x3s2_bf16 runs.  Source row
+    2y + dy is phase dy of cell y for dy = 0, 1 and phase 0 of cell y + 1 for dy = 2 (the same in x), so the taps -1 and the phase-1 blocks of
+    the taps +1 stay zero: 9 of the 36 (tap, phase) blocks are live."""
+    co, ci = wt.shape[:2]
+    cell = {0: (1, 0), 1: (1, 1), 2: (2, 0)}                       # kernel index -> (tap index of the 3x3 kernel on cells, phase)
+    out = torch.zeros(cop, 3, 3, 4, cip, dtype=wt.dtype)
+    for dy in range(3):
+        for dx in range(3):
+            (ty, py), (tx, px) = cell[dy], cell[dx]
+            out[:co, ty, tx, 2 * py + px, :ci] = wt[:, :, dy, dx]
+    return out.reshape(cop, 36 * cip)
+
+
+def conv_in_weights(wt: torch.Tensor, b: torch.Tensor, cop: int) -> torch.Tensor:
+    """[Cout, 3, 3, 3] kernel + bias of conv_in (padding 1) -> [cop, 64]: the matrix applied to the rows of afx_image_to_cols27
+    (column (3 dy + dx) * 3 + channel, the bias in column 27, which multiplies that layout's constant 1)."""
+    co = wt.shape[0]
+    out = torch.zeros(cop, 64, dtype=wt.dtype)
+    out[:co, :27] = wt.permute(0, 2, 3, 1).reshape(co, 27)
+    out[:co, 27] = b
+    return out
+
+
+def kl_encoder_shapes(block_out_channels: Sequence[int] = (128, 256, 512, 512), layers_per_block: int = 2, latent_channels: int = 16,
+                      in_channels: int = 3) -> Dict[str, tuple]:
+    """State-dict keys and shapes of the diffusers AutoencoderKL encoder (double_z, mid-block attention, no quant_conv)."""
+    sh: Dict[str, tuple] = {}
+
+    def conv(n, co, ci, k=3):
+        sh[n + '.weight'], sh[n + '.bias'] = (co, ci, k, k), (co,)
+
+    def norm(n, c):
+        sh[n + '.weight'], sh[n + '.bias'] = (c,), (c,)
+
+    def res(p, ci, co):
+        norm(p + 'norm1', ci); conv(p + 'conv1', co, ci); norm(p + 'norm2', co); conv(p + 'conv2', co, co)
+        if ci != co:
+            conv(p + 'conv_shortcut', co, ci, 1)
+    c = block_out_channels[0]
+    conv('encoder.conv_in', c, in_channels)
+    for i, co in enumerate(block_out_channels):
+        for j in range(layers_per_block):
+            res(f'encoder.down_blocks.{i}.resnets.{j}.', c, co)
+            c = co
+        if i < len(block_out_channels) - 1:
+            conv(f'encoder.down_blocks.{i}.downsamplers.0.conv', c, c)
+    res('encoder.mid_block.resnets.0.', c, c)
+    a = 'encoder.mid_block.attentions.0.'
+    norm(a + 'group_norm', c)
+    for n in ('to_q', 'to_k', 'to_v', 'to_out.0'):
+        sh[a + n + '.weight'], sh[a + n + '.bias'] = (c, c), (c,)
+    res('encoder.mid_block.resnets.1.', c, c)
+    norm('encoder.conv_norm_out', c)
+    conv('encoder.conv_out', 2 * latent_channels, c)
+    return sh
+
+
+def qwen_encoder_shapes(dim: int = 96, z_dim: int = 16, dim_mult: Sequence[int] = (1, 2, 4, 4), num_res_blocks: int = 2,
+                        temporal_downsample: Sequence[bool] = (False, True, True)) -> Dict[str, tuple]:
+    """State-dict keys and shapes of the diffusers AutoencoderKLQwenImage encoder + quant_conv (down_blocks is one flat list of residual blocks and
+    Resample modules)."""
+    sh: Dict[str, tuple] = {}
+
+    def conv3(n, co, ci, k):
+        sh[n + '.weight'], sh[n + '.bias'] = (co, ci, k, k, k), (co,)
+
+    def res(p, ci, co):
+        sh[p + 'norm1.gamma'] = (ci, 1, 1, 1); conv3(p + 'conv1', co, ci, 3)
+        sh[p + 'norm2.gamma'] = (co, 1, 1, 1); conv3(p + 'conv2', co, co, 3)
+        if ci != co:
+            conv3(p + 'conv_shortcut', co, ci, 1)
+    dims = [dim * u for u in [1] + list(dim_mult)]
+    conv3('encoder.conv_in', dims[0], 3, 3)
+    n = 0
+    for i, (ci, co) in enumerate(zip(dims[:-1], dims[1:])):
+        for _ in range(num_res_blocks):
+            res(f'encoder.down_blocks.{n}.', ci, co)
+            ci = co
+            n += 1
+        if i != len(dim_mult) - 1:
+            sh[f'encoder.down_blocks.{n}.resample.1.weight'], sh[f'encoder.down_blocks.{n}.resample.1.bias'] = (co, co, 3, 3), (co,)
+            if temporal_downsample[i]:
+                sh[f'encoder.down_blocks.{n}.time_conv.weight'], sh[f'encoder.down_blocks.{n}.time_conv.bias'] = (co, co, 3, 1, 1), (co,)
+            n += 1
+    c = dims[-1]
+    res('encoder.mid_block.resnets.0.', c, c)
+    a = 'encoder.mid_block.attentions.0.'
+    sh[a + 'norm.gamma'] = (c, 1, 1)
+    sh[a + 'to_qkv.weight'], sh[a + 'to_qkv.bias'] = (3 * c, c, 1, 1), (3 * c,)
+    sh[a + 'proj.weight'], sh[a + 'proj.bias'] = (c, c, 1, 1), (c,)
+    res('encoder.mid_block.resnets.1.', c, c)
+    sh['encoder.norm_out.gamma'] = (c, 1, 1, 1)
+    conv3('encoder.conv_out', 2 * z_dim, c, 3)
+    conv3('quant_conv', 2 * z_dim, 2 * z_dim, 1)
+    return sh
+
+
+def _check_keys(state_dict, expected: Dict[str, tuple], prefixes, what: str):
+    """Every expected key present with its shape, and no other key under the encoder's prefixes: nothing is skipped silently."""
+    have = {k for k in state_dict if k.startswith(tuple(prefixes))}
+    missing, extra = sorted(set(expected) - have), sorted(have - set(expected))
+    bad = [f'{k}: {tuple(state_dict[k].shape)} != {expected[k]}' for k in sorted(have & set(expected)) if tuple(state_dict[k].shape) != tuple(expected[k])]
+    if missing or extra or bad:
+        raise KeyError(f'{what}: missing keys {missing[:8]}{" ..." if len(missing) > 8 else ""}, unknown keys {extra[:8]}'
+                       f'{" ..." if len(extra) > 8 else ""}, wrong shapes {bad[:8]}')
+
+
+class _EncodeMixin:
+    """The public side both encoders share: batching, the noise, the posterior kernel."""
+
+    def encode(self, images: torch.Tensor, generator=None, noise: torch.Tensor = None, sample: bool = True, packed: bool = False,
+               return_moments: bool = False, images01: bool = False):
+        """images [B, 3, H, W] fp32 / bf16 in [-1, 1] as the reference passes them to vae.encode (images01: in [0, 1], the ``* 2 - 1`` of
+        latent_diffusion_text_image.py:43 is applied by the kernel); H, W multiples of 16.  Returns the latents the reference wrappers return
+        (pretrained.py:67 / :140): fp32 [B, 16, H/8, W/8], or packed [B, (H/16)(W/16), 64] tokens, so ``decoder.decode_packed(encoder.encode(x,
+        packed=True), H // 16, W // 16)`` is the round trip.  sample: z = mean + std * noise with ``noise`` [B, 16, H/8, W/8] (drawn from
+        ``generator`` when not given); sample=False: the mode.  return_moments: also the fp32 moments [B, 32, H/8, W/8] (mean | clamped logvar)."""
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] % 16 or images.shape[3] % 16:
+            raise ValueError(f'encode: need images [B, 3, H, W] with H, W multiples of 16, got {tuple(images.shape)}')
+        B, _, H, W = images.shape
+        h, w = H // 8, W // 8
+        if images.dtype != torch.bfloat16:
+            images = images.to(torch.float32)
+        images = images.to(self.dev).contiguous()
+        if sample:
+            if noise is None:
+                gdev = self.dev if generator is None else generator.device
+                noise = torch.randn(B, 16, h, w, generator=generator, device=gdev, dtype=torch.float32)
+            if tuple(noise.shape) != (B, 16, h, w):
+                raise ValueError(f'encode: noise must be {(B, 16, h, w)}, got {tuple(noise.shape)}')
+            noise = noise.to(self.dev, torch.float32).contiguous()
+        out = torch.empty((B, (h // 2) * (w // 2), 64) if packed else (B, 16, h, w), dtype=torch.float32, device=self.dev)
+        mom = torch.empty(B, 32, h, w, dtype=torch.float32, device=self.dev)
+        for i in range(B):
+            g = self._moments_grid(images[i], images01)
+            _lib.check(self.lib.afx_posterior_latents(_p(g.t), g.C, h, w, _p(self._qA), _p(self._qb), _p(noise[i]) if sample else None, _p(self._sub),
+                                                      _p(self._fac), self._divide, _p(out[i]), int(packed), _p(mom[i]), _s()))
+        return (out, mom) if return_moments else out
+
+    def encode_images01(self, images: torch.Tensor, **kw):
+        """``encode`` of images in [0, 1] (the ``images`` branch of a training batch, latent_diffusion_text_image.py:34-45)."""
+        return self.encode(images, images01=True, **kw)
+
+    def _first_grid(self, img: torch.Tensor, images01: bool, name: str) -> _Grid:
+        """conv_in: the 27-in-64 neighbourhood rows, then a K = 64 GEMM (3 channels padded to 64 for the 3x3 kernel would be 21x the work)."""
+        H, W = img.shape[1:]
+        cols = self._pool.grid(H, W, 64)
+        _lib.check(self.lib.afx_image_to_cols27(_p(img), int(img.dtype == torch.bfloat16), _p(cols.t), H, W, int(images01), _s()))
+        w = self.w[name + '.weight']
+        x = self._pool.grid(H, W, w.shape[0])
+        ops.linear(cols.t, w, None, out=x.t)
+        return x
+
+    def _down(self, name: str, x: _Grid, stats) -> _Grid:
+        w, b = self.w[name + '.weight'], self.w[name + '.bias']
+        ws = self._pool.grid(x.H // 2, x.W // 2, 4 * x.C)
+        y = self._pool.grid(x.H // 2, x.W // 2, w.shape[0])
+        y.stats = stats
+        _lib.check(self.lib.afx_conv3x3s2_bf16(_p(x.t), _p(w), _p(b), _p(y.t), _p(ws.t), x.H, x.W, x.C, w.shape[0], _p(stats),
+                                               self.groups if stats is not None else 0, _s()))
+        return y
+
+
+class AutoencoderKLEncoder(_KLBlocks, _EncodeMixin):
+    """Encoder of the diffusers AutoencoderKL (FLUX: block_out_channels (128, 256, 512, 512), 2 layers per block, 32 groups, 16 latent channels,
+    double_z, no quant_conv) on the decoder's kernels -- the ``vae.encode(img).latent_dist.sample()`` behind
+    lakonlab/models/architecture/diffusers/pretrained.py:60-67.  conv_in is a K = 64 GEMM on 27-value neighbourhood rows, the three
+    Downsample2D(padding=0) layers are afx_conv3x3s2_bf16, the posterior (clamp, exp, noise, shift / scale, packing) is one fp32 kernel."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], block_out_channels: Sequence[int] = (128, 256, 512, 512),
+                 norm_num_groups: int = 32, layers_per_block: int = 2, scaling_factor: float = 0.3611,
+                 shift_factor: float = 0.1159, device='cuda'):
+        _check_keys(state_dict, kl_encoder_shapes(block_out_channels, layers_per_block), ('encoder.', 'quant_conv.'), 'AutoencoderKLEncoder')
+        self._setup(state_dict, 'encoder.', norm_num_groups, device)
+        self.chans, self.lpb = list(block_out_channels), layers_per_block
+        self.scaling_factor = 1.0 if scaling_factor is None else scaling_factor
+        self.shift_factor = 0.0 if shift_factor is None else shift_factor
+        self.config = type('cfg', (), dict(scaling_factor=scaling_factor, shift_factor=shift_factor))()
+        self._qA = self._qb = None
+        self._sub = torch.full((16,), float(self.shift_factor), dtype=torch.float32, device=self.dev)
+        self._fac = torch.full((16,), float(self.scaling_factor), dtype=torch.float32, device=self.dev)
+        self._divide = 0
+
+    def _relay(self, name, wt, b):
+        if name == 'encoder.conv_in':
+            self.w[name + '.weight'] = conv_in_weights(wt.float(), b.float(), (wt.shape[0] + 7) // 8 * 8).to(self.dev, torch.bfloat16)
+        elif '.downsamplers.0.conv' in name:
+            co, ci = wt.shape[:2]
+            self.w[name + '.weight'] = s2d_weights(wt.float(), _c64(ci), (co + 7) // 8 * 8).to(self.dev, torch.bfloat16)
+            bp = torch.zeros((co + 7) // 8 * 8, dtype=torch.bfloat16)
+            bp[:co] = b.to(torch.bfloat16)
+            self.w[name + '.bias'] = bp.to(self.dev)
+        else:
+            return False
+        return True
+
+    @torch.no_grad()
+    def _moments_grid(self, img: torch.Tensor, images01: bool) -> _Grid:
+        x = self._first_grid(img, images01, 'encoder.conv_in')
+        n = len(self.chans)
+        for i in range(n):
+            for j in range(self.lpb):
+                x = self._resnet(f'encoder.down_blocks.{i}.resnets.{j}.', x)
+            if i < n - 1:
+                x = self._down(f'encoder.down_blocks.{i}.downsamplers.0.conv', x, self._stat_slot(x.C))
+        x = self._resnet('encoder.mid_block.resnets.0.', x)
+        x = self._attention('encoder.mid_block.attentions.0.', x)
+        x = self._resnet('encoder.mid_block.resnets.1.', x)
+        return self._conv('encoder.conv_out', self._gn('encoder.conv_norm_out', x, True), 0, stats=False)
+
+
+class AutoencoderKLQwenImageEncoder(_QwenBlocks, _EncodeMixin):
+    """Encoder of AutoencoderKLQwenImage for single images -- ``vae.encode(img.unsqueeze(-3)).latent_dist.sample()`` normalised by latents_mean /
+    latents_std (lakonlab/models/architecture/diffusers/pretrained.py:133-140).  Two reductions hold on ONE frame and are checked against a real
+    conv3d on the one-frame clip by the test oracle: (1) every causal 3x3x3 convolution pads two zero frames in front, so it reduces to its LAST
+    temporal tap as a 2-D kernel (as in the decoder); (2) the temporal ``time_conv`` of the ``downsample3d`` stages never runs: the first chunk only
+    fills its cache, so those stages are the spatial Resample alone (pad (0, 1, 0, 1) + stride-2 Conv2d).  The 1x1x1 ``quant_conv`` is applied in
+    fp32 by the posterior kernel; the 96-channel stage runs on grids padded to 128."""
+    groups = 0
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], latents_mean: Sequence[float], latents_std: Sequence[float], dim: int = None,
+                 dim_mult: Sequence[int] = (1, 2, 4, 4), num_res_blocks: int = 2, temporal_downsample: Sequence[bool] = (False, True, True),
+                 z_dim: int = 16, device='cuda'):
+        assert z_dim == 16, 'the packed-latent layout of the pipelines has 16 latent channels'
+        if dim is None:
+            dim = state_dict['encoder.conv_in.weight'].shape[0]
+        _check_keys(state_dict, qwen_encoder_shapes(dim, z_dim, dim_mult, num_res_blocks, temporal_downsample), ('encoder.', 'quant_conv.'),
+                    'AutoencoderKLQwenImageEncoder')
+        sd = self._setup(state_dict, 'encoder.', {'encoder.conv_out': 2 * z_dim}, device)
+        self.n_down, self.nrb = len(dim_mult), num_res_blocks
+        self.latents_mean, self.latents_std = list(latents_mean), list(latents_std)
+        self.config = type('cfg', (), dict(latents_mean=self.latents_mean, latents_std=self.latents_std, z_dim=z_dim))()
+        self._qA = sd['quant_conv.weight'].float().reshape(32, 32).contiguous().to(self.dev)
+        self._qb = sd['quant_conv.bias'].float().contiguous().to(self.dev)
+        self._sub = torch.tensor(self.latents_mean, dtype=torch.float32, device=self.dev)
+        self._fac = torch.tensor(self.latents_std, dtype=torch.float32, device=self.dev)
+        self._divide = 1
+
+    def _relay(self, name, wt, b, cop):
+        if name == 'encoder.conv_in':
+            self.w[name + '.weight'] = conv_in_weights(wt, b, cop).to(self.dev, torch.bfloat16)
+        elif name.endswith('.resample.1'):
+            self.w[name + '.weight'] = s2d_weights(wt, _c64(wt.shape[1]), cop).to(self.dev, torch.bfloat16)
+            bp = torch.zeros(cop, dtype=torch.bfloat16)
+            bp[:wt.shape[0]] = b.to(torch.bfloat16)
+            self.w[name + '.bias'] = bp.to(self.dev)
+        else:
+            return False
+        return True
+
+    @torch.no_grad()
+    def _moments_grid(self, img: torch.Tensor, images01: bool) -> _Grid:
+        x = self._first_grid(img, images01, 'encoder.conv_in')
+        n = 0
+        for i in range(self.n_down):
+            for _ in range(self.nrb):
+                x = self._resnet(f'encoder.down_blocks.{n}.', x)
+                n += 1
+            if i != self.n_down - 1:
+                x = self._down(f'encoder.down_blocks.{n}.resample.1', x, None)
+                n += 1
+        x = self._resnet('encoder.mid_block.resnets.0.', x)
+        x = self._mid_attention('encoder.mid_block.attentions.0.', x)
+        x = self._resnet('encoder.mid_block.resnets.1.', x)
+        return self._conv('encoder.conv_out', self._norm('encoder.norm_out', x, True))

@@ -349,6 +349,28 @@ int afx_latent_to_nhwc_affine(const float* tokens, void* y, int32_t hp, int32_t 
 int afx_rmsnorm_nhwc(const void* x, void* y, int64_t rows, int32_t Cpad, int32_t Creal, const float* gamma, int32_t act,
                      void* stream);
 
+/* ---- VAE encoders (images -> latents: vae.encode behind lakonlab/models/architecture/diffusers/pretrained.py:60-67 and :133-140) ----
+ * The encoders' downsample (diffusers Downsample2D(padding=0) / Qwen Resample('downsample2d')): y = conv3x3(pad(x, (0,1,0,1)), stride 2) + bias,
+ * out[y][x] = sum w[dy][dx] in[2y+dy][2x+dx] with input row H / column W read as zero.  x: zero-bordered grid [(H+2)*(W+2), Cin], y: zero-bordered
+ * grid [(H/2+2)*(W/2+2), Cout] (border re-zeroed).  An implicit GEMM, no im2col: x is first re-laid space-to-depth into ws, a zero-bordered
+ * [(H/2+2)*(W/2+2), 4 Cin] grid with (W/2+3) readable rows before and after it (channel (2 py + px) Cin + c of cell (Y, X) = x[2Y+py][2X+px][c]),
+ * on which the stride-2 kernel is a stride-1 3x3 kernel with taps 0 / +1: w = [Cout][3][3][4 Cin] bf16 from arcflow_amd.vae.s2d_weights.
+ * H, W even, Cin % 64 == 0, Cout % 8 == 0, else AFX_E_INVALID.  gn_stats / groups as afx_conv3x3_bf16_stats, or null / 0. */
+int afx_conv3x3s2_bf16(const void* x, const void* w, const void* bias, void* y, void* ws, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                       double* gn_stats, int32_t groups, void* stream);
+/* The encoder's first layer operand (the inverse direction of afx_nhwc_to_image): image [3, H, W] fp32 (img_bf16 0) or bf16 (1), in [-1, 1], or
+ * in [0, 1] with from01 != 0 (the images * 2 - 1 of lakonlab/models/latent_diffusion_text_image.py:43 applied here) -> zero-bordered grid
+ * [(H+2)*(W+2), 64] bf16 whose interior rows hold the pixel's 3x3x3 neighbourhood, k = (3 dy + dx) * 3 + channel, k = 27 the constant 1, the
+ * rest zero: conv_in (3 -> C, padding 1) is then afx_linear_bf16 with K = 64 on the weight from arcflow_amd.vae.conv_in_weights (bias in column 27). */
+int afx_image_to_cols27(const void* img, int32_t img_bf16, void* y, int32_t H, int32_t W, int32_t from01, void* stream);
+/* DiagonalGaussianDistribution + the latent normalisation of pretrained.py:67 / :140 in one pass.  grid: zero-bordered [(h+2)*(w+2), Cpad >= 32]
+ * bf16, channels 0-15 mean, 16-31 logvar (conv_out's output); A [32][32] / b [32] fp32: optional 1x1 quant_conv applied first (both or neither).
+ * moments [32, h, w] fp32 = mean | clamp(logvar, -30, 20); z = mean + exp(logvar / 2) * eps (eps [16, h, w] fp32; null: z = mean, the mode);
+ * out = (z - sub[c]) * fac[c] (divide 0: FLUX, sub = shift, fac = scaling) or (z - sub[c]) / fac[c] (divide 1: Qwen-Image, latents_mean / latents_std),
+ * fp32 as [16, h, w] (packed 0) or packed tokens [(h/2)*(w/2), 64], channel c * 4 + (y & 1) * 2 + (x & 1) (packed 1; h, w even). */
+int afx_posterior_latents(const void* grid, int32_t Cpad, int32_t h, int32_t w, const float* A, const float* b, const float* eps, const float* sub,
+                          const float* fac, int32_t divide, float* out, int32_t packed, float* moments, void* stream);
+
 /* ---- text encoders: T5-XXL + CLIP-L (FLUX), Qwen2.5-VL language model (Qwen-Image) -----------------------
  * Replaces the transformers modules behind lakonlab/models/architecture/diffusers/pretrained.py:152-238
  * (PretrainedFluxTextEncoder / PretrainedQwenImageTextEncoder -> pipeline.encode_prompt). */

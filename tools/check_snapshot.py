@@ -57,6 +57,21 @@ def main(argv=None):
     cfg = json.load(open(os.path.join(tdir, 'config.json')))
     family = a.family or ('qwen' if 'Qwen' in cfg.get('_class_name', '') else 'flux')
     ok = report(f'{tdir} [{family}]', *check_state_shapes(header_shapes(tdir), expected_transformer_keys(family, cfg)))
+    vdir = os.path.join(a.snapshot, 'vae')
+    if os.path.isdir(vdir):                        # VAE encoder (optional: decoder-only snapshots stay valid): keys and shapes vae.encode needs
+        from arcflow_amd.vae import kl_encoder_shapes, qwen_encoder_shapes
+        vcfg = json.load(open(os.path.join(vdir, 'config.json')))
+        shapes = {k: v for k, v in header_shapes(vdir).items() if k.startswith(('encoder.', 'quant_conv.'))}
+        if not shapes:
+            print(f'{vdir} [{family} encoder]: no encoder.* tensors (decoder-only snapshot: pipe.vae.encode is unavailable)')
+        else:
+            if family == 'qwen':
+                exp = qwen_encoder_shapes(vcfg.get('base_dim', 96), vcfg.get('z_dim', 16), tuple(vcfg.get('dim_mult', (1, 2, 4, 4))),
+                                          vcfg.get('num_res_blocks', 2), tuple(vcfg.get('temperal_downsample', (False, True, True))))
+            else:
+                exp = kl_encoder_shapes(tuple(vcfg.get('block_out_channels', (128, 256, 512, 512))), vcfg.get('layers_per_block', 2),
+                                        vcfg.get('latent_channels', 16))
+            ok = report(f'{vdir} [{family} encoder]', *check_state_shapes(shapes, exp)) and ok
     if a.adapter:
         acfg = json.load(open(os.path.join(a.adapter, 'config.json')))
         K, L = acfg.get('num_gaussians', 16), acfg.get('logweights_channels', 4)
