@@ -16,15 +16,14 @@
 namespace afx {
 
 // ---- GroupNorm statistics: stats[g] = {sum, sum of squares} in fp64 (border rows are zero and do not count) ----
-// Every thread owns one 16-byte channel chunk and strides over the rows (the grid is sized to ~4 blocks per CU, so the
-// fp64 atomics on the 2 * groups result words stay in the low thousands).
+// Every thread owns one 16-byte channel chunk and strides over the rows with fp32 running sums; the block then folds its lanes' sums per group
+// in fp64 in a fixed order (through LDS, no atomics) and adds the result, rounded to fp32, to one of GN_SLOTS copies of the 2 * groups result
+// words with an fp64 atomic.  The sums are the same bits on every run as long as the <= 32 block sums that meet in a slot span less than 2^24.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, int64_t rows, int C, int groups,
                                                        double* __restrict__ stats) {
-  __shared__ float part[64][2];
-  const int cpr = C >> 3;                       // 16-byte chunks per row
-  const int gs = C / groups;                    // channels per group (>= 4)
-  if (threadIdx.x < 64) part[threadIdx.x][0] = part[threadIdx.x][1] = 0.f;
-  __syncthreads();
+  __shared__ float part[256][4];                // every lane's {sum, sum of squares} of its two 4-channel halves
+  const int cpr = C >> 3;                       // 16-byte chunks per row (divides 256: every lane owns one)
+  const int gs = C / groups;                    // channels per group (>= 4, a multiple of 4)
   const int rstep = 256 / cpr;
   const int c = threadIdx.x % cpr, rl = threadIdx.x / cpr;
   float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
@@ -55,17 +54,27 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
         s1 += v[4 + e]; q1 += v[4 + e] * v[4 + e];
       }
     }
-    const int g0 = (c * 8) / gs, g1 = (c * 8 + 4) / gs;
-    atomicAdd(&part[g0][0], s0); atomicAdd(&part[g0][1], q0);
-    atomicAdd(&part[g1][0], s1); atomicAdd(&part[g1][1], q1);
   }
+  part[threadIdx.x][0] = s0; part[threadIdx.x][1] = q0;
+  part[threadIdx.x][2] = s1; part[threadIdx.x][3] = q1;
   __syncthreads();
+  // The block's sums of group g: its gs / 4 halves of every row lane, 512 / groups values, added in fp64 in a FIXED order (fp32 LDS atomics
+  // here made the sums, and with them whole decodes, differ in the last bit from run to run with the order the waves arrived in).
   // 2048 blocks adding to the same 2 * groups doubles serialise in the L2's atomic unit: 93 us for a 17 MB grid.  One of GN_SLOTS copies per
-  // block (gn_coeff_kernel folds them): 32 atomics per address instead of 2048.
+  // block (gn_coeff_kernel folds them): 32 atomics per address instead of 2048.  The block's sums are rounded to fp32 first: a sum of 32
+  // fp32-valued doubles is exact in fp64 (unless they span more than 2^24), so the order of those atomics does not show in the result.
   if (threadIdx.x < groups) {
+    const int h0 = threadIdx.x * (gs >> 2), h1 = h0 + (gs >> 2);
+    double s = 0.0, q = 0.0;
+    for (int rl2 = 0; rl2 < rstep; ++rl2)
+      for (int h = h0; h < h1; ++h) {
+        const float* e = part[rl2 * cpr + (h >> 1)] + (h & 1) * 2;
+        s += (double)e[0];
+        q += (double)e[1];
+      }
     double* dst = stats + ((int64_t)(blockIdx.x % GN_SLOTS) * groups + threadIdx.x) * 2;
-    atomicAdd(dst, (double)part[threadIdx.x][0]);
-    atomicAdd(dst + 1, (double)part[threadIdx.x][1]);
+    atomicAdd(dst, (double)(float)s);
+    atomicAdd(dst + 1, (double)(float)q);
   }
 }
 
@@ -81,7 +90,7 @@ __global__ void gn_coeff_kernel(const double* __restrict__ stats, double count, 
     s1 += stats[((int64_t)sl * groups + gi) * 2 + 1];
   }
   const double mean = s0 / count;
-  const double var = s1 / count - mean * mean;
+  const double var = fmax(s1 / count - mean * mean, 0.0);        // (the fp32 partial sums can leave a constant group's variance below zero: NaN through rsqrtf)
   const float a = rsqrtf((float)var + eps) * gamma[ch];
   coef[ch] = a;
   coef[C + ch] = beta[ch] - (float)mean * a;

@@ -1,5 +1,6 @@
 """Shared checks of the fp64 parity tests (test_hip_train_kernels.py, test_text_encoders.py, test_hip_forward_operands.py, test_hip_gemm_fp64.py,
-test_hip_attention_fp64.py): bf16 / fp32 outputs against an fp64 reference, and the fp64 GEMM reference with its fp32 summation bound."""
+test_hip_attention_fp64.py, test_hip_vae_fp64.py): bf16 / fp32 outputs against an fp64 reference, the fp64 GEMM reference with its fp32 summation bound
+and the fp64 convolution reference built from shifted matmuls."""
 import math
 
 import torch
@@ -51,3 +52,30 @@ def proj64(a, w, b, kstep=32):
 
 def gelu64(x):
     return x * torch.sigmoid(2 * math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3))
+
+
+def silu64(x):
+    return x * torch.sigmoid(x)
+
+
+def conv64(x_pad, w, b, Ho, Wo, stride=1, oy=0, ox=0, skip=None, kstep=32):
+    """The convolution reference of the VAE tests: y[i, j, :] = sum over taps (dy, dx) of x_pad[oy + dy + stride i, ox + dx + stride j, :] @ w[:, :, dy, dx].T + b
+    as kh * kw shifted fp64 matmuls on the PADDED NHWC grid x_pad [Hp, Wp, Cin] (w [Cout, Cin, kh, kw], any dtype; no fp64 convolution of the backend is
+    used).  skip = (dy, dx): that tap is left out (the mutated references of the teeth checks).  Returns y [Ho, Wo, Cout] fp64, mag = |x| |w| + |b| of the
+    same shape and the fp32 summation floor of proj64 for K = kh kw Cin: (K / kstep + kstep + 1) 2^-24 mag."""
+    xd, wd = x_pad.double(), w.double()
+    co, ci, kh, kw = wd.shape
+    y = torch.zeros(Ho, Wo, co, dtype=torch.float64, device=xd.device)
+    mag = torch.zeros_like(y)
+    for dy in range(kh):
+        for dx in range(kw):
+            if skip == (dy, dx):
+                continue
+            xs = xd[oy + dy:oy + dy + stride * (Ho - 1) + 1:stride, ox + dx:ox + dx + stride * (Wo - 1) + 1:stride].reshape(Ho * Wo, ci)
+            wt = wd[:, :, dy, dx].T.contiguous()
+            y += (xs @ wt).view(Ho, Wo, co)
+            mag += (xs.abs() @ wt.abs()).view(Ho, Wo, co)
+    if b is not None:
+        y += b.double()
+        mag += b.double().abs()
+    return y, mag, (kh * kw * ci // kstep + kstep + 1) * U32 * mag
