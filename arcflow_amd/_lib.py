@@ -32,7 +32,7 @@ EXPORTS = [
     'afx_arcflow_step_dropout', 'afx_arcflow_backward', 'afx_mse_loss', 'afx_euler_roll', 'afx_axpby_rows', 'afx_cfg_combine',
     'afx_head_grad', 'afx_linear_bf16_f32out', 'afx_linear_tn_f32out', 'afx_linear_tn_f32out_ws', 'afx_linear_tn_ws_bytes', 'afx_linear_bf16_dropres', 'afx_transpose_bf16', 'afx_colsum_bf16', 'afx_normout_backward', 'afx_normout_backward_split',
     'afx_outer_accum', 'afx_mmdit_export', 'afx_sumsq', 'afx_adamw_step', 'afx_adamw8bit_step', 'afx_ema_lerp', 'afx_cast_f32_bf16',
-    'afx_qkv_operands', 'afx_norm_modulate_joint_bf16', 'afx_norm_modulate_mx8',
+    'afx_qkv_operands', 'afx_norm_modulate_joint_bf16', 'afx_norm_modulate_mx8', 'afx_forward_diffuse_pack',
 ]
 
 AFX_BLOCK_DOUBLE, AFX_BLOCK_SINGLE = 0, 1
@@ -158,6 +158,7 @@ def load() -> C.CDLL:
     lib.afx_mse_loss.argtypes = [vp, vp, f32, vp, vp, i64, vp]
     lib.afx_euler_roll.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp]
     lib.afx_axpby_rows.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp]
+    lib.afx_forward_diffuse_pack.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.afx_cfg_combine.argtypes = [vp, vp, f32, vp, i64, vp]
     lib.afx_head_grad.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]
     lib.afx_linear_bf16_f32out.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp]

@@ -540,6 +540,58 @@ __global__ __launch_bounds__(256) void cfg_kernel(const float* __restrict__ pos,
   if (i < n) out[i] = pos[i] + (pos[i] - neg[i]) * (scale - 1.0f);
 }
 
+// x_t = x0 (1 - sigma[b]) + noise sigma[b], folded from the cache's [B,C,H,W] latents into the engine's [B,N,4C] tokens
+// (channel = c*4 + ph*2 + pw) in the same pass (gaussian_flow.py:83-88 after latent_diffusion_text_image.py:51).
+// One thread = (sample, token row hh, channel quad, token column ww), ww fastest: consecutive lanes read consecutive
+// float2 of one latent row (8 B x wp contiguous per (channel, sub-row)) and each lane owns 16 consecutive output channels
+// (64 B of noise in, 64 B of fp32 + 32 B of bf16 out).
+__global__ __launch_bounds__(256) void forward_diffuse_pack_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                   const float* __restrict__ sigma, float* __restrict__ xt,
+                                                                   bf16_t* __restrict__ xt16, int C, int H, int W, int64_t total) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int wp = W >> 1, hp = H >> 1, nq = C >> 2;
+  const int ww = (int)(t % wp);
+  int64_t r = t / wp;
+  const int cq = (int)(r % nq);
+  r /= nq;
+  const int hh = (int)(r % hp);
+  const int64_t b = r / hp;
+  const float s = sigma[b], a = 1.0f - s;
+  const float* src = x0 + ((b * C + cq * 4) * H + 2 * hh) * (int64_t)W + 2 * ww;
+  const int64_t o = ((b * hp + hh) * (int64_t)wp + ww) * (4 * C) + cq * 16;
+  float v[16];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph) {
+      const float2 p = *reinterpret_cast<const float2*>(src + ((int64_t)c * H + ph) * W);
+      v[c * 4 + ph * 2] = p.x;
+      v[c * 4 + ph * 2 + 1] = p.y;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 n = *reinterpret_cast<const float4*>(noise + o + 4 * i);
+    float4 y;
+    y.x = v[4 * i] * a + n.x * s;
+    y.y = v[4 * i + 1] * a + n.y * s;
+    y.z = v[4 * i + 2] * a + n.z * s;
+    y.w = v[4 * i + 3] * a + n.w * s;
+    *reinterpret_cast<float4*>(xt + o + 4 * i) = y;
+    v[4 * i] = y.x; v[4 * i + 1] = y.y; v[4 * i + 2] = y.z; v[4 * i + 3] = y.w;
+  }
+  if (xt16 != nullptr) {
+    float h[8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) h[e] = v[8 * i + e];
+      *reinterpret_cast<u32x4_t*>(xt16 + o + 8 * i) = pack8(h);
+    }
+  }
+}
+
 // LoRA input dropout (peft: y = W x + B A dropout(x); the engine folds B A into W, so what remains is the zero-mean
 // correction B A (x . delta), delta = keep / (1 - p) - 1).  keep(row, col) is a counter-based hash of (seed, global row, col):
 // the batched forward and the per-sample recompute / backward regenerate identical masks from the seed.
@@ -798,6 +850,20 @@ int afx_euler_roll(const float* x_a, const float* u, const float* sigma_a, const
   if (n == 0) return AFX_OK;
   hipLaunchKernelGGL(euler_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, x_a, u, sigma_a, sigma_b, out,
                      per_sample, n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_forward_diffuse_pack(const float* x0, const float* noise, const float* sigma, float* xt_f32, void* xt_bf16,
+                             int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+  if (!x0 || !noise || !sigma || !xt_f32 || B < 0 || C * 4 != 64 || H < 2 || W < 2 || (H & 1) || (W & 1))
+    return fail(AFX_E_INVALID, "bad argument to afx_forward_diffuse_pack (need 4 C = 64 channels, even H and W)");
+  if (((uintptr_t)x0 & 7) || ((uintptr_t)noise & 15) || ((uintptr_t)xt_f32 & 15) || ((uintptr_t)xt_bf16 & 15))
+    return fail(AFX_E_INVALID, "afx_forward_diffuse_pack: x0 must be 8-byte aligned, noise / xt_f32 / xt_bf16 16-byte aligned");
+  const int64_t total = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
+  if (total == 0) return AFX_OK;
+  hipLaunchKernelGGL(forward_diffuse_pack_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x0, noise, sigma,
+                     xt_f32, (bf16_t*)xt_bf16, C, H, W, total);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

@@ -415,6 +415,26 @@ def euler_roll(x_a, u, sigma_a, sigma_b):
     return out
 
 
+def forward_diffuse_pack(x0, noise, sigma, want_bf16: bool = True):
+    """x_t = x0 (1 - sigma[b]) + noise sigma[b] in the engine's token layout: x0 [B,16,H,W] fp32 latents, noise [B,N,64] token-major,
+    sigma [B] -> (x_t [B,N,64] fp32, its bf16 rounding or None)."""
+    lib = _lib.load()
+    x0, noise = _cuda(x0, torch.float32), _cuda(noise, torch.float32)
+    if x0.dim() != 4 or x0.shape[2] % 2 or x0.shape[3] % 2:
+        raise ValueError(f'x0: need [B, C, H, W] latents with even H and W, got {tuple(x0.shape)}')
+    B, Cc, H, W = x0.shape
+    N = (H // 2) * (W // 2)
+    if tuple(noise.shape) != (B, N, 4 * Cc):
+        raise ValueError(f'noise: need the token layout {(B, N, 4 * Cc)}, got {tuple(noise.shape)}')
+    sg = _cuda(sigma.flatten(), torch.float32)
+    if sg.numel() != B:
+        raise ValueError(f'sigma: need {B} values, got {sg.numel()}')
+    xt = torch.empty_like(noise)
+    xt16 = torch.empty(noise.shape, dtype=torch.bfloat16, device=noise.device) if want_bf16 else None
+    _lib.check(lib.afx_forward_diffuse_pack(_p(x0), _p(noise), _p(sg), _p(xt), _p(xt16), B, Cc, H, W, _s()))
+    return xt, xt16
+
+
 def axpby_rows(a, alpha, b, beta):
     """alpha[s] * a + beta[s] * b with per-sample scalars alpha, beta [B]."""
     lib = _lib.load()

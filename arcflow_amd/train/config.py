@@ -13,6 +13,7 @@ from typing import Any, Dict, Tuple
 from .distill import DistillConfig
 
 _FAMILY = {'ArcFluxTransformer2DModel': 'flux', 'ArcQwenImageTransformer2DModel': 'qwen'}
+_MODE = {'ArcFlowImitationDataFree': 'data_free', 'ArcFlowImitation': 'data'}        # diffusion.type -> DistillConfig.mode (arcflow.py:275,339)
 
 
 def _merge(base: Dict[str, Any], over: Dict[str, Any]) -> Dict[str, Any]:
@@ -61,6 +62,8 @@ def distill_setup(cfg: Dict[str, Any]) -> Tuple[str, Dict[str, Any], DistillConf
     """-> (family, MMDiTEngine kwargs, DistillConfig, run parameters)."""
     diff = cfg['model']['diffusion']
     den = diff['denoising']
+    if diff.get('type') not in _MODE:
+        raise ValueError(f"unsupported diffusion type {diff.get('type')!r} (supported: {sorted(_MODE)})")
     if den['type'] not in _FAMILY:
         raise ValueError(f"unsupported denoising type {den['type']!r}")
     family = _FAMILY[den['type']]
@@ -95,7 +98,8 @@ def distill_setup(cfg: Dict[str, Any]) -> Tuple[str, Dict[str, Any], DistillConf
         lora_rank=den.get('lora_rank', 0) if den.get('use_lora', False) else 0,
         lora_dropout=den.get('lora_dropout', 0.0) if den.get('use_lora', False) else 0.0,
         # not in the reference's configs (it has no fp8 path): train_cfg.teacher_fp8 / student_fp8, e.g. --cfg-options train_cfg.student_fp8=True
-        teacher_fp8=bool(tc.get('teacher_fp8', False)), student_fp8=bool(tc.get('student_fp8', False)))
+        teacher_fp8=bool(tc.get('teacher_fp8', False)), student_fp8=bool(tc.get('student_fp8', False)),
+        mode=_MODE[diff['type']])
     runner = cfg.get('runner', {})
     ck = cfg.get('checkpoint_config', {})
     run = dict(name=cfg.get('name', 'arcflow'), total_iters=cfg.get('total_iters', 10000),

@@ -227,7 +227,8 @@ class PromptEmbedCache:
 
 
 def collate(items: List[dict], device='cuda') -> dict:
-    """A batch of cache items -> the ``cond`` dict ``ArcFlowDistiller.train_step`` takes."""
+    """A batch of cache items -> the ``cond`` dict ``ArcFlowDistiller.train_step`` takes.  Items read with ``load_latents=True`` also
+    give ``latents`` [B, C, H, W] fp32 on ``device``: the ``x0`` of the data mode (the caller takes it out of the dict)."""
     sizes = {it['latent_size'] for it in items}
     if len(sizes) != 1:
         raise ValueError(f'mixed latent sizes in one batch: {sorted(sizes)} (use bucketize=True)')
@@ -251,4 +252,9 @@ def collate(items: List[dict], device='cuda') -> dict:
         cond['negative_prompt_embeds'] = stack(nk)
         if 'pooled_projections' in nk[0]:
             cond['negative_pooled'] = torch.stack([k['pooled_projections'] for k in nk]).to(device=device, dtype=torch.bfloat16)
+    if 'latents' in items[0]:
+        lat = torch.stack([it['latents'].reshape(it['latents'].shape[-3:]) for it in items])
+        if tuple(lat.shape[2:]) != (h, w):
+            raise ValueError(f'latents {tuple(lat.shape)} do not match latent_size {(h, w)} of the records')
+        cond['latents'] = lat.to(device=device, dtype=torch.float32)
     return cond

@@ -1,5 +1,6 @@
-"""Data-free trajectory-matching distillation step (the reference's ``ArcFlowImitationDataFree``,
-lakonlab/models/diffusions/arcflow.py:338-426, driven by ``train_fwd_bwd`` lakonlab/models/base_diffusion.py:14-62
+"""Trajectory-matching distillation step: data-free (the reference's ``ArcFlowImitationDataFree``,
+lakonlab/models/diffusions/arcflow.py:338-426; ``DistillConfig.mode = 'data_free'``, the default) or from cached latents
+(``ArcFlowImitation``, arcflow.py:275-335; ``mode = 'data'``, described at the end), driven by ``train_fwd_bwd`` lakonlab/models/base_diffusion.py:14-62
 and ``BaseModel.train_step`` lakonlab/models/base.py:76-103,162-189) on one MI355X per process.
 
 Per iteration and student step (nfe = 2):
@@ -19,6 +20,11 @@ norm_out and (``lora_rank`` > 0) the rank-r LoRA adapters incl. the timestep-emb
 both student steps accumulate into ONE gradient buffer whose slices are all-reduced once each (train/reducer.py).
 Batches above 4 samples per GPU run as micro-batches of <= 4 (the engine's grouped launches hold 4 samples; the
 reference micro-batches the same way, ``grad_accum_batch_size``, configs/flux/_ddp_train.py:14).
+
+Data mode (``train_step(..., x0=latents)``): every sample draws ONE segment of the nfe grid (``sample_t``), its latent is noised to
+that segment's start and folded into the token layout by one kernel (``ops.forward_diffuse_pack``), and that one segment is
+trained -- no roll to the segment end, no segment weight on the loss (arcflow.py:331 against :403).  Segment size, window and
+interval scalings are then per-sample [B] tensors, as in the reference where ``segment_size`` is a tensor (arcflow.py:130-161).
 """
 from __future__ import annotations
 
@@ -69,11 +75,31 @@ class DistillConfig:
     teacher_fp8: bool = False             # BASELINE.json configs[4]: frozen teacher forwards on the fp8 MFMA (student + grads stay bf16)
     student_fp8: bool = False             # configs[4] "fp8 MFMA fwd + bf16 grads": the student's block linears run their forward (and the
                                           # backward's recompute) on the fp8 MFMA, dgrad / LoRA gradients stay bf16 (train/trunk.py enable_fp8)
+    mode: str = 'data_free'               # 'data_free': ArcFlowImitationDataFree (noise start, all nfe segments); 'data': ArcFlowImitation
+                                          # (cached latents, one drawn segment per sample)
+
+    def __post_init__(self):
+        if self.mode not in ('data_free', 'data'):
+            raise ValueError(f"mode must be 'data_free' or 'data', got {self.mode!r}")
 
 
 def warp(t: torch.Tensor, shift: float) -> torch.Tensor:
     """sigma = s t / (1 + (s-1) t)   (ContinuousTimeStepSampler.warp_t, sampler.py:46-48)."""
     return shift * t / (1 + (shift - 1) * t)
+
+
+def sample_t(u: torch.Tensor, nfe: int, timestep_ratio: float = 1.0, shift: float = 3.2, eps: float = 1e-4):
+    """One segment of the nfe grid per sample from uniform draws u [B] (ArcFlowImitation.sample_t, arcflow.py:277-302; the sampler
+    draws raw_t = 1 - rand, sampler.py:68).  Segments are counted from the clean end: index 1 is the final (``timestep_ratio``-scaled)
+    one, index nfe starts at raw_t = 1.  Returns (raw_t_src [B], sigma_src [B], segment [B])."""
+    ratio = max(timestep_ratio, eps)
+    rest = 1 - ratio
+    base = 1 / (nfe - rest)
+    raw_t = (1 - u).clamp(min=eps)
+    idx = torch.ceil(raw_t / base + rest).clamp(min=1).clamp(max=nfe)
+    raw_src = ((idx - rest) * base).clamp(min=eps, max=1)
+    segment = torch.where(idx == 1, ratio * base, base).to(raw_src.dtype)
+    return raw_src, warp(raw_src, shift), segment
 
 
 class ArcFlowDistiller:
@@ -235,10 +261,10 @@ class ArcFlowDistiller:
         """Seed of the LoRA dropout masks of one student step: differs per iteration, step and rank (train.py --diff_seed)."""
         return (self.iteration * 7919 + step_id * 104729 + self.reducer.rank * 15485863 + getattr(self, '_chunk', 0) * 32452843 + 12345) & 0x7fffffff
 
-    def _student(self, x, sigma, cond):
+    def _student(self, x, sigma, cond, x_bf16=None):
         if self.trunk is not None:
             self.trunk.ensure_merged()      # the engine must see W + B A of the LIVE adapters (stale after every optimizer step / checkpoint load)
-        return self.student(x.to(torch.bfloat16), sigma, cond['prompt_embeds'], cond.get('pooled'),
+        return self.student(x.to(torch.bfloat16) if x_bf16 is None else x_bf16, sigma, cond['prompt_embeds'], cond.get('pooled'),
                             self._guid(x.shape[0]), cond['hp'], cond['wp'])
 
     def student_forward(self, x, sigma, cond):
@@ -280,12 +306,12 @@ class ArcFlowDistiller:
         neg = self.teacher(xb, sigma, cond['negative_prompt_embeds'], cond.get('negative_pooled'), g, cond['hp'], cond['wp'], prepared_step=neg_prep).float()
         return ops.cfg_combine(pos, neg, self.cfg.teacher_guidance_scale)
 
-    def student_forward_unmerged(self, x_src, sigma_src, cond, p_drop: float = 0.0, seed: int = 0):
+    def student_forward_unmerged(self, x_src, sigma_src, cond, p_drop: float = 0.0, seed: int = 0, x_bf16=None):
         """The student's forward as peft evaluates it -- y = W x + B (A dropout(x)) per adapted linear, NOT folded into W -- on the
         LoRA trunk: the engine runs conditioning + embedders (stage 1, with the timestep embedding of the LoRA-adapted embedder
         handed in) and norm_out + head (stage 2); the blocks in between go through the trunk's own block forward, which also keeps
         every block's input (checkpoint) and the pre-gate branch outputs the modulation gradients need.  Returns
-        (ArcFlowModelOutput, mod_all [B, n_mod])."""
+        (ArcFlowModelOutput, mod_all [B, n_mod]).  x_bf16: the bf16 rounding of x_src when the caller already has it."""
         B, N, _ = x_src.shape
         T = cond['prompt_embeds'].shape[1]
         dev = self.device
@@ -297,7 +323,7 @@ class ArcFlowDistiller:
         self.student.set_checkpoint_buffer(None)
         temb_t = self.trunk.temb_forward(sigma_src)
         self.student.set_temb_override(temb_t)
-        args = (x_src.to(torch.bfloat16), sigma_src, cond['prompt_embeds'], cond.get('pooled'), self._guid(B), cond['hp'], cond['wp'])
+        args = (x_src.to(torch.bfloat16) if x_bf16 is None else x_bf16, sigma_src, cond['prompt_embeds'], cond.get('pooled'), self._guid(B), cond['hp'], cond['wp'])
         self.student(*args, stage=1)
         xt = torch.empty(B * (T + N), self.D, dtype=torch.bfloat16, device=dev)
         mod_all = torch.empty(B, self.student.n_mod, dtype=torch.float32, device=dev)
@@ -311,9 +337,15 @@ class ArcFlowDistiller:
         return out, mod_all
 
     # ------------------------------------------------------------------ one student segment
-    def _segment(self, step_id: int, x_src, raw_src, cond, teacher_ratio: float, segment: float, rng, draws=None,
-                 batch_total: Optional[int] = None, final: bool = False):
+    def _segment(self, step_id: int, x_src, raw_src, cond, teacher_ratio: float, segment, rng, draws=None,
+                 batch_total: Optional[int] = None, final: bool = False, loss_weight: Optional[float] = None, roll: bool = True,
+                 x_bf16=None):
         """piid_segment_momentum + the head backward of this student step.  Returns (x_dst, raw_dst).
+        segment: the segment size, a float (every sample on the same segment: the data-free walk) or a [B] tensor (data mode;
+        sub-step count, window and interval scalings are then per sample, arcflow.py:130-161).
+        loss_weight: factor on the segment's loss; None = the float ``segment`` (arcflow.py:403), data mode passes 1 (arcflow.py:331).
+        roll: also roll the policy to the segment end (get_x_t_dst); without it x_dst is None.
+        x_bf16: the bf16 rounding of x_src when the caller already has it (ops.forward_diffuse_pack).
         batch_total: samples of the whole per-GPU batch (the loss is a mean over it; x_src may be a micro-batch of it).
         final: this is the last gradient-producing call of the iteration -> finished slices of the flat gradient buffer
         are handed to the reducer as the last sample's backward leaves them."""
@@ -332,9 +364,9 @@ class ArcFlowDistiller:
                 self._ckpt = torch.empty(nb, B * (T + N), self.D, dtype=torch.bfloat16, device=dev)
         mod_all = None
         if self.trunk is not None:
-            out, mod_all = self.student_forward_unmerged(x_src, sigma_src, cond, c.lora_dropout, self.dropout_seed(step_id))
+            out, mod_all = self.student_forward_unmerged(x_src, sigma_src, cond, c.lora_dropout, self.dropout_seed(step_id), x_bf16=x_bf16)
         else:
-            out = self._student(x_src, sigma_src, cond)
+            out = self._student(x_src, sigma_src, cond, x_bf16=x_bf16)
         means, logw, logg = out.means, out.logweights, out.loggammas
         xn = torch.empty(B * N, self.D, dtype=torch.bfloat16, device=dev)
         xf = torch.empty(B * N, self.D, dtype=torch.bfloat16, device=dev)
@@ -349,8 +381,18 @@ class ArcFlowDistiller:
             mod_all = torch.empty(B, self.student.n_mod, dtype=torch.float32, device=dev)
             self.student.export('mod_all', mod_all, B, N, T)
 
-        n_sub = max(round(segment * c.total_substeps), 1)
-        window = min(c.window_substeps * (segment / n_sub), segment)
+        if torch.is_tensor(segment):            # per sample, fp32 like the reference's tensor segment_size
+            if loss_weight is None:
+                raise ValueError('a per-sample segment needs an explicit loss_weight')
+            segment = segment.to(device=dev, dtype=torch.float32).flatten().expand(B)
+            n_sub = (segment * c.total_substeps).round().clamp(min=1)
+            window = torch.minimum(c.window_substeps * (segment / n_sub), segment)
+            span = (segment - window).unsqueeze(-1)                          # [B, 1]: scales the [B, n] interval draws
+        else:
+            n_sub = max(round(segment * c.total_substeps), 1)
+            window = min(c.window_substeps * (segment / n_sub), segment)
+            span = segment - window
+            loss_weight = segment if loss_weight is None else loss_weight
         raw_dst = raw_src - segment
         # GM dropout of the roll-out policy (policies/arcflow.py:96-106)
         n = c.num_intermediate_states
@@ -362,7 +404,6 @@ class ArcFlowDistiller:
         drop &= ~drop.all(dim=1, keepdim=True)
         if c.gm_dropout <= 0:
             drop = None
-        span = segment - window
         s_iv = torch.sort(u_stu * ((1 - teacher_ratio) * span), dim=-1)[0]
         s_iv = torch.diff(s_iv, dim=-1, prepend=torch.zeros(B, 1, device=dev))
         t_iv = torch.sort(u_tea, dim=-1)[0]
@@ -372,7 +413,7 @@ class ArcFlowDistiller:
         d_means = torch.zeros(B, N, K, ch, dtype=torch.float32, device=dev)
         d_logw = torch.zeros(B, N, K, pp, dtype=torch.float32, device=dev)
         d_logg = torch.zeros(B, N, K - 1, pp, dtype=torch.float32, device=dev)
-        coef = c.loss_scale / (n * batch_total * N * ch) * segment          # mean over the 4B stacked states x segment weight
+        coef = c.loss_scale / (n * batch_total * N * ch) * loss_weight      # mean over the 4B stacked states x segment weight
         x, raw, sigma = x_src, raw_src, sigma_src
         one = torch.ones(B, device=dev)
         # the teacher's timesteps depend on the interval draws only, not on the roll-out: the modulation vectors of the next `chunk` teacher states come out of
@@ -409,7 +450,7 @@ class ArcFlowDistiller:
             sigma_b = warp(raw_b, c.shift)
             x = ops.euler_roll(x_a, tgt, sigma_a, sigma_b)
             raw, sigma = raw_b, sigma_b
-        x_dst = ops.arcflow_step_dropout(x, means, logw, logg, sigma_src, sigma, warp(raw_dst, c.shift), drop, c.eps)
+        x_dst = ops.arcflow_step_dropout(x, means, logw, logg, sigma_src, sigma, warp(raw_dst, c.shift), drop, c.eps) if roll else None
 
         # ---- backward: head logits -> head weights / bias, norm_out modulation -> norm_out.linear ---------------
         gbuf = self.grad
@@ -470,17 +511,34 @@ class ArcFlowDistiller:
         return c.lr
 
     def train_step(self, cond: dict, batch: int, rng: Optional[torch.Generator] = None, x_init: Optional[torch.Tensor] = None,
-                   draws=None):
+                   draws=None, x0: Optional[torch.Tensor] = None, t_draws: Optional[torch.Tensor] = None,
+                   noise: Optional[torch.Tensor] = None):
         """cond: prompt_embeds [B,T,joint] (+ pooled, negative_*), hp, wp.  Returns a dict of python floats
-        (loss, grad_norm, lr, teacher_ratio, skipped) -- one host sync per step, like the reference's float(loss)."""
+        (loss, grad_norm, lr, teacher_ratio, skipped) -- one host sync per step, like the reference's float(loss).
+        Data mode: x0 = the latents [batch, 16, 2 hp, 2 wp] (fp32, on the device); t_draws [batch] uniforms for ``sample_t`` and
+        noise [batch, N, 64] (token layout) are drawn from ``rng`` when absent, in the reference's order (arcflow.py:319-321);
+        ``draws`` holds the one segment's tuple, ``draws[0]``."""
         c = self.cfg
+        data = c.mode == 'data'
+        if data and x0 is None:
+            raise ValueError("mode 'data' trains from latents: pass x0 [batch, 16, H, W]")
+        if not data and (x0 is not None or t_draws is not None or noise is not None):
+            raise ValueError("x0 / t_draws / noise belong to mode 'data'; this distiller is configured 'data_free'")
+        if data and x_init is not None:
+            raise ValueError("x_init belongs to mode 'data_free'; in mode 'data' the start state is x0 noised to the drawn segment")
         N = cond['hp'] * cond['wp']
+        if data and (x0.dim() != 4 or x0.shape[0] != batch or tuple(x0.shape[2:]) != (2 * cond['hp'], 2 * cond['wp'])):
+            raise ValueError(f"x0 must be [batch={batch}, C, {2 * cond['hp']}, {2 * cond['wp']}] (cond hp / wp), got {tuple(x0.shape)}")
         it = self.iteration
         teacher_ratio = 1 - min(it, c.num_decay_iters) / c.num_decay_iters if c.num_decay_iters > 0 else 0.0
         self.grad.zero_()
         self._loss_acc.zero_()
         self._launched = []
-        x_all = x_init if x_init is not None else torch.randn(batch, N, self.C, device=self.device, generator=rng)
+        if data:
+            u_all = t_draws.to(self.device) if t_draws is not None else torch.rand(batch, device=self.device, generator=rng)
+            x_all = noise if noise is not None else torch.randn(batch, N, self.C, device=self.device, generator=rng)
+        else:
+            x_all = x_init if x_init is not None else torch.randn(batch, N, self.C, device=self.device, generator=rng)
         base = 1.0 / (c.nfe - 1 + max(c.timestep_ratio, c.eps))
         chunks = [(a, min(a + 4, batch)) for a in range(0, batch, 4)]      # micro-batches of <= 4 samples
         outs = []
@@ -490,6 +548,14 @@ class ArcFlowDistiller:
             raw = torch.ones(b - a, device=self.device)
             cc = cond if len(chunks) == 1 else {k: (v[a:b] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == batch else v)
                                                 for k, v in cond.items()}
+            if data:       # one drawn segment per sample, from x0 noised to its start
+                raw, sigma, seg = sample_t(u_all[a:b], c.nfe, c.timestep_ratio, c.shift, c.eps)
+                x, x16 = ops.forward_diffuse_pack(x0[a:b], x, sigma)
+                dr = None if draws is None else tuple(d[a:b] for d in draws[0])
+                self._segment(0, x, raw, cc, teacher_ratio, seg, rng, dr, batch_total=batch, final=(ci == len(chunks) - 1),
+                              loss_weight=1.0, roll=False, x_bf16=x16)
+                outs.append(x)
+                continue
             for step_id in range(c.nfe):
                 seg = base * max(c.timestep_ratio, c.eps) if step_id == c.nfe - 1 else base
                 dr = None if draws is None else tuple(d[a:b] for d in draws[step_id])

@@ -191,6 +191,12 @@ int afx_mse_loss(const float* pred, const float* target, float coef, float* grad
 /* x_out = x_a + u * (sigma_b[b] - sigma_a[b])   teacher Euler roll (arcflow.py:189-192) */
 int afx_euler_roll(const float* x_a, const float* u, const float* sigma_a, const float* sigma_b, float* out,
                    int32_t batch, int64_t per_sample, void* stream);
+/* xt = x0 * (1 - sigma[b]) + noise * sigma[b] (fp32), with x0 the cached latents [B,C,H,W] and noise / xt in the engine's token
+ * layout [B, (H/2)(W/2), 4C], channel = c*4 + ph*2 + pw: the patchify of latent_diffusion_text_image.py:51 and the forward
+ * diffusion of the data-based trainer (gaussian_flow.py:83-88, called at arcflow.py:321-322) in one pass.  xt_bf16 (may be NULL)
+ * receives the round-to-nearest-even bf16 copy the engine reads.  4C must be 64, H and W even; x0 8-byte, the others 16-byte aligned. */
+int afx_forward_diffuse_pack(const float* x0, const float* noise, const float* sigma, float* xt_f32, void* xt_bf16,
+                             int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
 /* out = alpha[b] * a + beta[b] * b, per-sample scalars: mean velocity (x_a - x_e) / (sigma_a - sigma_e) and the
  * short/long roll-out select of policy_average_u_momentum (arcflow.py:92-110) */
 int afx_axpby_rows(const float* a, const float* alpha, const float* b, const float* beta, float* out, int32_t batch,

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Data-free ArcFlow distillation from one of the reference's config files (same command line as its train.py:47-94):
+"""ArcFlow distillation from one of the reference's config files (same command line as its train.py:47-94), data-free
+(``diffusion.type = 'ArcFlowImitationDataFree'``) or from cached latents (``'ArcFlowImitation'``: ``--data-dir`` must hold records
+with latents, tools/cache_latents.py; ``--synthetic`` draws them):
 
     python tools/train.py configs/flux/arcflux_2nfe_k16.py --diff_seed
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py <config> --launcher pytorch --diff_seed
@@ -116,7 +118,7 @@ def main():
             raise SystemExit(f'teacher_guidance_scale = {dc.teacher_guidance_scale} (true CFG) needs the negative prompt embeddings: '
                              'pass --negative-prompt-embeds <file> (or data.train.negative_prompt_embeds_path in the config)')
         ds = data.PromptEmbedCache(args.data_dir, pad_seq_len=512 if family == 'flux' else None, bucketize=True,
-                                   negative_prompt_embeds_path=neg_path)
+                                   negative_prompt_embeds_path=neg_path, load_latents=dc.mode == 'data')
         sampler = data.DistributedSampler(ds, world, rank, shuffle=True, samples_per_gpu=B, seed=args.seed)
         sampler.set_iter(dist_.iteration)
 
@@ -145,18 +147,28 @@ def main():
                 i += B * world
         loader = prompt_batches()
     else:
+        if dc.mode == 'data' and not args.synthetic:
+            raise SystemExit("diffusion.type 'ArcFlowImitation' trains from latents: pass --data-dir (records with latents) or --synthetic")
         T = 512 if family == 'flux' else 128
         synth = dict(prompt_embeds=(torch.randn(B, T, eng['joint_dim'], device=dev, generator=rng) * 0.1).bfloat16(), hp=args.latent_tokens[0], wp=args.latent_tokens[1])
         if family == 'flux':
             synth['pooled'] = (torch.randn(B, eng['pooled_dim'], device=dev, generator=rng) * 0.1).bfloat16()
         if dc.teacher_guidance_scale > 1.0:
             synth['negative_prompt_embeds'] = (torch.randn(B, T, eng['joint_dim'], device=dev, generator=rng) * 0.1).bfloat16()
+        if dc.mode == 'data':
+            synth['latents'] = torch.randn(B, eng['in_channels'] // 4, 2 * args.latent_tokens[0], 2 * args.latent_tokens[1], device=dev, generator=rng)
 
     total = args.iters if args.iters is not None else run['total_iters']
     t_last = time.perf_counter()
     while dist_.iteration < total:
         cond = next(loader) if loader is not None else synth
-        info = dist_.train_step(cond, B, rng=rng)
+        if dc.mode == 'data':              # the batch's latents are x0; hp / wp in cond come from their size (bucketed batches never mix sizes)
+            if 'latents' not in cond:
+                raise SystemExit("diffusion.type 'ArcFlowImitation' needs latents with every batch (--data-dir with cached latents, or --synthetic)")
+            cond = dict(cond)
+            info = dist_.train_step(cond, B, rng=rng, x0=cond.pop('latents'))
+        else:
+            info = dist_.train_step(cond, B, rng=rng)
         # a background save that failed stops the run now -- on EVERY rank: only the writer's rank sees the error, the others would otherwise walk into the
         # next gradient all-reduce and sit there until the RCCL timeout.  One scalar MAX-reduce per iteration (an iteration is seconds).
         if dist_.reducer.all_reduce_max(1.0 if checkpoint.pending_save_failed() else 0.0, dev) > 0:
