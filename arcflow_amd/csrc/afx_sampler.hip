@@ -1,0 +1,161 @@
+// Teacher sampling (GaussianFlow.forward_test, lakonlab/models/diffusions/gaussian_flow.py:149-222): what runs between two
+// teacher forwards of the Euler ODE loop, on the packed token layout the engine reads and writes.
+//   * teacher_euler_step_kernel: true-CFG combine (guidance_jit, gaussian_flow.py:18-26) + FlowEulerODEScheduler.step
+//     (schedulers/flow_euler_ode.py:141-150) + the bf16 copy of the new latents the next forward reads, in one pass:
+//     16 B per lane and operand (8 bf16 of pos / neg, two float4 of x), grid-stride, no LDS, no atomics.
+//   * cfg_ortho_partial_kernel / cfg_ortho_finish_kernel: the per-sample projection coefficient of orthogonal guidance,
+//     mean(bias pos) / max(mean(pos pos), 1e-6) over all n elements of a sample.  A fixed number of work-groups per sample
+//     (a function of n alone), every product exact in fp64, one workspace slot per work-group, the slots added in index order
+//     by the second launch: bit-reproducible.
+#include <algorithm>
+
+#include "afx_api_util.h"
+#include "afx_common.h"
+
+namespace afx {
+
+// One chunk = 8 consecutive elements of one sample (n % 64 == 0: a chunk never straddles two samples, and a sample's first chunk
+// is 16-byte aligned in every operand).
+__global__ __launch_bounds__(256) void teacher_euler_step_kernel(const float* x, const bf16_t* __restrict__ pos,
+                                                                 const bf16_t* __restrict__ neg, const float* __restrict__ sigma,
+                                                                 const float* __restrict__ sigma_to, const float* __restrict__ coef,
+                                                                 float scale, float* x_out, bf16_t* __restrict__ x_bf16,
+                                                                 int64_t chunks_per_sample, int64_t chunks) {
+  const float sm1 = scale - 1.0f;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += stride) {
+    const int64_t b = c / chunks_per_sample;
+    const float dt = sigma_to[b] - sigma[b];
+    const float cf = coef != nullptr ? coef[b] : 0.f;
+    float p[8], q[8], o[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(pos + c * 8), p);
+    if (neg != nullptr) unpack8(*reinterpret_cast<const u32x4_t*>(neg + c * 8), q);
+    const f32x4_t x0 = *reinterpret_cast<const f32x4_t*>(x + c * 8);        // (x_out may be x: both loads precede both stores)
+    const f32x4_t x1 = *reinterpret_cast<const f32x4_t*>(x + c * 8 + 4);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float u = p[e];
+      if (neg != nullptr) u = p[e] + (p[e] - q[e]) * sm1;
+      if (coef != nullptr) u = u - cf * p[e];
+      o[e] = (e < 4 ? x0[e & 3] : x1[e & 3]) + u * dt;
+    }
+    const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8 + 4) = o1;
+    *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
+  }
+}
+
+AFX_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// grid (parts, B): work-group w of sample b owns the chunks [w cpw, min((w + 1) cpw, chunks_per_sample)) and writes
+// ws[(b parts + w) 2 + {0, 1}] = sum bias pos, sum pos pos  (bias = fl(fl(pos - neg) (scale - 1)), the step kernel's fp32 value)
+__global__ __launch_bounds__(256) void cfg_ortho_partial_kernel(const bf16_t* __restrict__ pos, const bf16_t* __restrict__ neg,
+                                                                float scale, double* __restrict__ ws, int64_t chunks_per_sample,
+                                                                int64_t cpw) {
+  __shared__ double red[4][2];
+  const float sm1 = scale - 1.0f;
+  const int64_t b = blockIdx.y;
+  const int64_t begin = (int64_t)blockIdx.x * cpw;
+  const int64_t end = begin + cpw < chunks_per_sample ? begin + cpw : chunks_per_sample;
+  const bf16_t* ps = pos + b * chunks_per_sample * 8;
+  const bf16_t* ns = neg + b * chunks_per_sample * 8;
+  double s_bp = 0.0, s_pp = 0.0;
+  for (int64_t c = begin + threadIdx.x; c < end; c += 256) {
+    float p[8], q[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(ps + c * 8), p);
+    unpack8(*reinterpret_cast<const u32x4_t*>(ns + c * 8), q);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float bias = (p[e] - q[e]) * sm1;
+      s_bp += (double)bias * (double)p[e];
+      s_pp += (double)p[e] * (double)p[e];
+    }
+  }
+  s_bp = wave_sum_f64(s_bp);
+  s_pp = wave_sum_f64(s_pp);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave][0] = s_bp;
+    red[wave][1] = s_pp;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* slot = ws + (b * gridDim.x + blockIdx.x) * 2;
+    slot[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    slot[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+  }
+}
+
+__global__ __launch_bounds__(64) void cfg_ortho_finish_kernel(const double* __restrict__ ws, float* __restrict__ coef, int batch,
+                                                              int parts, double inv_n) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch) return;
+  double s_bp = 0.0, s_pp = 0.0;
+  for (int w = 0; w < parts; ++w) {            // index order: the sum does not depend on which work-group finished first
+    s_bp += ws[((int64_t)b * parts + w) * 2];
+    s_pp += ws[((int64_t)b * parts + w) * 2 + 1];
+  }
+  const double den = s_pp * inv_n > 1e-6 ? s_pp * inv_n : 1e-6;
+  coef[b] = (float)(s_bp * inv_n / den);
+}
+
+}  // namespace afx
+
+using namespace afx;
+
+// work-groups per sample of the coefficient reduction: one per 8192 elements, at most 64 -- a function of n alone
+static inline int ortho_parts(int64_t n) { return (int)std::min<int64_t>(64, std::max<int64_t>(1, (n + 8191) / 8192)); }
+
+extern "C" {
+
+int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, const float* sigma, const float* sigma_to,
+                           const float* coef, float scale, float* x_out, void* x_out_bf16, int32_t batch, int64_t n,
+                           int32_t max_blocks, void* stream) {
+  if (!x || !pos || !sigma || !sigma_to || !x_out || !x_out_bf16) return fail(AFX_E_INVALID, "null argument to afx_teacher_euler_step");
+  if (batch < 0 || n < 64 || n % 64 || max_blocks < 0)
+    return fail(AFX_E_INVALID, "bad argument to afx_teacher_euler_step (n = tokens x channels must be a positive multiple of 64)");
+  if (((uintptr_t)x & 15) || ((uintptr_t)pos & 15) || ((uintptr_t)neg & 15) || ((uintptr_t)x_out & 15) || ((uintptr_t)x_out_bf16 & 15))
+    return fail(AFX_E_INVALID, "afx_teacher_euler_step: x, pos, neg, x_out and x_out_bf16 must be 16-byte aligned");
+  if (batch == 0) return AFX_OK;
+  const int64_t cps = n / 8, chunks = cps * batch;
+  // 8 work-groups per CU (256 CUs) hide the load latency of a streaming pass; more only add launch work
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
+  hipLaunchKernelGGL(teacher_euler_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos,
+                     (const bf16_t*)neg, sigma, sigma_to, coef, scale, x_out, (bf16_t*)x_out_bf16, cps, chunks);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int64_t afx_cfg_ortho_ws_bytes(int32_t batch, int64_t n) {
+  if (batch < 0 || n < 64 || n % 64) return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_cfg_ortho_ws_bytes");
+  return (int64_t)batch * ortho_parts(n) * 2 * (int64_t)sizeof(double);
+}
+
+int afx_cfg_ortho_coef(const void* pos, const void* neg, float scale, float* coef, void* ws, int64_t ws_bytes, int32_t batch,
+                       int64_t n, void* stream) {
+  if (!pos || !neg || !coef || !ws) return fail(AFX_E_INVALID, "null argument to afx_cfg_ortho_coef");
+  if (batch < 0 || batch > 65535 || n < 64 || n % 64)
+    return fail(AFX_E_INVALID, "bad argument to afx_cfg_ortho_coef (n = tokens x channels must be a positive multiple of 64)");
+  if (((uintptr_t)pos & 15) || ((uintptr_t)neg & 15) || ((uintptr_t)ws & 7))
+    return fail(AFX_E_INVALID, "afx_cfg_ortho_coef: pos and neg must be 16-byte aligned, ws 8-byte aligned");
+  const int parts = ortho_parts(n);
+  if (ws_bytes < (int64_t)batch * parts * 2 * (int64_t)sizeof(double))
+    return fail(AFX_E_INVALID, "afx_cfg_ortho_coef: workspace smaller than afx_cfg_ortho_ws_bytes()");
+  if (batch == 0) return AFX_OK;
+  const int64_t cps = n / 8, cpw = (cps + parts - 1) / parts;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cfg_ortho_partial_kernel, dim3(parts, batch), dim3(256), 0, st, (const bf16_t*)pos, (const bf16_t*)neg, scale,
+                     (double*)ws, cps, cpw);
+  hipLaunchKernelGGL(cfg_ortho_finish_kernel, dim3((batch + 63) / 64), dim3(64), 0, st, (const double*)ws, coef, batch, parts,
+                     1.0 / (double)n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+}  // extern "C"

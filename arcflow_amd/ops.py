@@ -454,6 +454,68 @@ def cfg_combine(pos, neg, scale: float):
     return out
 
 
+def _packed(t: torch.Tensor, dtype, shape, name: str) -> torch.Tensor:
+    """An operand of the teacher-sampler kernels: on the GPU, ``dtype``, contiguous, exactly ``shape`` -- passed as it is (no copy)."""
+    if t.device.type != 'cuda':
+        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name}: need a contiguous {dtype} tensor of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype} strides {t.stride()}')
+    return t
+
+
+def cfg_ortho_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
+    """Workspace of cfg_ortho_coef for [batch, n] velocities (afx_cfg_ortho_ws_bytes): fp64 partial sums, one pair per work-group."""
+    need = _lib.load().afx_cfg_ortho_ws_bytes(batch, n)
+    if need < 0:
+        _lib.check(int(need))
+    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+
+
+def cfg_ortho_coef(pos, neg, scale: float, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """coef [B] fp32 = mean(bias pos) / max(mean(pos pos), 1e-6) per sample over every other dimension, bias = (pos - neg)(scale - 1):
+    the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25).  pos, neg [B, ...] bf16 teacher velocities with
+    numel / B a multiple of 64.  Bit-reproducible (fixed partition, exact fp64 products, ordered sum).  out / ws: reuse buffers."""
+    lib = _lib.load()
+    if pos.device.type != 'cuda' or neg.device.type != 'cuda':
+        raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    B = pos.shape[0]
+    n = pos[0].numel() if B else 0
+    pos = _packed(pos, torch.bfloat16, pos.shape, 'pos')
+    neg = _packed(neg, torch.bfloat16, pos.shape, 'neg')
+    out = torch.empty(B, dtype=torch.float32, device=pos.device) if out is None else _packed(out, torch.float32, (B,), 'out')
+    if ws is None:
+        ws = cfg_ortho_ws(B, n, pos.device)
+    elif ws.device.type != 'cuda' or not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.cfg_ortho_ws)')
+    _lib.check(lib.afx_cfg_ortho_coef(_p(pos), _p(neg), scale, _p(out), _p(ws), ws.numel() * ws.element_size(), B, n, _s()))
+    return out
+
+
+def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
+    """One step of the teacher's Euler ODE sampler in one launch (afx_teacher_euler_step):
+    x + (pos + (pos - neg)(scale - 1) - coef[b] pos)(sigma_to[b] - sigma[b]) -> (fp32 latents, their bf16 rounding).
+    x [B, ...] fp32; pos, neg (None: no guidance) bf16 of the same shape; sigma, sigma_to, coef (None: not orthogonal) [B] fp32.
+    out may be x (in place).  numel / B must be a multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
+    lib = _lib.load()
+    for t in (x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
+        if t is not None and t.device.type != 'cuda':
+            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    B = x.shape[0]
+    n = x[0].numel() if B else 0
+    x = _packed(x, torch.float32, x.shape, 'x')
+    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
+    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
+    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
+    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
+    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    _lib.check(lib.afx_teacher_euler_step(_p(x), _p(pos), _p(neg), _p(sigma), _p(sigma_to), _p(coef), scale, _p(out), _p(out_bf16), B, n,
+                                          max_blocks, _s()))
+    return out, out_bf16
+
+
 def head_grad(d_means, d_logw, d_logg, logw_out, ldy: int):
     lib = _lib.load()
     B, N, K, ch = d_means.shape

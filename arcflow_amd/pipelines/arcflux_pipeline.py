@@ -151,6 +151,41 @@ class _PipelineBase(ArcFlowLoaderMixin):
         self._current_timestep = None
         return latents
 
+    # teacher sampling ------------------------------------------------------------------------------
+    def _teacher_engine(self) -> MMDiTEngine:
+        """The ``teacher_head=True`` engine of the plain snapshot: the pipeline's own transformer until an adapter is loaded,
+        afterwards a second engine built once from the kept base weights."""
+        if self.transformer is not None and self.transformer.teacher_head:
+            return self.transformer
+        if getattr(self, '_teacher', None) is None:
+            if 'proj_out.weight' not in self._base_state_dict:
+                raise RuntimeError('sample_teacher() needs the plain snapshot\'s velocity head: this pipeline holds an ArcFlow student only and '
+                                   'no base `proj_out` was kept (build it with from_pretrained(<plain snapshot>), or from a state dict that '
+                                   'contains proj_out.weight / proj_out.bias)')
+            self._teacher = self._build_engine(teacher_head=True)
+            self._teacher.load_state_dict(self._base_state_dict)
+        return self._teacher
+
+    def _euler_scheduler_kwargs(self) -> Dict[str, Any]:
+        """The pipeline scheduler's shift settings in FlowEulerODEScheduler's names (diffusers counts ``image_seq_len`` in tokens)."""
+        c = self.scheduler.config
+        return dict(num_train_timesteps=c.get('num_train_timesteps', 1000), shift=c.get('shift', 1.0),
+                    use_dynamic_shifting=bool(c.get('use_dynamic_shifting', False)), base_seq_len=c.get('base_image_seq_len', 256),
+                    max_seq_len=c.get('max_image_seq_len', 4096), base_logshift=c.get('base_shift', 0.5), max_logshift=c.get('max_shift', 1.15),
+                    terminal_sigma=c.get('shift_terminal') or None)
+
+    def _sample_teacher(self, cond, batch, height, width, num_inference_steps, guidance_scale, true_cfg_scale, generator, latents,
+                        guidance_interval, orthogonal_guidance):
+        from ..teacher import TeacherSampler
+        engine = self._teacher_engine()
+        latents, hp, wp = self._prepare_latents(batch, height, width, generator, latents)
+        cond = dict(cond, hp=hp, wp=wp)
+        sampler = TeacherSampler(engine, num_inference_steps, guidance_scale=true_cfg_scale, distilled_guidance=guidance_scale,
+                                 guidance_interval=guidance_interval, orthogonal_guidance=orthogonal_guidance, tokens_as_seq_len=True,
+                                 **self._euler_scheduler_kwargs())
+        self._num_timesteps = num_inference_steps
+        return sampler(cond, latents), hp, wp
+
     def _unpack(self, latents, hp, wp):
         b = latents.shape[0]
         return latents.view(b, hp, wp, 16, 2, 2).permute(0, 3, 1, 4, 2, 5).reshape(b, 16, 2 * hp, 2 * wp)
@@ -314,6 +349,10 @@ class ArcFluxPipeline(_PipelineBase):
             return self.transformer.prepare_steps(sigmas, pooled, guidance, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare)
+        return self._finish(latents, hp, wp, output_type, return_dict)
+
+    def _finish(self, latents, hp, wp, output_type, return_dict):
+        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``."""
         if output_type == 'latent':
             image = latents
         else:
@@ -331,3 +370,41 @@ class ArcFluxPipeline(_PipelineBase):
         if not return_dict:
             return (image,)
         return FluxPipelineOutput(images=image)
+
+    @torch.inference_mode()
+    def sample_teacher(self, prompt: Union[str, List[str]] = None, negative_prompt: Union[str, List[str]] = None,
+                       height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
+                       guidance_scale: float = 3.5, true_cfg_scale: float = 1.0,
+                       generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
+                       latents: Optional[torch.FloatTensor] = None, prompt_embeds: Optional[torch.FloatTensor] = None,
+                       pooled_prompt_embeds: Optional[torch.FloatTensor] = None, negative_prompt_embeds: Optional[torch.FloatTensor] = None,
+                       negative_pooled_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = 'pil',
+                       return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
+                       num_images_per_prompt: int = 1, max_sequence_length: int = 512):
+        """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
+        shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
+        guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
+        t = 1000 sigma limits it, ``orthogonal_guidance`` projects it).  Works before ``load_arcflow_adapter()`` on the pipeline's
+        own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
+        transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
+        height = height or self.default_sample_size * self.vae_scale_factor
+        width = width or self.default_sample_size * self.vae_scale_factor
+        self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
+        device = self._execution_device
+        pe, pooled = self.encode_prompt(prompt, None, prompt_embeds, pooled_prompt_embeds, device, num_images_per_prompt, max_sequence_length)
+        cond = dict(prompt_embeds=pe, pooled=pooled)
+        if true_cfg_scale > 1.0:
+            if negative_prompt is None and negative_prompt_embeds is None:
+                raise ValueError('true_cfg_scale > 1 needs `negative_prompt` or `negative_prompt_embeds` (+ `negative_pooled_prompt_embeds`)')
+            if negative_prompt_embeds is not None and negative_pooled_prompt_embeds is None:
+                raise ValueError('If `negative_prompt_embeds` are provided, `negative_pooled_prompt_embeds` also have to be passed.')
+            if negative_prompt_embeds is None and isinstance(negative_prompt, str):
+                negative_prompt = [negative_prompt] * (pe.shape[0] // num_images_per_prompt)
+            ne, npooled = self.encode_prompt(negative_prompt if negative_prompt_embeds is None else None, None, negative_prompt_embeds,
+                                             negative_pooled_prompt_embeds, device, num_images_per_prompt, max_sequence_length)
+            if ne.shape[0] != pe.shape[0]:
+                raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
+            cond.update(negative_prompt_embeds=ne, negative_pooled=npooled)
+        out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
+                                           generator, latents, guidance_interval, orthogonal_guidance)
+        return self._finish(out, hp, wp, output_type, return_dict)

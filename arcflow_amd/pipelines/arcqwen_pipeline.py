@@ -147,6 +147,11 @@ class ArcQwenImagePipeline(_PipelineBase):
             return self.transformer.prepare_steps(sigmas, None, None, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare)
+        return self._finish(latents, hp, wp, output_type, return_dict)
+
+    def _finish(self, latents, hp, wp, output_type, return_dict):
+        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``."""
+        device = self._execution_device
         if output_type == 'latent':
             image = latents
         else:
@@ -164,3 +169,52 @@ class ArcQwenImagePipeline(_PipelineBase):
         if not return_dict:
             return (image,)
         return QwenImagePipelineOutput(images=image)
+
+    def _teacher_text(self, prompt, embeds, mask, num_images_per_prompt, max_sequence_length):
+        """-> [B, T_real, D] bf16 on the device: only the real tokens enter the transformer, as in ``__call__``."""
+        if embeds is None:
+            embeds, mask = self.encode_prompt(prompt, max_sequence_length=max_sequence_length)
+        embeds = embeds.to(self._execution_device, torch.bfloat16).repeat_interleave(num_images_per_prompt, dim=0)
+        if mask is not None:
+            embeds = embeds[:, :int(max(mask.sum(dim=1).tolist()))]
+        return embeds
+
+    @torch.inference_mode()
+    def sample_teacher(self, prompt: Union[str, List[str]] = None, negative_prompt: Union[str, List[str]] = None,
+                       height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
+                       guidance_scale: Optional[float] = None, true_cfg_scale: float = 4.0,
+                       generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
+                       latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
+                       prompt_embeds_mask: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
+                       negative_prompt_embeds_mask: Optional[torch.Tensor] = None, output_type: Optional[str] = 'pil',
+                       return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
+                       num_images_per_prompt: int = 1, max_sequence_length: int = 512):
+        """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
+        shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
+        ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
+        (Qwen-Image has no guidance embedding).  Works before ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a
+        teacher engine is built once from the kept base weights, which holds a SECOND copy of the transformer on the GPU
+        (Qwen-Image: about 41 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
+        height = height or self.default_sample_size * self.vae_scale_factor
+        width = width or self.default_sample_size * self.vae_scale_factor
+        if height % 16 or width % 16:
+            raise ValueError('`height` and `width` have to be divisible by 16')
+        if prompt is not None and prompt_embeds is not None:
+            raise ValueError('Cannot forward both `prompt` and `prompt_embeds`.')
+        if prompt is None and prompt_embeds is None:
+            raise ValueError('Provide either `prompt` or `prompt_embeds`.')
+        pe = self._teacher_text(prompt, prompt_embeds, prompt_embeds_mask, num_images_per_prompt, max_sequence_length)
+        cond = dict(prompt_embeds=pe)
+        if true_cfg_scale > 1.0:
+            if negative_prompt is None and negative_prompt_embeds is None:
+                raise ValueError('true_cfg_scale > 1 needs `negative_prompt` or `negative_prompt_embeds`')
+            if negative_prompt_embeds is None and isinstance(negative_prompt, str):
+                negative_prompt = [negative_prompt] * (pe.shape[0] // num_images_per_prompt)
+            ne = self._teacher_text(negative_prompt, negative_prompt_embeds, negative_prompt_embeds_mask, num_images_per_prompt,
+                                    max_sequence_length)
+            if ne.shape[0] != pe.shape[0]:
+                raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
+            cond['negative_prompt_embeds'] = ne
+        out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
+                                           latents, guidance_interval, orthogonal_guidance)
+        return self._finish(out, hp, wp, output_type, return_dict)

@@ -1,6 +1,7 @@
 """Time grid of the ArcFlow sampler and the flow-matching scheduler object the reference's entry
 scripts configure (inference_flux.py:14-15: ``FlowMatchEulerDiscreteScheduler.from_config(
-pipe.scheduler.config, shift=3.2, shift_terminal=None, use_dynamic_shifting=False)``).
+pipe.scheduler.config, shift=3.2, shift_terminal=None, use_dynamic_shifting=False)``), and the
+``FlowEulerODEScheduler`` of the reference's own teacher sampling (GaussianFlow.forward_test).
 
 Host-side float arithmetic only (128 numbers per image) -- nothing here runs on the GPU.
 """
@@ -93,3 +94,109 @@ class FlowMatchEulerDiscreteScheduler:
 def calculate_shift(image_seq_len, base_seq_len=256, max_seq_len=4096, base_shift=0.5, max_shift=1.15):
     m = (max_shift - base_shift) / (max_seq_len - base_seq_len)
     return image_seq_len * m + (base_shift - m * base_seq_len)
+
+
+class FlowEulerODEScheduler:
+    """The reference's own Euler ODE scheduler (lakonlab/models/diffusions/schedulers/flow_euler_ode.py:20-164), the default
+    ``sampler`` of ``GaussianFlow.forward_test``, without diffusers: ``config``, ``from_config()``, ``get_shift()``,
+    ``stretch_to_terminal()``, ``set_timesteps(n, seq_len=...)`` and ``step()`` for ``prediction_type='u'``.
+
+    Grid: n points of linspace(1, 0, endpoint=False), warped by sigma' = s sigma / (1 + (s - 1) sigma) with the static ``shift`` or,
+    with ``use_dynamic_shifting``, s = exp(logshift) interpolated linearly in ``seq_len`` between (base_seq_len, base_logshift)
+    and (max_seq_len, max_logshift); optionally stretched so that the last sigma is ``terminal_sigma``; a trailing 0 is appended to
+    ``sigmas`` (the last step lands on the clean sample).  Same fp32 operations in the same order as the reference
+    (tests/golden/g12_teacher_sampler.npz)."""
+    order = 1
+    _DEFAULTS = dict(num_train_timesteps=1000, shift=1.0, use_dynamic_shifting=False, base_seq_len=256, max_seq_len=4096,
+                     base_logshift=0.5, max_logshift=1.15, terminal_sigma=None)
+
+    def __init__(self, num_train_timesteps: int = 1000, **kwargs: Any):
+        cfg = dict(self._DEFAULTS)
+        cfg['num_train_timesteps'] = num_train_timesteps
+        unknown = set(kwargs) - set(cfg)
+        if unknown:
+            raise TypeError(f'FlowEulerODEScheduler got unexpected arguments {sorted(unknown)}')
+        cfg.update(kwargs)
+        self.config = _Config(cfg)
+        shift = self.config.shift
+        sigmas = torch.from_numpy(1 - np.linspace(0, 1, num_train_timesteps, dtype=np.float32, endpoint=False))
+        self.sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
+        self.timesteps = self.sigmas * num_train_timesteps
+        self._step_index = None
+        self._begin_index = None
+        self.sigma_min = self.sigmas[-1].item()
+        self.sigma_max = self.sigmas[0].item()
+
+    @classmethod
+    def from_config(cls, config: Optional[Dict[str, Any]] = None, **overrides: Any):
+        cfg = dict(config or {})
+        cfg.update(overrides)
+        cfg = {k: v for k, v in cfg.items() if k in cls._DEFAULTS}       # a foreign scheduler's config: only the shared keys apply
+        return cls(**cfg)
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index: int = 0):
+        self._begin_index = begin_index
+
+    def get_shift(self, seq_len=None):
+        c = self.config
+        if c.use_dynamic_shifting and seq_len is not None:
+            m = (c.max_logshift - c.base_logshift) / (c.max_seq_len - c.base_seq_len)
+            logshift = (seq_len - c.base_seq_len) * m + c.base_logshift
+            return torch.exp(logshift) if isinstance(logshift, torch.Tensor) else np.exp(logshift)
+        return c.shift
+
+    def stretch_to_terminal(self, sigma: torch.Tensor) -> torch.Tensor:
+        one_minus_sigma = 1 - sigma
+        return 1 - (one_minus_sigma * (1 - self.config.terminal_sigma) / one_minus_sigma[-1])
+
+    def set_timesteps(self, num_inference_steps: int, seq_len=None, device=None):
+        self.num_inference_steps = num_inference_steps
+        sigmas = torch.from_numpy(np.linspace(1, 0, num_inference_steps, dtype=np.float32, endpoint=False))
+        shift = self.get_shift(seq_len=seq_len)
+        sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
+        if self.config.terminal_sigma is not None:
+            sigmas = self.stretch_to_terminal(sigmas)
+        self.timesteps = (sigmas * self.config.num_train_timesteps).to(device)
+        self.sigmas = torch.cat([sigmas, torch.zeros(1)])
+        self._step_index = None
+        self._begin_index = None
+        return self.timesteps
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        indices = (ts == timestep).nonzero()
+        return indices[1 if len(indices) > 1 else 0].item()
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True,
+             prediction_type: str = 'u'):
+        """prev_sample = sample + model_output (sigma_next - sigma) in fp32, cast back to model_output's dtype."""
+        if prediction_type != 'u':
+            raise NotImplementedError("FlowEulerODEScheduler.step: only prediction_type='u' (the teacher predicts a velocity)")
+        if isinstance(timestep, int) or (isinstance(timestep, torch.Tensor) and not timestep.is_floating_point()):
+            raise ValueError('pass one of scheduler.timesteps as the timestep, not an integer index')
+        if self._step_index is None:
+            if self._begin_index is None:
+                t = timestep.to(self.timesteps.device) if isinstance(timestep, torch.Tensor) else timestep
+                self._step_index = self.index_for_timestep(t)
+            else:
+                self._step_index = self._begin_index
+        ori_dtype = model_output.dtype
+        sigma = self.sigmas[self._step_index]
+        sigma_to = self.sigmas[self._step_index + 1]
+        dt = (sigma_to - sigma).to(sample.device)
+        prev_sample = (sample.to(torch.float32) + model_output.to(torch.float32) * dt).to(ori_dtype)
+        self._step_index += 1
+        if not return_dict:
+            return (prev_sample,)
+        return _Config(prev_sample=prev_sample)
+
+    def __len__(self):
+        return self.config.num_train_timesteps

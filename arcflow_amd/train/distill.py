@@ -306,6 +306,24 @@ class ArcFlowDistiller:
         neg = self.teacher(xb, sigma, cond['negative_prompt_embeds'], cond.get('negative_pooled'), g, cond['hp'], cond['wp'], prepared_step=neg_prep).float()
         return ops.cfg_combine(pos, neg, self.cfg.teacher_guidance_scale)
 
+    @torch.no_grad()
+    def sample_teacher(self, cond, noise, num_steps: int = 28, guidance_scale: Optional[float] = None,
+                       distilled_guidance: Optional[float] = None, **sampler_kwargs):
+        """Roll the frozen teacher from ``noise`` [B, N, C] (packed tokens, fp32) to latents with the Euler ODE sampler
+        (arcflow_amd.teacher.TeacherSampler; GaussianFlow.forward_test in the reference) on this distiller's teacher context -- no
+        new weights.  Defaults are _teacher_u's: true CFG ``cfg.teacher_guidance_scale`` (needs cond['negative_prompt_embeds'] when
+        > 1), guidance embedding ``cfg.teacher_guidance`` (else ``cfg.guidance``), time shift ``cfg.shift``.  Further keywords
+        (guidance_interval, orthogonal_guidance, terminal_sigma ...) go to TeacherSampler."""
+        from ..teacher import TeacherSampler
+        c = self.cfg
+        if guidance_scale is None:
+            guidance_scale = c.teacher_guidance_scale
+        if distilled_guidance is None:
+            distilled_guidance = c.teacher_guidance if c.teacher_guidance is not None else c.guidance
+        sampler_kwargs.setdefault('shift', c.shift)
+        return TeacherSampler(self.teacher, num_steps, guidance_scale=guidance_scale, distilled_guidance=distilled_guidance,
+                              **sampler_kwargs)(cond, noise)
+
     def student_forward_unmerged(self, x_src, sigma_src, cond, p_drop: float = 0.0, seed: int = 0, x_bf16=None):
         """The student's forward as peft evaluates it -- y = W x + B (A dropout(x)) per adapted linear, NOT folded into W -- on the
         LoRA trunk: the engine runs conditioning + embedders (stage 1, with the timestep embedding of the LoRA-adapted embedder

@@ -204,6 +204,27 @@ int afx_axpby_rows(const float* a, const float* alpha, const float* b, const flo
 /* out = pos + (pos - neg) * (scale - 1)   teacher CFG (gaussian_flow.py:18-26, orthogonal=False) */
 int afx_cfg_combine(const float* pos, const float* neg, float scale, float* out, int64_t n, void* stream);
 
+/* One step of the teacher's Euler ODE sampler (GaussianFlow.forward_test, gaussian_flow.py:196-215) on the engine's packed
+ * token layout: true-CFG combine (guidance_jit, gaussian_flow.py:18-26) + FlowEulerODEScheduler.step, prediction_type 'u'
+ * (schedulers/flow_euler_ode.py:141-150) + the bf16 copy of the new latents that the next forward reads, in one launch.
+ *   bias  = (pos - neg) (scale - 1)                  (0 when neg is NULL: no guidance on this step)
+ *   u     = pos + bias - coef[b] pos                 (coef NULL: no orthogonal term)
+ *   x_out = x + u (sigma_to[b] - sigma[b])           all in fp32
+ * x, x_out [batch, n] fp32 (x_out may alias x); pos, neg [batch, n] bf16 teacher velocities; sigma, sigma_to, coef [batch] fp32;
+ * x_out_bf16 [batch, n] = round-to-nearest-even of x_out.  n = tokens x channels must be a multiple of 64 and every tensor
+ * 16-byte aligned, else AFX_E_INVALID.  max_blocks: cap on the grid of the grid-stride loop (0 = the default, 2048). */
+int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, const float* sigma, const float* sigma_to,
+                           const float* coef, float scale, float* x_out, void* x_out_bf16, int32_t batch, int64_t n,
+                           int32_t max_blocks, void* stream);
+/* coef[b] = mean(bias pos) / max(mean(pos pos), 1e-6) over the n elements of sample b, bias = (pos - neg) (scale - 1) rounded to
+ * fp32 as the step kernel computes it: the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25, dim = [1..]).
+ * Deterministic: a number of work-groups per sample that depends on n alone, exact fp64 products, one slot of `ws` per
+ * work-group, the slots added in index order by a second launch; no atomics.  ws: afx_cfg_ortho_ws_bytes(batch, n) bytes,
+ * 8-byte aligned, private to the call until it completes.  n a multiple of 64, pos / neg 16-byte aligned. */
+int64_t afx_cfg_ortho_ws_bytes(int32_t batch, int64_t n);
+int afx_cfg_ortho_coef(const void* pos, const void* neg, float scale, float* coef, void* ws, int64_t ws_bytes, int32_t batch,
+                       int64_t n, void* stream);
+
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,
                   int64_t ldy, int64_t rows, int32_t K, int32_t ch, int32_t lw, void* stream);

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Teacher sampling on one MI355X, synthetic FLUX weights at full depth, 1024^2 (4096 image + 512 text tokens):
+
+  * the fused step (afx_cfg_ortho_coef when orthogonal + afx_teacher_euler_step) against the composed one (bf16 cast of x,
+    .float() of both velocities, ops.cfg_combine, ops.euler_roll), interleaved in every round;
+  * a 28-step teacher image without CFG and with true CFG 4.0 (TeacherSampler).
+
+HIP events, 3 warm-up rounds, the median of 11 rounds; one JSON line per measurement (also written to ``--out``).
+
+    python tools/teacher_sampler_bench.py --out profiles/teacher_sampler_bench.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out')
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--rounds', type=int, default=11)
+    ap.add_argument('--steps', type=int, default=28)
+    ap.add_argument('--skip-image', action='store_true')
+    args = ap.parse_args()
+    from arcflow_amd import MMDiTEngine, TeacherSampler, ops
+    from arcflow_amd.weights import random_packed
+    dev = 'cuda'
+    g = torch.Generator(device=dev).manual_seed(0)
+    B, N, C, T = 1, 4096, 64, 512
+    lines = []
+
+    def emit(rec):
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+
+    # ---- the step alone --------------------------------------------------------------------------------------------------
+    x = torch.randn(B, N, C, generator=g, device=dev)
+    pos = torch.randn(B, N, C, generator=g, device=dev).bfloat16()
+    neg = torch.randn(B, N, C, generator=g, device=dev).bfloat16()
+    sig, sig_to = torch.full((B,), 0.7, device=dev), torch.full((B,), 0.65, device=dev)
+    xo, xb = torch.empty_like(x), torch.empty(B, N, C, dtype=torch.bfloat16, device=dev)
+    coef, ws = torch.empty(B, device=dev), ops.cfg_ortho_ws(B, N * C, dev)
+
+    def fused():
+        ops.teacher_euler_step(x, pos, neg, sig, sig_to, 4.0, None, out=xo, out_bf16=xb)
+
+    def fused_ortho():
+        ops.cfg_ortho_coef(pos, neg, 4.0, out=coef, ws=ws)
+        ops.teacher_euler_step(x, pos, neg, sig, sig_to, 4.0, coef, out=xo, out_bf16=xb)
+
+    def composed():
+        ops.euler_roll(x, ops.cfg_combine(pos.float(), neg.float(), 4.0), sig, sig_to).to(torch.bfloat16)
+
+    variants = dict(fused=fused, fused_orthogonal=fused_ortho, composed=composed)
+    samples = {k: [] for k in variants}
+    for r in range(args.warmup + args.rounds):
+        for k, fn in variants.items():                 # interleaved: every round times every variant
+            t = timed(fn, 50)
+            if r >= args.warmup:
+                samples[k].append(t)
+    for k, v in samples.items():
+        emit(dict(what='teacher_step', variant=k, shape=[B, N, C], us_median=1e3 * statistics.median(v), us_min=1e3 * min(v), us_max=1e3 * max(v),
+                  rounds=len(v), reps_per_round=50))
+
+    # ---- a whole teacher image ---------------------------------------------------------------------------------------------
+    if not args.skip_image:
+        eng = MMDiTEngine('flux', 19, 38, teacher_head=True)
+        eng.bind_packed(random_packed('flux', 19, 38, dev, teacher=True))
+        cond = dict(prompt_embeds=(torch.randn(B, T, 4096, generator=g, device=dev) * 0.5).bfloat16(),
+                    negative_prompt_embeds=(torch.randn(B, T, 4096, generator=g, device=dev) * 0.5).bfloat16(),
+                    pooled=(torch.randn(B, 768, generator=g, device=dev) * 0.5).bfloat16(),
+                    negative_pooled=(torch.randn(B, 768, generator=g, device=dev) * 0.5).bfloat16(), hp=64, wp=64)
+        noise = torch.randn(B, N, C, generator=g, device=dev)
+        runs = dict(no_cfg=TeacherSampler(eng, args.steps, guidance_scale=1.0, distilled_guidance=3.5, shift=3.2),
+                    true_cfg_4=TeacherSampler(eng, args.steps, guidance_scale=4.0, distilled_guidance=3.5, shift=3.2))
+        samples = {k: [] for k in runs}
+        for r in range(args.warmup + args.rounds):
+            for k, s in runs.items():
+                t = timed(lambda: s(cond, noise), 1)
+                if r >= args.warmup:
+                    samples[k].append(t)
+        for k, v in samples.items():
+            emit(dict(what='teacher_image_1024', variant=k, steps=args.steps, ms_median=statistics.median(v), ms_min=min(v), ms_max=max(v), rounds=len(v),
+                      forwards=args.steps * (2 if k == 'true_cfg_4' else 1)))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + '\n')
+
+
+if __name__ == '__main__':
+    main()
