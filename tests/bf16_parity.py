@@ -1,6 +1,6 @@
 """Shared checks of the fp64 parity tests (test_hip_train_kernels.py, test_text_encoders.py, test_hip_forward_operands.py, test_hip_gemm_fp64.py,
-test_hip_attention_fp64.py, test_hip_vae_fp64.py): bf16 / fp32 outputs against an fp64 reference, the fp64 GEMM reference with its fp32 summation bound
-and the fp64 convolution reference built from shifted matmuls."""
+test_hip_attention_fp64.py, test_hip_vae_fp64.py, test_hip_attention_bwd_fp64.py with attention_bwd_ref.py and test_attention_bwd_ref_cpu.py): bf16 / fp32
+outputs against an fp64 reference, the fp64 GEMM reference with its fp32 summation bound and the fp64 convolution reference built from shifted matmuls."""
 import math
 
 import torch
@@ -24,6 +24,18 @@ def check_bf16(out, ref, floor=0.0, min_equal=0.99, what=''):
                              f'ref {ref.flatten()[i].item()} tol {torch.as_tensor(tol).expand_as(err).flatten()[i].item():.3e}')
     eq = (out == ref.float().bfloat16()).double().mean().item()
     assert eq >= min_equal, f'{what}: only {eq:.4f} of the elements equal the fp64 reference rounded to nearest even (need {min_equal})'
+
+
+def check_bf16_bound(out, ref, bound, what=''):
+    """out (bf16) against ref (fp64) with a derived per-element bound: |out - ref| <= ulp_bf16(ref) + bound.  Returns the worst err / tol."""
+    err = (out.double() - ref).abs()
+    tol = bf16_ulp(ref) + bound
+    bad = err > tol
+    if bool(bad.any()):
+        i = int((err - tol).flatten().argmax())
+        raise AssertionError(f'{what}: {int(bad.sum())} of {err.numel()} elements beyond the bound; worst out {out.flatten()[i].item()} '
+                             f'ref {ref.flatten()[i].item()} tol {tol.flatten()[i].item():.3e}')
+    return (err / tol).max().item()
 
 
 def check_f32(out, ref, bound, what=''):

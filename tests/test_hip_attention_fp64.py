@@ -34,7 +34,8 @@ import math
 import numpy as np
 import pytest
 import torch
-from bf16_parity import U32, bf16_ulp, check_f32
+from attention_inputs import head_design_inputs as _inputs
+from bf16_parity import U32, check_bf16_bound as _check_o, check_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -47,30 +48,6 @@ LN2 = math.log(2.0)
 def ops():
     from arcflow_amd import ops as _ops
     return _ops
-
-
-def _inputs(B, S, H, seed):
-    """q, k, v [B, S, H, 128] bf16 with head h of design h % 4 (see the module docstring)."""
-    g = torch.Generator(device='cuda').manual_seed(seed)
-    rn = lambda *s: torch.randn(*s, generator=g, device='cuda')         # noqa: E731
-    q, k, v = rn(B, S, H, 128), rn(B, S, H, 128), rn(B, S, H, 128)
-    for h in range(H):
-        d = h % 4
-        if d == 0:
-            v[:, :, h] = v[:, :, h].abs() * 0.5 + 1.0
-        elif d == 1:
-            for b in range(B):
-                pi = torch.randperm(S, generator=g, device='cuda')
-                k[b, pi, h] = q[b, :, h] * 1.77                     # score of the planted key ~ 20 nats, the others ~ N(0, 1.8^2)
-        elif d == 2:
-            base = rn(128)
-            base = base / base.norm()
-            q[:, :, h] += 6.0 * base
-            k[:, :, h] += (torch.arange(S, device='cuda').float() / S * 60.0)[None, :, None] * base
-        else:
-            q[:, :, h] *= 0.6
-            k[:, :, h] *= 0.6
-    return q.bfloat16(), k.bfloat16(), v.bfloat16()
 
 
 def _reference(q, k, v, split, drop_last=False):
@@ -130,16 +107,6 @@ def _run(ops, q, k, v, impl):
     assert bool((buf[mask] == SENT).all()), f'impl {impl}: a write landed in the guard band'
     assert bool(torch.isinf(lse[:, :, S:]).all()), f'impl {impl}: lse written past S'
     return qo, lse[:, :, :S]
-
-
-def _check_o(out, ref, bound, what):
-    err = (out.double() - ref).abs()
-    tol = bf16_ulp(ref) + bound
-    bad = err > tol
-    if bool(bad.any()):
-        i = int((err - tol).flatten().argmax())
-        raise AssertionError(f'{what}: {int(bad.sum())} of {err.numel()} elements beyond the bound; worst out {out.flatten()[i].item()} '
-                             f'ref {ref.flatten()[i].item()} tol {tol.flatten()[i].item():.3e}')
 
 
 SHAPES = [(1, 4608, 24), (1, 4224, 24), (1, 4173, 24), (3, 4608, 24), (2, 1101, 24), (1, 65, 4), (1, 191, 4), (1, 576, 9)]
