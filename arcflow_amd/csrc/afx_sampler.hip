@@ -3,6 +3,12 @@
 //   * teacher_euler_step_kernel: true-CFG combine (guidance_jit, gaussian_flow.py:18-26) + FlowEulerODEScheduler.step
 //     (schedulers/flow_euler_ode.py:141-150) + the bf16 copy of the new latents the next forward reads, in one pass:
 //     16 B per lane and operand (8 bf16 of pos / neg, two float4 of x), grid-stride, no LDS, no atomics.
+//   * teacher_sde_step_kernel: the same combine + FlowSDEScheduler.step (schedulers/flow_sde.py:143-166) + the bf16 copy, in one
+//     pass of the same shape.  The scheduler's per-step scalars (sigma, sigma_to, m, c_noise = sqrt(max(1 - m^2, 0))) come from the
+//     host (FlowSDEScheduler.coefficients: the pow is evaluated once per step in the reference's arithmetic); the fresh noise z is
+//     an fp32 operand drawn by torch, so that a torch.Generator reproduces the run.  Traffic at 1024 x 1024 (4096 tokens x 64
+//     channels = 262144 elements per image): 4 (x) + 2 (pos) + 2 (neg) + 4 (z) B read and 4 (x') + 2 (bf16 x') B written per
+//     element = 18 B, about 4.7 MB per image and step.
 //   * cfg_ortho_partial_kernel / cfg_ortho_finish_kernel: the per-sample projection coefficient of orthogonal guidance,
 //     mean(bias pos) / max(mean(pos pos), 1e-6) over all n elements of a sample.  A fixed number of work-groups per sample
 //     (a function of n alone), every product exact in fp64, one workspace slot per work-group, the slots added in index order
@@ -13,6 +19,17 @@
 #include "afx_common.h"
 
 namespace afx {
+
+// The guided velocity of one element, shared by both step kernels so that the CFG arithmetic cannot drift between them:
+//   u = pos                                  no guidance on this step
+//   u = pos + (pos - neg) (scale - 1)        true CFG (guidance_jit, orthogonal off)
+//   u = u - coef pos                         orthogonal guidance: the projection on pos removed (coef from afx_cfg_ortho_coef)
+AFX_DEV float cfg_velocity(const float (&p)[8], const float (&q)[8], int e, bool has_neg, bool has_coef, float sm1, float cf) {
+  float u = p[e];
+  if (has_neg) u = p[e] + (p[e] - q[e]) * sm1;
+  if (has_coef) u = u - cf * p[e];
+  return u;
+}
 
 // One chunk = 8 consecutive elements of one sample (n % 64 == 0: a chunk never straddles two samples, and a sample's first chunk
 // is 16-byte aligned in every operand).
@@ -34,10 +51,51 @@ __global__ __launch_bounds__(256) void teacher_euler_step_kernel(const float* x,
     const f32x4_t x1 = *reinterpret_cast<const f32x4_t*>(x + c * 8 + 4);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float u = p[e];
-      if (neg != nullptr) u = p[e] + (p[e] - q[e]) * sm1;
-      if (coef != nullptr) u = u - cf * p[e];
+      const float u = cfg_velocity(p, q, e, neg != nullptr, coef != nullptr, sm1, cf);
       o[e] = (e < 4 ? x0[e & 3] : x1[e & 3]) + u * dt;
+    }
+    const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8 + 4) = o1;
+    *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
+  }
+}
+
+// FlowSDEScheduler.step, prediction_type 'u', on the same chunks:
+//   x0 = x - sigma u,   eps = x + (1 - sigma) u,   x' = (1 - sigma_to) x0 + sigma_to (m eps + c_noise z)
+// noise == nullptr: the term c_noise z is skipped together with its read (the host passes it when sigma_to c_noise = 0 for every sample).
+__global__ __launch_bounds__(256) void teacher_sde_step_kernel(const float* x, const bf16_t* __restrict__ pos,
+                                                               const bf16_t* __restrict__ neg, const float* __restrict__ noise,
+                                                               const float* __restrict__ sigma, const float* __restrict__ sigma_to,
+                                                               const float* __restrict__ m, const float* __restrict__ c_noise,
+                                                               const float* __restrict__ coef, float scale, float* x_out,
+                                                               bf16_t* __restrict__ x_bf16, int64_t chunks_per_sample, int64_t chunks) {
+  const float sm1 = scale - 1.0f;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += stride) {
+    const int64_t b = c / chunks_per_sample;
+    const float sg = sigma[b], sg_to = sigma_to[b], mb = m[b], cn = c_noise[b];
+    const float alpha = 1.0f - sg, alpha_to = 1.0f - sg_to;
+    const float cf = coef != nullptr ? coef[b] : 0.f;
+    float p[8], q[8], o[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(pos + c * 8), p);
+    if (neg != nullptr) unpack8(*reinterpret_cast<const u32x4_t*>(neg + c * 8), q);
+    const f32x4_t x0 = *reinterpret_cast<const f32x4_t*>(x + c * 8);        // (x_out may be x: every load precedes every store)
+    const f32x4_t x1 = *reinterpret_cast<const f32x4_t*>(x + c * 8 + 4);
+    f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = z0;
+    if (noise != nullptr) {
+      z0 = *reinterpret_cast<const f32x4_t*>(noise + c * 8);
+      z1 = *reinterpret_cast<const f32x4_t*>(noise + c * 8 + 4);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float u = cfg_velocity(p, q, e, neg != nullptr, coef != nullptr, sm1, cf);
+      const float xe = e < 4 ? x0[e & 3] : x1[e & 3];
+      const float clean = xe - sg * u;
+      const float eps = xe + alpha * u;
+      float mix = mb * eps;
+      if (noise != nullptr) mix = mix + cn * (e < 4 ? z0[e & 3] : z1[e & 3]);
+      o[e] = alpha_to * clean + sg_to * mix;
     }
     const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
     *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
@@ -128,6 +186,26 @@ int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, con
   const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
   hipLaunchKernelGGL(teacher_euler_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos,
                      (const bf16_t*)neg, sigma, sigma_to, coef, scale, x_out, (bf16_t*)x_out_bf16, cps, chunks);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma,
+                         const float* sigma_to, const float* m, const float* c_noise, const float* coef, float scale, float* x_out,
+                         void* x_out_bf16, int32_t batch, int64_t n, int32_t max_blocks, void* stream) {
+  if (!x || !pos || !sigma || !sigma_to || !m || !c_noise || !x_out || !x_out_bf16)
+    return fail(AFX_E_INVALID, "null argument to afx_teacher_sde_step");
+  if (batch < 0 || n < 64 || n % 64 || max_blocks < 0)
+    return fail(AFX_E_INVALID, "bad argument to afx_teacher_sde_step (n = tokens x channels must be a positive multiple of 64)");
+  if (((uintptr_t)x & 15) || ((uintptr_t)pos & 15) || ((uintptr_t)neg & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)x_out & 15) ||
+      ((uintptr_t)x_out_bf16 & 15))
+    return fail(AFX_E_INVALID, "afx_teacher_sde_step: x, pos, neg, noise, x_out and x_out_bf16 must be 16-byte aligned");
+  if (batch == 0) return AFX_OK;
+  const int64_t cps = n / 8, chunks = cps * batch;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;          // as afx_teacher_euler_step: 8 work-groups per CU
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
+  hipLaunchKernelGGL(teacher_sde_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos, (const bf16_t*)neg,
+                     noise, sigma, sigma_to, m, c_noise, coef, scale, x_out, (bf16_t*)x_out_bf16, cps, chunks);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

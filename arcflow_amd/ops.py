@@ -516,6 +516,36 @@ def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: O
     return out, out_bf16
 
 
+def teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
+    """One step of the teacher's stochastic sampler (FlowSDEScheduler) in one launch (afx_teacher_sde_step): with
+    u = pos + (pos - neg)(scale - 1) - coef[b] pos as teacher_euler_step forms it, x0 = x - sigma[b] u and e = x + (1 - sigma[b]) u,
+    (1 - sigma_to[b]) x0 + sigma_to[b] (m[b] e + c_noise[b] noise) -> (fp32 latents, their bf16 rounding).
+    x, noise (None: no noise term, nothing read) [B, ...] fp32; pos, neg (None: no guidance) bf16 of the same shape; sigma, sigma_to,
+    m, c_noise (FlowSDEScheduler.coefficients), coef (None: not orthogonal) [B] fp32.  out may be x (in place).  numel / B must be a
+    multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
+    lib = _lib.load()
+    for t in (x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, out, out_bf16):
+        if t is not None and t.device.type != 'cuda':
+            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    B = x.shape[0]
+    n = x[0].numel() if B else 0
+    x = _packed(x, torch.float32, x.shape, 'x')
+    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
+    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    noise = None if noise is None else _packed(noise, torch.float32, x.shape, 'noise')
+    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
+    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
+    m = _packed(m, torch.float32, (B,), 'm')
+    c_noise = _packed(c_noise, torch.float32, (B,), 'c_noise')
+    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
+    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    _lib.check(lib.afx_teacher_sde_step(_p(x), _p(pos), _p(neg), _p(noise), _p(sigma), _p(sigma_to), _p(m), _p(c_noise), _p(coef), scale,
+                                        _p(out), _p(out_bf16), B, n, max_blocks, _s()))
+    return out, out_bf16
+
+
 def head_grad(d_means, d_logw, d_logg, logw_out, ldy: int):
     lib = _lib.load()
     B, N, K, ch = d_means.shape

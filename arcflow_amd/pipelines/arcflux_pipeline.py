@@ -175,16 +175,16 @@ class _PipelineBase(ArcFlowLoaderMixin):
                     terminal_sigma=c.get('shift_terminal') or None)
 
     def _sample_teacher(self, cond, batch, height, width, num_inference_steps, guidance_scale, true_cfg_scale, generator, latents,
-                        guidance_interval, orthogonal_guidance):
+                        guidance_interval, orthogonal_guidance, sampler='FlowEulerODE', h=None):
         from ..teacher import TeacherSampler
         engine = self._teacher_engine()
         latents, hp, wp = self._prepare_latents(batch, height, width, generator, latents)
         cond = dict(cond, hp=hp, wp=wp)
         sampler = TeacherSampler(engine, num_inference_steps, guidance_scale=true_cfg_scale, distilled_guidance=guidance_scale,
                                  guidance_interval=guidance_interval, orthogonal_guidance=orthogonal_guidance, tokens_as_seq_len=True,
-                                 **self._euler_scheduler_kwargs())
+                                 sampler=sampler, **({} if h is None else dict(h=h)), **self._euler_scheduler_kwargs())
         self._num_timesteps = num_inference_steps
-        return sampler(cond, latents), hp, wp
+        return sampler(cond, latents, generator=generator), hp, wp          # (the generator's stream continues from the start noise into FlowSDE's step draws)
 
     def _unpack(self, latents, hp, wp):
         b = latents.shape[0]
@@ -380,11 +380,14 @@ class ArcFluxPipeline(_PipelineBase):
                        pooled_prompt_embeds: Optional[torch.FloatTensor] = None, negative_prompt_embeds: Optional[torch.FloatTensor] = None,
                        negative_pooled_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = 'pil',
                        return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
-                       num_images_per_prompt: int = 1, max_sequence_length: int = 512):
+                       num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
+                       h: Optional[Union[float, str]] = None):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
-        t = 1000 sigma limits it, ``orthogonal_guidance`` projects it).  Works before ``load_arcflow_adapter()`` on the pipeline's
+        t = 1000 sigma limits it, ``orthogonal_guidance`` projects it).  ``sampler='FlowSDE'`` takes the stochastic steps of
+        FlowSDEScheduler instead, with noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator``
+        after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's
         own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
         transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
         height = height or self.default_sample_size * self.vae_scale_factor
@@ -406,5 +409,5 @@ class ArcFluxPipeline(_PipelineBase):
                 raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
             cond.update(negative_prompt_embeds=ne, negative_pooled=npooled)
         out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
-                                           generator, latents, guidance_interval, orthogonal_guidance)
+                                           generator, latents, guidance_interval, orthogonal_guidance, sampler, h)
         return self._finish(out, hp, wp, output_type, return_dict)

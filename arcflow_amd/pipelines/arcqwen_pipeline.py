@@ -188,11 +188,13 @@ class ArcQwenImagePipeline(_PipelineBase):
                        prompt_embeds_mask: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                        negative_prompt_embeds_mask: Optional[torch.Tensor] = None, output_type: Optional[str] = 'pil',
                        return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
-                       num_images_per_prompt: int = 1, max_sequence_length: int = 512):
+                       num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
+                       h: Optional[Union[float, str]] = None):
         """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
         ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
-        (Qwen-Image has no guidance embedding).  Works before ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a
+        (Qwen-Image has no guidance embedding).  ``sampler='FlowSDE'`` takes the stochastic steps of FlowSDEScheduler instead, with
+        noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator`` after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a
         teacher engine is built once from the kept base weights, which holds a SECOND copy of the transformer on the GPU
         (Qwen-Image: about 41 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
         height = height or self.default_sample_size * self.vae_scale_factor
@@ -216,5 +218,5 @@ class ArcQwenImagePipeline(_PipelineBase):
                 raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
             cond['negative_prompt_embeds'] = ne
         out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
-                                           latents, guidance_interval, orthogonal_guidance)
+                                           latents, guidance_interval, orthogonal_guidance, sampler, h)
         return self._finish(out, hp, wp, output_type, return_dict)

@@ -96,26 +96,24 @@ def calculate_shift(image_seq_len, base_seq_len=256, max_seq_len=4096, base_shif
     return image_seq_len * m + (base_shift - m * base_seq_len)
 
 
-class FlowEulerODEScheduler:
-    """The reference's own Euler ODE scheduler (lakonlab/models/diffusions/schedulers/flow_euler_ode.py:20-164), the default
-    ``sampler`` of ``GaussianFlow.forward_test``, without diffusers: ``config``, ``from_config()``, ``get_shift()``,
-    ``stretch_to_terminal()``, ``set_timesteps(n, seq_len=...)`` and ``step()`` for ``prediction_type='u'``.
+class _FlowSchedulerTables:
+    """What the reference's own flow schedulers share (schedulers/flow_euler_ode.py:20-118 and schedulers/flow_sde.py:21-111 are the
+    same text up to ``step()``): ``config``, ``from_config()``, ``get_shift()``, ``stretch_to_terminal()``, ``set_timesteps(n, seq_len=...)``
+    and the step index.  A subclass sets ``_DEFAULTS`` and adds ``step()``.
 
     Grid: n points of linspace(1, 0, endpoint=False), warped by sigma' = s sigma / (1 + (s - 1) sigma) with the static ``shift`` or,
     with ``use_dynamic_shifting``, s = exp(logshift) interpolated linearly in ``seq_len`` between (base_seq_len, base_logshift)
     and (max_seq_len, max_logshift); optionally stretched so that the last sigma is ``terminal_sigma``; a trailing 0 is appended to
-    ``sigmas`` (the last step lands on the clean sample).  Same fp32 operations in the same order as the reference
-    (tests/golden/g12_teacher_sampler.npz)."""
+    ``sigmas`` (the last step lands on the clean sample)."""
     order = 1
-    _DEFAULTS = dict(num_train_timesteps=1000, shift=1.0, use_dynamic_shifting=False, base_seq_len=256, max_seq_len=4096,
-                     base_logshift=0.5, max_logshift=1.15, terminal_sigma=None)
+    _DEFAULTS: Dict[str, Any] = {}
 
     def __init__(self, num_train_timesteps: int = 1000, **kwargs: Any):
         cfg = dict(self._DEFAULTS)
         cfg['num_train_timesteps'] = num_train_timesteps
         unknown = set(kwargs) - set(cfg)
         if unknown:
-            raise TypeError(f'FlowEulerODEScheduler got unexpected arguments {sorted(unknown)}')
+            raise TypeError(f'{type(self).__name__} got unexpected arguments {sorted(unknown)}')
         cfg.update(kwargs)
         self.config = _Config(cfg)
         shift = self.config.shift
@@ -175,11 +173,10 @@ class FlowEulerODEScheduler:
         indices = (ts == timestep).nonzero()
         return indices[1 if len(indices) > 1 else 0].item()
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True,
-             prediction_type: str = 'u'):
-        """prev_sample = sample + model_output (sigma_next - sigma) in fp32, cast back to model_output's dtype."""
+    def _begin_step(self, timestep, prediction_type: str) -> int:
+        """The checks both ``step()``s open with; -> the index of the step about to be taken."""
         if prediction_type != 'u':
-            raise NotImplementedError("FlowEulerODEScheduler.step: only prediction_type='u' (the teacher predicts a velocity)")
+            raise NotImplementedError(f"{type(self).__name__}.step: only prediction_type='u' (the teacher predicts a velocity)")
         if isinstance(timestep, int) or (isinstance(timestep, torch.Tensor) and not timestep.is_floating_point()):
             raise ValueError('pass one of scheduler.timesteps as the timestep, not an integer index')
         if self._step_index is None:
@@ -188,9 +185,27 @@ class FlowEulerODEScheduler:
                 self._step_index = self.index_for_timestep(t)
             else:
                 self._step_index = self._begin_index
+        return self._step_index
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class FlowEulerODEScheduler(_FlowSchedulerTables):
+    """The reference's own Euler ODE scheduler (lakonlab/models/diffusions/schedulers/flow_euler_ode.py:20-164), the default
+    ``sampler`` of ``GaussianFlow.forward_test``, without diffusers: ``config``, ``from_config()``, ``get_shift()``,
+    ``stretch_to_terminal()``, ``set_timesteps(n, seq_len=...)`` and ``step()`` for ``prediction_type='u'``.  Same fp32 operations in the
+    same order as the reference (tests/golden/g12_teacher_sampler.npz)."""
+    _DEFAULTS = dict(num_train_timesteps=1000, shift=1.0, use_dynamic_shifting=False, base_seq_len=256, max_seq_len=4096,
+                     base_logshift=0.5, max_logshift=1.15, terminal_sigma=None)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True,
+             prediction_type: str = 'u'):
+        """prev_sample = sample + model_output (sigma_next - sigma) in fp32, cast back to model_output's dtype."""
+        i = self._begin_step(timestep, prediction_type)
         ori_dtype = model_output.dtype
-        sigma = self.sigmas[self._step_index]
-        sigma_to = self.sigmas[self._step_index + 1]
+        sigma = self.sigmas[i]
+        sigma_to = self.sigmas[i + 1]
         dt = (sigma_to - sigma).to(sample.device)
         prev_sample = (sample.to(torch.float32) + model_output.to(torch.float32) * dt).to(ori_dtype)
         self._step_index += 1
@@ -198,5 +213,58 @@ class FlowEulerODEScheduler:
             return (prev_sample,)
         return _Config(prev_sample=prev_sample)
 
-    def __len__(self):
-        return self.config.num_train_timesteps
+
+class FlowSDEScheduler(_FlowSchedulerTables):
+    """The reference's stochastic scheduler (lakonlab/models/diffusions/schedulers/flow_sde.py:21-180; ``sampler='FlowSDE'`` in a
+    ``test_cfg``) without diffusers: the tables of FlowEulerODEScheduler, and a ``step()`` that re-injects fresh noise with a strength
+    set by ``h`` -- a float, or the string ``'inf'``.  With x0 = x - sigma u and eps = x + (1 - sigma) u the predictions of the clean
+    sample and of the noise,
+
+        prev = (1 - sigma_to) x0 + sigma_to (m eps + sqrt(max(1 - m^2, 0)) z),      z ~ N(0, 1) fresh per step,
+        m = (sigma_to (1 - sigma) / max(sigma (1 - sigma_to), 1e-6)) ^ (h^2)
+
+    h = 0 gives m = 1: the ODE step (algebraically x + u (sigma_to - sigma)); h = 'inf' gives m = 0: the predicted clean sample is
+    re-noised completely.  Same fp32 operations in the same order as the reference (tests/golden/g13_sde_sampler.npz)."""
+    _DEFAULTS = dict(FlowEulerODEScheduler._DEFAULTS, h=1.0)
+
+    def __init__(self, num_train_timesteps: int = 1000, **kwargs: Any):
+        super().__init__(num_train_timesteps, **kwargs)
+        h = self.config.h
+        if isinstance(h, str) and h != 'inf':
+            raise ValueError(f"h: a float or the string 'inf', got {h!r}")
+
+    def coefficients(self, i: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (sigma, sigma_to, m, c_noise) of step i as fp32 scalars, c_noise = sqrt(max(1 - m^2, 0)): what ``step()`` mixes with,
+        and what the fused step kernel (afx_teacher_sde_step) is handed.  Needs ``set_timesteps()``."""
+        sigma, sigma_to = self.sigmas[i], self.sigmas[i + 1]
+        alpha, alpha_to = 1 - sigma, 1 - sigma_to
+        h = self.config.h
+        if h == 'inf':
+            m = torch.zeros_like(sigma)
+        elif h == 0.0:
+            m = torch.ones_like(sigma)
+        else:
+            if not h > 0.0:
+                raise ValueError(f'h must be >= 0 (or the string \'inf\'), got {h!r}')
+            m = (sigma_to * alpha / (sigma * alpha_to).clamp(min=1e-6)) ** (h * h)
+        return sigma, sigma_to, m, (1 - m.square()).clamp(min=0).sqrt()
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True,
+             prediction_type: str = 'u', noise: Optional[torch.Tensor] = None):
+        """One stochastic step in fp32, cast back to model_output's dtype.  noise: the step's N(0, 1) draw (default: torch.randn of
+        model_output's shape on its device from ``generator``)."""
+        i = self._begin_step(timestep, prediction_type)
+        ori_dtype = model_output.dtype
+        sample = sample.to(torch.float32)
+        model_output = model_output.to(torch.float32)
+        sigma, sigma_to, m, c_noise = self.coefficients(i)
+        alpha, alpha_to = 1 - sigma, 1 - sigma_to
+        x0 = sample - sigma * model_output
+        epsilon = sample + alpha * model_output
+        if noise is None:
+            noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
+        prev_sample = (alpha_to * x0 + sigma_to * (m * epsilon + c_noise * noise)).to(ori_dtype)
+        self._step_index += 1
+        if not return_dict:
+            return (prev_sample,)
+        return _Config(prev_sample=prev_sample)

@@ -1,11 +1,13 @@
-"""Teacher sampling: the Euler ODE loop with true classifier-free guidance that the reference runs in
-``GaussianFlow.forward_test`` (lakonlab/models/diffusions/gaussian_flow.py:149-222) with its ``FlowEulerODEScheduler``
-(schedulers/flow_euler_ode.py) -- what the student is judged against, and a source of latents for the data mode.
+"""Teacher sampling: the loop with true classifier-free guidance that the reference runs in ``GaussianFlow.forward_test``
+(lakonlab/models/diffusions/gaussian_flow.py:149-222) with one of its own schedulers, chosen by name as ``test_cfg['sampler']`` does:
+``FlowEulerODEScheduler`` (schedulers/flow_euler_ode.py, the default) or the stochastic ``FlowSDEScheduler`` (schedulers/flow_sde.py)
+-- what the student is judged against, and a source of latents for the data mode.
 
 Per step: the positive teacher forward, the negative one when guidance is active on that step, the projection coefficient of
-orthogonal guidance (``afx_cfg_ortho_coef``, orthogonal only) and ONE step kernel (``afx_teacher_euler_step``) that combines the
-two bf16 velocities, advances the fp32 latents in place and writes the bf16 copy the next forward reads.  No torch arithmetic
-runs inside the loop; the latents never leave the packed token layout.
+orthogonal guidance (``afx_cfg_ortho_coef``, orthogonal only) and ONE step kernel (``afx_teacher_euler_step`` /
+``afx_teacher_sde_step``) that combines the two bf16 velocities, advances the fp32 latents in place and writes the bf16 copy the next
+forward reads.  No torch arithmetic runs inside the loop -- with FlowSDE, nothing but the step's N(0, 1) draw, which stays torch's so
+that a ``torch.Generator`` reproduces a run; the latents never leave the packed token layout.
 """
 from __future__ import annotations
 
@@ -15,11 +17,13 @@ import torch
 
 from . import ops
 from .engine import MMDiTEngine
-from .schedule import FlowEulerODEScheduler
+from .schedule import FlowEulerODEScheduler, FlowSDEScheduler
+
+SAMPLERS = {'FlowEulerODE': FlowEulerODEScheduler, 'FlowSDE': FlowSDEScheduler}
 
 
 class TeacherSampler:
-    """``sampler(cond, noise) -> latents``: noise / latents [B, N, C] fp32 packed tokens.
+    """``sampler(cond, noise, generator=None, step_noise=None) -> latents``: noise / latents [B, N, C] fp32 packed tokens.
 
     engine: a ``teacher_head=True`` MMDiTEngine.
     cond: ``prompt_embeds`` [B, T, joint] (+ ``pooled`` for FLUX), ``hp``, ``wp``, and for true CFG ``negative_prompt_embeds``
@@ -31,22 +35,30 @@ class TeacherSampler:
     terminal_sigma ...); its ``seq_len`` is the number of latent pixels 4 hp wp, as the reference counts it
     (gaussian_flow.py:186 on [B, C, H, W] latents), or with ``tokens_as_seq_len`` the number of tokens hp wp, which is what a
     diffusers scheduler config's ``base_image_seq_len`` / ``max_image_seq_len`` are written for (the pipelines pass it).
-    prepare_steps=False evaluates the modulation vectors per forward (the plain path; same numbers)."""
+    prepare_steps=False evaluates the modulation vectors per forward (the plain path; same numbers).
+    sampler: 'FlowEulerODE' (the default) or 'FlowSDE', the scheduler class as the reference's ``test_cfg['sampler']`` names it;
+    FlowSDE's ``h`` (a float or 'inf') travels in scheduler_kwargs.  With FlowSDE every step takes a fresh N(0, 1) draw of the latents'
+    shape: from ``generator`` (one torch.randn per step, also on the steps whose draw is not read, so that the generator advances as in
+    the reference), or from ``step_noise`` [num_steps, B, N, C].  With FlowEulerODE both are accepted and ignored."""
 
     def __init__(self, engine: MMDiTEngine, num_steps: int = 28, guidance_scale: float = 1.0, distilled_guidance: Optional[float] = None,
                  guidance_interval: Optional[Sequence[float]] = None, orthogonal_guidance: bool = False,
-                 num_train_timesteps: int = 1000, prepare_steps: bool = True, tokens_as_seq_len: bool = False, **scheduler_kwargs: Any):
+                 num_train_timesteps: int = 1000, prepare_steps: bool = True, tokens_as_seq_len: bool = False, sampler: str = 'FlowEulerODE',
+                 **scheduler_kwargs: Any):
         if not engine.teacher_head:
             raise ValueError('TeacherSampler needs a teacher_head=True engine (a single velocity, not an ArcFlow policy)')
         if num_steps < 1:
             raise ValueError('num_steps must be >= 1')
+        if sampler not in SAMPLERS:
+            raise ValueError(f'sampler: one of {sorted(SAMPLERS)}, got {sampler!r}')
         self.engine, self.num_steps = engine, int(num_steps)
         self.guidance_scale, self.distilled_guidance = float(guidance_scale), distilled_guidance
         self.guidance_interval = None if guidance_interval is None else (float(guidance_interval[0]), float(guidance_interval[1]))
         self.orthogonal_guidance = bool(orthogonal_guidance)
         self.prepare_steps = bool(prepare_steps)
         self.tokens_as_seq_len = bool(tokens_as_seq_len)
-        self.scheduler = FlowEulerODEScheduler(num_train_timesteps, **scheduler_kwargs)
+        self.sampler = sampler
+        self.scheduler = SAMPLERS[sampler](num_train_timesteps, **scheduler_kwargs)
 
     # ------------------------------------------------------------------ schedule
     def schedule(self, hp: int, wp: int):
@@ -60,8 +72,10 @@ class TeacherSampler:
 
     # ------------------------------------------------------------------ one step
     def step(self, x: torch.Tensor, x_bf16: torch.Tensor, cond: Dict[str, Any], sigma: torch.Tensor, sigma_to: torch.Tensor,
-             active: bool, prepared_step: Optional[int] = None, scratch: Optional[dict] = None) -> None:
-        """Advance x (fp32, in place) and x_bf16 (its rounding, in place) from sigma [B] to sigma_to [B]."""
+             active: bool, prepared_step: Optional[int] = None, scratch: Optional[dict] = None, m: Optional[torch.Tensor] = None,
+             c_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None) -> None:
+        """Advance x (fp32, in place) and x_bf16 (its rounding, in place) from sigma [B] to sigma_to [B].  FlowSDE: m, c_noise [B]
+        (FlowSDEScheduler.coefficients) and the step's draw ``noise`` like x (None: no noise term on this step)."""
         eng = self.engine
         B = x.shape[0]
         s = scratch if scratch is not None else {}
@@ -80,10 +94,27 @@ class TeacherSampler:
                     s['coef'] = torch.empty(B, dtype=torch.float32, device=x.device)
                     s['ws'] = ops.cfg_ortho_ws(B, x[0].numel(), x.device)
                 coef = ops.cfg_ortho_coef(pos, neg, self.guidance_scale, out=s['coef'], ws=s['ws'])
-        ops.teacher_euler_step(x, pos, neg, sigma, sigma_to, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+        if self.sampler == 'FlowSDE':
+            if m is None or c_noise is None:
+                raise ValueError('a FlowSDE step needs m and c_noise (FlowSDEScheduler.coefficients)')
+            ops.teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+        else:
+            ops.teacher_euler_step(x, pos, neg, sigma, sigma_to, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+
+    # ------------------------------------------------------------------ the draws of the stochastic sampler
+    def _draw(self, shape, generator) -> torch.Tensor:
+        """One step's N(0, 1) draw [B, N, C] fp32 on the engine's device.  A generator draws on its own device (a CPU generator gives
+        the CPU stream); a list of generators draws one sample each."""
+        dev = self.engine.device
+        if isinstance(generator, (list, tuple)):
+            if len(generator) != shape[0]:
+                raise ValueError(f'{len(generator)} generators for a batch of {shape[0]}')
+            return torch.cat([torch.randn((1,) + tuple(shape[1:]), device=g.device, dtype=torch.float32, generator=g).to(dev) for g in generator])
+        gdev = generator.device if generator is not None else dev
+        return torch.randn(tuple(shape), device=gdev, dtype=torch.float32, generator=generator).to(dev)
 
     # ------------------------------------------------------------------ the loop
-    def _roll(self, cond: Dict[str, Any], noise: torch.Tensor) -> torch.Tensor:
+    def _roll(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         eng = self.engine
         B, N, _ = noise.shape
         hp, wp = cond['hp'], cond['wp']
@@ -92,6 +123,15 @@ class TeacherSampler:
         cond = {k: (v.to(dev, torch.bfloat16).contiguous() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in cond.items()}
         sigmas, active = self.schedule(hp, wp)
         sig = sigmas[:, None].expand(-1, B).contiguous().to(dev)             # [num_steps + 1, B]: row i is the per-sample sigma of step i
+        sde = self.sampler == 'FlowSDE'
+        if sde:
+            # the scheduler's per-step scalars, once: rows [num_steps, B] of m and c_noise, and whether the step's draw is read at all
+            co = torch.stack([torch.stack(self.scheduler.coefficients(i)) for i in range(self.num_steps)])           # [num_steps, 4]
+            m_rows = co[:, 2, None].expand(-1, B).contiguous().to(dev)
+            c_rows = co[:, 3, None].expand(-1, B).contiguous().to(dev)
+            reads_noise = ((co[:, 1] * co[:, 3]) != 0).tolist()               # sigma_to c_noise = 0 (always so on the final step): the kernel gets no noise
+            if step_noise is not None:
+                step_noise = step_noise.to(dev, torch.float32).contiguous()
         x = noise.to(dev, torch.float32).clone().contiguous()
         xb = x.to(torch.bfloat16)
         T = cond['prompt_embeds'].shape[1]
@@ -107,11 +147,16 @@ class TeacherSampler:
         for i in range(self.num_steps):
             if chunk > 1 and i % chunk == 0:
                 prepared = eng.prepare_steps(sig[i:min(i + chunk, self.num_steps)], cond.get('pooled'), g, B, N, T)
-            self.step(x, xb, cond, sig[i], sig[i + 1], active[i], (i % chunk) if (chunk > 1 and prepared) else None, scratch)
+            prep = (i % chunk) if (chunk > 1 and prepared) else None
+            if sde:
+                z = step_noise[i] if step_noise is not None else self._draw(x.shape, generator)
+                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, m_rows[i], c_rows[i], z if reads_noise[i] else None)
+            else:
+                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch)
         return x
 
     @torch.no_grad()
-    def __call__(self, cond: Dict[str, Any], noise: torch.Tensor) -> torch.Tensor:
+    def __call__(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         if noise.dim() != 3:
             raise ValueError(f'noise: need packed tokens [B, N, C], got {tuple(noise.shape)}')
         if noise.shape[1] != cond['hp'] * cond['wp']:
@@ -119,11 +164,61 @@ class TeacherSampler:
         if self.guidance_scale > 1.0 and 'negative_prompt_embeds' not in cond:
             raise ValueError('guidance_scale > 1 (true CFG) needs cond["negative_prompt_embeds"]')
         B = noise.shape[0]
+        if self.sampler != 'FlowSDE':
+            generator = step_noise = None
+        elif step_noise is not None:
+            if tuple(step_noise.shape) != (self.num_steps,) + tuple(noise.shape):
+                raise ValueError(f'step_noise: need [num_steps, B, N, C] = {(self.num_steps,) + tuple(noise.shape)}, got {tuple(step_noise.shape)}')
+        elif B > 4:
+            # the whole batch's draws first, step by step as a single roll would make them: the result does not depend on the micro-batch split
+            step_noise = torch.stack([self._draw(noise.shape, generator) for _ in range(self.num_steps)])
         if B <= 4:
-            return self._roll(cond, noise)
+            return self._roll(cond, noise, generator, step_noise)
         # the engine's prepared steps hold at most 4 samples: larger batches run as micro-batches of 4 (per-sample results are the same)
         outs: List[torch.Tensor] = []
         for a in range(0, B, 4):
             mb = {k: (v[a:a + 4] if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == B else v) for k, v in cond.items()}
-            outs.append(self._roll(mb, noise[a:a + 4]))
+            outs.append(self._roll(mb, noise[a:a + 4], None, None if step_noise is None else step_noise[:, a:a + 4]))
         return torch.cat(outs)
+
+
+_SHIFT_KEYS = ('shift', 'use_dynamic_shifting', 'base_seq_len', 'max_seq_len', 'base_logshift', 'max_logshift')
+# ContinuousTimeStepSampler's own defaults (lakonlab/models/diffusions/sampler.py:11-22), for a config dict that leaves a key out
+_TIMESTEP_SAMPLER_DEFAULTS = dict(shift=1.0, use_dynamic_shifting=False, base_seq_len=256, max_seq_len=4096, base_logshift=0.5, max_logshift=1.15)
+
+
+def sampler_kwargs_from_test_cfg(test_cfg: Optional[Dict[str, Any]] = None, timestep_sampler: Any = None, num_timesteps: int = 1000) -> Dict[str, Any]:
+    """A reference ``test_cfg`` (what ``GaussianFlow.forward_test`` reads, gaussian_flow.py:157-181) -> the keyword arguments of
+    ``TeacherSampler(engine, **kwargs)``.
+
+    ``sampler`` (default 'FlowEulerODE') picks the scheduler; ``sampler_kwargs`` go to it (FlowSDE's ``h``); the shift family
+    (shift, use_dynamic_shifting, base_seq_len, max_seq_len, base_logshift, max_logshift) that ``sampler_kwargs`` leaves out is
+    taken from ``test_cfg`` itself and otherwise from ``timestep_sampler`` -- the model's training timestep sampler, as an object
+    with these attributes or as its config dict (a key it leaves out has ContinuousTimeStepSampler's default) -- exactly as
+    gaussian_flow.py:167-171 fills them.  ``num_timesteps`` of the test_cfg is the number of sampling steps (default: the model's
+    ``num_timesteps``, the argument here, which is also the scheduler's ``num_train_timesteps``).  A sampler this project does
+    not have (FlowAdapter, any diffusers scheduler) raises ValueError."""
+    cfg = dict(test_cfg or {})
+    name = cfg.get('sampler', 'FlowEulerODE')
+    if name not in SAMPLERS:
+        raise ValueError(f'test_cfg sampler {name!r} is not available here: one of {sorted(SAMPLERS)} (FlowAdapter and the diffusers schedulers are not built)')
+    kw = dict(cfg.get('sampler_kwargs') or {})
+    unknown = set(kw) - set(SAMPLERS[name]._DEFAULTS)
+    if unknown:
+        raise TypeError(f'{name}Scheduler takes no {sorted(unknown)}')
+    for key in _SHIFT_KEYS:
+        if key in kw:
+            continue
+        if key in cfg:
+            kw[key] = cfg[key]
+        elif isinstance(timestep_sampler, dict):
+            kw[key] = timestep_sampler.get(key, _TIMESTEP_SAMPLER_DEFAULTS[key])
+        elif timestep_sampler is not None:
+            kw[key] = getattr(timestep_sampler, key)
+        else:
+            kw[key] = _TIMESTEP_SAMPLER_DEFAULTS[key]
+    kw.update(sampler=name, num_steps=int(cfg.get('num_timesteps', num_timesteps)), num_train_timesteps=int(num_timesteps),
+              orthogonal_guidance=bool(cfg.get('orthogonal_guidance', False)))
+    if cfg.get('guidance_interval') is not None:
+        kw['guidance_interval'] = [float(v) for v in cfg['guidance_interval']]
+    return kw

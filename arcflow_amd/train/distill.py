@@ -308,12 +308,15 @@ class ArcFlowDistiller:
 
     @torch.no_grad()
     def sample_teacher(self, cond, noise, num_steps: int = 28, guidance_scale: Optional[float] = None,
-                       distilled_guidance: Optional[float] = None, **sampler_kwargs):
+                       distilled_guidance: Optional[float] = None, sampler: str = 'FlowEulerODE', h=None, generator=None,
+                       step_noise=None, **sampler_kwargs):
         """Roll the frozen teacher from ``noise`` [B, N, C] (packed tokens, fp32) to latents with the Euler ODE sampler
         (arcflow_amd.teacher.TeacherSampler; GaussianFlow.forward_test in the reference) on this distiller's teacher context -- no
         new weights.  Defaults are _teacher_u's: true CFG ``cfg.teacher_guidance_scale`` (needs cond['negative_prompt_embeds'] when
         > 1), guidance embedding ``cfg.teacher_guidance`` (else ``cfg.guidance``), time shift ``cfg.shift``.  Further keywords
-        (guidance_interval, orthogonal_guidance, terminal_sigma ...) go to TeacherSampler."""
+        (guidance_interval, orthogonal_guidance, terminal_sigma ...) go to TeacherSampler.  sampler='FlowSDE': the stochastic
+        sampler with noise strength ``h`` (a float, default 1.0, or 'inf'), its per-step draws from ``generator`` or from
+        ``step_noise`` [num_steps, B, N, C]."""
         from ..teacher import TeacherSampler
         c = self.cfg
         if guidance_scale is None:
@@ -321,8 +324,10 @@ class ArcFlowDistiller:
         if distilled_guidance is None:
             distilled_guidance = c.teacher_guidance if c.teacher_guidance is not None else c.guidance
         sampler_kwargs.setdefault('shift', c.shift)
+        if h is not None:
+            sampler_kwargs['h'] = h
         return TeacherSampler(self.teacher, num_steps, guidance_scale=guidance_scale, distilled_guidance=distilled_guidance,
-                              **sampler_kwargs)(cond, noise)
+                              sampler=sampler, **sampler_kwargs)(cond, noise, generator=generator, step_noise=step_noise)
 
     def student_forward_unmerged(self, x_src, sigma_src, cond, p_drop: float = 0.0, seed: int = 0, x_bf16=None):
         """The student's forward as peft evaluates it -- y = W x + B (A dropout(x)) per adapted linear, NOT folded into W -- on the

@@ -216,6 +216,19 @@ int afx_cfg_combine(const float* pos, const float* neg, float scale, float* out,
 int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, const float* sigma, const float* sigma_to,
                            const float* coef, float scale, float* x_out, void* x_out_bf16, int32_t batch, int64_t n,
                            int32_t max_blocks, void* stream);
+/* One step of the teacher's stochastic sampler (FlowSDEScheduler.step, prediction_type 'u', schedulers/flow_sde.py:143-166) with the
+ * same operands, layout and CFG combine as afx_teacher_euler_step, in one launch:
+ *   u     = pos + (pos - neg) (scale - 1) - coef[b] pos          exactly as afx_teacher_euler_step forms it
+ *   x0    = x - sigma[b] u,    e = x + (1 - sigma[b]) u
+ *   x_out = (1 - sigma_to[b]) x0 + sigma_to[b] (m[b] e + c_noise[b] noise)          all in fp32
+ * m, c_noise [batch] fp32: the scheduler's mixing weight (sigma_to alpha / (sigma alpha_to))^(h^2) and sqrt(max(1 - m^2, 0)), computed
+ * on the host (FlowSDEScheduler.coefficients); m = 1, c_noise = 0 is the ODE step.  noise [batch, n] fp32 N(0, 1) draws, 16-byte
+ * aligned; NULL skips the noise term and its read (every sample's sigma_to c_noise is 0, as on the final step).  neg, coef, x_out
+ * aliasing x, x_out_bf16, n, alignment and max_blocks as for afx_teacher_euler_step.  Traffic at 1024 x 1024 (262144 elements per
+ * image): 4 + 2 + 2 + 4 B read and 4 + 2 B written per element, about 4.7 MB per image and step. */
+int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma,
+                         const float* sigma_to, const float* m, const float* c_noise, const float* coef, float scale, float* x_out,
+                         void* x_out_bf16, int32_t batch, int64_t n, int32_t max_blocks, void* stream);
 /* coef[b] = mean(bias pos) / max(mean(pos pos), 1e-6) over the n elements of sample b, bias = (pos - neg) (scale - 1) rounded to
  * fp32 as the step kernel computes it: the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25, dim = [1..]).
  * Deterministic: a number of work-groups per sample that depends on n alone, exact fp64 products, one slot of `ws` per

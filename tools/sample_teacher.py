@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sample the TEACHER into the distillation cache: every record of ``--cache-dir`` (tools/cache_prompts.py, or written here from
 ``--prompts``) gets the ``latents`` (+ ``latent_size``) of a teacher sample for its prompt -- the third source of latents for the
-data mode next to encoded images (tools/cache_latents.py) and the reference's own caches.  Euler ODE steps with optional true
+data mode next to encoded images (tools/cache_latents.py) and the reference's own caches.  Euler ODE steps, or with
+``--sampler FlowSDE --h <float | inf>`` the stochastic steps of FlowSDEScheduler (diverse latents for one prompt), with optional true
 classifier-free guidance (arcflow_amd.teacher.TeacherSampler; GaussianFlow.forward_test in the reference).
 
     python tools/sample_teacher.py --family flux --snapshot /path/to/FLUX.1-dev --prompts prompts.txt --cache-dir data/teacher_flux
@@ -30,7 +31,8 @@ def unpack(latents: torch.Tensor, hp: int, wp: int) -> torch.Tensor:
 
 def add_teacher_latents(sampler, cache_dir: str, negative=None, seed: int = 0, dtype=torch.float16, device='cuda'):
     """sampler(cond, noise [1, N, 64]) -> packed latents.  Every record of ``cache_dir`` is sampled at its own ``latent_size`` from
-    noise seeded with ``seed + index`` and rewritten with ``latents``.  negative: prompt_embed_kwargs of the negative prompt (true
+    noise seeded with ``seed + index`` (the same generator goes on to the step draws of a stochastic sampler) and rewritten with
+    ``latents``.  negative: prompt_embed_kwargs of the negative prompt (true
     CFG).  Returns {file name: the fp32 latents [16, H, W] before the cast to ``dtype``}."""
     from arcflow_amd.train import data
     ds = data.PromptEmbedCache(cache_dir)
@@ -41,8 +43,9 @@ def add_teacher_latents(sampler, cache_dir: str, negative=None, seed: int = 0, d
             item['negative_prompt_embed_kwargs'] = negative
         cond = data.collate([item], device=device)
         _, h, w = item['latent_size']
-        noise = torch.randn(1, cond['hp'] * cond['wp'], 64, generator=torch.Generator().manual_seed(seed + i)).to(device)
-        lat = unpack(sampler(cond, noise), cond['hp'], cond['wp'])[0].float().cpu()
+        gen = torch.Generator().manual_seed(seed + i)
+        noise = torch.randn(1, cond['hp'] * cond['wp'], 64, generator=gen).to(device)
+        lat = unpack(sampler(cond, noise, generator=gen), cond['hp'], cond['wp'])[0].float().cpu()
         assert tuple(lat.shape) == (16, h, w)
         path = os.path.join(cache_dir, fn)
         rec = read_record(path)
@@ -94,6 +97,9 @@ def main(argv=None):
     ap.add_argument('--guidance-interval', type=float, nargs=2, default=None)
     ap.add_argument('--orthogonal-guidance', action='store_true')
     ap.add_argument('--shift', type=float, default=3.2)
+    ap.add_argument('--sampler', choices=['FlowEulerODE', 'FlowSDE'], default='FlowEulerODE')
+    ap.add_argument('--h', type=lambda v: v if v == 'inf' else float(v), default=None,
+                    help='--sampler FlowSDE: noise strength, a float (0 = the ODE; default 1.0) or inf (re-noise the clean prediction completely)')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--max-sequence-length', type=int, default=512)
     args = ap.parse_args(argv)
@@ -131,7 +137,8 @@ def main(argv=None):
     if args.true_cfg_scale > 1.0 and negative is None:
         raise SystemExit('--true-cfg-scale > 1 needs --negative-prompt (with --prompts) or --negative-prompt-embeds')
     sampler = TeacherSampler(engine, args.steps, guidance_scale=args.true_cfg_scale, distilled_guidance=args.guidance_scale,
-                             guidance_interval=args.guidance_interval, orthogonal_guidance=args.orthogonal_guidance, shift=args.shift)
+                             guidance_interval=args.guidance_interval, orthogonal_guidance=args.orthogonal_guidance, shift=args.shift,
+                             sampler=args.sampler, **({} if args.h is None else dict(h=args.h)))
     done = add_teacher_latents(sampler, args.cache_dir, negative, args.seed, device=dev)
     print(f'wrote teacher latents into {len(done)} records of {args.cache_dir}')
     return done
