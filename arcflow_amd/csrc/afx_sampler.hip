@@ -13,6 +13,10 @@
 //     mean(bias pos) / max(mean(pos pos), 1e-6) over all n elements of a sample.  A fixed number of work-groups per sample
 //     (a function of n alone), every product exact in fp64, one workspace slot per work-group, the slots added in index order
 //     by the second launch: bit-reproducible.
+//   * sample_score_partial_kernel / sample_score_finish_kernel: per-sample agreement sums of two batches (training-time evaluation:
+//     student against teacher samples), sum (a-b)^2, sum a^2, sum b^2, sum a b over the n elements of a sample, on the coefficient's
+//     reduction scheme: the same fixed partition, elements widened to fp64 (after the optional image-range transform in fp32), one slot
+//     of 4 doubles per work-group, the slots added in index order by the second launch.  16 B per lane and operand: 8 bf16 or 4 fp32.
 #include <algorithm>
 
 #include "afx_api_util.h"
@@ -162,6 +166,72 @@ __global__ __launch_bounds__(64) void cfg_ortho_finish_kernel(const double* __re
   coef[b] = (float)(s_bp * inv_n / den);
 }
 
+// The image range val_step produces: clamp(v / 2 + 0.5, 0, 1) in fp32 (v / 2 is exact, so a contracted multiply-add gives the same value).
+AFX_DEV float unit_range(float v) { return fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f); }
+
+// One unit = 16 B of an operand: 8 bf16 or 4 fp32 elements (n % 64 == 0: a unit never straddles two samples).
+template <bool BF16>
+AFX_DEV void load_unit(const void* p, int64_t unit, float (&v)[BF16 ? 8 : 4]) {
+  if constexpr (BF16) {
+    unpack8(*reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(p) + unit * 8), v);
+  } else {
+    const f32x4_t t = *reinterpret_cast<const f32x4_t*>(reinterpret_cast<const float*>(p) + unit * 4);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  }
+}
+
+// grid (parts, B): work-group w of sample s owns the units [w upw, min((w + 1) upw, units_per_sample)) and writes
+// ws[(s parts + w) 4 + {0, 1, 2, 3}] = sum (a-b)^2, sum a^2, sum b^2, sum a b.  Every element is widened to fp64 first; the products
+// of two widened fp32 values are exact, the difference and its square round once each.
+template <bool BF16>
+__global__ __launch_bounds__(256) void sample_score_partial_kernel(const void* __restrict__ a, const void* __restrict__ b, int transform,
+                                                                   double* __restrict__ ws, int64_t units_per_sample, int64_t upw) {
+  constexpr int E = BF16 ? 8 : 4;
+  __shared__ double red[4][4];
+  const int64_t s = blockIdx.y;
+  const int64_t begin = (int64_t)blockIdx.x * upw;
+  const int64_t end = begin + upw < units_per_sample ? begin + upw : units_per_sample;
+  const int64_t base = s * units_per_sample;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t u = begin + threadIdx.x; u < end; u += 256) {
+    float p[E], q[E];
+    load_unit<BF16>(a, base + u, p);
+    load_unit<BF16>(b, base + u, q);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const double x = (double)(transform ? unit_range(p[e]) : p[e]);
+      const double y = (double)(transform ? unit_range(q[e]) : q[e]);
+      const double d = x - y;
+      acc[0] += d * d;
+      acc[1] += x * x;
+      acc[2] += y * y;
+      acc[3] += x * y;
+    }
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double v = wave_sum_f64(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {      // an empty work-group (upw rounded up) writes zeros: every slot the finish reads is written
+    const int k = threadIdx.x;
+    ws[(s * gridDim.x + blockIdx.x) * 4 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// one lane per (sample, sum): out[s][k] = the slots of sample s added in index order
+__global__ __launch_bounds__(64) void sample_score_finish_kernel(const double* __restrict__ ws, double* __restrict__ out, int batch,
+                                                                 int parts) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= batch * 4) return;
+  const int s = i >> 2, k = i & 3;
+  double v = 0.0;
+  for (int w = 0; w < parts; ++w) v += ws[((int64_t)s * parts + w) * 4 + k];
+  out[i] = v;
+}
+
 }  // namespace afx
 
 using namespace afx;
@@ -232,6 +302,36 @@ int afx_cfg_ortho_coef(const void* pos, const void* neg, float scale, float* coe
                      (double*)ws, cps, cpw);
   hipLaunchKernelGGL(cfg_ortho_finish_kernel, dim3((batch + 63) / 64), dim3(64), 0, st, (const double*)ws, coef, batch, parts,
                      1.0 / (double)n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int64_t afx_sample_score_ws_bytes(int32_t batch, int64_t n) {
+  if (batch < 0 || n < 64 || n % 64) return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_sample_score_ws_bytes");
+  return (int64_t)batch * ortho_parts(n) * 4 * (int64_t)sizeof(double);
+}
+
+int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transform, double* out, void* ws, int64_t ws_bytes,
+                     int32_t batch, int64_t n, void* stream) {
+  if (!a || !b || !out || !ws) return fail(AFX_E_INVALID, "null argument to afx_sample_score");
+  if (dtype != AFX_DT_BF16 && dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "afx_sample_score: dtype must be AFX_DT_BF16 or AFX_DT_F32");
+  if (transform != 0 && transform != 1) return fail(AFX_E_INVALID, "afx_sample_score: transform must be 0 or 1");
+  if (batch < 0 || batch > 65535 || n < 64 || n % 64)
+    return fail(AFX_E_INVALID, "bad argument to afx_sample_score (n = elements per sample must be a positive multiple of 64)");
+  if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7))
+    return fail(AFX_E_INVALID, "afx_sample_score: a and b must be 16-byte aligned, out and ws 8-byte aligned");
+  const int parts = ortho_parts(n);
+  if (ws_bytes < (int64_t)batch * parts * 4 * (int64_t)sizeof(double))
+    return fail(AFX_E_INVALID, "afx_sample_score: workspace smaller than afx_sample_score_ws_bytes()");
+  if (batch == 0) return AFX_OK;
+  const bool bf16 = dtype == AFX_DT_BF16;
+  const int64_t ups = n / (bf16 ? 8 : 4), upw = (ups + parts - 1) / parts;
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16)
+    hipLaunchKernelGGL(sample_score_partial_kernel<true>, dim3(parts, batch), dim3(256), 0, st, a, b, (int)transform, (double*)ws, ups, upw);
+  else
+    hipLaunchKernelGGL(sample_score_partial_kernel<false>, dim3(parts, batch), dim3(256), 0, st, a, b, (int)transform, (double*)ws, ups, upw);
+  hipLaunchKernelGGL(sample_score_finish_kernel, dim3((batch * 4 + 63) / 64), dim3(64), 0, st, (const double*)ws, out, batch, parts);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

@@ -491,6 +491,39 @@ def cfg_ortho_coef(pos, neg, scale: float, out: Optional[torch.Tensor] = None, w
     return out
 
 
+def sample_score_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
+    """Workspace of sample_score for [batch, n] operands (afx_sample_score_ws_bytes): fp64 partial sums, 4 per work-group."""
+    need = _lib.load().afx_sample_score_ws_bytes(batch, n)
+    if need < 0:
+        _lib.check(int(need))
+    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+
+
+def sample_score(a, b, transform: bool = False, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, 4] float64 = (sum (a-b)^2, sum a^2, sum b^2, sum a b) per sample over every other dimension (afx_sample_score).
+    a, b [B, ...], both fp32 or both bf16, contiguous, numel / B a multiple of 64.  transform: score clamp(v / 2 + 0.5, 0, 1)
+    (fp32) of both operands, the [0, 1] image range.  Elements are widened to fp64; bit-reproducible (fixed partition, ordered sum).
+    Nothing is copied or cast: a wrong dtype or layout raises.  out / ws: reuse buffers (ops.sample_score_ws)."""
+    lib = _lib.load()
+    for t in (a, b, out, ws):
+        if t is not None and t.device.type != 'cuda':
+            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
+    B = a.shape[0]
+    n = a[0].numel() if B else 0
+    a = _packed(a, a.dtype, a.shape, 'a')
+    b = _packed(b, a.dtype, a.shape, 'b')
+    out = torch.empty(B, 4, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 4), 'out')
+    if ws is None:
+        ws = sample_score_ws(B, n, a.device)
+    elif not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.sample_score_ws)')
+    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    _lib.check(lib.afx_sample_score(_p(a), _p(b), dt, int(bool(transform)), _p(out), _p(ws), ws.numel() * ws.element_size(), B, n, _s()))
+    return out
+
+
 def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
     """One step of the teacher's Euler ODE sampler in one launch (afx_teacher_euler_step):

@@ -33,6 +33,22 @@ def retrieve_raw_timesteps(num_inference_steps: int, total_substeps: int, timest
     return times, per_step, sum(per_step)
 
 
+def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
+                   num_train_timesteps: int = 1000) -> List[float]:
+    """sigma at the start of every student step plus the terminal 0, as the pipelines' ``__call__`` walks them: the raw sub-step grid
+    (retrieve_raw_timesteps) through the static shift of FlowMatchEulerDiscreteScheduler in fp32, every step reading the first
+    sub-step of its segment as ``timestep / num_train_timesteps``.  For samplers outside the pipelines (ArcFlowDistiller.sample_student)."""
+    raw, per_step, total = retrieve_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio)
+    sch = FlowMatchEulerDiscreteScheduler(num_train_timesteps=num_train_timesteps, shift=shift, use_dynamic_shifting=False)
+    ts = sch.set_timesteps(sigmas=raw).float().tolist()
+    out, tid = [], 0
+    for n in per_step:
+        out.append(ts[tid] / num_train_timesteps)
+        tid += n
+    assert tid == total == len(ts)
+    return out + [0.0]
+
+
 class _Config(dict):
     """dict with attribute access, like diffusers' FrozenDict configs."""
     __getattr__ = dict.get

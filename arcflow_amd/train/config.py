@@ -13,6 +13,8 @@ from typing import Any, Dict, Tuple
 from .distill import DistillConfig
 
 _FAMILY = {'ArcFluxTransformer2DModel': 'flux', 'ArcQwenImageTransformer2DModel': 'qwen'}
+# this project's own key (absent from the reference's configs): how the training-time evaluation samples -- evaluate.Evaluator
+EVAL_CFG_DEFAULTS = dict(num_batches=1, seed=0, teacher_steps=28, use_ema=True)
 _MODE = {'ArcFlowImitationDataFree': 'data_free', 'ArcFlowImitation': 'data'}        # diffusion.type -> DistillConfig.mode (arcflow.py:275,339)
 
 
@@ -102,11 +104,21 @@ def distill_setup(cfg: Dict[str, Any]) -> Tuple[str, Dict[str, Any], DistillConf
         mode=_MODE[diff['type']])
     runner = cfg.get('runner', {})
     ck = cfg.get('checkpoint_config', {})
+    # evaluation (latent_diffusion_text_image.py:108-170 val_step): the reference's eval_interval + test_cfg, and the optional eval_cfg of this project
+    test_cfg = dict(cfg.get('test_cfg') or {})
+    eval_cfg = dict(EVAL_CFG_DEFAULTS)
+    unknown = set(cfg.get('eval_cfg') or {}) - set(eval_cfg)
+    if unknown:
+        raise ValueError(f'eval_cfg: unknown keys {sorted(unknown)} (known: {sorted(eval_cfg)})')
+    eval_cfg.update(cfg.get('eval_cfg') or {})
     run = dict(name=cfg.get('name', 'arcflow'), total_iters=cfg.get('total_iters', 10000),
                samples_per_gpu=cfg.get('data', {}).get('train_dataloader', {}).get('samples_per_gpu', 1),
                save_interval=ck.get('interval', 500), ckpt_dir=os.path.join(ck.get('out_dir', 'checkpoints/'), cfg.get('name', 'arcflow')),
                ckpt_fp16=runner.get('ckpt_fp16', False), ckpt_fp16_ema=runner.get('ckpt_fp16_ema', False),
                resume_from=cfg.get('resume_from'), load_from=cfg.get('load_from'), work_dir=cfg.get('work_dir'),
                lora_dropout=den.get('lora_dropout', 0.0), policy_kwargs=diff.get('policy_kwargs', {}),
-               pretrained=den.get('pretrained'), data_train=cfg.get('data', {}).get('train', {}))
+               pretrained=den.get('pretrained'), data_train=cfg.get('data', {}).get('train', {}),
+               eval_interval=cfg.get('eval_interval'), eval_cfg=eval_cfg,
+               test_cfg=dict(nfe=test_cfg.get('nfe'), timestep_ratio=test_cfg.get('timestep_ratio'),
+                             distilled_guidance_scale=test_cfg.get('distilled_guidance_scale')))
     return family, eng, dc, run

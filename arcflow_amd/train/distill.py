@@ -28,6 +28,7 @@ interval scalings are then per-sample [B] tensors, as in the reference where ``s
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -328,6 +329,59 @@ class ArcFlowDistiller:
             sampler_kwargs['h'] = h
         return TeacherSampler(self.teacher, num_steps, guidance_scale=guidance_scale, distilled_guidance=distilled_guidance,
                               sampler=sampler, **sampler_kwargs)(cond, noise, generator=generator, step_noise=step_noise)
+
+    # ------------------------------------------------------------------ evaluation: the student's own samples
+    def _exchange_ema(self, scratch: torch.Tensor) -> None:
+        """params <-> ema through ``scratch`` (three device copies, bit-exact), then the bf16 working copies of what is now live."""
+        scratch.copy_(self.params)
+        self.params.copy_(self.ema)
+        self.ema.copy_(scratch)
+        self._sync_working_copies()
+        if self.trunk is not None:
+            self.trunk.refresh()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate the EMA weights (the reference's ``diffusion_use_ema``): inside the block the flat ``params`` buffer holds the EMA
+        and ``ema`` holds the live parameters, and the bf16 working copies / LoRA operands are those of the EMA.  On exit -- also when
+        the body raises -- the contents are exchanged back and the working copies rebuilt, so params, ema, the optimizer moments,
+        iteration, opt_steps and the working copies are bit-equal to their state before entry (copies and deterministic casts only).
+        One scratch buffer of the flat size lives for the duration of the block.  Do not train inside it."""
+        scratch = torch.empty_like(self.params)
+        self._exchange_ema(scratch)
+        try:
+            yield self
+        finally:
+            self._exchange_ema(scratch)
+            del scratch
+
+    @torch.no_grad()
+    def sample_student(self, cond, noise, nfe: Optional[int] = None, timestep_ratio: Optional[float] = None, ema: bool = False):
+        """Roll the student from ``noise`` [B, N, C] (packed tokens) to latents [B, N, C] fp32 as the pipelines' ``__call__`` does: ``nfe``
+        forwards of the merged engine (student_forward: W + B A of the live adapters, no dropout), each followed by the analytic step
+        ``ops.arcflow_step`` to the next step's sigma (schedule.student_sigmas with cfg.shift / cfg.total_substeps; defaults cfg.nfe,
+        cfg.timestep_ratio).  ema=True: on the EMA weights (ema_weights()).  B > 4 runs as micro-batches of 4, as TeacherSampler does."""
+        from ..schedule import student_sigmas
+        if ema:
+            with self.ema_weights():
+                return self.sample_student(cond, noise, nfe, timestep_ratio)
+        c = self.cfg
+        nfe = c.nfe if nfe is None else int(nfe)
+        ratio = c.timestep_ratio if timestep_ratio is None else float(timestep_ratio)
+        if noise.dim() != 3 or noise.shape[1] != cond['hp'] * cond['wp'] or noise.shape[2] != self.C:
+            raise ValueError(f"noise: need packed tokens [B, {cond['hp'] * cond['wp']}, {self.C}], got {tuple(noise.shape)}")
+        sig = student_sigmas(nfe, c.total_substeps, ratio, c.shift)
+        B = noise.shape[0]
+        outs = []
+        for a in range(0, B, 4):
+            b = min(a + 4, B)
+            cc = cond if B <= 4 else {k: (v[a:b] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B else v) for k, v in cond.items()}
+            x = noise[a:b].to(self.device, torch.float32).contiguous()
+            for i in range(nfe):
+                out = self.student_forward(x, torch.full((b - a,), sig[i], dtype=torch.float32, device=self.device), cc)
+                x = ops.arcflow_step(x, out.means, out.logweights, out.loggammas, sig[i], sig[i], sig[i + 1], eps=c.eps)
+            outs.append(x)
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     def student_forward_unmerged(self, x_src, sigma_src, cond, p_drop: float = 0.0, seed: int = 0, x_bf16=None):
         """The student's forward as peft evaluates it -- y = W x + B (A dropout(x)) per adapted linear, NOT folded into W -- on the

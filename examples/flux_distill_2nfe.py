@@ -26,5 +26,11 @@ runner = dict(ckpt_trainable_only=True, ckpt_fp16=True, ckpt_fp16_ema=True)
 data = dict(train_dataloader=dict(samples_per_gpu=4))
 checkpoint_config = dict(interval=500, out_dir='checkpoints/')
 total_iters = 10000
+# evaluation, off unless tools/train.py gets --eval-interval (an integer, or 'config' for eval_interval below): rank 0 scores the student's
+# samples against the teacher's ODE from the same noise and appends one line to <work-dir>/eval.jsonl.  eval_interval and test_cfg are the
+# reference's keys; eval_cfg is this project's own and may be left out (these are its defaults).
+eval_interval = 500
+test_cfg = dict(nfe=2, timestep_ratio=1.0, total_substeps=128, distilled_guidance_scale=3.5)
+eval_cfg = dict(num_batches=1, seed=0, teacher_steps=28, use_ema=True)
 custom_hooks = [dict(type='ExponentialMovingAverageHookMod', start_iter=100, momentum_cfg=dict(gamma=7.0))]
 resume_from = f'checkpoints/{name}/latest.pth'

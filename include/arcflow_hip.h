@@ -237,6 +237,20 @@ int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const
 int64_t afx_cfg_ortho_ws_bytes(int32_t batch, int64_t n);
 int afx_cfg_ortho_coef(const void* pos, const void* neg, float scale, float* coef, void* ws, int64_t ws_bytes, int32_t batch,
                        int64_t n, void* stream);
+/* Per-sample agreement sums of two batches (training-time evaluation: student samples a against teacher samples b):
+ *   out[s] = { sum (a-b)^2, sum a^2, sum b^2, sum a b }  over the n elements of sample s, as fp64.
+ * a, b [batch, n], both `dtype` (AFX_DT_BF16 or AFX_DT_F32), 16-byte aligned; n a positive multiple of 64; out [batch, 4] fp64.
+ * transform 0: the values as they are (packed latents).  transform 1: clamp(v / 2 + 0.5, 0, 1) in fp32 on both operands before
+ * anything else -- the image range of the reference's val_step, so decoded images are scored in [0, 1].
+ * Every element is widened to fp64 after the transform; differences, products and sums are fp64.  Deterministic on the scheme of
+ * afx_cfg_ortho_coef: min(64, ceil(n / 8192)) work-groups per sample (a function of n alone), one slot of 4 doubles of `ws` per
+ * work-group, the slots added in index order by a second launch; no atomics, bit-reproducible.  ws: afx_sample_score_ws_bytes(batch,
+ * n) bytes, 8-byte aligned, private to the call until it completes.  Traffic: 2 x 2 B (bf16) or 2 x 4 B (fp32) read per element,
+ * 32 B written per work-group and per sample: 1 MB per 1024 x 1024 latent pair in bf16 (262144 elements), 12.6 MB per decoded
+ * 3 x 1024 x 1024 bf16 image pair. */
+int64_t afx_sample_score_ws_bytes(int32_t batch, int64_t n);
+int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transform, double* out, void* ws, int64_t ws_bytes,
+                     int32_t batch, int64_t n, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,

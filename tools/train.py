@@ -24,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='ArcFlow distillation on MI355X')
     ap.add_argument('config')
     ap.add_argument('--work-dir')
@@ -43,7 +43,28 @@ def parse_args():
     ap.add_argument('--snapshot', help='local FLUX.1-dev / Qwen-Image snapshot (text_encoder*/, tokenizer*/) for --prompts')
     ap.add_argument('--latent-tokens', type=int, nargs=2, default=[64, 64], help='synthetic data: packed latent grid (64 64 = 1024^2)')
     ap.add_argument('--export', help='write the EMA adapter (diffusers layout) here when done')
-    return ap.parse_args()
+    ap.add_argument('--eval-interval', help="score student against teacher samples before the first and after every N-th iteration: an integer, or "
+                                            "'config' for the config's eval_interval (default: off)")
+    ap.add_argument('--eval-batches', type=int, help='evaluate on the first K batches of the data source (default: eval_cfg.num_batches, 1)')
+    ap.add_argument('--eval-teacher-steps', type=int, help='steps of the teacher ODE the student is scored against (default: eval_cfg.teacher_steps, 28)')
+    return ap.parse_args(argv)
+
+
+def eval_interval(args, run) -> int:
+    """Iterations between two evaluations; 0 = off, which is what a command line without --eval-interval gives."""
+    if args.eval_interval is None:
+        return 0
+    if args.eval_interval == 'config':
+        if not run.get('eval_interval'):
+            raise SystemExit('--eval-interval config: the config has no eval_interval')
+        return int(run['eval_interval'])
+    try:
+        n = int(args.eval_interval)
+    except ValueError:
+        raise SystemExit(f"--eval-interval: an integer or 'config', got {args.eval_interval!r}")
+    if n < 0:
+        raise SystemExit('--eval-interval must be >= 0')
+    return n
 
 
 def _options(pairs):
@@ -57,10 +78,10 @@ def _options(pairs):
     return out
 
 
-def main():
+def main(argv=None):
     # the host driver only supports dmabuf IPC: must be in the environment BEFORE the first torch.cuda call initialises the HIP / HSA runtime
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    args = parse_args()
+    args = parse_args(argv)
     from arcflow_amd.train import ArcFlowDistiller, checkpoint, config, data
     cfg = config.apply_options(config.load_config(args.config), _options(args.cfg_options))
     family, eng, dc, run = config.distill_setup(cfg)
@@ -112,6 +133,16 @@ def main():
     # ---- data ---------------------------------------------------------------------------------------------
     B = run['samples_per_gpu']
     loader = None
+    n_eval = eval_interval(args, run)
+    ecfg = dict(run['eval_cfg'])
+    if args.eval_batches is not None:
+        ecfg['num_batches'] = args.eval_batches
+    if args.eval_teacher_steps is not None:
+        ecfg['teacher_steps'] = args.eval_teacher_steps
+    eval_conds = None                  # rank 0, evaluation on: the first num_batches batches of the data source, drawn apart from the training order
+    want_eval = n_eval > 0 and rank == 0
+    if n_eval > 0 and ecfg['num_batches'] < 1:
+        raise SystemExit('evaluation needs at least one batch (--eval-batches / eval_cfg.num_batches)')
     if args.data_dir:
         neg_path = args.negative_prompt_embeds or run['data_train'].get('negative_prompt_embeds_path')
         if dc.teacher_guidance_scale > 1.0 and not neg_path:
@@ -131,6 +162,9 @@ def main():
                     yield data.collate([ds[j] for j in idx[i:i + B]], device=dev)
                 epoch += 1
         loader = batches()
+        if want_eval:
+            order = list(iter(data.DistributedSampler(ds, world, rank, shuffle=False, samples_per_gpu=B, seed=args.seed)))
+            eval_conds = [data.collate([ds[j] for j in order[i:i + B]], device=dev) for i in range(0, min(len(order), ecfg['num_batches'] * B) - B + 1, B)]
     elif args.prompts:          # text encoder inside the training process (the uncommented text_encoder of _ddp_train.py)
         if not args.snapshot:
             raise SystemExit('--prompts needs --snapshot')
@@ -146,6 +180,9 @@ def main():
                 yield enc.cond([lines[(i + j) % len(lines)] for j in range(B)], args.latent_tokens[0], args.latent_tokens[1], neg)
                 i += B * world
         loader = prompt_batches()
+        if want_eval:
+            eval_conds = [enc.cond([lines[(k * B + j) % len(lines)] for j in range(B)], args.latent_tokens[0], args.latent_tokens[1], neg)
+                          for k in range(ecfg['num_batches'])]
     else:
         if dc.mode == 'data' and not args.synthetic:
             raise SystemExit("diffusion.type 'ArcFlowImitation' trains from latents: pass --data-dir (records with latents) or --synthetic")
@@ -157,8 +194,37 @@ def main():
             synth['negative_prompt_embeds'] = (torch.randn(B, T, eng['joint_dim'], device=dev, generator=rng) * 0.1).bfloat16()
         if dc.mode == 'data':
             synth['latents'] = torch.randn(B, eng['in_channels'] // 4, 2 * args.latent_tokens[0], 2 * args.latent_tokens[1], device=dev, generator=rng)
+        if want_eval:          # one synthetic batch: K copies of its conditions, each with its own start noise
+            eval_conds = [synth] * ecfg['num_batches']
+
+    # ---- evaluation (off unless --eval-interval): rank 0 scores the student's samples against the teacher's, the other ranks wait ----------
+    evaluator = eval_path = None
+    if want_eval:
+        from arcflow_amd.train.evaluate import Evaluator
+        tcfg = run['test_cfg']
+        if tcfg['distilled_guidance_scale'] is not None and tcfg['distilled_guidance_scale'] != dc.guidance:
+            print(f"[eval] test_cfg.distilled_guidance_scale = {tcfg['distilled_guidance_scale']} differs from the training value {dc.guidance}: "
+                  'the student is evaluated with the guidance it is trained with', flush=True)
+        eval_conds = [{k: v for k, v in c.items() if k != 'latents'} for c in eval_conds]
+        evaluator = Evaluator(dist_, eval_conds, seed=ecfg['seed'], teacher_steps=ecfg['teacher_steps'], nfe=tcfg['nfe'],
+                              timestep_ratio=tcfg['timestep_ratio'], use_ema=ecfg['use_ema'])
+        eval_dir = args.work_dir or run['work_dir'] or ckpt_dir
+        os.makedirs(eval_dir, exist_ok=True)
+        eval_path = os.path.join(eval_dir, 'eval.jsonl')
+
+    def run_eval():
+        if evaluator is not None:
+            res = evaluator.evaluate()
+            with open(eval_path, 'a', encoding='utf-8') as f:
+                f.write(json.dumps(res) + '\n')
+            means = {k: round(v, 6) for k, v in res.items() if k.endswith('_mean')}
+            print(f"[eval] iter {res['iteration']} ({res['seconds']:.2f} s) " + json.dumps(means), flush=True)
+        if pg is not None:
+            torch.distributed.barrier(group=pg)
 
     total = args.iters if args.iters is not None else run['total_iters']
+    if n_eval > 0 and dist_.iteration == 0:
+        run_eval()
     t_last = time.perf_counter()
     while dist_.iteration < total:
         cond = next(loader) if loader is not None else synth
@@ -183,6 +249,9 @@ def main():
             if rank == 0:       # host copy here, pickling + the file write in a thread (the Qwen-Image adapter set is ~6 GB: 14 s of disk time per save)
                 path = checkpoint.save_checkpoint_async(dist_, ckpt_dir, fp16=run['ckpt_fp16'], fp16_ema=run['ckpt_fp16_ema'])
                 print(f'[train] saving {path}', flush=True)
+        if n_eval > 0 and dist_.iteration % n_eval == 0:
+            run_eval()
+            t_last = time.perf_counter()
     checkpoint.wait_pending_save()
     if args.export and rank == 0:
         print('[train] exported', checkpoint.export_adapter(dist_, args.export, ema=True, policy_kwargs=run['policy_kwargs']))
