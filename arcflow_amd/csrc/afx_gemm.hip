@@ -29,14 +29,12 @@
 #include <utility>
 
 #include "afx_common.h"
-#include "afx_kernels.h"
+#include "afx_gemm_plan.h"
 
 namespace afx {
 
-constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int GEMM_THREADS = 512;
 constexpr int GEMM_LDS_BYTES = 139264;                  // dynamic LDS of an 8-phase launch (its two stages of A + W tiles use 131072)
-constexpr int GROUP_M = 6;                              // super-row height of the tile order
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
@@ -1079,7 +1077,7 @@ constexpr int v3_lds_bytes(int MI, int NJ) { return 2 * (32 * MI) * 128 + 3 * (3
 // the CU count, a multiple of 8: the walk stays on the work-group's XCD chunk) and issues the NEXT tile's first four DMA batches
 // (A(0) W(0) W(1) A(1)) between its last K-tile and its epilogue, so their latency -- and the launch of a fresh work-group -- hide
 // behind the epilogue's stores.  VMEM operations retire in order: the epilogue's own residual loads then queue behind those batches.
-template <int MI, int NJ, bool CONV, int PERSIST>      // PERSIST 1: next tile's DMA in front of the epilogue, 2: behind it; 3: no walk, ONE copy of the K-tile body (see the loop)
+template <int MI, int NJ, bool CONV, int PERSIST>      // PERSIST 1: next tile's DMA in front of the epilogue, 2: behind it
 AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
   constexpr int TM = 32 * MI, TN = 32 * NJ;
   constexpr int A_SLOT = TM * 128, W_SLOT = TN * 128;          // bytes: rows of 64 bf16, chunk-swizzled like every tile here
@@ -1230,14 +1228,11 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
   // Two copies of the K-tile body: tiles whose successor t+2 exists issue its DMA, the last two tiles issue nothing -- as a
   // compile-time flag, because a scalar branch around each DMA issue costs the lone wave ~30 cycles of instruction refetch
   // (16 per K-tile: +20 %).
-  // PERSIST == 3: ONE copy instead -- the last two tiles re-fetch tile nk - 1 into slots nobody reads any more (as the attention kernel does).
-  // The two copies meet in a block where hipcc moves all 4 MI NJ accumulators to the registers the second copy was allocated
-  // (255 v_accvgpr_mov_b32 per tile for 8 x 8: ~1-2 k cycles of a 125 k-cycle K = 3072 tile); one copy has no such seam.
   int t = 0;
 #pragma unroll
-  for (int part = 0; part < (PERSIST == 3 ? 1 : 2); ++part) {
+  for (int part = 0; part < 2; ++part) {
   const bool more = part == 0;                 // a constant once the two parts are unrolled
-  const int t_end = (more && PERSIST != 3) ? nk - 2 : (TAIL ? nk - 1 : nk);      // TAIL: the last K-tile's MFMAs are issued from inside the epilogue (below)
+  const int t_end = more ? nk - 2 : (TAIL ? nk - 1 : nk);      // TAIL: the last K-tile's MFMAs are issued from inside the epilogue (below)
 #pragma unroll 1
   for (; t < t_end; ++t) {
     const char* sa = smem + (t & 1) * A_SLOT;
@@ -1245,7 +1240,7 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
     AFX_TR(0)
     // ---- k-half 0 multiplies; the k-half-1 fragments stream in; W(t+2) -> slot (t+2) % 3 ------------------------------------
     {
-      const uint64_t wsrc_u = v3_uniform_u64((uintptr_t)(wbase + (int64_t)(PERSIST == 3 ? min(t + 2, nk - 1) : t + 2) * (BK * 2)));
+      const uint64_t wsrc_u = v3_uniform_u64((uintptr_t)(wbase + (int64_t)(t + 2) * (BK * 2)));
       char* wdst = smem_w + ((t + 2) % 3) * W_SLOT;
       static_for<NM>([&](auto m_c) AFX_INL {          // one memory instruction at most between two MFMAs (12 free issue cycles)
         constexpr int m = decltype(m_c)::value;
@@ -1275,7 +1270,7 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
     AFX_TR(3)
     // ---- k-half 1 multiplies; DMA of A(t+2) -> slot t & 1 and the k-half-0 fragments of tile t+1 ---------------------------
     {
-      const uint64_t asrc_u = v3_uniform_u64((uintptr_t)(abase + ka(PERSIST == 3 ? min(t + 2, nk - 1) : t + 2)));
+      const uint64_t asrc_u = v3_uniform_u64((uintptr_t)(abase + ka(t + 2)));
       char* adst = smem + (t & 1) * A_SLOT;
       const char* na = smem + ((t + 1) & 1) * A_SLOT;
       const char* nw = smem_w + ((t + 1) % 3) * W_SLOT;
@@ -1400,7 +1395,6 @@ AFX_DEV void gemm_v3_body(const GemmBatch& batch) {
       for (int i = 0; i < 24; ++i) g_gemm_trace[blockIdx.x ? 1 : 0][wave2][i] = tr[i];
 #endif
     if constexpr (PERSIST == 2) next_tile();
-    if constexpr (PERSIST == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-fetched tiles must have landed before the LDS is handed on
     if (!has_next) break;
   }
   }
@@ -1856,22 +1850,8 @@ template __global__ void gemm_kernel_v3f8<V3F8_ONLY>(const GemmBatch);
 #endif
 }  // namespace afx
 #else
-// ---- settings / kernel choice ---------------------------------------------------------------------------------------------
-// The GEMM's environment settings, read ONCE (the launcher and the predicates below agree on every launch):
-//   AFX_GEMM_IMPL       2 = the 8-phase kernel only, 3 (default; any other value) = the one-wave-per-SIMD kernels for the launches they take
-//   AFX_GEMM_TILE       (impl 3) 0 = pick per launch, 1 ... 6 = force 256x256 / 288x192 / 320x192 / 128x128 / 256x224 / 224x256
-//   AFX_QK_FUSE=0       keep the separate kv_prep launch (A/B)
-//   AFX_FP8_V3=0        fp8 launches on the 8-phase kernel (A/B);  AFX_FP8_V3_MIN: fewest 256x256 tiles of a launch for the fp8 v3 kernel;
-//   AFX_FP8_TILE        1 / 2 force its 256x256 / 224x256 shape
-//   AFX_GEMM_GROUP_M    tile-order super-row height;  AFX_GEMM_PEN224 / AFX_GEMM_PEN_QK224: cost factors of the 256x224 / 224x256 shapes (1e9 = never)
-// afx_gemm_set_mode() overrides impl and tile, afx_gemm_set_fp8_tile() fp8_tile (parity tests, A/B runs).
-struct GemmMode {
-  int impl = 3, tile = 0;
-  bool qk_fuse = true, fp8_v3 = true;
-  int fp8_v3_min = -1;            // < 0: half the CUs
-  int fp8_tile = 0, group_m = 0;  // group_m 0: the tile shape's own
-  double pen224 = 1.03, pen_qk224 = 1.03;
-};
+// ---- settings / launch -----------------------------------------------------------------------------------------------------
+// The environment settings of GemmMode (afx_gemm_plan.h), read ONCE.
 static GemmMode& gemm_mode() {
   static GemmMode m = [] {
     GemmMode r;
@@ -1884,16 +1864,17 @@ static GemmMode& gemm_mode() {
     if (const char* e = getenv("AFX_GEMM_GROUP_M")) r.group_m = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = getenv("AFX_GEMM_PEN224")) r.pen224 = atof(e);
     if (const char* e = getenv("AFX_GEMM_PEN_QK224")) r.pen_qk224 = atof(e);
+    if (const char* e = getenv("AFX_GEMM_PERSIST")) r.persist = atoi(e);
     return r;
   }();
   return m;
 }
-bool gemm_conv_stats_available() {                      // convolution launches go to the kernel whose epilogue accumulates GroupNorm sums
-  return gemm_mode().impl == 3 && gemm_mode().tile == 0;
-}
-bool gemm_qk_fusion_available() { return gemm_mode().impl == 3 && gemm_mode().qk_fuse; }
-bool gemm_dropres_available() {                         // launch_gemm would take a problem with drop_on: the masked residual add exists in the one-wave-per-SIMD
-  return gemm_mode().impl == 3;                         // kernel's permlane-paired epilogue only
+bool gemm_conv_stats_available() { return gemm_conv_stats_available(gemm_mode()); }
+bool gemm_qk_fusion_available() { return gemm_qk_fusion_available(gemm_mode()); }
+bool gemm_dropres_available() { return gemm_dropres_available(gemm_mode()); }
+bool gemm_fp8_mx_ok(int64_t rows_total, int N, int K) {
+  (void)rows_total; (void)N;
+  return gemm_fp8_mx_ok(gemm_mode(), K);
 }
 void gemm_set_mode(int impl, int tile) {
   gemm_mode().impl = impl == 2 ? 2 : 3;
@@ -1903,278 +1884,71 @@ int gemm_set_fp8_tile(int tile) {
   gemm_mode().fp8_tile = (tile >= 0 && tile <= 2) ? tile : 0;
   return gemm_mode().fp8_tile;
 }
-struct TileCfg { int tm, tn, group_m; };
-// {4,4} = 128x128: 64 accumulators and 80 KiB of LDS, TWO work-groups per CU -- for launches that would leave most CUs without a
-// 256x256 tile (the rank-256 LoRA products of the distillation step: N = 256 or M = 256, 12-84 tiles at 256x256)
-// {8,7} = 256x224: the shape that makes the forward's N = 3072 launches (18 row tiles of the 4096 + 512 row problems x 14 column
-// tiles = 252) and the N = 12288 launch (990 tiles = 3.87 rounds of 7/8-size tiles) fill their last round -- what hipBLASLt's
-// MT256x224 kernels do for these shapes (1295 vs 1161 TF at 4608 x 3072 x 3072 in profiles/r02s_microbench.log)
-// {7,8} = 224x256: the k|q|v^T launch of the Qwen-Image shape (4096 + 128 rows: 612 tiles of 256x256 = 2.39 rounds -> 718 tiles of 7/8 the size =
-// 2.8 rounds); a wave keeps its 128 columns = one head, so the fused q / k epilogue works unchanged (FLUX's 4096 + 512 rows stay 256x256: 648 tiles)
-static const TileCfg kTileCfg[6] = {{256, 256, GROUP_M}, {288, 192, 5}, {320, 192, 4}, {128, 128, 8}, {256, 224, GROUP_M}, {224, 256, GROUP_M}};
 
-static int count_tiles(GemmBatch& batch, int tm, int tn, bool fill) {
-  int total = 0;
-  for (int i = 0; i < batch.nprob; ++i) {
-    GemmProblem& p = batch.p[i];
-    const int tiles_m = (p.M + tm - 1) / tm, tiles_n = (p.N + tn - 1) / tn;
-    const int sk = (p.split_k < 1 || p.out_f32 != 3) ? 1 : p.split_k;
-    if (fill) {
-      p.tiles_m = tiles_m;
-      p.tiles_n = tiles_n;
-      p.tile_start = total;
-      p.split_k = sk;
-    }
-    total += tiles_m * tiles_n * sk;
-  }
-  return total;
-}
-
-template <int MI, int NJ, bool CONV = false, int PERSIST = 0>
-static hipError_t launch_v3_impl(GemmBatch& batch, int total, hipStream_t stream) {
-  static bool attr = false;
-  void (*kern)(const GemmBatch);
-  if constexpr (4 * MI * NJ <= 64) kern = gemm_kernel_v3s<MI, NJ, CONV, PERSIST>;
-  else kern = gemm_kernel_v3<MI, NJ, CONV, PERSIST>;
-  if (!attr) {
-    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(MI, NJ));
-    if (r != hipSuccess) return r;
-    attr = true;
-  }
-  if (launch_timer().start != nullptr && launch_timer().stop != nullptr)
-    hipExtLaunchKernelGGL(kern, dim3(total), dim3(V3_THREADS), v3_lds_bytes(MI, NJ), stream, launch_timer().start, launch_timer().stop, 0, batch);
-  else
-    hipLaunchKernelGGL(kern, dim3(total), dim3(V3_THREADS), v3_lds_bytes(MI, NJ), stream, batch);
-  return hipGetLastError();
-}
-
-// AFX_GEMM_PERSIST=1 (or afx_gemm_set_persist(1)): launches with more tiles than resident work-groups run the persistent tile walk
-// (grid = CUs x resident work-groups per CU); off by default -- see DESIGN 4.1 for the same-box A/B.
-int& gemm_persist() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AFX_GEMM_PERSIST");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-template <int MI, int NJ, bool CONV = false>
-static hipError_t launch_v3(GemmBatch& batch, int total, hipStream_t stream) {
+static int gemm_cus() {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
     hipDeviceProp_t prop;
     cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
   }
-  const int slots = cus * (4 * MI * NJ <= 64 ? 2 : 1);
-  if constexpr (!CONV) {
-    if (gemm_persist() == 1 && total > slots && slots % 8 == 0) return launch_v3_impl<MI, NJ, CONV, 1>(batch, slots, stream);
-    if (gemm_persist() == 2 && total > slots && slots % 8 == 0) return launch_v3_impl<MI, NJ, CONV, 2>(batch, slots, stream);
-  }
-  // (The VAE's convolutions ran the persistent walk as an A/B in round 5 -- AFX_CONV_PERSIST, measured level, profiles/r05*: with the accumulator file asm-owned
-  // (round 6) those instances no longer fit hipcc's arch VGPRs and it parked values in accumulator registers: dropped rather than shipped unsafe.)
-  return launch_v3_impl<MI, NJ, CONV, 0>(batch, total, stream);
+  return cus;
 }
 
-bool gemm_fp8_mx_ok(int64_t rows_total, int N, int K) {
-  (void)rows_total; (void)N;                       // a block-scaled launch always takes the one-wave-per-SIMD kernel, whatever its tile count
-  return gemm_mode().fp8_v3 && gemm_mode().impl == 3 && K % 512 == 0 && K >= 512;      // the same predicate launch_gemm applies
+// One launch of KERN: its dynamic-LDS limit is raised once; an armed launch_timer() stamps the kernel's own begin / end.
+template <void (*KERN)(const GemmBatch)>
+static hipError_t launch_kernel(const GemmBatch& batch, int grid, int threads, int lds_bytes, hipStream_t stream) {
+  static bool attr = false;
+  if (!attr) {
+    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (r != hipSuccess) return r;
+    attr = true;
+  }
+  if (launch_timer().start != nullptr && launch_timer().stop != nullptr)
+    hipExtLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds_bytes, stream, launch_timer().start, launch_timer().stop, 0, batch);
+  else
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds_bytes, stream, batch);
+  return hipGetLastError();
+}
+
+template <int MI, int NJ, bool CONV, int PERSIST>
+static hipError_t launch_v3_impl(const GemmBatch& batch, int grid, hipStream_t stream) {
+  if constexpr (4 * MI * NJ <= 64) return launch_kernel<gemm_kernel_v3s<MI, NJ, CONV, PERSIST>>(batch, grid, V3_THREADS, v3_lds_bytes(MI, NJ), stream);
+  else return launch_kernel<gemm_kernel_v3<MI, NJ, CONV, PERSIST>>(batch, grid, V3_THREADS, v3_lds_bytes(MI, NJ), stream);
+}
+template <int MI, int NJ, bool CONV = false>
+static hipError_t launch_v3(const GemmBatch& batch, const GemmPlan& pl, hipStream_t stream) {
+  if constexpr (!CONV) {
+    if (pl.persist == 1) return launch_v3_impl<MI, NJ, false, 1>(batch, pl.grid, stream);
+    if (pl.persist == 2) return launch_v3_impl<MI, NJ, false, 2>(batch, pl.grid, stream);
+  }
+  return launch_v3_impl<MI, NJ, CONV, 0>(batch, pl.grid, stream);
+}
+template <int MI, int NJ>
+static hipError_t launch_v3f8(const GemmBatch& batch, const GemmPlan& pl, hipStream_t stream) {
+  return pl.flag ? launch_kernel<gemm_kernel_v3f8<MI, NJ, true>>(batch, pl.grid, V3_THREADS, v3_lds_bytes(MI, NJ), stream)
+                 : launch_kernel<gemm_kernel_v3f8<MI, NJ, false>>(batch, pl.grid, V3_THREADS, v3_lds_bytes(MI, NJ), stream);
 }
 
 hipError_t launch_gemm(GemmBatch& batch, hipStream_t stream) {
-  static int cus = 256;
-  static bool init = false;
-  const GemmMode& mode = gemm_mode();
-  const int impl = mode.impl, tile_env = mode.tile, group_m_env = mode.group_m;
-  if (!init) {
-    init = true;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v2<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    if (r != hipSuccess) return r;
-    r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v2<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    if (r != hipSuccess) return r;
+  const GemmPlan pl = plan_gemm(batch, gemm_mode(), gemm_cus());
+  if (pl.status != GemmPlan::OK) return pl.status == GemmPlan::EMPTY ? hipSuccess : hipErrorInvalidValue;
+  switch (pl.family) {
+    case GemmPlan::V3_CONV: return pl.nj == 4 ? launch_v3<8, 4, true>(batch, pl, stream) : launch_v3<8, 8, true>(batch, pl, stream);
+    case GemmPlan::V3_FP8: return pl.mi == 7 ? launch_v3f8<7, 8>(batch, pl, stream) : launch_v3f8<8, 8>(batch, pl, stream);
+    case GemmPlan::PHASE8:
+      return pl.flag ? launch_kernel<gemm_kernel_v2<true>>(batch, pl.grid, GEMM_THREADS, GEMM_LDS_BYTES, stream)
+                     : launch_kernel<gemm_kernel_v2<false>>(batch, pl.grid, GEMM_THREADS, GEMM_LDS_BYTES, stream);
+    case GemmPlan::V3_BF16: break;
   }
-  // ---- one-wave-per-SIMD kernel: bf16 launches whose every problem is in a fast epilogue mode.  The tile shape is the one with
-  // the least (rounds of `cus` tiles) x (tile area): the launch is as long as its fullest CU.
-  bool v3_ok = impl == 3;
-  for (int i = 0; i < batch.nprob; ++i) {
-    const GemmProblem& p = batch.p[i];
-    const bool bf16_out = p.out_f32 == 0, f32_out = (p.out_f32 == 1 || p.out_f32 == 2) && p.epi == EPI_NONE;     // (3 = split-K slabs: 8-phase)
-    v3_ok = v3_ok && (bf16_out || f32_out) && p.fp8 == 0 && p.conv_cin_tiles == 0 && p.conv_wp == 0 && p.pre == nullptr && p.K >= BK;
-    if (p.drop_on && (p.epi != EPI_GATE_RES || p.gate != nullptr || p.out_f32 != 0)) return hipErrorInvalidValue;
+  switch (pl.mi * 16 + pl.nj) {        // the six shapes of kTileCfg
+    case 9 * 16 + 6: return launch_v3<9, 6>(batch, pl, stream);
+    case 10 * 16 + 6: return launch_v3<10, 6>(batch, pl, stream);
+    case 4 * 16 + 4: return launch_v3<4, 4>(batch, pl, stream);
+    case 8 * 16 + 7: return launch_v3<8, 7>(batch, pl, stream);
+    case 7 * 16 + 8: return launch_v3<7, 8>(batch, pl, stream);
+    default: return launch_v3<8, 8>(batch, pl, stream);
   }
-  for (int i = 0; i < batch.nprob; ++i)
-    if (batch.p[i].drop_on && !v3_ok) return hipErrorInvalidValue;        // the masked residual add lives in the one-wave-per-SIMD kernel's epilogue only
-  // ---- the VAE decoders' 3x3 convolutions: the same kernel with the implicit-GEMM address stream and the border-zeroing epilogue;
-  // 256x128 tiles for the <= 128-channel layers (the full-resolution stage and conv_out, half of a 256-wide tile otherwise)
-  bool conv_all = impl == 3 && tile_env == 0 && batch.nprob >= 1;
-  for (int i = 0; i < batch.nprob; ++i) {
-    const GemmProblem& p = batch.p[i];
-    conv_all = conv_all && p.conv_cin_tiles > 0 && p.conv_wp > 0 && p.out_f32 == 0 && p.fp8 == 0 && p.pre == nullptr && p.epi != EPI_GELU &&
-               p.split_k <= 1 && p.N == batch.p[0].N && (p.up_phase == 0 || (p.epi == EPI_NONE && p.gn_stats == nullptr));
-  }
-  if (conv_all) {
-    // 256x128 tiles for the <= 128-channel layers only: for the 128^2 stage (134 tiles of 256x256 for 256 CUs, K = 4608) 268 narrow tiles measured
-    // 116 us per launch against 93
-    const bool narrow = batch.p[0].N <= 128;
-    const int total = count_tiles(batch, 256, narrow ? 128 : 256, true);
-    batch.total_tiles = total;
-    if (total == 0) return hipSuccess;
-    batch.group_m = group_m_env ? group_m_env : GROUP_M;
-    return narrow ? launch_v3<8, 4, true>(batch, total, stream) : launch_v3<8, 8, true>(batch, total, stream);
-  }
-  bool qk = false;
-  for (int i = 0; i < batch.nprob; ++i) {
-    const GemmProblem& p = batch.p[i];
-    if (p.qk_D > 0) {
-      qk = true;
-      if (p.qk_D % 128 || p.N < p.qk_D || !p.qk_wk || !p.qk_wq || !p.rope_cos || !p.rope_sin || p.rope_period < 1 || p.rope_rows < 1 ||
-          p.epi == EPI_GATE_RES)
-        return hipErrorInvalidValue;
-    }
-  }
-  for (int i = 0; i < batch.nprob; ++i)
-    if (batch.p[i].w_perm16 || batch.p[i].bias_rows) {
-      qk = true;                                         // same kernel requirement (and the 256x256 shape: tested there)
-      if (batch.p[i].out_f32 != 0 || batch.p[i].epi != EPI_NONE || (batch.p[i].w_perm16 && batch.p[i].N % 16)) return hipErrorInvalidValue;
-    }
-  bool all_fp8 = batch.nprob >= 1;
-  for (int i = 0; i < batch.nprob; ++i) all_fp8 = all_fp8 && batch.p[i].fp8 != 0;
-  if (qk && !v3_ok && !all_fp8) return hipErrorInvalidValue;        // callers ask gemm_qk_fusion_available() first (fp8: checked below)
-  if (v3_ok) {
-    int best = 0;
-    bool f32_any = false;                               // fp32-output launches: the shapes with an even number of column tiles per wave only
-    for (int i = 0; i < batch.nprob; ++i) f32_any = f32_any || batch.p[i].out_f32 != 0;
-    if (qk) {                                           // one head = one wave's 128 columns: the two 256-wide shapes only
-      best = 0;
-      if (tile_env == 6) best = 5;
-      else if (tile_env == 0) {
-        const int t0 = count_tiles(batch, 256, 256, false), t5 = count_tiles(batch, 224, 256, false);
-        if (t0 == 0) return hipSuccess;
-        const double c0 = (double)((t0 + cus - 1) / cus) * 256, c5 = (double)((t5 + cus - 1) / cus) * 224 * mode.pen_qk224;
-        if (c5 < c0) best = 5;
-      }
-    } else if (tile_env >= 1 && tile_env <= 6) best = (tile_env == 5 && f32_any) ? 0 : tile_env - 1;
-    else {
-      double best_cost = 0;
-      int tiles256 = 0;
-      for (int c = 0; c < 5; ++c) {
-        const int tiles = count_tiles(batch, kTileCfg[c].tm, kTileCfg[c].tn, false);
-        if (tiles == 0) return hipSuccess;
-        if (c == 0) tiles256 = tiles;
-        if (c == 3 && tiles256 * 2 > cus) continue;   // 128x128 only where 256x256 leaves half the CUs idle (measured: the 864-tile
-                                                      // mlp GEMM as 3456 small tiles takes 362 us against 287)
-        const int slots = c == 3 ? 2 * cus : cus;
-        const int rounds = (tiles + slots - 1) / slots;
-        // 256x256 has the best MFMA : LDS-read ratio (4 : 1 against 3.6 : 1 / 3.75 : 1) and the chip is power-capped: a tile
-        // shape that fills the last round only makes every CU clock lower.  Measured with weights streaming from HBM
-        // (tools/gemm_trace.hip TRACE_COLD=1, r02s): 288x192 wins 4-6 % at K = 3072 where it saves a round or fills a 216-tile
-        // launch, is level at K = 12288 and loses 3 % at K = 15360 (its W slots leave the DMA the shorter lead); 320x192 never won.
-        double pen = 1.0;
-        if (c == 1) pen = batch.p[0].K <= 8192 ? 1.05 : 1.5;
-        if (c == 2) pen = 1.10;
-        if (c == 3) pen = 2.0;          // 16 MFMAs per 8 fragment reads and 4 DMA issues per k-half: the loop runs at about half rate
-        if (c == 4) pen = f32_any ? 1e9 : mode.pen224;   // 56 MFMAs per 15 fragment reads (256x256: 64 per 16); bf16 epilogues only
-        const double cost = (double)rounds * kTileCfg[c].tm * kTileCfg[c].tn * pen;
-        if (c == 0 || cost < best_cost) { best = c; best_cost = cost; }
-      }
-    }
-    const int total = count_tiles(batch, kTileCfg[best].tm, kTileCfg[best].tn, true);
-    batch.total_tiles = total;
-    if (total == 0) return hipSuccess;
-    batch.group_m = group_m_env ? group_m_env : kTileCfg[best].group_m;
-    return best == 0 ? launch_v3<8, 8>(batch, total, stream) : best == 1 ? launch_v3<9, 6>(batch, total, stream)
-         : best == 2 ? launch_v3<10, 6>(batch, total, stream) : best == 3 ? launch_v3<4, 4>(batch, total, stream)
-         : best == 4 ? launch_v3<8, 7>(batch, total, stream) : launch_v3<7, 8>(batch, total, stream);
-  }
-  // ---- fp8 launches with at least one full round of 256x256 tiles: the one-wave-per-SIMD fp8 kernel (AFX_FP8_V3=0: 8-phase kernel, A/B)
-  {
-    bool ok = mode.fp8_v3 && impl == 3 && batch.nprob >= 1;
-    bool mx_any = false, mx_all = true, c8_any = false, qk_any = false;
-    for (int i = 0; i < batch.nprob; ++i) {
-      const GemmProblem& p = batch.p[i];
-      ok = ok && p.fp8 != 0 && p.out_f32 == 0 && p.conv_cin_tiles == 0 && p.conv_wp == 0 && p.pre == nullptr && p.K % 128 == 0 && p.K >= 256 &&
-           !p.w_perm16 && !p.bias_rows && p.split_k <= 1;
-      qk_any = qk_any || p.qk_D > 0;
-      mx_any = mx_any || p.a_mx != nullptr;
-      if (p.c8 != nullptr && (p.epi == EPI_GATE_RES || p.c8_col0 % 128 || !p.c_mx || p.ldc8 % 8 || (p.gelu_col0 != 0 && p.gelu_col0 != p.c8_col0))) return hipErrorInvalidValue;
-      c8_any = c8_any || p.c8 != nullptr;
-      mx_all = mx_all && p.a_mx != nullptr && p.K % 512 == 0 && p.ld_mx % 4 == 0;
-    }
-    // fewest 256x256 tiles of a launch that takes this kernel: by default half a round -- 216-tile launches (N = 3072): 2.1-2.2 -> 2.7 PF; below half a
-    // round the 8-phase kernel's 2 waves per SIMD win
-    const int min_tiles = mode.fp8_v3_min >= 0 ? mode.fp8_v3_min : cus / 2;
-    if (mx_any && !(ok && mx_all)) return hipErrorInvalidValue;      // block scales are this kernel's format only (callers ask gemm_fp8_mx_ok() first)
-    if ((c8_any || qk_any) && !ok) return hipErrorInvalidValue;     // (the fused q / k epilogue: this kernel only; the engine asks for it with block scales only)
-    if (ok && (mx_any || c8_any || qk_any || count_tiles(batch, 256, 256, false) >= min_tiles)) {
-      // 224x256 (round 5): a launch costs ceil(rounds) x tile area and the fp8 kernel had ONE shape -- Qwen-Image's 4096 + 128 rows are 17 + 1
-      // row tiles of 256 (N = 3072: 216 tiles = 0.84 round, N = 12288: 864 = 3.4 -> 4 rounds, N = 9216: 648 = 2.5 -> 3) but 19 + 1 of 224 (240 tiles = 0.94,
-      // 960 = 3.75 -> 4, 720 = 2.8 -> 3 rounds of tiles 7/8 the size); FLUX's joint 4608 rows of the single blocks likewise (out-projection: 252 tiles).
-      // AFX_FP8_TILE=1 / 2 force 256x256 / 224x256 (A/B).  The fused q / k epilogue keeps 256x256 (one head = one wave's 128 columns either way, but its
-      // row-tile loop is written for 8).
-      const int tile_env8 = mode.fp8_tile;
-      const int t8 = count_tiles(batch, 256, 256, false), t7 = count_tiles(batch, 224, 256, false);
-      const int r8 = (t8 + cus - 1) / cus, r7 = (t7 + cus - 1) / cus;
-      bool use7 = !qk_any && (tile_env8 == 2 || (tile_env8 == 0 && (double)r7 * 224 * 1.02 < (double)r8 * 256));
-      const int total = use7 ? count_tiles(batch, 224, 256, true) : count_tiles(batch, 256, 256, true);
-      batch.total_tiles = total;
-      if (total == 0) return hipSuccess;
-      batch.group_m = group_m_env ? group_m_env : GROUP_M;
-        static bool attr = false;
-      if (!attr) {
-        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v3f8<8, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(8, 8));
-        if (r != hipSuccess) return r;
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v3f8<8, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(8, 8));
-        if (r != hipSuccess) return r;
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v3f8<7, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(7, 8));
-        if (r != hipSuccess) return r;
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel_v3f8<7, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, v3_lds_bytes(7, 8));
-        if (r != hipSuccess) return r;
-        attr = true;
-      }
-      const bool timed = launch_timer().start != nullptr && launch_timer().stop != nullptr;
-      if (use7) {
-        if (mx_any) {
-          if (timed) hipExtLaunchKernelGGL((gemm_kernel_v3f8<7, 8, true>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(7, 8), stream, launch_timer().start, launch_timer().stop, 0, batch);
-          else hipLaunchKernelGGL((gemm_kernel_v3f8<7, 8, true>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(7, 8), stream, batch);
-        } else {
-          if (timed) hipExtLaunchKernelGGL((gemm_kernel_v3f8<7, 8, false>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(7, 8), stream, launch_timer().start, launch_timer().stop, 0, batch);
-          else hipLaunchKernelGGL((gemm_kernel_v3f8<7, 8, false>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(7, 8), stream, batch);
-        }
-        return hipGetLastError();
-      }
-      if (mx_any) {
-        if (timed) hipExtLaunchKernelGGL((gemm_kernel_v3f8<8, 8, true>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(8, 8), stream, launch_timer().start, launch_timer().stop, 0, batch);
-        else hipLaunchKernelGGL((gemm_kernel_v3f8<8, 8, true>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(8, 8), stream, batch);
-      } else {
-        if (timed) hipExtLaunchKernelGGL((gemm_kernel_v3f8<8, 8, false>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(8, 8), stream, launch_timer().start, launch_timer().stop, 0, batch);
-        else hipLaunchKernelGGL((gemm_kernel_v3f8<8, 8, false>), dim3(total), dim3(V3_THREADS), v3_lds_bytes(8, 8), stream, batch);
-      }
-      return hipGetLastError();
-    }
-  }
-  const int total = count_tiles(batch, BM, BN, true);
-  batch.total_tiles = total;
-  if (total == 0) return hipSuccess;
-  batch.group_m = group_m_env ? group_m_env : GROUP_M;
-  bool fp8 = false;
-  for (int i = 0; i < batch.nprob; ++i) fp8 = fp8 || batch.p[i].fp8 != 0;     // a launch is all-bf16 or all-fp8
-  if (fp8 && launch_timer().start != nullptr && launch_timer().stop != nullptr)
-    hipExtLaunchKernelGGL(gemm_kernel_v2<true>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, launch_timer().start,
-                          launch_timer().stop, 0, batch);
-  else if (fp8)
-    hipLaunchKernelGGL(gemm_kernel_v2<true>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, batch);
-  else if (launch_timer().start != nullptr && launch_timer().stop != nullptr)
-    hipExtLaunchKernelGGL(gemm_kernel_v2<false>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, launch_timer().start,
-                          launch_timer().stop, 0, batch);
-  else
-    hipLaunchKernelGGL(gemm_kernel_v2<false>, dim3(total), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, batch);
-  return hipGetLastError();
 }
 
 }  // namespace afx

@@ -73,7 +73,7 @@ struct GemmProblem {
   uint32_t drop_thresh, drop_seed;
   float drop_inv_keep;
   int64_t drop_row0;
-  int32_t tiles_m, tiles_n, tile_start;   // filled by the launcher
+  int32_t tiles_m, tiles_n, tile_start;   // filled by the launcher (plan_gemm, afx_gemm_plan.h)
 };
 
 struct GemmBatch {
@@ -92,7 +92,7 @@ int64_t gemm_tn_ws_bytes(int M, int N1, int N2);
 bool gemm_conv_stats_available();           // GemmProblem::gn_stats is honoured (kernel mode 3, no forced tile shape)
 bool gemm_qk_fusion_available();            // the launcher would take a problem with qk_D > 0 (kernel mode 3, AFX_QK_FUSE not 0)
 bool gemm_dropres_available();              // ... a problem with drop_on (the LoRA branch's masked residual add in the epilogue)
-void gemm_set_mode(int impl, int tile);      // kernel / tile-shape override of AFX_GEMM_IMPL / AFX_GEMM_TILE (see launch_gemm)
+void gemm_set_mode(int impl, int tile);      // kernel / tile-shape override of AFX_GEMM_IMPL / AFX_GEMM_TILE (see GemmMode, afx_gemm_plan.h)
 int gemm_set_fp8_tile(int tile);             // ... of AFX_FP8_TILE (0 = per launch, 1 = 256x256, 2 = 224x256; else 0); returns the value in force
 constexpr int GN_SLOTS = 64;
 
