@@ -2,10 +2,13 @@
 //
 // The forward is a fixed launch plan over the kernels in afx_gemm / afx_attn / afx_elementwise:
 //   temb MLPs (gemv) -> ONE gemv over all stacked AdaLN modulation linears -> embedders (grouped GEMM)
-//   -> per block { LN+modulate, QKV GEMM (rows k|v|q), RMSNorm+RoPE in place, V transpose,
+//   -> per block { LN+modulate, k|v|q projection with the q / k / V^T preparation (below),
 //                  flash attention (O overwrites Q), out-proj GEMM with fused gate*x+residual,
 //                  LN+modulate, MLP-up GEMM + GELU, MLP-down GEMM with fused gate*x+residual }
 //   -> norm_out + head GEMM -> log_softmax split.
+// The preparation is one of three paths, picked per shape by qkv_path(): AFX_QKV_VT_PROJ (q / k RMSNorm + RoPE in the projection's epilogue, V^T
+// computed by the projection itself: no launch in between), AFX_QKV_QK_EPI (that epilogue, then a V transpose launch) or AFX_QKV_KV_PREP (the plain
+// projection, then one launch for RMSNorm + RoPE in place and the V transpose).  The steps are fwd_conditioning ... fwd_head below.
 // Activations live in the caller-provided workspace in the joint [B][text;image] token layout, so the
 // FLUX single-stream blocks run on the same buffers without a concat, and attention / proj_out read
 // the [O | mlp] operand in place (lda-strided) from the fused QKV+MLP buffer.
@@ -56,6 +59,9 @@ struct LinW {
 };
 struct DoubleW { LinW qkv[2], out[2], mlp1[2], mlp2[2]; const float* qkn = nullptr; };   // [0] image stream, [1] text stream
 struct SingleW { LinW fused, out; const float* qkn = nullptr; };
+// ... and of everything around the blocks: the conditioning MLPs (timestep, guidance, pooled text), the stacked modulation linear, a separately
+// bound norm_out.linear (mod_final: optional, w stays null), the embedders, Qwen's text RMSNorm weight (f32 [joint_dim]) and the head
+struct OuterW { LinW t1, t2, g1, g2, p1, p2, mod, mod_final, x_in, ctx_in, head; const float* txt_norm = nullptr; };
 
 struct afx_ctx {
   afx_model_desc d;
@@ -63,6 +69,7 @@ struct afx_ctx {
   bool finalized = false;
   std::vector<DoubleW> dbl;
   std::vector<SingleW> sgl;
+  OuterW ow;
   char* ws = nullptr;
   int64_t ws_bytes = 0;
   int D = 0;
@@ -85,18 +92,10 @@ struct afx_ctx {
 
 namespace {
 
-const uint16_t* W16(const afx_ctx* c, const std::string& n) {
+template <class T>
+const T* wptr(const afx_ctx* c, const std::string& n) {
   auto it = c->w.find(n);
-  return it == c->w.end() ? nullptr : (const uint16_t*)it->second.ptr;
-}
-const float* W32(const afx_ctx* c, const std::string& n) {
-  auto it = c->w.find(n);
-  return it == c->w.end() ? nullptr : (const float*)it->second.ptr;
-}
-
-const void* WQ(const afx_ctx* c, const std::string& n) {
-  auto it = c->w.find(n);
-  return it == c->w.end() ? nullptr : it->second.ptr;
+  return it == c->w.end() ? nullptr : (const T*)it->second.ptr;
 }
 
 int need(const afx_ctx* c, const std::string& n, int dtype, std::vector<int64_t> shape) {
@@ -259,15 +258,18 @@ void stream_qk_epilogue(GemmProblem& p, const BlockShape& q, const float* qkn, i
   set_qk_epilogue(p, q, qkn + (s == 0 ? 0 : 2) * 128, qkn + (s == 0 ? 1 : 3) * 128, s == 0 ? q.T : 0, 1 << 30);
 }
 
+// the plain linear C [M, N] = A [M, K] . W^T + bias over the rows of lw from wrow0 on
+void linear_problem(GemmProblem& p, const uint16_t* A, int64_t lda, const LinW& lw, int64_t wrow0, uint16_t* C, int64_t ldc, int M, int N, int K) {
+  p = GemmProblem{};
+  p.A = A; p.lda = lda; p.W = lw.w + wrow0 * K; p.ldw = K; p.bias = lw.b ? lw.b + wrow0 : nullptr;
+  p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+}
+
 // the image (s = 0) or text (s = 1) rows of sample b in a per-stream linear over the joint token matrix
 void stream_problem(GemmProblem& p, const BlockShape& q, const uint16_t* A, int64_t lda, int K, const LinW& lw, uint16_t* C, int64_t ldc,
                     int Nout, int b, int s) {
-  p = GemmProblem{};
   const int64_t row0 = (int64_t)b * q.S + (s == 0 ? q.T : 0);
-  p.A = A + row0 * lda; p.lda = lda;
-  p.W = lw.w; p.ldw = K; p.bias = lw.b;
-  p.C = C + row0 * ldc; p.ldc = ldc;
-  p.M = (s == 0 ? q.N : q.T); p.N = Nout; p.K = K;
+  linear_problem(p, A + row0 * lda, lda, lw, 0, C + row0 * ldc, ldc, s == 0 ? q.N : q.T, Nout, K);
 }
 
 // VT_PROJ: the k, q and transposed-v problems of one k|v|q(|mlp) projection over `rows` joint rows starting at joint row `row0g` of sample b
@@ -280,9 +282,7 @@ void kqv_problems(GemmBatch& gb, const BlockShape& q, const uint16_t* A, int64_t
     p.K = (int)D; p.epi = EPI_NONE;
     if (part < 2) {
       const int64_t wrow = part == 0 ? 0 : 2 * D;
-      p.A = A + row0g * lda; p.lda = lda;
-      p.W = lw.w + wrow * D; p.ldw = D; p.bias = lw.b ? lw.b + wrow : nullptr;
-      p.C = C + row0g * ldc + wrow; p.ldc = ldc; p.M = rows; p.N = (int)D;
+      linear_problem(p, A + row0g * lda, lda, lw, wrow, C + row0g * ldc + wrow, ldc, rows, (int)D, (int)D);
       set_qk_epilogue(p, q, part == 0 ? wk : wq, part == 0 ? wk : wq, pos0, period);     // a problem of its own: its columns are "region 0"
     } else {
       p.A = lw.w + D * D; p.lda = D; p.bias = lw.b ? lw.b + D : nullptr; p.bias_rows = 1;
@@ -308,16 +308,14 @@ void single_qkv_batch(GemmBatch& gb, int path, const BlockShape& q, const uint16
   const int R = q.B * q.S;
   gb.nprob = 1;
   GemmProblem& f = gb.p[0];
-  f = GemmProblem{};
-  f.A = A; f.lda = lda; f.W = lw.w; f.ldw = D; f.bias = lw.b;
-  f.C = F; f.ldc = ldf; f.M = R; f.N = (int)(7 * D); f.K = (int)D; f.epi = EPI_GELU; f.gelu_col0 = (int)(3 * D);
+  linear_problem(f, A, lda, lw, 0, F, ldf, R, (int)(7 * D), (int)D);
+  f.epi = EPI_GELU; f.gelu_col0 = (int)(3 * D);
   if (path == AFX_QKV_VT_PROJ) {
     gb.nprob = 0;
     kqv_problems(gb, q, A, lda, lw, F, ldf, 0, R, 0, 0, q.S, qkn, qkn + 128, false);
     GemmProblem& m = gb.p[gb.nprob++];
-    m = GemmProblem{};
-    m.A = A; m.lda = lda; m.W = lw.w + 3 * D * D; m.ldw = D; m.bias = lw.b ? lw.b + 3 * D : nullptr;
-    m.C = F + 3 * D; m.ldc = ldf; m.M = R; m.N = (int)(4 * D); m.K = (int)D; m.epi = EPI_GELU; m.gelu_col0 = 0;
+    linear_problem(m, A, lda, lw, 3 * D, F + 3 * D, ldf, R, (int)(4 * D), (int)D);
+    m.epi = EPI_GELU; m.gelu_col0 = 0;
     for (int b = 0; b < q.B; ++b) {
       GemmProblem& v = gb.p[gb.nprob++];
       v = GemmProblem{};
@@ -338,6 +336,296 @@ hipError_t qkv_finish(int path, const BlockShape& q, uint16_t* F, int64_t ldf, c
   if (path == AFX_QKV_KV_PREP)
     return launch_kv_prep(F, F + 2 * q.D, ldf, wk_txt, wk_img, wq_txt, wq_img, q.rope_cos, q.rope_sin, q.T, F + q.D, ldf, q.Vt, q.B, q.H, q.S, st);
   return hipSuccess;
+}
+
+#define AFX_TRY(expr) do { const int rc_ = (expr); if (rc_ != AFX_OK) return rc_; } while (0)
+
+// ---- conditioning: temb = t_mlp(sincos(1000 t)) [+ g_mlp(sincos(1000 g))] [+ p_mlp(pooled)] ------
+// ... of nsteps x B rows (step-major, then sample; t == nullptr: temb already holds the timestep part), then their SiLU and modulation vectors.
+// sc [B, 256] / pf [B, pooled_dim] take the MLPs' inputs, hid [nsteps B, D] their hidden rows (may be semb: overwritten by the SiLU).
+struct CondBufs { float *sc, *pf, *hid, *temb, *semb, *mod; };
+int conditioning(const afx_ctx* c, const float* t, int nsteps, const float* g, const void* pooled, int B, const CondBufs& o, hipStream_t st) {
+  const afx_model_desc& d = c->d;
+  const OuterW& w = c->ow;
+  const int D = c->D, rows = B * nsteps;
+  for (int k = 0; k < nsteps; ++k) {
+    float *hid = o.hid + (int64_t)k * B * D, *temb = o.temb + (int64_t)k * B * D;
+    if (t != nullptr) {
+      HIP_TRY(launch_sincos(t + (int64_t)k * B, 1000.0f, o.sc, B, d.family == 0 ? 1 : 2, st));
+      HIP_TRY(launch_gemv(o.sc, w.t1.w, w.t1.b, hid, B, D, 256, 1, 0, st));
+      HIP_TRY(launch_gemv(hid, w.t2.w, w.t2.b, temb, B, D, D, 0, 0, st));
+    }
+    if (d.guidance_embeds) {
+      HIP_TRY(launch_sincos(g, 1000.0f, o.sc, B, 1, st));
+      HIP_TRY(launch_gemv(o.sc, w.g1.w, w.g1.b, hid, B, D, 256, 1, 0, st));
+      HIP_TRY(launch_gemv(hid, w.g2.w, w.g2.b, temb, B, D, D, 0, 1, st));
+    }
+    if (d.pooled_dim > 0) {
+      HIP_TRY(launch_bf16_to_f32((const uint16_t*)pooled, o.pf, (int64_t)B * d.pooled_dim, st));
+      HIP_TRY(launch_gemv(o.pf, w.p1.w, w.p1.b, hid, B, D, d.pooled_dim, 1, 0, st));
+      HIP_TRY(launch_gemv(hid, w.p2.w, w.p2.b, temb, B, D, D, 0, 1, st));
+    }
+  }
+  HIP_TRY(launch_silu(o.temb, o.semb, (int64_t)rows * D, st));
+  // Every AdaLN modulation vector of the whole network in one weight-streaming pass over the stacked [n_mod, D] matrix
+  // (6.5 GB for FLUX: 1.3 ms of pure HBM streaming), on the forward's stream.  (Measured and dropped, r02c: the rows of all but the first blocks
+  // on a side stream under the embedders' and first blocks' MFMA work, 140.2 vs 139.5 ms per image -- the GEMMs lose more to the shared HBM / issue
+  // slots than the 1.3 ms the stream hides.)
+  HIP_TRY(launch_gemv(o.semb, w.mod.w, w.mod.b, o.mod, rows, (int)c->n_mod, D, 0, 0, st, c->n_mod));
+  // a separately bound norm_out.linear (the distillation student trains its own copy while the teacher keeps the
+  // frozen one inside the stacked matrix: lakonlab/configs/flux/arcflux_2nfe_k16.py:20-25 freeze_exclude 'norm_out')
+  if (w.mod_final.w != nullptr)
+    HIP_TRY(launch_gemv(o.semb, w.mod_final.w, w.mod_final.b, o.mod + ModLayout{D, d.num_double, d.num_single}.fin(0), rows, 2 * D, D, 0, 0, st, c->n_mod));
+  return AFX_OK;
+}
+
+// ---- the forward of one micro-batch: one state, named steps ----------------------------------------
+// The fp8 switches, resolved once per call (fwd_resolve_fp8).  mx: block-scaled activations; norm_rows: ... except the operands the LayerNorm kernel writes, one scale per row; attn_mx: the
+// attention epilogue writes the out-projection's operand; qk_fuse_fp8: the fp8 kernel's q / k epilogue is switched on
+struct Fp8Mode { bool mx = false, norm_rows = false, attn_mx = false, qk_fuse_fp8 = false; };
+// where the A operand of an fp8 block GEMM is when its launch is built
+enum class ASrc {
+  Bf16,   // bf16 in memory: a pass in front of the GEMM quantises it
+  Wide,   // the wide operand a GEMM epilogue left in q8 / mxw (mlp hidden; the single blocks' [O | mlp], O added by the attention kernel or a pass)
+  Norm,   // the LayerNorm kernel left it in q8n, with one scale per row in qs or (AFX_FP8_NORM_MX) block scales in mxn
+  Attn,   // the attention kernel of a double block left it in q8n / mxn
+};
+struct Fwd {
+  afx_ctx* c; Workspace ws; hipStream_t st; BlockShape bs; ModLayout ml; int64_t ldm, D, R;
+  Fp8Mode fp8; int dpath, spath;          // dpath / spath: how the double / single blocks prepare their attention operands (AFX_QKV_*)
+};
+
+int fwd_gemm(Fwd& f, GemmBatch& gb) {
+  ProfScope ps_(f.c, f.st, 0, gemm_flops(gb));
+  HIP_TRY(launch_gemm(gb, f.st));
+  return AFX_OK;
+}
+
+int fwd_resolve_fp8(Fwd& f) {
+  afx_ctx* c = f.c;
+  Fp8Mode& m = f.fp8;
+  // fp8 with block-scaled activations (DESIGN 11): every block GEMM reads e4m3 rows + one E8M0 byte per row and 128 columns.  The D-wide
+  // operands are quantised into q8n / mxn (by the pass below until their producers write them), the wide ones (mlp hidden, [O | mlp]) leave
+  // the producing GEMM's epilogue in q8 / mxw.
+  if (c->fp8 && c->fp8_mx < 0) {          // latched per context on the first fp8 forward; the other switches are read on every call
+    const char* e = getenv("AFX_FP8_MX");
+    c->fp8_mx = (e && e[0] == '0') ? 0 : 1;
+  }
+  m.mx = c->fp8 && c->fp8_mx == 1 && f.D % 512 == 0 && gemm_fp8_mx_ok(f.R, (int)f.D, (int)f.D);
+  if (m.mx) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)f.ws.ones, 0x3f800000, (size_t)f.R, f.st));
+  // The fused q / k epilogue also exists on the one-wave-per-SIMD fp8 kernel (epi_store_qk<MI, true>; V is then transposed by its own launch), opt-in:
+  // measured level with the separate preparation launch (11.30 vs 11.30 images/s) -- with 256 accumulators in the file the fp8 variant of that epilogue
+  // has to re-read the weight scales per row tile, which costs what the saved launch gave (AFX_FP8_QK_FUSE=1).
+  // LayerNorm-produced operands (a row sits in one wave there) carry ONE scale per row and run on the plain fp8 MFMA; only the operands written by
+  // GEMM / attention epilogues need block scales (AFX_FP8_NORM_MX=1: block scales everywhere, A/B)
+  m.norm_rows = m.mx && getenv("AFX_FP8_NORM_MX") == nullptr;
+  m.attn_mx = m.mx && f.bs.H * 128 == f.D && getenv("AFX_FP8_ATTN_MX_OFF") == nullptr;      // the attention epilogue as the last producer of the format
+  const char* qkf8 = getenv("AFX_FP8_QK_FUSE");
+  m.qk_fuse_fp8 = m.mx && qkf8 != nullptr && qkf8[0] == '1';
+  // how each block prepares its attention operands (see qkv_path): q / k RMSNorm + RoPE in the epilogue of the k|v|q projections when
+  // the GEMM kernel in use offers it (not in fp8 mode unless AFX_FP8_QK_FUSE), and V^T straight out of the projection where the shape
+  // allows: then no preparation launch is left between the projection and the attention
+  f.dpath = qkv_path(f.bs, false, c->fp8, m.qk_fuse_fp8);
+  f.spath = qkv_path(f.bs, true, c->fp8, m.qk_fuse_fp8);
+  return AFX_OK;
+}
+
+// The fp8 operand side of problem p (bf16 mode: nothing): its M rows are the rows from row0 on of the K-wide operand `src`, its weight is lw
+void bind_fp8_operand(GemmProblem& p, const Fwd& f, ASrc src, int64_t row0, int K, const LinW& lw) {
+  const Workspace& ws = f.ws;
+  if (!f.c->fp8) return;
+  p.W = (const uint16_t*)lw.wq; p.fp8 = 1; p.w_scale = lw.wscale; p.lda = K;
+  if (!f.fp8.mx) {                                     // per-token scales: the pass in front of every GEMM wrote q8 / qs
+    p.A = (const uint16_t*)(ws.q8 + row0 * K); p.a_scale = ws.qs + row0;
+  } else if (src == ASrc::Norm && f.fp8.norm_rows) {   // LayerNorm rows: one scale per row, the plain fp8 MFMA
+    p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.qs + row0;
+  } else if (src == ASrc::Wide) {
+    p.A = (const uint16_t*)(ws.q8 + row0 * K); p.a_scale = ws.ones + row0; p.a_mx = ws.mxw + row0 * ws.ld_mxw; p.ld_mx = ws.ld_mxw;
+  } else {
+    p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.ones + row0; p.a_mx = ws.mxn + row0 * ws.ld_mxn; p.ld_mx = ws.ld_mxn;
+  }
+}
+// ... and the producer side (block-scaled mode): the epilogue of p stores its columns from col0 on as columns dst_col0.. of rows row0.. of
+// the wide operand (ld8 bytes per row) instead of bf16 to C
+void bind_fp8_producer(GemmProblem& p, const Fwd& f, int64_t row0, int64_t ld8, int64_t dst_col0, int col0) {
+  p.c8 = f.ws.q8 + row0 * ld8 + dst_col0; p.ldc8 = ld8; p.c8_col0 = col0;
+  p.c_mx = f.ws.mxw + row0 * f.ws.ld_mxw + dst_col0 / 128; p.ld_cmx = f.ws.ld_mxw;
+}
+// the quantisation pass in front of an fp8 GEMM whose K-wide operand no producer wrote
+int fwd_quant_operand(Fwd& f, ASrc src, const uint16_t* A, int64_t lda, int K) {
+  const Workspace& ws = f.ws;
+  if (f.fp8.mx && src == ASrc::Bf16) HIP_TRY(launch_quant_rows_mx8(A, lda, ws.q8n, K, ws.mxn, ws.ld_mxn, (int)f.R, K, f.st));
+  else if (f.c->fp8 && !f.fp8.mx) HIP_TRY(launch_quant_rows_fp8(A, lda, ws.q8, K, ws.qs, (int)f.R, K, f.st));     // per-token scales, all rows at once
+  return AFX_OK;
+}
+
+// One per-stream linear of a double block: 2 problems per sample in one grouped launch.  wide_out: this GEMM's epilogue writes the wide operand.
+// A launch costs ceil(rounds) x tile area, so a SHORT text stream (Qwen-Image: 128 rows) costs the grouped launch a row of half-empty tiles;
+// the text problems as a launch of their own were level at best and are gone (docs/DESIGN_HISTORY_r04_r05.md, "short text stream").
+int stream_gemm(Fwd& f, const uint16_t* A, int64_t lda, int K, const LinW (&lw)[2], uint16_t* C, int64_t ldc, int Nout, int epi, int blk,
+                int gate_chunk, const float* qkn = nullptr, ASrc src = ASrc::Bf16, bool wide_out = false) {
+  GemmBatch gb{};
+  AFX_TRY(fwd_quant_operand(f, src, A, lda, K));
+  for (int b = 0; b < f.bs.B; ++b)
+    for (int s = 0; s < 2; ++s) {   // 0 image rows, 1 text rows
+      GemmProblem& p = gb.p[gb.nprob++];
+      stream_problem(p, f.bs, A, lda, K, lw[s], C, ldc, Nout, b, s);
+      const int64_t row0 = (int64_t)b * f.bs.S + (s == 0 ? f.bs.T : 0);
+      bind_fp8_operand(p, f, src, row0, K, lw[s]);
+      if (wide_out) bind_fp8_producer(p, f, row0, Nout, 0, 0);
+      p.epi = epi; p.gelu_col0 = 0;
+      if (qkn != nullptr) stream_qk_epilogue(p, f.bs, qkn, s);          // [img_q, img_k, txt_q, txt_k][128]
+      if (epi == EPI_GATE_RES) {
+        p.gate = f.ws.mod + (int64_t)b * f.ldm + f.ml.dbl(blk, s, gate_chunk); p.ldg = 0; p.rows_per_batch = 1 << 30;
+        p.res = C + row0 * ldc; p.ldr = ldc;
+      }
+    }
+  return fwd_gemm(f, gb);
+}
+
+// LN + modulate of both streams of every sample in one launch (text rows take the text stream's vectors).  *out: where the next GEMM finds
+// the rows -- Norm when (block-scaled mode) the kernel wrote the GEMM operand itself, else Bf16 (Xn)
+int stream_norm(Fwd& f, int blk, int shift_chunk, int scale_chunk, ASrc* out) {
+  const Workspace& ws = f.ws;
+  const float *sc_i = ws.mod + f.ml.dbl(blk, 0, scale_chunk), *sh_i = ws.mod + f.ml.dbl(blk, 0, shift_chunk);
+  const float *sc_t = ws.mod + f.ml.dbl(blk, 1, scale_chunk), *sh_t = ws.mod + f.ml.dbl(blk, 1, shift_chunk);
+  bool fused = false;
+  if (f.fp8.mx)
+    HIP_TRY(launch_norm_modulate_mx8(ws.X, f.D, ws.q8n, f.D, ws.mxn, ws.ld_mxn, (int)f.R, (int)f.D, sc_i, sh_i, sc_t, sh_t, f.ldm, f.bs.S, f.bs.T, f.st,
+                                     &fused, f.fp8.norm_rows ? ws.qs : nullptr));
+  if (!fused) HIP_TRY(launch_norm_modulate_joint(ws.X, f.D, ws.Xn, f.D, (int)f.R, (int)f.D, sc_i, sh_i, sc_t, sh_t, f.ldm, f.bs.S, f.bs.T, f.st));
+  *out = fused ? ASrc::Norm : ASrc::Bf16;
+  return AFX_OK;
+}
+
+// the modulation vectors and embeddings of this call: copied from a prepared step, or computed here
+int fwd_conditioning(Fwd& f, const void* pooled, const float* t, const float* g) {
+  afx_ctx* c = f.c;
+  const Workspace& ws = f.ws;
+  const int B = f.bs.B;
+  const int prep_k = c->prep_use;
+  c->prep_use = -1;                              // one-shot
+  if (prep_k >= 0 && prep_k < c->prep_steps && c->prep_B == B && c->temb_override == nullptr) {
+    // the modulation vectors (and temb, for afx_mmdit_export) of this step were computed by afx_mmdit_prepare_steps
+    const int64_t r0 = (int64_t)prep_k * B;
+    HIP_TRY(hipMemcpyAsync(ws.mod, ws.prep_mod + r0 * f.ldm, (size_t)B * f.ldm * 4, hipMemcpyDeviceToDevice, f.st));
+    HIP_TRY(hipMemcpyAsync(ws.temb, ws.prep_temb + r0 * f.D, (size_t)B * f.D * 4, hipMemcpyDeviceToDevice, f.st));
+    HIP_TRY(hipMemcpyAsync(ws.semb, ws.prep_semb + r0 * f.D, (size_t)B * f.D * 4, hipMemcpyDeviceToDevice, f.st));
+    return AFX_OK;
+  }
+  if (c->temb_override != nullptr) HIP_TRY(hipMemcpyAsync(ws.temb, c->temb_override, (size_t)B * f.D * 4, hipMemcpyDeviceToDevice, f.st));
+  return conditioning(c, c->temb_override != nullptr ? nullptr : t, 1, g, pooled, B, CondBufs{ws.sincos, ws.pooled, ws.tmp, ws.temb, ws.semb, ws.mod}, f.st);
+}
+
+// embedders into the joint layout X[b][text T | image N]
+int fwd_embed(Fwd& f, const void* x, const void* ctx_emb) {
+  const afx_model_desc& d = f.c->d;
+  const OuterW& w = f.c->ow;
+  const Workspace& ws = f.ws;
+  const int64_t B = f.bs.B, N = f.bs.N, T = f.bs.T, S = f.bs.S, D = f.D;
+  const uint16_t* ctx_src = (const uint16_t*)ctx_emb;
+  if (d.family == 1) {   // Qwen: RMSNorm(joint_dim) on the text states before txt_in (arcqwen.py:129)
+    HIP_TRY(launch_norm_modulate(ctx_src, d.joint_dim, ws.F, d.joint_dim, (int)(B * T), d.joint_dim, w.txt_norm, nullptr, 0, (int)(B * T), 1, f.st));
+    ctx_src = ws.F;
+  }
+  GemmBatch gb{};
+  for (int b = 0; b < B; ++b) {
+    linear_problem(gb.p[gb.nprob++], (const uint16_t*)x + b * N * d.in_channels, d.in_channels, w.x_in, 0, ws.X + (b * S + T) * D, D, (int)N, (int)D, d.in_channels);
+    linear_problem(gb.p[gb.nprob++], ctx_src + b * T * d.joint_dim, d.joint_dim, w.ctx_in, 0, ws.X + b * S * D, D, (int)T, (int)D, d.joint_dim);
+  }
+  return fwd_gemm(f, gb);
+}
+
+// attention over the [k | v | q ...] rows of stride ldf (O overwrites Q).  omx: the fp8 operand the kernel writes too where it can (*o_fused)
+int fwd_attention(Fwd& f, uint16_t* F, int64_t ldf, const AttnMx8& omx, bool* o_fused) {
+  const BlockShape& bs = f.bs;
+  ProfScope ps_(f.c, f.st, 1, 4.0 * bs.B * bs.H * (double)bs.S * bs.S * 128);
+  HIP_TRY(launch_attention(F + 2 * f.D, ldf, F, ldf, f.ws.Vt, F + 2 * f.D, ldf, bs.B, bs.H, bs.S, f.st, nullptr, f.fp8.attn_mx ? &omx : nullptr, o_fused));
+  return AFX_OK;
+}
+
+// dual-stream block i
+int fwd_double_block(Fwd& f, int i) {
+  const Workspace& ws = f.ws;
+  const int64_t D = f.D, R = f.R;
+  const bool mx = f.fp8.mx;
+  const DoubleW& bw = f.c->dbl[i];
+  const float* qkn = bw.qkn;            // [img_q, img_k, txt_q, txt_k][128]
+  uint16_t* QKV = ws.F;                 // [R, 3D]  rows k|v|q
+  uint16_t* Hb = ws.F + R * 3 * D;      // [R, 4D]  MLP hidden
+  if (f.c->ckpt) HIP_TRY(hipMemcpyAsync(f.c->ckpt + (int64_t)i * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, f.st));
+  ASrc normed;
+  AFX_TRY(stream_norm(f, i, 0, 1, &normed));
+  if (f.dpath == AFX_QKV_VT_PROJ) {     // per sample: img k, q, v^T + txt k, q, v^T = 6 problems in one launch
+    for (int b = 0; b < f.bs.B; ++b) {
+      GemmBatch gb{};
+      double_vt_batch(gb, f.bs, ws.Xn, D, bw.qkv, QKV, 3 * D, qkn, b);
+      AFX_TRY(fwd_gemm(f, gb));
+    }
+  } else AFX_TRY(stream_gemm(f, ws.Xn, D, (int)D, bw.qkv, QKV, 3 * D, (int)(3 * D), EPI_NONE, i, 0, f.dpath == AFX_QKV_QK_EPI ? qkn : nullptr, normed));
+  // V -> V^T (QK_EPI), or k, q: RMSNorm + RoPE in place and V -> V^T in one launch (KV_PREP)
+  HIP_TRY(qkv_finish(f.dpath, f.bs, QKV, 3 * D, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, f.st));
+  bool o_fused = false;                 // mx: the attention kernel wrote the out-projection's operand itself (q8n / mxn)
+  AFX_TRY(fwd_attention(f, QKV, 3 * D, AttnMx8{ws.q8n, D, ws.mxn, ws.ld_mxn}, &o_fused));
+  AFX_TRY(stream_gemm(f, QKV + 2 * D, 3 * D, (int)D, bw.out, ws.X, D, (int)D, EPI_GATE_RES, i, 2, nullptr, o_fused ? ASrc::Attn : ASrc::Bf16));
+  AFX_TRY(stream_norm(f, i, 3, 4, &normed));
+  AFX_TRY(stream_gemm(f, ws.Xn, D, (int)D, bw.mlp1, Hb, 4 * D, (int)(4 * D), EPI_GELU, i, 0, nullptr, normed, mx));      // (mx: the hidden leaves as the next GEMM's operand, Hb stays unwritten)
+  return stream_gemm(f, Hb, 4 * D, (int)(4 * D), bw.mlp2, ws.X, D, (int)D, EPI_GATE_RES, i, 5, nullptr, mx ? ASrc::Wide : ASrc::Bf16);
+}
+
+// single-stream block i on the joint sequence
+int fwd_single_block(Fwd& f, int i) {
+  const Workspace& ws = f.ws;
+  const int64_t D = f.D, R = f.R, ldm = f.ldm;
+  const int S = f.bs.S;
+  const bool mx = f.fp8.mx;
+  const SingleW& bw = f.c->sgl[i];
+  const float* qkn = bw.qkn;            // [q, k][128]
+  const float *scale = ws.mod + f.ml.sgl(i, 1), *shift = ws.mod + f.ml.sgl(i, 0);
+  if (f.c->ckpt)
+    HIP_TRY(hipMemcpyAsync(f.c->ckpt + (int64_t)(f.c->d.num_double + i) * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, f.st));
+  bool sgl_fused = false;
+  if (mx) HIP_TRY(launch_norm_modulate_mx8(ws.X, D, ws.q8n, D, ws.mxn, ws.ld_mxn, (int)R, (int)D, scale, shift, nullptr, nullptr, ldm, S, 0, f.st,
+                                           &sgl_fused, f.fp8.norm_rows ? ws.qs : nullptr));
+  if (!sgl_fused) HIP_TRY(launch_norm_modulate(ws.X, D, ws.Xn, D, (int)R, (int)D, scale, shift, ldm, S, 0, f.st));
+  const ASrc normed = sgl_fused ? ASrc::Norm : ASrc::Bf16;
+  GemmBatch gb{};
+  single_qkv_batch(gb, f.spath, f.bs, ws.Xn, D, bw.fused, ws.F, 7 * D, qkn);      // (VT_PROJ is never taken in fp8 mode)
+  AFX_TRY(fwd_quant_operand(f, normed, ws.Xn, D, (int)D));
+  bind_fp8_operand(gb.p[0], f, normed, 0, (int)D, bw.fused);
+  if (mx) bind_fp8_producer(gb.p[0], f, 0, 5 * D, D, (int)(3 * D));      // the mlp columns leave as columns [D, 5D) of the proj_out operand
+  AFX_TRY(fwd_gemm(f, gb));
+  HIP_TRY(qkv_finish(f.spath, f.bs, ws.F, 7 * D, qkn + 128, qkn + 128, qkn, qkn, f.st));
+  bool o_fused = false;                 // mx: ... columns [0, D) of the [O | mlp] operand (q8 / mxw)
+  AFX_TRY(fwd_attention(f, ws.F, 7 * D, AttnMx8{ws.q8, 5 * D, ws.mxw, ws.ld_mxw}, &o_fused));
+  GemmBatch go{};
+  GemmProblem& o = go.p[go.nprob++];
+  linear_problem(o, ws.F + 2 * D, 7 * D, bw.out, 0, ws.X, D, (int)R, (int)D, (int)(5 * D));
+  o.epi = EPI_GATE_RES; o.gate = ws.mod + f.ml.sgl(i, 2); o.ldg = ldm; o.rows_per_batch = S; o.res = ws.X; o.ldr = D;
+  // mx: the attention output joins the mlp columns the projection's epilogue left in q8 (a pass of D columns unless the attention kernel wrote
+  // them); per-token scales: the usual pass over all 5D columns.  Either way the operand is the wide one.
+  if (mx && !o_fused) HIP_TRY(launch_quant_rows_mx8(ws.F + 2 * D, 7 * D, ws.q8, 5 * D, ws.mxw, ws.ld_mxw, (int)R, (int)D, f.st));
+  if (!mx) AFX_TRY(fwd_quant_operand(f, ASrc::Bf16, ws.F + 2 * D, 7 * D, (int)(5 * D)));
+  bind_fp8_operand(o, f, ASrc::Wide, 0, (int)(5 * D), bw.out);
+  return fwd_gemm(f, go);
+}
+
+// norm_out (scale first) + velocity head on the image tokens
+int fwd_head(Fwd& f, void* means, void* logw, void* logg) {
+  afx_ctx* c = f.c;
+  const afx_model_desc& d = c->d;
+  const Workspace& ws = f.ws;
+  const int64_t B = f.bs.B, N = f.bs.N, T = f.bs.T, S = f.bs.S, D = f.D, ldm = f.ldm;
+  for (int b = 0; b < B; ++b)
+    HIP_TRY(launch_norm_modulate(ws.X + (b * S + T) * D, D, ws.Xn + b * N * D, D, (int)N, (int)D, ws.mod + b * ldm + f.ml.fin(0),
+                                 ws.mod + b * ldm + f.ml.fin(1), 0, 1 << 30, 0, f.st));
+  GemmBatch gb{};      // (teacher: velocity [B*N, in_channels] written directly)
+  linear_problem(gb.p[gb.nprob++], ws.Xn, D, c->ow.head, 0, d.head_mode == 0 ? ws.head : (uint16_t*)means, c->head_n, (int)(B * N), c->head_n, (int)D);
+  AFX_TRY(fwd_gemm(f, gb));
+  if (d.head_mode == 0)
+    HIP_TRY(launch_head_split(ws.head, c->head_n, (uint16_t*)means, (uint16_t*)logw, (uint16_t*)logg, B * N,
+                              d.num_gaussians, d.in_channels, d.logweights_channels, f.st));
+  return AFX_OK;
 }
 
 }  // namespace
@@ -392,47 +680,36 @@ int afx_finalize(afx_ctx* c) {
   if (!c) return fail(AFX_E_INVALID, "null ctx");
   const int64_t D = c->D;
   const afx_model_desc& d = c->d;
-  int r;
-#define NEED(x) \
-  if ((r = (x)) != AFX_OK) return r
-  NEED(need_linear(c, "x_in", D, d.in_channels));
-  NEED(need_linear(c, "ctx_in", D, d.joint_dim));
-  if (d.family == 1) NEED(need(c, "txt_norm.weight", AFX_DT_F32, {d.joint_dim}));
-  NEED(need_linear(c, "temb.t.l1", D, 256));
-  NEED(need_linear(c, "temb.t.l2", D, D));
-  if (d.guidance_embeds) {
-    NEED(need_linear(c, "temb.g.l1", D, 256));
-    NEED(need_linear(c, "temb.g.l2", D, D));
-  }
-  if (d.pooled_dim > 0) {
-    NEED(need_linear(c, "temb.p.l1", D, d.pooled_dim));
-    NEED(need_linear(c, "temb.p.l2", D, D));
-  }
-  NEED(need_linear(c, "mod", c->n_mod, D));
+  AFX_TRY(need_linear(c, "x_in", D, d.in_channels));
+  AFX_TRY(need_linear(c, "ctx_in", D, d.joint_dim));
+  if (d.family == 1) AFX_TRY(need(c, "txt_norm.weight", AFX_DT_F32, {d.joint_dim}));
+  AFX_TRY(need_linear(c, "temb.t.l1", D, 256));
+  AFX_TRY(need_linear(c, "temb.t.l2", D, D));
+  if (d.guidance_embeds) AFX_TRY(need_linear(c, "temb.g.l1", D, 256));
+  if (d.guidance_embeds) AFX_TRY(need_linear(c, "temb.g.l2", D, D));
+  if (d.pooled_dim > 0) AFX_TRY(need_linear(c, "temb.p.l1", D, d.pooled_dim));
+  if (d.pooled_dim > 0) AFX_TRY(need_linear(c, "temb.p.l2", D, D));
+  AFX_TRY(need_linear(c, "mod", c->n_mod, D));
   for (int i = 0; i < d.num_double; ++i) {
     const std::string p = "d" + std::to_string(i) + ".";
     for (const char* s : {"img", "txt"}) {
-      NEED(need_linear(c, p + s + "_qkv", 3 * D, D));
-      NEED(need_linear(c, p + s + "_out", D, D));
-      NEED(need_linear(c, p + s + "_mlp1", 4 * D, D));
-      NEED(need_linear(c, p + s + "_mlp2", D, 4 * D));
+      AFX_TRY(need_linear(c, p + s + "_qkv", 3 * D, D));
+      AFX_TRY(need_linear(c, p + s + "_out", D, D));
+      AFX_TRY(need_linear(c, p + s + "_mlp1", 4 * D, D));
+      AFX_TRY(need_linear(c, p + s + "_mlp2", D, 4 * D));
     }
-    NEED(need(c, p + "qknorm", AFX_DT_F32, {4, 128}));
+    AFX_TRY(need(c, p + "qknorm", AFX_DT_F32, {4, 128}));
   }
   for (int i = 0; i < d.num_single; ++i) {
     const std::string p = "s" + std::to_string(i) + ".";
-    NEED(need_linear(c, p + "fused", 7 * D, D));
-    NEED(need_linear(c, p + "out", D, 5 * D));
-    NEED(need(c, p + "qknorm", AFX_DT_F32, {2, 128}));
+    AFX_TRY(need_linear(c, p + "fused", 7 * D, D));
+    AFX_TRY(need_linear(c, p + "out", D, 5 * D));
+    AFX_TRY(need(c, p + "qknorm", AFX_DT_F32, {2, 128}));
   }
-  NEED(need_linear(c, "head", c->head_n, D));
-  if (c->w.count("mod_final.weight")) NEED(need_linear(c, "mod_final", 2 * D, D));
-#undef NEED
+  AFX_TRY(need_linear(c, "head", c->head_n, D));
+  if (c->w.count("mod_final.weight")) AFX_TRY(need_linear(c, "mod_final", 2 * D, D));
   auto lin = [&](const std::string& n) {
-    LinW l;
-    l.w = W16(c, n + ".weight"); l.b = W16(c, n + ".bias");
-    l.wq = WQ(c, n + ".weight_q"); l.wscale = W32(c, n + ".wscale");
-    return l;
+    return LinW{wptr<uint16_t>(c, n + ".weight"), wptr<uint16_t>(c, n + ".bias"), wptr<void>(c, n + ".weight_q"), wptr<float>(c, n + ".wscale")};
   };
   c->dbl.assign(d.num_double, DoubleW{});
   for (int i = 0; i < d.num_double; ++i) {
@@ -442,14 +719,16 @@ int afx_finalize(afx_ctx* c) {
       c->dbl[i].qkv[s] = lin(q + "qkv"); c->dbl[i].out[s] = lin(q + "out");
       c->dbl[i].mlp1[s] = lin(q + "mlp1"); c->dbl[i].mlp2[s] = lin(q + "mlp2");
     }
-    c->dbl[i].qkn = W32(c, p + "qknorm");
+    c->dbl[i].qkn = wptr<float>(c, p + "qknorm");
   }
   c->sgl.assign(d.num_single, SingleW{});
   for (int i = 0; i < d.num_single; ++i) {
     const std::string p = "s" + std::to_string(i) + ".";
     c->sgl[i].fused = lin(p + "fused"); c->sgl[i].out = lin(p + "out");
-    c->sgl[i].qkn = W32(c, p + "qknorm");
+    c->sgl[i].qkn = wptr<float>(c, p + "qknorm");
   }
+  c->ow = OuterW{lin("temb.t.l1"), lin("temb.t.l2"), lin("temb.g.l1"), lin("temb.g.l2"), lin("temb.p.l1"), lin("temb.p.l2"), lin("mod"),
+                 lin("mod_final"), lin("x_in"), lin("ctx_in"), lin("head"), wptr<float>(c, "txt_norm.weight")};
   c->finalized = true;
   return AFX_OK;
 }
@@ -516,274 +795,20 @@ int afx_mmdit_forward_stage(afx_ctx* c, const void* x, const void* ctx_emb, cons
   if (d.head_mode == 0 && (!logw || !logg)) return fail(AFX_E_INVALID, "logw/logg outputs required");
   Workspace ws = carve(c, c->ws, B, N, T);
   if (!c->ws || ws.total > c->ws_bytes)
-    return fail(AFX_E_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)ws.total,
-                (long long)c->ws_bytes);
-  hipStream_t st = (hipStream_t)stream_;
-  const int64_t D = c->D;
-  const int H = d.heads, S = N + T;
-  const int64_t R = (int64_t)B * S;
-  ModLayout ml{D, d.num_double, d.num_single};
-  const int64_t ldm = c->n_mod;
-
-  const bool use_prep = c->prep_use >= 0 && c->prep_use < c->prep_steps && c->prep_B == B && stage != 2 && c->temb_override == nullptr;
-  const int prep_k = c->prep_use;
-  if (stage != 2) c->prep_use = -1;                              // one-shot
-  if (use_prep) {
-    // the modulation vectors (and temb, for afx_mmdit_export) of this step were computed by afx_mmdit_prepare_steps
-    const int64_t r0 = (int64_t)prep_k * B;
-    HIP_TRY(hipMemcpyAsync(ws.mod, ws.prep_mod + r0 * ldm, (size_t)B * ldm * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ws.temb, ws.prep_temb + r0 * D, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ws.semb, ws.prep_semb + r0 * D, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (stage != 2 && !use_prep) {
-  // ---- conditioning: temb = t_mlp(sincos(1000 t)) [+ g_mlp(sincos(1000 g))] [+ p_mlp(pooled)] ------
-  if (c->temb_override != nullptr) {
-    HIP_TRY(hipMemcpyAsync(ws.temb, c->temb_override, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
-  } else {
-    HIP_TRY(launch_sincos(t, 1000.0f, ws.sincos, B, d.family == 0 ? 1 : 2, st));
-    HIP_TRY(launch_gemv(ws.sincos, W16(c, "temb.t.l1.weight"), W16(c, "temb.t.l1.bias"), ws.tmp, B, (int)D, 256, 1, 0, st));
-    HIP_TRY(launch_gemv(ws.tmp, W16(c, "temb.t.l2.weight"), W16(c, "temb.t.l2.bias"), ws.temb, B, (int)D, (int)D, 0, 0, st));
-  }
-  if (d.guidance_embeds) {
-    HIP_TRY(launch_sincos(g, 1000.0f, ws.sincos, B, 1, st));
-    HIP_TRY(launch_gemv(ws.sincos, W16(c, "temb.g.l1.weight"), W16(c, "temb.g.l1.bias"), ws.tmp, B, (int)D, 256, 1, 0, st));
-    HIP_TRY(launch_gemv(ws.tmp, W16(c, "temb.g.l2.weight"), W16(c, "temb.g.l2.bias"), ws.temb, B, (int)D, (int)D, 0, 1, st));
-  }
-  if (d.pooled_dim > 0) {
-    HIP_TRY(launch_bf16_to_f32((const uint16_t*)pooled, ws.pooled, (int64_t)B * d.pooled_dim, st));
-    HIP_TRY(launch_gemv(ws.pooled, W16(c, "temb.p.l1.weight"), W16(c, "temb.p.l1.bias"), ws.tmp, B, (int)D, d.pooled_dim, 1, 0, st));
-    HIP_TRY(launch_gemv(ws.tmp, W16(c, "temb.p.l2.weight"), W16(c, "temb.p.l2.bias"), ws.temb, B, (int)D, (int)D, 0, 1, st));
-  }
-  HIP_TRY(launch_silu(ws.temb, ws.semb, (int64_t)B * D, st));
-  // Every AdaLN modulation vector of the whole network in one weight-streaming pass over the stacked [n_mod, D] matrix
-  // (6.5 GB for FLUX: 1.3 ms of pure HBM streaming), on the forward's stream.  (Measured and dropped, r02c: the rows of all but the first blocks
-  // on a side stream under the embedders' and first blocks' MFMA work, 140.2 vs 139.5 ms per image -- the GEMMs lose more to the shared HBM / issue
-  // slots than the 1.3 ms the stream hides.)
-  HIP_TRY(launch_gemv(ws.semb, W16(c, "mod.weight"), W16(c, "mod.bias"), ws.mod, B, (int)c->n_mod, (int)D, 0, 0, st, ldm));
-  // a separately bound norm_out.linear (the distillation student trains its own copy while the teacher keeps the
-  // frozen one inside the stacked matrix: lakonlab/configs/flux/arcflux_2nfe_k16.py:20-25 freeze_exclude 'norm_out')
-  if (W16(c, "mod_final.weight") != nullptr)
-    HIP_TRY(launch_gemv(ws.semb, W16(c, "mod_final.weight"), W16(c, "mod_final.bias"), ws.mod + ml.fin(0), B, (int)(2 * D),
-                        (int)D, 0, 0, st, ldm));
-  }   // conditioning
+    return fail(AFX_E_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)ws.total, (long long)c->ws_bytes);
+  Fwd f{c, ws, (hipStream_t)stream_, block_shape(d.heads, B, N, T, rope_cos, rope_sin, ws.Vt), ModLayout{c->D, d.num_double, d.num_single},
+        c->n_mod, c->D, (int64_t)B * (N + T), Fp8Mode{}, 0, 0};
   if (stage != 2) {
-  // ---- embedders into the joint layout X[b][text T | image N] ---------------------------------------
-  const uint16_t* ctx_src = (const uint16_t*)ctx_emb;
-  if (d.family == 1) {   // Qwen: RMSNorm(joint_dim) on the text states before txt_in (arcqwen.py:129)
-    HIP_TRY(launch_norm_modulate(ctx_src, d.joint_dim, ws.F, d.joint_dim, B * T, d.joint_dim,
-                                 W32(c, "txt_norm.weight"), nullptr, 0, B * T, 1, st));
-    ctx_src = ws.F;
+    AFX_TRY(fwd_conditioning(f, pooled, t, g));
+    AFX_TRY(fwd_embed(f, x, ctx_emb));
   }
-  {
-    GemmBatch gb{};
-    for (int b = 0; b < B; ++b) {
-      GemmProblem& pi = gb.p[gb.nprob++];
-      pi = GemmProblem{};
-      pi.A = (const uint16_t*)x + (int64_t)b * N * d.in_channels; pi.lda = d.in_channels;
-      pi.W = W16(c, "x_in.weight"); pi.ldw = d.in_channels; pi.bias = W16(c, "x_in.bias");
-      pi.C = ws.X + ((int64_t)b * S + T) * D; pi.ldc = D; pi.M = N; pi.N = (int)D; pi.K = d.in_channels;
-      GemmProblem& pt = gb.p[gb.nprob++];
-      pt = GemmProblem{};
-      pt.A = ctx_src + (int64_t)b * T * d.joint_dim; pt.lda = d.joint_dim;
-      pt.W = W16(c, "ctx_in.weight"); pt.ldw = d.joint_dim; pt.bias = W16(c, "ctx_in.bias");
-      pt.C = ws.X + (int64_t)b * S * D; pt.ldc = D; pt.M = T; pt.N = (int)D; pt.K = d.joint_dim;
-    }
-    { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-  }
-  }   // stage != 2
   if (stage == 1) return AFX_OK;       // the caller runs the blocks itself on the exported token matrix
-
-  // fp8 with block-scaled activations (DESIGN 11): every block GEMM reads e4m3 rows + one E8M0 byte per row and 128 columns.  The D-wide
-  // operands are quantised into q8n / mxn (by the pass below until their producers write them), the wide ones (mlp hidden, [O | mlp]) leave
-  // the producing GEMM's epilogue in q8 / mxw.
-  if (c->fp8 && c->fp8_mx < 0) {
-    const char* e = getenv("AFX_FP8_MX");
-    c->fp8_mx = (e && e[0] == '0') ? 0 : 1;
+  AFX_TRY(fwd_resolve_fp8(f));
+  if (stage == 0) {
+    for (int i = 0; i < d.num_double; ++i) AFX_TRY(fwd_double_block(f, i));
+    for (int i = 0; i < d.num_single; ++i) AFX_TRY(fwd_single_block(f, i));
   }
-  const bool mx = c->fp8 && c->fp8_mx == 1 && D % 512 == 0 && gemm_fp8_mx_ok(R, (int)D, (int)D);
-  if (mx) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ws.ones, 0x3f800000, (size_t)R, st));
-  // The fused q / k epilogue also exists on the one-wave-per-SIMD fp8 kernel (epi_store_qk<MI, true>; V is then transposed by its own launch), opt-in:
-  // measured level with the separate preparation launch (11.30 vs 11.30 images/s) -- with 256 accumulators in the file the fp8 variant of that epilogue
-  // has to re-read the weight scales per row tile, which costs what the saved launch gave (AFX_FP8_QK_FUSE=1).
-  // LayerNorm-produced operands (a row sits in one wave there) carry ONE scale per row and run on the plain fp8 MFMA; only the operands written by
-  // GEMM / attention epilogues need block scales (AFX_FP8_NORM_MX=1: block scales everywhere, A/B)
-  const bool norm_rows = mx && getenv("AFX_FP8_NORM_MX") == nullptr;
-  const bool attn_mx = mx && H * 128 == D && getenv("AFX_FP8_ATTN_MX_OFF") == nullptr;      // the attention epilogue as the last producer of the format
-  const char* qkf8 = getenv("AFX_FP8_QK_FUSE");
-  const bool qk_fuse_fp8 = mx && qkf8 != nullptr && qkf8[0] == '1';
-  // how each block prepares its attention operands (see qkv_path): q / k RMSNorm + RoPE in the epilogue of the k|v|q projections when
-  // the GEMM kernel in use offers it (not in fp8 mode unless AFX_FP8_QK_FUSE), and V^T straight out of the projection where the shape
-  // allows: then no preparation launch is left between the projection and the attention
-  const BlockShape bs = block_shape(H, B, N, T, rope_cos, rope_sin, ws.Vt);
-  const int dpath = qkv_path(bs, false, c->fp8, qk_fuse_fp8), spath = qkv_path(bs, true, c->fp8, qk_fuse_fp8);
-  // mx_in: 0 = quantise A here; 1 = A is the wide operand a previous epilogue left in q8 / mxw; 2 = the LayerNorm kernel left it in q8n (+ qs: one scale
-  // per row, or + mxn with AFX_FP8_NORM_MX); 3 = the attention kernel left it in q8n / mxn.
-  // mx_out: this GEMM's epilogue writes the wide operand.
-  const int split_txt_default = 0;
-  auto stream_gemm = [&](const uint16_t* A, int64_t lda, int K, const LinW (&lw)[2], uint16_t* C, int64_t ldc, int Nout, int epi,
-                         int blk, int gate_chunk, const float* qkn = nullptr, int mx_in = 0, bool mx_out = false, int kind = 0) -> int {
-    GemmBatch gb{};
-    if (mx && mx_in == 0) HIP_TRY(launch_quant_rows_mx8(A, lda, ws.q8n, K, ws.mxn, ws.ld_mxn, (int)R, K, st));      // (mx_in 2: the LayerNorm kernel wrote q8n / mxn itself)
-    else if (c->fp8 && !mx) HIP_TRY(launch_quant_rows_fp8(A, lda, ws.q8, K, ws.qs, (int)R, K, st));     // per-token scales, all rows at once
-    for (int b = 0; b < B; ++b)
-      for (int s = 0; s < 2; ++s) {   // 0 image rows, 1 text rows
-        GemmProblem& p = gb.p[gb.nprob++];
-        stream_problem(p, bs, A, lda, K, lw[s], C, ldc, Nout, b, s);
-        const int64_t row0 = (int64_t)b * S + (s == 0 ? T : 0);
-        if (mx) {
-          p.W = (const uint16_t*)lw[s].wq; p.fp8 = 1; p.a_scale = ws.ones + row0; p.w_scale = lw[s].wscale; p.lda = K;
-          if (mx_in == 2 && norm_rows) { p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.qs + row0; }      // LayerNorm rows: one scale per row, the plain fp8 MFMA
-          else if (mx_in != 1) { p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_mx = ws.mxn + row0 * ws.ld_mxn; p.ld_mx = ws.ld_mxn; }
-          else { p.A = (const uint16_t*)(ws.q8 + row0 * K); p.a_mx = ws.mxw + row0 * ws.ld_mxw; p.ld_mx = ws.ld_mxw; }
-          if (mx_out) { p.c8 = ws.q8 + row0 * Nout; p.ldc8 = Nout; p.c_mx = ws.mxw + row0 * ws.ld_mxw; p.ld_cmx = ws.ld_mxw; p.c8_col0 = 0; }
-        } else if (c->fp8) {
-          p.A = (const uint16_t*)(ws.q8 + row0 * K); p.lda = K;
-          p.W = (const uint16_t*)lw[s].wq; p.fp8 = 1; p.a_scale = ws.qs + row0; p.w_scale = lw[s].wscale;
-        }
-        p.epi = epi; p.gelu_col0 = 0;
-        if (qkn != nullptr) stream_qk_epilogue(p, bs, qkn, s);          // [img_q, img_k, txt_q, txt_k][128]
-        if (epi == EPI_GATE_RES) {
-          p.gate = ws.mod + (int64_t)b * ldm + ml.dbl(blk, s, gate_chunk); p.ldg = 0; p.rows_per_batch = 1 << 30;
-          p.res = C + row0 * ldc; p.ldr = ldc;
-        }
-      }
-    // A launch costs ceil(rounds) x tile area: a SHORT text stream (Qwen-Image: 128 rows) costs the grouped launch a whole row of half-empty tiles --
-    // at N = 12288, 4096 + 128 rows are 816 tiles of 256x256 (3.2 -> 4 rounds; the launcher settles for 1024 tiles of 288x192 = 4 rounds) where the image rows
-    // alone are 768 = exactly 3.  split_txt (bit per launch kind: 1 qkv, 2 out, 4 mlp1, 8 mlp2; AFX_SPLIT_TXT overrides): the text problems go out as a launch
-    // of their own (small tiles, two work-groups per CU) behind the image problems'.
-    static int split_env = -2;
-    if (split_env == -2) {
-      const char* e = getenv("AFX_SPLIT_TXT");
-      split_env = e ? atoi(e) : -1;
-    }
-    const int split_mask = split_env >= 0 ? split_env : split_txt_default;
-    if ((split_mask & kind) != 0 && T > 0 && N > 0 && !mx && !c->fp8) {
-      GemmBatch gi{}, gt{};
-      for (int j = 0; j < gb.nprob; ++j) ((j & 1) ? gt : gi).p[((j & 1) ? gt : gi).nprob++] = gb.p[j];
-      { ProfScope ps_(c, st, 0, gemm_flops(gi)); HIP_TRY(launch_gemm(gi, st)); }
-      { ProfScope ps_(c, st, 0, gemm_flops(gt)); HIP_TRY(launch_gemm(gt, st)); }
-      return AFX_OK;
-    }
-    { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-    return AFX_OK;
-  };
-  // LN + modulate of both streams of every sample in one launch (text rows take the text stream's vectors)
-  bool norm_fused = false;      // mx: the last stream_norm wrote the GEMM operand itself
-  auto stream_norm = [&](int blk, int shift_chunk, int scale_chunk) -> int {
-    norm_fused = false;
-    if (mx) {
-      HIP_TRY(launch_norm_modulate_mx8(ws.X, D, ws.q8n, D, ws.mxn, ws.ld_mxn, (int)R, (int)D, ws.mod + ml.dbl(blk, 0, scale_chunk),
-                                       ws.mod + ml.dbl(blk, 0, shift_chunk), ws.mod + ml.dbl(blk, 1, scale_chunk),
-                                       ws.mod + ml.dbl(blk, 1, shift_chunk), ldm, (int)S, T, st, &norm_fused, norm_rows ? ws.qs : nullptr));
-      if (norm_fused) return AFX_OK;
-    }
-    HIP_TRY(launch_norm_modulate_joint(ws.X, D, ws.Xn, D, (int)R, (int)D, ws.mod + ml.dbl(blk, 0, scale_chunk),
-                                       ws.mod + ml.dbl(blk, 0, shift_chunk), ws.mod + ml.dbl(blk, 1, scale_chunk),
-                                       ws.mod + ml.dbl(blk, 1, shift_chunk), ldm, S, T, st));
-    return AFX_OK;
-  };
-
-  int rc;
-  // ---- dual-stream blocks ---------------------------------------------------------------------------
-  uint16_t* QKV = ws.F;                 // [R, 3D]  rows k|v|q
-  uint16_t* Hb = ws.F + R * 3 * D;      // [R, 4D]  MLP hidden
-  for (int i = 0; stage == 0 && i < d.num_double; ++i) {
-    const DoubleW& bw = c->dbl[i];
-    const float* qkn = bw.qkn;          // [img_q, img_k, txt_q, txt_k][128]
-    if (c->ckpt) HIP_TRY(hipMemcpyAsync(c->ckpt + (int64_t)i * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, st));
-    if ((rc = stream_norm(i, 0, 1))) return rc;
-    if (dpath == AFX_QKV_VT_PROJ) {       // per sample: img k, q, v^T + txt k, q, v^T = 6 problems in one launch
-      for (int b = 0; b < B; ++b) {
-        GemmBatch gb{};
-        double_vt_batch(gb, bs, ws.Xn, D, bw.qkv, QKV, 3 * D, qkn, b);
-        { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-      }
-    } else
-    if ((rc = stream_gemm(ws.Xn, D, (int)D, bw.qkv, QKV, 3 * D, (int)(3 * D), EPI_NONE, i, 0, dpath == AFX_QKV_QK_EPI ? qkn : nullptr,
-                          norm_fused ? 2 : 0, false, 1))) return rc;
-    // V -> V^T (QK_EPI), or k, q: RMSNorm + RoPE in place and V -> V^T in one launch (KV_PREP)
-    HIP_TRY(qkv_finish(dpath, bs, QKV, 3 * D, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, st));
-    bool o_fused = false;            // mx: the attention kernel wrote the out-projection's operand itself (q8n / mxn)
-    const AttnMx8 omx_d{ws.q8n, D, ws.mxn, ws.ld_mxn};
-    { ProfScope ps_(c, st, 1, 4.0 * B * H * (double)S * S * 128);
-      HIP_TRY(launch_attention(QKV + 2 * D, 3 * D, QKV, 3 * D, ws.Vt, QKV + 2 * D, 3 * D, B, H, S, st, nullptr, attn_mx ? &omx_d : nullptr, &o_fused)); }
-    if ((rc = stream_gemm(QKV + 2 * D, 3 * D, (int)D, bw.out, ws.X, D, (int)D, EPI_GATE_RES, i, 2, nullptr, o_fused ? 3 : 0, false, 2))) return rc;
-    if ((rc = stream_norm(i, 3, 4))) return rc;
-    if ((rc = stream_gemm(ws.Xn, D, (int)D, bw.mlp1, Hb, 4 * D, (int)(4 * D), EPI_GELU, i, 0, nullptr, norm_fused ? 2 : 0, mx, 4))) return rc;      // (mx: the hidden leaves as the next GEMM's operand, Hb stays unwritten)
-    if ((rc = stream_gemm(Hb, 4 * D, (int)(4 * D), bw.mlp2, ws.X, D, (int)D, EPI_GATE_RES, i, 5, nullptr, mx ? 1 : 0, false, 8))) return rc;
-  }
-
-  // ---- single-stream blocks on the joint sequence -------------------------------------------------
-  for (int i = 0; stage == 0 && i < d.num_single; ++i) {
-    const SingleW& bw = c->sgl[i];
-    const float* qkn = bw.qkn;          // [q, k][128]
-    if (c->ckpt)
-      HIP_TRY(hipMemcpyAsync(c->ckpt + (int64_t)(d.num_double + i) * R * D, ws.X, (size_t)R * D * 2, hipMemcpyDeviceToDevice, st));
-    bool sgl_fused = false;
-    if (mx) HIP_TRY(launch_norm_modulate_mx8(ws.X, D, ws.q8n, D, ws.mxn, ws.ld_mxn, (int)R, (int)D, ws.mod + ml.sgl(i, 1), ws.mod + ml.sgl(i, 0),
-                                             nullptr, nullptr, ldm, (int)S, 0, st, &sgl_fused, norm_rows ? ws.qs : nullptr));
-    if (!sgl_fused) HIP_TRY(launch_norm_modulate(ws.X, D, ws.Xn, D, (int)R, (int)D, ws.mod + ml.sgl(i, 1), ws.mod + ml.sgl(i, 0), ldm, S, 0, st));
-    GemmBatch gb{};
-    single_qkv_batch(gb, spath, bs, ws.Xn, D, bw.fused, ws.F, 7 * D, qkn);      // (VT_PROJ is never taken in fp8 mode)
-    GemmProblem& f = gb.p[0];
-    if (mx) {             // A: the LayerNorm rows, block-scaled; the mlp columns leave as columns [D, 5D) of the proj_out operand
-      if (!sgl_fused) HIP_TRY(launch_quant_rows_mx8(ws.Xn, D, ws.q8n, D, ws.mxn, ws.ld_mxn, (int)R, (int)D, st));
-      f.A = (const uint16_t*)ws.q8n; f.W = (const uint16_t*)bw.fused.wq; f.fp8 = 1; f.a_scale = ws.ones; f.w_scale = bw.fused.wscale;
-      if (sgl_fused && norm_rows) f.a_scale = ws.qs;      // the LayerNorm kernel wrote one scale per row: the plain fp8 MFMA
-      else { f.a_mx = ws.mxn; f.ld_mx = ws.ld_mxn; }
-      f.c8 = ws.q8 + D; f.ldc8 = 5 * D; f.c_mx = ws.mxw + D / 128; f.ld_cmx = ws.ld_mxw; f.c8_col0 = (int)(3 * D);
-    } else if (c->fp8) {
-      HIP_TRY(launch_quant_rows_fp8(ws.Xn, D, ws.q8, D, ws.qs, (int)R, (int)D, st));
-      f.A = (const uint16_t*)ws.q8; f.W = (const uint16_t*)bw.fused.wq; f.fp8 = 1; f.a_scale = ws.qs; f.w_scale = bw.fused.wscale;
-    }
-    { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-    HIP_TRY(qkv_finish(spath, bs, ws.F, 7 * D, qkn + 128, qkn + 128, qkn, qkn, st));
-    bool o_fused = false;            // mx: ... columns [0, D) of the [O | mlp] operand (q8 / mxw)
-    const AttnMx8 omx_s{ws.q8, 5 * D, ws.mxw, ws.ld_mxw};
-    { ProfScope ps_(c, st, 1, 4.0 * B * H * (double)S * S * 128);
-      HIP_TRY(launch_attention(ws.F + 2 * D, 7 * D, ws.F, 7 * D, ws.Vt, ws.F + 2 * D, 7 * D, B, H, S, st, nullptr, attn_mx ? &omx_s : nullptr, &o_fused)); }
-    GemmBatch go{};
-    go.nprob = 1;
-    GemmProblem& o = go.p[0];
-    o = GemmProblem{};
-    o.A = ws.F + 2 * D; o.lda = 7 * D; o.W = bw.out.w; o.ldw = 5 * D; o.bias = bw.out.b;
-    o.C = ws.X; o.ldc = D; o.M = (int)R; o.N = (int)D; o.K = (int)(5 * D); o.epi = EPI_GATE_RES;
-    o.gate = ws.mod + ml.sgl(i, 2); o.ldg = ldm; o.rows_per_batch = S; o.res = ws.X; o.ldr = D;
-    if (mx) {             // the attention output joins the mlp columns the projection's epilogue left in q8
-      if (!o_fused) HIP_TRY(launch_quant_rows_mx8(ws.F + 2 * D, 7 * D, ws.q8, 5 * D, ws.mxw, ws.ld_mxw, (int)R, (int)D, st));
-      o.A = (const uint16_t*)ws.q8; o.lda = 5 * D; o.W = (const uint16_t*)bw.out.wq; o.fp8 = 1; o.a_scale = ws.ones; o.w_scale = bw.out.wscale;
-      o.a_mx = ws.mxw; o.ld_mx = ws.ld_mxw;
-    } else if (c->fp8) {
-      HIP_TRY(launch_quant_rows_fp8(ws.F + 2 * D, 7 * D, ws.q8, 5 * D, ws.qs, (int)R, (int)(5 * D), st));
-      o.A = (const uint16_t*)ws.q8; o.lda = 5 * D; o.W = (const uint16_t*)bw.out.wq; o.fp8 = 1; o.a_scale = ws.qs;
-      o.w_scale = bw.out.wscale;
-    }
-    { ProfScope ps_(c, st, 0, gemm_flops(go)); HIP_TRY(launch_gemm(go, st)); }
-  }
-
-  // ---- norm_out (scale first) + velocity head on the image tokens --------------------------------------
-  for (int b = 0; b < B; ++b)
-    HIP_TRY(launch_norm_modulate(ws.X + ((int64_t)b * S + T) * D, D, ws.Xn + (int64_t)b * N * D, D, N, (int)D,
-                                 ws.mod + (int64_t)b * ldm + ml.fin(0), ws.mod + (int64_t)b * ldm + ml.fin(1), 0,
-                                 1 << 30, 0, st));
-  {
-    GemmBatch gb{};
-    gb.nprob = 1;
-    GemmProblem& hp = gb.p[0];
-    hp = GemmProblem{};
-    hp.A = ws.Xn; hp.lda = D; hp.W = W16(c, "head.weight"); hp.ldw = D; hp.bias = W16(c, "head.bias");
-    hp.M = B * N; hp.N = c->head_n; hp.K = (int)D; hp.epi = EPI_NONE;
-    if (d.head_mode == 0) {
-      hp.C = ws.head; hp.ldc = c->head_n;
-    } else {
-      hp.C = (uint16_t*)means; hp.ldc = c->head_n;    // teacher: velocity [B*N, in_channels] written directly
-    }
-    { ProfScope ps_(c, st, 0, gemm_flops(gb)); HIP_TRY(launch_gemm(gb, st)); }
-  }
-  if (d.head_mode == 0)
-    HIP_TRY(launch_head_split(ws.head, c->head_n, (uint16_t*)means, (uint16_t*)logw, (uint16_t*)logg, (int64_t)B * N,
-                              d.num_gaussians, d.in_channels, d.logweights_channels, st));
-  return AFX_OK;
+  return fwd_head(f, means, logw, logg);
 }
 
 int afx_mmdit_prepare_steps(afx_ctx* c, const void* pooled, const float* t_steps, const float* g, int32_t B, int32_t nsteps,
@@ -798,42 +823,14 @@ int afx_mmdit_prepare_steps(afx_ctx* c, const void* pooled, const float* t_steps
   if (c->temb_override) return fail(AFX_E_INVALID, "afx_mmdit_prepare_steps: not with a timestep-embedding override");
   Workspace ws = carve(c, c->ws, 1, 1, 1);                       // (only the shape-independent head of the workspace is used)
   if (!c->ws || ws.total > c->ws_bytes) return fail(AFX_E_WORKSPACE, "workspace not set / too small");
-  hipStream_t st = (hipStream_t)stream_;
-  const int64_t D = c->D, ldm = c->n_mod;
-  const int rows = B * nsteps;
-  c->prep_steps = 0;
-  c->prep_use = -1;
-  // temb of every (step, sample): the same three tiny MLPs as the forward, B rows at a time into row block k
-  float* sc = ws.prep_semb;                                      // scratch: sincos / hidden rows live in the semb block until the SiLU
-  for (int k = 0; k < nsteps; ++k) {
-    float* temb = ws.prep_temb + (int64_t)k * B * D;
-    float* hid = sc + (int64_t)k * B * D;                        // [B, D] hidden of the current MLP (overwritten by the SiLU below)
-    float* sin_ = ws.prep_mod;                                   // [B, 256] / [B, pooled_dim]: free until the big pass
-    HIP_TRY(launch_sincos(t_steps + (int64_t)k * B, 1000.0f, sin_, B, d.family == 0 ? 1 : 2, st));
-    HIP_TRY(launch_gemv(sin_, W16(c, "temb.t.l1.weight"), W16(c, "temb.t.l1.bias"), hid, B, (int)D, 256, 1, 0, st));
-    HIP_TRY(launch_gemv(hid, W16(c, "temb.t.l2.weight"), W16(c, "temb.t.l2.bias"), temb, B, (int)D, (int)D, 0, 0, st));
-    if (d.guidance_embeds) {
-      HIP_TRY(launch_sincos(g, 1000.0f, sin_, B, 1, st));
-      HIP_TRY(launch_gemv(sin_, W16(c, "temb.g.l1.weight"), W16(c, "temb.g.l1.bias"), hid, B, (int)D, 256, 1, 0, st));
-      HIP_TRY(launch_gemv(hid, W16(c, "temb.g.l2.weight"), W16(c, "temb.g.l2.bias"), temb, B, (int)D, (int)D, 0, 1, st));
-    }
-    if (d.pooled_dim > 0) {
-      HIP_TRY(launch_bf16_to_f32((const uint16_t*)pooled, sin_, (int64_t)B * d.pooled_dim, st));
-      HIP_TRY(launch_gemv(sin_, W16(c, "temb.p.l1.weight"), W16(c, "temb.p.l1.bias"), hid, B, (int)D, d.pooled_dim, 1, 0, st));
-      HIP_TRY(launch_gemv(hid, W16(c, "temb.p.l2.weight"), W16(c, "temb.p.l2.bias"), temb, B, (int)D, (int)D, 0, 1, st));
-    }
-  }
-  HIP_TRY(launch_silu(ws.prep_temb, ws.prep_semb, (int64_t)rows * D, st));
-  // ONE pass over the stacked [n_mod, D] matrix for all steps: the matrix (6.5 GB for FLUX) is what the time goes into, the
+  c->prep_steps = 0; c->prep_use = -1;
+  // temb of every (step, sample): the same three tiny MLPs as the forward, B rows at a time into row block k.  Scratch: the hidden rows live in
+  // the semb block until the SiLU overwrites them, the sincos / pooled rows ([B, 256] / [B, pooled_dim]) in the mod block, free until the big pass.
+  // Then ONE pass over the stacked [n_mod, D] matrix for all steps: the matrix (6.5 GB for FLUX) is what the time goes into, the
   // number of right-hand sides is free up to the GEMV's 8
-  HIP_TRY(launch_gemv(ws.prep_semb, W16(c, "mod.weight"), W16(c, "mod.bias"), ws.prep_mod, rows, (int)c->n_mod, (int)D, 0, 0, st, ldm));
-  if (W16(c, "mod_final.weight") != nullptr) {
-    ModLayout ml{D, d.num_double, d.num_single};
-    HIP_TRY(launch_gemv(ws.prep_semb, W16(c, "mod_final.weight"), W16(c, "mod_final.bias"), ws.prep_mod + ml.fin(0), rows, (int)(2 * D),
-                        (int)D, 0, 0, st, ldm));
-  }
-  c->prep_steps = nsteps;
-  c->prep_B = B;
+  AFX_TRY(conditioning(c, t_steps, nsteps, g, pooled, B, CondBufs{ws.prep_mod, ws.prep_mod, ws.prep_semb, ws.prep_temb, ws.prep_semb, ws.prep_mod},
+                       (hipStream_t)stream_));
+  c->prep_steps = nsteps; c->prep_B = B;
   return AFX_OK;
 }
 

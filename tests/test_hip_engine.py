@@ -217,6 +217,46 @@ def test_fp8_block_scaled_mode_tracks_bf16(family, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('switch', ['AFX_FP8_NORM_MX', 'AFX_FP8_ATTN_MX_OFF', 'AFX_FP8_QK_FUSE'])
+@pytest.mark.parametrize('family', ['flux', 'qwen'])
+def test_fp8_block_scaled_switches_track_bf16(family, switch, monkeypatch):
+    """The three switches of the block-scaled fp8 engine, each set alone to 1 on a fresh engine: block scales on the LayerNorm operands too
+    (AFX_FP8_NORM_MX), the out-projection's operand from a quantisation pass instead of the attention epilogue (AFX_FP8_ATTN_MX_OFF), q / k RMSNorm +
+    RoPE in the fp8 projection's epilogue (AFX_FP8_QK_FUSE).  Each moves a GEMM's A operand to another buffer; the output stays within the
+    mode's stated tolerance of the bf16 engine (shape of test_fp8_block_scaled_mode_tracks_bf16: width 512 is the smallest that takes the path)."""
+    from arcflow_amd import MMDiTEngine
+    from oracle import dit_ref as D
+    g = torch.Generator().manual_seed(23)
+    hp = wp = 16
+    T = 40
+    if family == 'flux':
+        w = D.make_flux_weights(D.FluxCfg(num_layers=2, num_single_layers=2, heads=4, joint_dim=128, pooled_dim=64), seed=6)
+        kw = dict(num_double=2, num_single=2, joint_dim=128, pooled_dim=64)
+        pooled, gd = (torch.randn(2, 64, generator=g) * 0.5).bfloat16().cuda(), torch.full((2,), 3.5).cuda()
+    else:
+        w = D.make_qwen_weights(D.QwenCfg(num_layers=3, heads=4, joint_dim=192), seed=6)
+        kw = dict(num_double=3, joint_dim=192)
+        pooled = gd = None
+    x = torch.randn(2, hp * wp, 64, generator=g).bfloat16().cuda()
+    ctx = (torch.randn(2, T, kw['joint_dim'], generator=g) * 0.5).bfloat16().cuda()
+    t = torch.tensor([0.6, 0.3]).cuda()
+    outs = {}
+    for mode in ('bf16', 'fp8'):
+        if mode == 'fp8':
+            monkeypatch.setenv(switch, '1')
+        eng = MMDiTEngine(family, kw['num_double'], kw.get('num_single', 0), heads=4, joint_dim=kw['joint_dim'], pooled_dim=kw.get('pooled_dim', 768))
+        eng.load_state_dict(w)
+        if mode == 'fp8':
+            eng.enable_fp8()
+        outs[mode] = {k: v.float().clone() for k, v in eng(x, t, ctx, pooled, gd, hp, wp).items()}
+    for k in ('means', 'logweights', 'loggammas'):
+        ref = outs['bf16'][k]
+        rel = ((outs['fp8'][k] - ref).norm() / ref.norm()).item()
+        print(family, switch, k, rel)
+        assert 0 < rel < 8e-2, (k, rel)
+
+
+@pytest.mark.gpu
 def test_profile_events_every_launch_and_sampled():
     """afx_profile_enable(ctx, N): an event pair on every GEMM / attention launch (N = 1) or on one launch in N (bench.py's default 8: the pairs cost
     ~4 us each).  The sampled sums must cover 1 / N of the launches and give the same FLOP / time ratio within the launch-to-launch spread."""
