@@ -34,7 +34,7 @@ EXPORTS = [
     'afx_outer_accum', 'afx_mmdit_export', 'afx_sumsq', 'afx_adamw_step', 'afx_adamw8bit_step', 'afx_ema_lerp', 'afx_cast_f32_bf16',
     'afx_qkv_operands', 'afx_norm_modulate_joint_bf16', 'afx_norm_modulate_mx8', 'afx_forward_diffuse_pack',
     'afx_teacher_euler_step', 'afx_cfg_ortho_ws_bytes', 'afx_cfg_ortho_coef', 'afx_teacher_sde_step',
-    'afx_sample_score_ws_bytes', 'afx_sample_score',
+    'afx_sample_score_ws_bytes', 'afx_sample_score', 'afx_lora_fold',
 ]
 
 AFX_BLOCK_DOUBLE, AFX_BLOCK_SINGLE = 0, 1
@@ -170,6 +170,7 @@ def load() -> C.CDLL:
     lib.afx_sample_score_ws_bytes.argtypes = [i32, i64]
     lib.afx_sample_score_ws_bytes.restype = i64
     lib.afx_sample_score.argtypes = [vp, vp, i32, i32, vp, vp, i64, i32, i64, vp]
+    lib.afx_lora_fold.argtypes = [vp, i64, vp, i64, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), vp]
     lib.afx_head_grad.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]
     lib.afx_linear_bf16_f32out.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp]
     lib.afx_linear_tn_f32out.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp]

@@ -70,6 +70,7 @@ class MMDiTEngine:
         self._ws: Optional[torch.Tensor] = None
         self._ws_key = (0, 0, 0)
         self._rope_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.fp8_linear = False     # enable_fp8(): the block linears read quantised copies of the bf16 weights
         self.config = dict(in_channels=in_channels, guidance_embeds=self.guidance_embeds, num_gaussians=num_gaussians)
 
     def __del__(self):
@@ -246,6 +247,7 @@ class MMDiTEngine:
             if extra:
                 self.bind_packed(extra)
         _lib.check(self.lib.afx_set_fp8_linear(self._ctx, int(on)))
+        self.fp8_linear = bool(on)
         self._ws, self._ws_key = None, (0, 0, 0)          # the workspace grows by the quantised-operand buffer
 
     def set_temb_override(self, temb_t: Optional[torch.Tensor]) -> None:

@@ -1053,3 +1053,29 @@ def attention_bwd_2d(q, k, v, o, dout, lse, dq, dk, dv, B: int, S: int, H: int):
     _lib.check(lib.afx_attention_bwd_bf16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
                                           _p(dout), dout.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dk), dk.stride(0),
                                           _p(dv), dv.stride(0), _p(ws), B, H, S, _s()))
+
+
+def lora_fold(base: torch.Tensor, dst: torch.Tensor, A=(), B=(), scales=()) -> torch.Tensor:
+    """dst = bf16(base + sum_j scales[j] * B[j] @ A[j]) (``afx_lora_fold``): base, dst [O, I] bf16 row slices (any row stride >= I) of
+    packed weights that do not overlap, A[j] [r_j, I] and B[j] [O, r_j] contiguous bf16 of any rank >= 1, scales[j] python floats applied
+    in fp32 to adapter j's fp32-accumulated product.  One rounding, at the store; bit-reproducible; no adapters = a copy."""
+    lib = _lib.load()
+    _mat(base, torch.bfloat16, 'lora_fold base')
+    _mat(dst, torch.bfloat16, 'lora_fold dst', base.shape)
+    O, I = base.shape
+    J = len(A)
+    if len(B) != J or len(scales) != J:
+        raise ValueError(f'lora_fold: {J} A, {len(B)} B and {len(scales)} scales')
+    for j in range(J):
+        _mat(A[j], torch.bfloat16, f'lora_fold A[{j}]')
+        _mat(B[j], torch.bfloat16, f'lora_fold B[{j}]')
+        r = A[j].shape[0]
+        if not (A[j].is_contiguous() and B[j].is_contiguous()) or tuple(A[j].shape) != (r, I) or tuple(B[j].shape) != (O, r):
+            raise ValueError(f'lora_fold: adapter {j} needs contiguous A [r, {I}] and B [{O}, r], got {tuple(A[j].shape)} and {tuple(B[j].shape)}')
+    n = max(J, 1)
+    pa = (C.c_void_p * n)(*[a.data_ptr() for a in A])
+    pb = (C.c_void_p * n)(*[b.data_ptr() for b in B])
+    rk = (C.c_int32 * n)(*[a.shape[0] for a in A])
+    sc = (C.c_float * n)(*[float(s) for s in scales])
+    _lib.check(lib.afx_lora_fold(_p(base), base.stride(0), _p(dst), dst.stride(0), O, I, J, pa, pb, rk, sc, _s()))
+    return dst

@@ -10,10 +10,12 @@ into the bf16 base weights at load (fp32 merge, one rounding) instead of running
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
+import re
 import warnings
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
@@ -50,15 +52,73 @@ def read_adapter(path: str, subfolder: Optional[str] = None, variant: Optional[s
     return config, sd, meta
 
 
+LORA_WEIGHT_NAME = 'pytorch_lora_weights.safetensors'
+_LORA_KEY = re.compile(r'^(?P<mod>.+)\.(?P<kind>lora_A|lora_B|lora_down|lora_up)(?:\.(?P<infix>[^.]+))?\.weight$')
+MAX_FOLD_ADAPTERS = 8          # AFX_LORA_MAX_ADAPTERS: adapters one afx_lora_fold launch sums
+
+
+def read_lora_file(path: str, weight_name: Optional[str] = None, subfolder: Optional[str] = None) -> Dict[str, torch.Tensor]:
+    """A local ``.safetensors`` file, or a directory (+ ``subfolder``) holding ``weight_name`` (default: diffusers'
+    ``pytorch_lora_weights.safetensors``) -> state dict.  Never reaches the network."""
+    from safetensors import safe_open
+    f = path
+    if os.path.isdir(path):
+        f = os.path.join(_resolve_dir(path, subfolder), weight_name or LORA_WEIGHT_NAME)
+    if not os.path.isfile(f):
+        raise EnvironmentError(f'{f} is not a local file. This build has no network access: pass a local .safetensors file, or a '
+                               f'directory and `weight_name`.')
+    with safe_open(f, framework='pt', device='cpu') as h:
+        return {k: h.get_tensor(k) for k in h.keys()}
+
+
+def parse_lora_state_dict(sd: Dict[str, torch.Tensor], prefix: str = 'transformer'):
+    """Group a diffusers / peft LoRA state dict by module -> ({module: dict(A=[r, in], B=[out, r], alpha=float or None)}, number of
+    skipped ``text_encoder*`` keys).  Accepted per module, with or without the leading ``transformer.``:
+    ``<module>.lora_A.weight`` / ``lora_B.weight`` (also with an adapter infix, ``lora_A.default.weight``), ``<module>.lora_down.weight``
+    / ``lora_up.weight``, and an optional scalar ``<module>.alpha``.  Kohya / ComfyUI checkpoints (``lora_unet_*`` keys, fused qkv /
+    linear1 tensors) are refused: convert them to the diffusers layout first."""
+    mods: Dict[str, Dict] = {}
+    skipped = 0
+    for k, v in sd.items():
+        if k.startswith('lora_unet_') or k.startswith('lora_te'):
+            raise ValueError(f'{k!r}: this is a Kohya / ComfyUI LoRA checkpoint (fused qkv / linear1 tensors under `lora_unet_*`), which '
+                             f'is not supported: convert it to the diffusers layout (transformer.<module>.lora_A/lora_B.weight) first')
+        if k.startswith('text_encoder'):
+            skipped += 1
+            continue
+        k2 = k[len(prefix) + 1:] if k.startswith(prefix + '.') else k
+        m = _LORA_KEY.match(k2)
+        if m is not None:
+            slot = 'A' if m.group('kind') in ('lora_A', 'lora_down') else 'B'
+            entry = mods.setdefault(m.group('mod'), dict(A=None, B=None, alpha=None))
+            if entry[slot] is not None:
+                raise ValueError(f'{k!r}: a second {m.group("kind")} tensor for module {m.group("mod")!r}')
+            entry[slot] = v
+        elif k2.endswith('.alpha'):
+            mods.setdefault(k2[:-len('.alpha')], dict(A=None, B=None, alpha=None))['alpha'] = float(v)
+        else:
+            raise ValueError(f'{k!r} is not a LoRA key (expected <module>.lora_A/lora_B[.<adapter>].weight, <module>.lora_down/lora_up.weight '
+                             f'or <module>.alpha)')
+    if skipped:
+        warnings.warn(f'{skipped} text-encoder LoRA tensors were skipped: only transformer LoRAs are applied.')
+    for name, e in mods.items():
+        if e['A'] is None or e['B'] is None:
+            raise ValueError(f'LoRA module {name!r}: lora_A / lora_B (lora_down / lora_up) pair is incomplete')
+    return mods, skipped
+
+
 class ArcFlowLoaderMixin:
-    """Adds ``load_arcflow_adapter`` to a pipeline that keeps ``self._base_state_dict`` (diffusers keys)
-    and ``self._transformer_config``."""
+    """Adds ``load_arcflow_adapter`` and the diffusers LoRA surface (``load_lora_weights``, ``set_adapters``, ``delete_adapters``,
+    ``unload_lora_weights``, ``get_active_adapters``, ``get_list_adapters``) to a pipeline that keeps ``self._base_state_dict``
+    (diffusers keys) and ``self._transformer_config``."""
 
     def load_arcflow_adapter(self, pretrained_model_name_or_path: str, target_module_name: str = 'transformer',
                              adapter_name: Optional[str] = None, **kwargs) -> Optional[str]:
         unknown = set(kwargs) - set(_HF_KWARGS)
         if unknown:
             raise TypeError(f'load_arcflow_adapter() got unexpected keyword arguments {sorted(unknown)}')
+        if getattr(self, '_style', None) is not None:
+            raise RuntimeError('style LoRAs are loaded: call unload_lora_weights() before loading an ArcFlow adapter')
         subfolder = kwargs.get('subfolder')
         config, adapter_sd, meta = read_adapter(pretrained_model_name_or_path, subfolder, kwargs.get('variant'))
         cls_name = config.get('_class_name')
@@ -93,13 +153,18 @@ class ArcFlowLoaderMixin:
     # ------------------------------------------------------------------ runtime LoRA scale
     def set_adapters(self, adapter_names, adapter_weights=None) -> None:
         """diffusers' `pipe.set_adapters(names, adapter_weights=w)` for the ArcFlow adapter (inference_flux.py:9 mentions it): the adapter's
-        LoRA branch is weighted by w from now on.  Only the loaded ArcFlow adapter is known here (style LoRAs would be further
-        `lora` dicts folded the same way)."""
+        LoRA branch is weighted by w from now on.  With style LoRAs loaded (`load_lora_weights`) this is diffusers' full form: the listed
+        adapters become active with `adapter_weights` (a float for all, a list, or None = 1.0), every adapter not listed becomes
+        inactive, and the weights are folded on the device at the next call (see `load_lora_weights`).  Leaving the ArcFlow adapter out
+        switches off its LoRA branch only -- its heads and `norm_out` stay, exactly as `adapter_weights=0` does."""
         names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
         known = getattr(self, '_adapters', [])
         for n in names:
             if n not in known:
                 raise ValueError(f'adapter {n!r} is not loaded (loaded: {known})')
+        if getattr(self, '_style', None) is not None:
+            self._set_style_adapters(names, adapter_weights)
+            return
         if adapter_weights is None:
             w = 1.0
         elif isinstance(adapter_weights, (int, float)):
@@ -116,6 +181,9 @@ class ArcFlowLoaderMixin:
         fp32-accumulating GEMM per adapted linear on the device + a re-pack, about a second for FLUX-12B), cached until s changes --
         a call with the same scale as the previous one costs nothing.  Deviation of the folded forward from the un-folded one:
         tests/test_distill.py::test_unmerged_trunk_forward_matches_merged_engine."""
+        if getattr(self, '_style', None) is not None:
+            self._fold_adapters(float(call_scale))
+            return
         st = getattr(self, '_adapter_state', None)
         if st is None:
             if call_scale != 1.0:
@@ -127,3 +195,192 @@ class ArcFlowLoaderMixin:
         from ..weights import merge_lora
         getattr(self, st['target']).load_state_dict(merge_lora(st['base'], st['lora'], scale=s))
         st['merged_scale'] = s
+
+    # ------------------------------------------------------------------ style LoRAs next to the ArcFlow adapter
+    def _lora_engine(self):
+        st = getattr(self, '_adapter_state', None)
+        return getattr(self, st['target'] if st else 'transformer')
+
+    def _arcflow_adapter_name(self) -> Optional[str]:
+        return self._adapters[0] if getattr(self, '_adapter_state', None) is not None else None
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name: Optional[str] = None,
+                          adapter_name: Optional[str] = None, subfolder: Optional[str] = None) -> str:
+        """diffusers' `pipe.load_lora_weights(...)` for transformer (style) LoRAs, to be combined with the ArcFlow adapter through
+        `set_adapters` as inference_flux.py:9 suggests.  Reads a local `.safetensors` file, a directory + `weight_name`
+        (default `pytorch_lora_weights.safetensors`), or a state dict; never the network.  Keys: see `parse_lora_state_dict`
+        (`text_encoder*` keys are skipped with one warning; Kohya / ComfyUI `lora_unet_*` checkpoints are refused).  A module the
+        transformer does not have, or a shape that does not fit its linear, raises ValueError; so does a duplicate `adapter_name`.
+        The new adapter becomes active with weight 1.0; the other adapters keep their state.  Returns the adapter's name.
+
+        Every adapter's tensors are uploaded once as bf16: fp32 / fp16 files are rounded once here, as `weights._merge_one` does for the
+        ArcFlow adapter.  Its factor is `alpha / r` per module (1 without `alpha`); the effective scale of adapter j is
+        `call_scale * adapter_weights[j] * alpha_j / r_j`, with `call_scale` = `joint_attention_kwargs['scale']` (`attention_kwargs`
+        on Qwen-Image) multiplying EVERY active adapter as the reference's `scale_lora_layers` does.
+
+        Folding: W = bf16(W_base + sum_j s_j B_j A_j) per adapted linear by `afx_lora_fold` straight into the engine's live packed
+        weights (same addresses, no re-bind, no host round trip, no re-pack), the scales applied in fp32 to fp32 sums and ONE rounding
+        at the store.  W_base is the plain snapshot plus the ArcFlow adapter's non-LoRA keys.  Folds are lazy: nothing runs before the
+        next `__call__`, only linears whose scale list changed are folded, and an unchanged state costs nothing.  Memory: while any
+        style LoRA is loaded the pipeline keeps a device-resident bf16 copy of W_base for every linear that ANY loaded adapter (the
+        ArcFlow one included) touches -- up to one more bf16 copy of the adapted matrices -- plus the small A / B tensors.
+        `unload_lora_weights()` frees it.  Not supported together with the engine's fp8 linear mode (NotImplementedError): the
+        quantised weight copies would have to be rebuilt after every fold.  `sample_teacher` is not affected by any of this."""
+        eng = self._lora_engine()
+        if eng is None or eng.teacher_head:
+            raise RuntimeError('load_lora_weights() needs the ArcFlow student: call load_arcflow_adapter() first')
+        if getattr(eng, 'fp8_linear', False):
+            raise NotImplementedError('style LoRAs with the fp8 linear mode on are not supported (the quantised weights are not rebuilt '
+                                      'after a fold): call enable_fp8(False) first')
+        sd = pretrained_model_name_or_path_or_dict
+        if not isinstance(sd, dict):
+            sd = read_lora_file(sd, weight_name, subfolder)
+        known = list(getattr(self, '_adapters', []))
+        if adapter_name is None:
+            n = 0
+            while f'default_{n}' in known:
+                n += 1
+            adapter_name = f'default_{n}'
+        if adapter_name in known:
+            raise ValueError(f'adapter {adapter_name!r} is already loaded (loaded: {known})')
+        mods, _ = parse_lora_state_dict(sd)
+        if not mods:
+            raise ValueError('no transformer LoRA weights were found')
+        sty = getattr(self, '_style', None)
+        fresh = sty is None
+        if fresh:
+            from ..weights import packed_row_slices
+            sty = dict(slices=packed_row_slices(self._family, self._transformer_config, True, eng.num_gaussians, eng.logweights_channels),
+                       loras={}, active={}, base={}, arc={}, folded={})
+            arc = self._arcflow_adapter_name()
+            if arc is not None:
+                arc_mods, _ = parse_lora_state_dict(self._adapter_state['lora'])
+                sty['arc'] = self._upload_adapter(sty, arc_mods, eng.device, 'the ArcFlow adapter')
+                sty['active'][arc] = float(self._adapter_state['weight'])
+        new = self._upload_adapter(sty, mods, eng.device, f'adapter {adapter_name!r}')
+        base_sd = self._adapter_state['base'] if getattr(self, '_adapter_state', None) is not None else self._base_state_dict
+        for m in list(sty['arc']) + list(new):
+            if m not in sty['base']:
+                w = base_sd.get(m + '.weight', base_sd.get(m + '.base_layer.weight'))
+                sty['base'][m] = w.to(device=eng.device, dtype=torch.bfloat16).contiguous()
+        sty['loras'][adapter_name] = new
+        sty['active'][adapter_name] = 1.0
+        self._style = sty
+        self._adapters = known + [adapter_name]
+        return adapter_name
+
+    def _upload_adapter(self, sty, mods, device, what: str):
+        """{module: dict(A, B, alpha)} -> {module: (A bf16 on the device, B bf16 on the device, alpha / r)}, checked against the linear it adapts."""
+        out = {}
+        for m, e in mods.items():
+            if m not in sty['slices']:
+                raise ValueError(f'{what}: the transformer has no linear {m!r}')
+            _, _, rows, in_f = sty['slices'][m]
+            a, b = e['A'], e['B']
+            if a.dim() != 2 or b.dim() != 2 or a.shape[0] < 1 or a.shape[0] != b.shape[1] or a.shape[1] != in_f or b.shape[0] != rows:
+                raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear, lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do not fit it')
+            if rows % 64 or in_f % 64:
+                raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear; LoRAs are folded on linears whose sizes are multiples of 64')
+            r = a.shape[0]
+            out[m] = (a.to(device=device, dtype=torch.bfloat16).contiguous(), b.to(device=device, dtype=torch.bfloat16).contiguous(),
+                      1.0 if e['alpha'] is None else e['alpha'] / r)
+        return out
+
+    def _set_style_adapters(self, names: List[str], adapter_weights) -> None:
+        if adapter_weights is None:
+            ws = [1.0] * len(names)
+        elif isinstance(adapter_weights, (int, float)):
+            ws = [float(adapter_weights)] * len(names)
+        else:
+            ws = [1.0 if w is None else float(w) for w in adapter_weights]
+            if len(ws) != len(names):
+                raise ValueError(f'{len(names)} adapters but {len(ws)} adapter_weights')
+        self._style['active'] = dict(zip(names, ws))
+        arc = self._arcflow_adapter_name()
+        if arc is not None:
+            self._adapter_state['weight'] = self._style['active'].get(arc, 0.0)
+
+    def get_active_adapters(self) -> List[str]:
+        sty = getattr(self, '_style', None)
+        if sty is None:
+            return list(getattr(self, '_adapters', []))
+        return [n for n in self._adapters if n in sty['active']]
+
+    def get_list_adapters(self) -> Dict[str, List[str]]:
+        names = list(getattr(self, '_adapters', []))
+        return {'transformer': names} if names else {}
+
+    def delete_adapters(self, adapter_names) -> None:
+        """Remove style LoRAs.  The ArcFlow adapter cannot be deleted (the student's heads would be left without a trunk to match)."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        known = getattr(self, '_adapters', [])
+        for n in names:
+            if n not in known:
+                raise ValueError(f'adapter {n!r} is not loaded (loaded: {known})')
+            if n == self._arcflow_adapter_name():
+                raise ValueError(f'{n!r} is the ArcFlow adapter: it cannot be deleted (set_adapters without it switches its LoRA branch off)')
+        sty = getattr(self, '_style', None)
+        if sty is None:
+            return
+        for n in names:
+            del sty['loras'][n]
+            sty['active'].pop(n, None)
+            self._adapters.remove(n)
+        if not sty['loras']:
+            self._restore_without_style()
+
+    def unload_lora_weights(self) -> None:
+        """Remove every style LoRA and free their device memory.  Deviation from diffusers: the ArcFlow adapter stays -- unloading it
+        would leave a model with no usable head.  Afterwards the weights are the ones `load_arcflow_adapter` / `set_adapters` alone
+        produce for the current ArcFlow weight, bit for bit (that path is run)."""
+        sty = getattr(self, '_style', None)
+        if sty is None:
+            return
+        for n in list(sty['loras']):
+            self._adapters.remove(n)
+        sty['loras'].clear()
+        self._restore_without_style()
+
+    def _restore_without_style(self) -> None:
+        sty, self._style = self._style, None
+        st = getattr(self, '_adapter_state', None)
+        if st is not None:
+            st['merged_scale'] = None            # whatever is folded now, the ArcFlow-only path below rebuilds the weights
+            self._apply_lora_scale(1.0)
+            return
+        from .. import ops
+        eng = self._lora_engine()
+        for m, sig in sty['folded'].items():
+            if sig:
+                packed, r0, rows, _ = sty['slices'][m]
+                ops.lora_fold(sty['base'][m], eng._weights[packed][r0:r0 + rows])
+
+    def _fold_adapters(self, call_scale: float) -> None:
+        """Bring the engine's packed weights to the active adapters at `call_scale`: one `afx_lora_fold` per linear whose list of
+        (adapter, fp32 scale) differs from what is folded in now."""
+        from .. import ops
+        sty = self._style
+        eng = self._lora_engine()
+        if getattr(eng, 'fp8_linear', False):
+            raise NotImplementedError('style LoRAs with the fp8 linear mode on are not supported (the quantised weights are not rebuilt '
+                                      'after a fold): unload_lora_weights() or enable_fp8(False)')
+        arc = self._arcflow_adapter_name()
+        sources = ([(arc, sty['arc'])] if arc is not None else []) + list(sty['loras'].items())
+        for m, base in sty['base'].items():
+            A, B, S, sig = [], [], [], []
+            for name, mods in sources:
+                if name in sty['active'] and m in mods:
+                    a, b, factor = mods[m]
+                    s = ctypes.c_float(call_scale * sty['active'][name] * factor).value
+                    if s != 0.0:
+                        A.append(a); B.append(b); S.append(s); sig.append((name, s))
+            sig = tuple(sig)
+            if sty['folded'].get(m, None if m in sty['arc'] else ()) == sig:        # (the ArcFlow-only path folded the arc linears so far)
+                continue
+            if len(A) > MAX_FOLD_ADAPTERS:
+                raise ValueError(f'{len(A)} active adapters on {m!r}: at most {MAX_FOLD_ADAPTERS} can be folded into one linear')
+            packed, r0, rows, _ = sty['slices'][m]
+            ops.lora_fold(base, eng._weights[packed][r0:r0 + rows], A, B, S)
+            sty['folded'][m] = sig
+            for k in (packed + '_q', packed[:-len('weight')] + 'wscale'):      # quantised copies of an earlier enable_fp8(): stale now, a later
+                eng._weights.pop(k, None)                                      # enable_fp8() quantises this matrix again

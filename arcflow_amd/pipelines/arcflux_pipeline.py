@@ -389,7 +389,8 @@ class ArcFluxPipeline(_PipelineBase):
         FlowSDEScheduler instead, with noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator``
         after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's
         own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
-        transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
+        transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the
+        adapter weights of ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s."""
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)

@@ -196,7 +196,8 @@ class ArcQwenImagePipeline(_PipelineBase):
         (Qwen-Image has no guidance embedding).  ``sampler='FlowSDE'`` takes the stochastic steps of FlowSDEScheduler instead, with
         noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator`` after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a
         teacher engine is built once from the kept base weights, which holds a SECOND copy of the transformer on the GPU
-        (Qwen-Image: about 41 GB in bf16) next to the student.  Decoding is ``__call__``'s."""
+        (Qwen-Image: about 41 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the adapter weights of
+        ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s."""
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:

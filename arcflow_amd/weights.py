@@ -308,3 +308,55 @@ def check_state_shapes(shapes: Dict[str, tuple], expected: Dict[str, tuple]):
     wrong = sorted((k, tuple(shapes[k]), tuple(expected[k])) for k in expected if k in shapes and tuple(shapes[k]) != tuple(expected[k]))
     extra = sorted(k for k in shapes if k not in expected)
     return missing, wrong, extra
+
+
+# ------------------------------------------------------------------------------------------------
+# Where every diffusers linear lives in the packed set.  pack_flux / pack_qwen only concatenate along the output dimension, so each
+# module is a contiguous row slice of one packed matrix: what a LoRA on that module has to be folded into (afx_lora_fold,
+# arcflow_amd/pipelines/arcflow_loader.py).  Checked against the pack functions in tests/test_lora_adapters_cpu.py.
+def packed_row_slices(family: str, cfg: Dict, student: bool = False, K: int = 16, L: int = 4) -> Dict[str, tuple]:
+    """-> {diffusers module name: (packed weight name, first row, rows, in_features)} for every linear ``pack_flux`` / ``pack_qwen``
+    consume; family, cfg, student, K, L as in ``expected_transformer_keys`` (the same shapes)."""
+    shapes = expected_transformer_keys(family, cfg, student, K, L)
+    m: Dict[str, tuple] = {}
+
+    def put(packed, names):
+        r0 = 0
+        for n in names:
+            o, i = shapes[n + '.weight']
+            m[n] = (packed + '.weight', r0, o, i)
+            r0 += o
+    mods = []
+    if family == 'flux':
+        put('x_in', ['x_embedder'])
+        put('ctx_in', ['context_embedder'])
+        for tag, nm in (('t', 'timestep_embedder'), ('p', 'text_embedder')) + ((('g', 'guidance_embedder'),) if cfg.get('guidance_embeds', True) else ()):
+            put(f'temb.{tag}.l1', [f'time_text_embed.{nm}.linear_1'])
+            put(f'temb.{tag}.l2', [f'time_text_embed.{nm}.linear_2'])
+        n_double, ffs, mod_names = cfg.get('num_layers', 19), ('ff', 'ff_context'), ('norm1.linear', 'norm1_context.linear')
+    elif family == 'qwen':
+        put('x_in', ['img_in'])
+        put('ctx_in', ['txt_in'])
+        put('temb.t.l1', ['time_text_embed.timestep_embedder.linear_1'])
+        put('temb.t.l2', ['time_text_embed.timestep_embedder.linear_2'])
+        n_double, ffs, mod_names = cfg.get('num_layers', 60), ('img_mlp', 'txt_mlp'), ('img_mod.1', 'txt_mod.1')
+    else:
+        raise ValueError(family)
+    for i in range(n_double):
+        s, d = f'transformer_blocks.{i}.', f'd{i}.'
+        mods += [s + nm for nm in mod_names]
+        for stream, (k, v, q, o), ff in (('img', ('attn.to_k', 'attn.to_v', 'attn.to_q', 'attn.to_out.0'), ffs[0]),
+                                         ('txt', ('attn.add_k_proj', 'attn.add_v_proj', 'attn.add_q_proj', 'attn.to_add_out'), ffs[1])):
+            put(d + stream + '_qkv', [s + k, s + v, s + q])
+            put(d + stream + '_out', [s + o])
+            put(d + stream + '_mlp1', [s + ff + '.net.0.proj'])
+            put(d + stream + '_mlp2', [s + ff + '.net.2'])
+    if family == 'flux':
+        for i in range(cfg.get('num_single_layers', 38)):
+            s, d = f'single_transformer_blocks.{i}.', f's{i}.'
+            mods.append(s + 'norm.linear')
+            put(d + 'fused', [s + 'attn.to_k', s + 'attn.to_v', s + 'attn.to_q', s + 'proj_mlp'])
+            put(d + 'out', [s + 'proj_out'])
+    put('mod', mods + ['norm_out.linear'])
+    put('head', ['proj_out_means', 'proj_out_logweights', 'proj_out_loggamma'] if student else ['proj_out'])
+    return m

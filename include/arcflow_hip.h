@@ -590,6 +590,24 @@ int afx_norm_modulate_mx8(const void* x, int64_t ldx, void* q8, int64_t ldq, voi
                           int32_t D, const float* scale, const float* shift, const float* scale_txt, const float* shift_txt,
                           int64_t ldmod, int32_t S, int32_t n_txt, int32_t* fused, void* stream);
 
+/* Fold J <= AFX_LORA_MAX_ADAPTERS weighted low-rank adapters into one linear (style LoRAs next to the ArcFlow adapter: what peft's
+ * side branches y += s (alpha / r) B A x of every active adapter add up to, lakonlab/models/architecture/arcflow/arcflux.py:147-154 with
+ * `pipe.set_adapters([...])` of inference_flux.py:9):
+ *   dst[o, i] = bf16_rne( float(base[o, i]) + sum_j scales[j] * ( sum_r B[j][o, r] * A[j][r, i] ) )
+ * base, dst  bf16 row slices [O, I] of packed weight matrices with leading dimensions ld_base / ld_dst (elements), so a slice may start
+ *            at any row of a taller matrix; 16-byte aligned, leading dimensions multiples of 8; the two ranges must not overlap.
+ * A, B, ranks, scales  HOST arrays of J entries: A[j] [ranks[j], I] bf16 (16-byte aligned), B[j] [O, ranks[j]] bf16, any rank >= 1 (the
+ *            kernel zero-fills the last MFMA K-step itself), scales[j] fp32.  They are read before the call returns.
+ * Arithmetic: bf16 MFMAs with fp32 accumulation per adapter; scales[j] multiplies adapter j's fp32 sum (never a bf16 operand); one
+ * rounding, at the store.  One work-group owns each 64 x 64 tile of dst and walks the whole rank of every adapter in order: no split
+ * over the rank, no atomics, no workspace, bit-reproducible.  J == 0 copies base into dst.
+ * AFX_E_INVALID (nothing is launched): a null pointer, J > 8, a rank < 1, O or I not a positive multiple of 64, a leading dimension
+ * < I, dst overlapping base, or an alignment above not met.
+ * Traffic: 4 B per element of the slice + the A / B panels out of L2; 2 sum(ranks) flop per element: HBM-bound. */
+#define AFX_LORA_MAX_ADAPTERS 8
+int afx_lora_fold(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
+                  const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Time ``afx_lora_fold`` (the device fold behind ``load_lora_weights`` / ``set_adapters``) on synthetic weights -- no snapshot needed.
+
+    python tools/lora_fold_bench.py [--double 19 --single 38] [--reps 3] [--iters 20] [--skip-parent]
+
+Prints
+  * per FLUX matrix shape: the kernel's time (device events around --iters launches, after a warm-up) and GB/s over the 4 * O * I bytes it
+    has to move (2 B read + 2 B written per element; the A / B panels are not counted), with one r = 256 and one r = 16 adapter;
+  * the whole-model time of ONE weight change with an ArcFlow-sized adapter (r = 256) plus one style adapter (r = 16) on every attention
+    and MLP linear of the FLUX trunk, every linear with its own base and live buffers (no reuse: a re-used 18 MB matrix would sit in the
+    Infinity Cache);
+  * beside it, interleaved on the same box, the path a scale change of the ArcFlow adapter alone takes without style LoRAs:
+    ``weights.merge_lora`` + ``MMDiTEngine.load_state_dict``.  Here its state dict is already device-resident, so the 24 GB host-to-device
+    upload the pipelines pay on that path (their base state dict lives on the host) is NOT in the number: it is a lower bound.
+One JSON line at the end.  Nothing is asserted; there is no fallback without a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+D = 3072
+SHAPES = [('attn to_q/k/v/out', D, D), ('mlp up (ff.net.0 / proj_mlp)', 4 * D, D), ('mlp down (ff.net.2)', D, 4 * D),
+          ('single proj_out', D, 5 * D), ('norm1.linear', 6 * D, D), ('norm.linear', 3 * D, D)]
+RANKS = (256, 16)
+
+
+def trunk_linears(n_double, n_single):
+    """(module, O, I) of every attention / MLP linear of the FLUX trunk: what the released ArcFlow adapter adapts."""
+    out = []
+    for i in range(n_double):
+        p = f'transformer_blocks.{i}.'
+        out += [(p + 'attn.' + n, D, D) for n in ('to_q', 'to_k', 'to_v', 'add_q_proj', 'add_k_proj', 'add_v_proj', 'to_out.0', 'to_add_out')]
+        for ff in ('ff', 'ff_context'):
+            out += [(p + ff + '.net.0.proj', 4 * D, D), (p + ff + '.net.2', D, 4 * D)]
+    for i in range(n_single):
+        p = f'single_transformer_blocks.{i}.'
+        out += [(p + 'attn.' + n, D, D) for n in ('to_q', 'to_k', 'to_v')] + [(p + 'proj_mlp', 4 * D, D), (p + 'proj_out', D, 5 * D)]
+    return out
+
+
+def main(argv=None):
+    import torch
+    from arcflow_amd import ops
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--double', type=int, default=19)
+    ap.add_argument('--single', type=int, default=38)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--skip-parent', action='store_true')
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit('lora_fold_bench needs the GPU: a CPU run measures nothing')
+    dev = 'cuda'
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*shape, std=0.02):
+        return (torch.randn(*shape, generator=g, device=dev) * std).to(torch.bfloat16)
+
+    def adapters(O, I):
+        return [rnd(r, I, std=0.05) for r in RANKS], [rnd(O, r, std=0.05) for r in RANKS]
+    res = dict(device=torch.cuda.get_device_name(0), ranks=list(RANKS), shapes=[], double=a.double, single=a.single)
+    # ---- per shape
+    for name, O, I in SHAPES:
+        base, dst = rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device=dev)
+        A, B = adapters(O, I)
+        for _ in range(3):
+            ops.lora_fold(base, dst, A, B, (1.0, 0.8))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            ops.lora_fold(base, dst, A, B, (1.0, 0.8))
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / a.iters
+        gbs = 4.0 * O * I / (ms * 1e-3) / 1e9
+        res['shapes'].append(dict(name=name, O=O, I=I, ms=ms, gb_per_s=gbs))
+        print(f'{name:32s} [{O:6d}, {I:6d}]  {ms * 1e3:9.1f} us  {gbs:8.1f} GB/s over 4 O I bytes (matrix re-used: {4 * O * I / 2 ** 20:.0f} MiB)')
+        del base, dst
+    # ---- whole model: one weight change, r = 256 + r = 16 on every trunk linear
+    lin = trunk_linears(a.double, a.single)
+    bufs = [(rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device=dev), *adapters(O, I)) for _, O, I in lin]
+    total_bytes = sum(4.0 * O * I for _, O, I in lin)
+
+    def new_path(s):
+        t0 = time.perf_counter()
+        for base, dst, A, B in bufs:
+            ops.lora_fold(base, dst, A, B, (s, 0.8))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    new_path(1.0)                                              # warm-up
+    sd = lora = eng = None
+    if not a.skip_parent:
+        from arcflow_amd import MMDiTEngine
+        from arcflow_amd.weights import expected_transformer_keys, merge_lora
+        cfg = dict(num_layers=a.double, num_single_layers=a.single)
+        sd = {k: rnd(*s) for k, s in expected_transformer_keys('flux', cfg, True).items()}
+        lora = {}
+        for m, O, I in lin:
+            lora[m + '.lora_A.weight'], lora[m + '.lora_B.weight'] = rnd(RANKS[0], I, std=0.05), rnd(O, RANKS[0], std=0.05)
+        eng = MMDiTEngine('flux', a.double, a.single)
+
+        def parent_path(s):
+            t0 = time.perf_counter()
+            eng.load_state_dict(merge_lora(sd, lora, scale=s))
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        parent_path(1.0)                                       # warm-up
+    new_s, par_s = [], []
+    for k in range(a.reps):                                    # interleaved: other work shares the box
+        new_s.append(new_path(0.9 - 0.1 * k))
+        if not a.skip_parent:
+            par_s.append(parent_path(0.9 - 0.1 * k))
+    res.update(linears=len(lin), fold_bytes=total_bytes, fold_seconds=new_s, fold_gb_per_s=[total_bytes / t / 1e9 for t in new_s], parent_seconds=par_s)
+    print(f'whole model, {len(lin)} linears, r = 256 + r = 16, {total_bytes / 1e9:.1f} GB to move: ' + ', '.join(f'{t * 1e3:.1f} ms' for t in new_s)
+          + f'  ({min(total_bytes / t / 1e9 for t in new_s):.0f} .. {max(total_bytes / t / 1e9 for t in new_s):.0f} GB/s, host clock around a synchronise)')
+    if par_s:
+        print('merge_lora + load_state_dict, ArcFlow adapter alone, device-resident state dict (no upload): ' + ', '.join(f'{t * 1e3:.1f} ms' for t in par_s))
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
