@@ -13,7 +13,8 @@ hand-written kernels: grouped MFMA GEMMs with fused bias / residual epilogues (q
 into one weight), the EXT instantiations of the flash-attention kernel (relative-position bias table for T5, causal mask
 for CLIP / Qwen, grouped KV heads for Qwen, head dim 64 / 128), and the row kernels of afx_text.hip.
 Parity: tests/test_text_encoders.py runs the real transformers modules (random-init small configs) on the CPU in fp32 as
-the oracle -- the third-party dependency itself, not a restatement.
+the oracle -- the third-party dependency itself, not a restatement.  The attention kernel itself is held per element against
+fp64 in tests/test_hip_attention_ext_fp64.py (short, ragged and batched lengths, strided operands, the encoders' head counts).
 """
 from __future__ import annotations
 

@@ -20,7 +20,8 @@ def _bf16_weights(m):
     return m
 
 
-# (H, Hkv, head_dim, causal, relative-position bias): toy configurations, then the production encoders
+# (H, Hkv, head_dim, causal, relative-position bias): toy configurations, then the production encoders.  One whole-tensor rel-L2 per configuration, B = 1,
+# packed rows: a smoke check.  The kernel is held per element against fp64 in test_hip_attention_ext_fp64.py.
 _ATTN_TOY = [(4, 4, 64, False, True), (3, 3, 64, True, False), (8, 2, 128, True, False), (2, 2, 128, False, False)]
 _T5_XXL, _CLIP_L, _QWEN25_LM = (64, 64, 64, False, True), (12, 12, 64, True, False), (28, 4, 128, True, False)
 
