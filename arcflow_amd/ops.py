@@ -21,9 +21,15 @@ def _s():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _gpu(*tensors, name: str = '') -> None:
+    """Every tensor given (None entries are skipped) must live on the GPU: the kernels take device pointers."""
+    for t in tensors:
+        if t is not None and t.device.type != 'cuda':
+            raise _lib.ArcflowHipError((name and name + ': ') + 'arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+
+
 def _cuda(t: torch.Tensor, dtype) -> torch.Tensor:
-    if t.device.type != 'cuda':
-        raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(t)
     return t.to(dtype).contiguous()
 
 
@@ -31,8 +37,7 @@ def _cuda(t: torch.Tensor, dtype) -> torch.Tensor:
 # transposed view, a wrong dtype or a short accumulator would give wrong numbers (or touch memory past the tensor) without an error.
 def _mat(t: torch.Tensor, dtype, name: str, shape=None) -> torch.Tensor:
     """A [rows, cols] operand read row by row: 2-D, on the GPU, ``dtype``, unit inner stride (any row stride)."""
-    if t.device.type != 'cuda':
-        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(t, name=name)
     if t.dim() != 2 or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError(f'{name}: need a 2-D {dtype} tensor with unit inner stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}')
     if shape is not None and tuple(t.shape) != tuple(shape):
@@ -42,8 +47,7 @@ def _mat(t: torch.Tensor, dtype, name: str, shape=None) -> torch.Tensor:
 
 def _acc(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     """An fp32 accumulator written through a flat index: contiguous, exactly ``shape``."""
-    if t.device.type != 'cuda':
-        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(t, name=name)
     if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name}: need a contiguous float32 accumulator of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype} '
                          f'strides {t.stride()}')
@@ -53,8 +57,7 @@ def _acc(t: torch.Tensor, shape, name: str) -> torch.Tensor:
 def _rows_f32(v: torch.Tensor, R: int, C: int, rows_per_batch: int, name: str) -> torch.Tensor:
     """A per-batch fp32 row vector (gate / scale) [C] or [Bg, C] -> [Bg, C] with unit inner stride.  A row-strided fp32 view is passed
     as it is (its rows 16-byte aligned: the kernels read it in float4); several rows need rows_per_batch with R == rows_per_batch * Bg."""
-    if v.device.type != 'cuda':
-        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(v, name=name)
     if v.dim() == 1:
         v = v[None]
     if v.dim() != 2 or v.shape[1] != C:
@@ -193,8 +196,7 @@ def _joint_vectors(vecs, B: int, D: int, name: str) -> int:
     same row stride (the kernels take one ldmod).  Returns that stride."""
     ld = None
     for v, n in vecs:
-        if v.device.type != 'cuda':
-            raise _lib.ArcflowHipError(f'{name} {n}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+        _gpu(v, name=f'{name} {n}')
         v2 = v[None] if v.dim() == 1 else v
         if v2.dim() != 2 or tuple(v2.shape) != (B, D) or v2.dtype != torch.float32 or v2.stride(1) != 1 or v2.data_ptr() % 16:
             raise ValueError(f'{name} {n}: need a [{B}, {D}] float32 tensor with unit inner stride and 16-byte aligned rows, got '
@@ -456,8 +458,7 @@ def cfg_combine(pos, neg, scale: float):
 
 def _packed(t: torch.Tensor, dtype, shape, name: str) -> torch.Tensor:
     """An operand of the teacher-sampler kernels: on the GPU, ``dtype``, contiguous, exactly ``shape`` -- passed as it is (no copy)."""
-    if t.device.type != 'cuda':
-        raise _lib.ArcflowHipError(f'{name}: arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(t, name=name)
     if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name}: need a contiguous {dtype} tensor of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype} strides {t.stride()}')
     return t
@@ -476,8 +477,7 @@ def cfg_ortho_coef(pos, neg, scale: float, out: Optional[torch.Tensor] = None, w
     the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25).  pos, neg [B, ...] bf16 teacher velocities with
     numel / B a multiple of 64.  Bit-reproducible (fixed partition, exact fp64 products, ordered sum).  out / ws: reuse buffers."""
     lib = _lib.load()
-    if pos.device.type != 'cuda' or neg.device.type != 'cuda':
-        raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(pos, neg)
     B = pos.shape[0]
     n = pos[0].numel() if B else 0
     pos = _packed(pos, torch.bfloat16, pos.shape, 'pos')
@@ -505,9 +505,7 @@ def sample_score(a, b, transform: bool = False, out: Optional[torch.Tensor] = No
     (fp32) of both operands, the [0, 1] image range.  Elements are widened to fp64; bit-reproducible (fixed partition, ordered sum).
     Nothing is copied or cast: a wrong dtype or layout raises.  out / ws: reuse buffers (ops.sample_score_ws)."""
     lib = _lib.load()
-    for t in (a, b, out, ws):
-        if t is not None and t.device.type != 'cuda':
-            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(a, b, out, ws)
     if a.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
     B = a.shape[0]
@@ -531,9 +529,7 @@ def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: O
     x [B, ...] fp32; pos, neg (None: no guidance) bf16 of the same shape; sigma, sigma_to, coef (None: not orthogonal) [B] fp32.
     out may be x (in place).  numel / B must be a multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
     lib = _lib.load()
-    for t in (x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
-        if t is not None and t.device.type != 'cuda':
-            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(x, pos, neg, sigma, sigma_to, coef, out, out_bf16)
     B = x.shape[0]
     n = x[0].numel() if B else 0
     x = _packed(x, torch.float32, x.shape, 'x')
@@ -558,9 +554,7 @@ def teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, scale: flo
     m, c_noise (FlowSDEScheduler.coefficients), coef (None: not orthogonal) [B] fp32.  out may be x (in place).  numel / B must be a
     multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
     lib = _lib.load()
-    for t in (x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, out, out_bf16):
-        if t is not None and t.device.type != 'cuda':
-            raise _lib.ArcflowHipError('arcflow_amd.ops works on GPU tensors only (no CPU fallback)')
+    _gpu(x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, out, out_bf16)
     B = x.shape[0]
     n = x[0].numel() if B else 0
     x = _packed(x, torch.float32, x.shape, 'x')

@@ -19,6 +19,8 @@ from typing import Dict, List, Optional
 
 import torch
 
+from .._lib import AFX_LORA_MAX_ADAPTERS as MAX_FOLD_ADAPTERS       # adapters one afx_lora_fold launch sums
+
 LOCAL_CLASS_MAPPING = {
     'ArcFluxTransformer2DModel': 'flux',
     'ArcQwenImageTransformer2DModel': 'qwen',
@@ -54,7 +56,6 @@ def read_adapter(path: str, subfolder: Optional[str] = None, variant: Optional[s
 
 LORA_WEIGHT_NAME = 'pytorch_lora_weights.safetensors'
 _LORA_KEY = re.compile(r'^(?P<mod>.+)\.(?P<kind>lora_A|lora_B|lora_down|lora_up)(?:\.(?P<infix>[^.]+))?\.weight$')
-MAX_FOLD_ADAPTERS = 8          # AFX_LORA_MAX_ADAPTERS: adapters one afx_lora_fold launch sums
 
 
 def read_lora_file(path: str, weight_name: Optional[str] = None, subfolder: Optional[str] = None) -> Dict[str, torch.Tensor]:

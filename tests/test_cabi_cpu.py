@@ -19,14 +19,132 @@ def lib():
     return _lib.load()
 
 
-def test_header_symbols_exported(lib):
+SYNTHETIC_HEADER = """
+/* block comment with a call-like token afx_fake(int x); and a
+ * second line: int afx_fake2(void); */
+#ifndef SYN_H_
+#define SYN_H_
+#include <stdint.h>
+extern "C" {
+#define AFX_OK 0
+#define AFX_E_BAD (-7)   /* trailing comment afx_fake( */
+#define AFX_WIDE 64      // line comment afx_fake(
+typedef struct afx_ctx afx_ctx;
+typedef struct afx_pair {
+  int32_t first;   /* a field comment */
+  int64_t second;
+  const float* third;
+} afx_pair;
+const char* afx_name(void);
+// int afx_fake3(int a);
+int afx_open(const afx_pair* desc, afx_ctx** out, const char* name);
+int64_t afx_bytes(const afx_ctx* ctx, int32_t rows,
+                  int64_t ld,   /* stride */
+                  uint32_t seed, float p, double q, int n);
+int afx_fold(const void* const* A, const float* const scales, const int32_t* ranks, const int64_t n, void* stream);
+}
+#endif
+"""
+
+
+def test_header_reader_on_synthetic_text():
+    """The reader of arcflow_amd/_lib.py on a header written here: comments that look like calls, a prototype over several lines, (void),
+    const char* as result and parameter, const-qualified pointers and scalars, a negative macro in parentheses, a struct."""
+    from arcflow_amd import _lib
+    vp, cp, i32, i64, u32, f32, f64 = C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double
+    assert _lib.parse_prototypes(SYNTHETIC_HEADER) == {
+        'afx_name': (cp, []),
+        'afx_open': (i32, [vp, vp, cp]),
+        'afx_bytes': (i64, [vp, i32, i64, u32, f32, f64, i32]),
+        'afx_fold': (i32, [vp, vp, vp, i64, vp]),
+    }
+    assert list(_lib.parse_prototypes(SYNTHETIC_HEADER)) == ['afx_name', 'afx_open', 'afx_bytes', 'afx_fold']
+    assert _lib.parse_struct(SYNTHETIC_HEADER, 'afx_pair') == [('first', i32), ('second', i64), ('third', vp)]
+    assert _lib.parse_constants(SYNTHETIC_HEADER) == {'AFX_OK': 0, 'AFX_E_BAD': -7, 'AFX_WIDE': 64}
+    # an unknown scalar type names the function it stands in
+    for bad in ('int afx_odd(size_t n);', 'int afx_odd(unsigned int n);', 'size_t afx_odd(void);', 'int afx_ok(int a);\nint afx_odd(long n);'):
+        with pytest.raises(ValueError, match='afx_o'):
+            _lib.parse_prototypes(SYNTHETIC_HEADER + bad)
+    # a declaration the pattern cannot take is caught by the count of "afx_*(" tokens, not skipped
+    for bad in ('int afx_cb(void (*fn)(int), void* arg);', 'static inline int afx_inl(int a);', 'int afx_nosemi(int a)',
+                '#define AFX_CALL(x) afx_name()'):
+        with pytest.raises(ValueError, match='tokens'):
+            _lib.parse_prototypes(SYNTHETIC_HEADER + bad)
+    with pytest.raises(ValueError):
+        _lib.parse_struct(SYNTHETIC_HEADER, 'afx_missing')
+    with pytest.raises(ValueError, match='afx_pair'):
+        _lib.parse_struct(SYNTHETIC_HEADER.replace('int64_t second', 'long second'), 'afx_pair')
+    for bad in ('#define AFX_F 1.5', '#define AFX_M(x) 3', '#define AFX_S "s"', '#define AFX_OK 1'):
+        with pytest.raises(ValueError):
+            _lib.parse_constants(SYNTHETIC_HEADER + bad + '\n')
+
+
+def _header_names():
+    from arcflow_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'arcflow_hip.h')).read()
     names = set(re.findall(r'^(?:int|int64_t|const char\*)\s+(afx_[a-z0-9_]+)\s*\(', hdr, flags=re.M))
+    return hdr, names, _lib
+
+
+def test_header_reader_on_real_header():
+    hdr, names, _lib = _header_names()
+    protos = _lib.parse_prototypes(hdr)
+    assert protos == _lib.PROTOTYPES and set(protos) == names and _lib.EXPORTS == sorted(names)
+    assert len(protos) == len(re.findall(r'afx_\w+\s*\(', re.sub(r'/\*.*?\*/|//[^\n]*', ' ', hdr, flags=re.S))) >= 110
+    for name, (restype, argtypes) in protos.items():
+        assert restype in (C.c_int32, C.c_int64, C.c_char_p), name
+        want = C.c_int64 if name.endswith('_ws_bytes') or name == 'afx_workspace_bytes' else \
+            C.c_char_p if name in ('afx_last_error', 'afx_version') else C.c_int32
+        assert restype is want, name
+        assert all(t in (C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double) for t in argtypes), name
+    assert protos['afx_linear_tn_ws_bytes'][0] is C.c_int64 and sum(n.endswith('_ws_bytes') for n in protos) >= 7
+    assert protos['afx_bind_weight'] == (C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p])
+    assert protos['afx_lora_dropout_bf16'][1][7:9] == [C.c_float, C.c_uint32]
+    assert _lib.ModelDesc._fields_ == [(n, C.c_int32) for n in (
+        'family', 'num_double', 'num_single', 'heads', 'head_dim', 'in_channels', 'joint_dim', 'pooled_dim', 'guidance_embeds',
+        'num_gaussians', 'logweights_channels', 'head_mode')]
+    assert C.sizeof(_lib.ModelDesc) == 48
+    assert (_lib.AFX_DT_BF16, _lib.AFX_DT_F32, _lib.AFX_DT_FP8, _lib.AFX_BLOCK_DOUBLE, _lib.AFX_BLOCK_SINGLE) == (1, 2, 3, 0, 1)
+    assert _lib.AFX_QKV_PATHS == {'auto': 0, 'vt_proj': 1, 'qk_epi': 2, 'kv_prep': 3}
+    assert (_lib.AFX_OK, _lib.AFX_E_INVALID, _lib.AFX_E_MISSING, _lib.AFX_E_WORKSPACE, _lib.AFX_E_HIP, _lib.AFX_E_UNSUPPORTED) == (0, -1, -2, -3, -4, -5)
+    from arcflow_amd.pipelines import arcflow_loader
+    assert arcflow_loader.MAX_FOLD_ADAPTERS == _lib.AFX_LORA_MAX_ADAPTERS == 8
+
+
+def test_loaded_functions_carry_the_header_types(lib):
+    _, _, _lib = _header_names()
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_missing_header_raises_with_its_path(tmp_path):
+    """The binding cannot be derived without the header: like a missing library, that is an ArcflowHipError naming the path."""
+    _, _, _lib = _header_names()
+    gone = str(tmp_path / 'include' / 'arcflow_hip.h')
+    with pytest.raises(_lib.ArcflowHipError, match=re.escape(gone)):
+        _lib.read_header(gone)
+    assert _lib.read_header() == open(os.path.join(ROOT, 'include', 'arcflow_hip.h')).read()
+
+
+def test_header_symbols_exported(lib):
+    hdr, names, _lib = _header_names()
     assert len(names) >= 17
     for n in names:
         assert hasattr(lib, n), f'{n} declared in arcflow_hip.h but not exported'
-    from arcflow_amd import _lib
-    assert set(_lib.EXPORTS) == names
+    # the other direction, from the built library: its unmangled afx_* functions are the header's, plus the undeclared debug hooks
+    import shutil
+    from arcflow_amd import build
+    rocm_bin = os.path.dirname(os.path.realpath(build._hipcc()))
+    cands = [os.path.join(rocm_bin, '..', 'llvm', 'bin', 'llvm-nm'), os.path.join(rocm_bin, '..', 'lib', 'llvm', 'bin', 'llvm-nm'),
+             shutil.which('llvm-nm'), shutil.which('nm')]
+    nm = next((c for c in cands if c and os.path.exists(c)), None)
+    if nm is None:
+        pytest.skip('no llvm-nm / nm found to list the dynamic symbols of the built library')
+    import subprocess
+    out = subprocess.run([nm, '-D', '--defined-only', lib._name], capture_output=True, text=True, check=True).stdout
+    syms = {f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] in 'TtWw' and f[2].startswith('afx_')}
+    assert {s for s in syms if not s.startswith('afx_debug_')} == names, (sorted(syms - names), sorted(names - syms))
 
 
 def test_argument_validation_no_gpu(lib):
