@@ -573,6 +573,38 @@ def teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, scale: flo
     return out, out_bf16
 
 
+def edit_blend(x, x0, noise, mask, sigma_to, out: Optional[torch.Tensor] = None, out_bf16=None, max_blocks: int = 0):
+    """The blend of image editing in one launch (afx_edit_blend): with known = (1 - sigma_to[b]) x0 + sigma_to[b] noise, the source
+    latents diffused to sigma_to, mask x + (1 - mask) known -> (fp32 latents, their bf16 rounding).
+    x0, noise (None: no noise term, nothing read) [B, N, 64] fp32 packed tokens; mask [B, N, 4] fp32 in [0, 1], one value per latent
+    pixel of the 2 x 2 patch (None: everything is known, x is ignored and may be None: the image-to-image start); x [B, N, 64] fp32
+    with a mask; sigma_to [B] fp32.  out may be x (in place).  out_bf16=False: no bf16 copy is written, (out, None) is returned.
+    m = 1 returns x, m = 0 known, sigma_to = 1 noise and sigma_to = 0 x0 bit for bit.  Nothing is copied or cast: a wrong dtype, device
+    or layout raises."""
+    lib = _lib.load()
+    _gpu(x, x0, noise, mask, sigma_to, out, None if out_bf16 is False else out_bf16)
+    if x0.dim() != 3:
+        raise ValueError(f'x0: need packed tokens [B, N, 64], got {tuple(x0.shape)}')
+    B, N, ch = x0.shape
+    x0 = _packed(x0, torch.float32, x0.shape, 'x0')
+    if mask is None:
+        x = None
+    else:
+        if x is None:
+            raise ValueError('x: required with a mask')
+        x = _packed(x, torch.float32, x0.shape, 'x')
+        mask = _packed(mask, torch.float32, (B, N, 4), 'mask')
+    noise = None if noise is None else _packed(noise, torch.float32, x0.shape, 'noise')
+    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
+    out = torch.empty_like(x0) if out is None else _packed(out, torch.float32, x0.shape, 'out')
+    if out_bf16 is False:
+        out_bf16 = None
+    else:
+        out_bf16 = torch.empty(x0.shape, dtype=torch.bfloat16, device=x0.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x0.shape, 'out_bf16')
+    _lib.check(lib.afx_edit_blend(_p(x), _p(x0), _p(noise), _p(mask), _p(sigma_to), _p(out), _p(out_bf16), B, N, ch, max_blocks, _s()))
+    return out, out_bf16
+
+
 def head_grad(d_means, d_logw, d_logg, logw_out, ldy: int):
     lib = _lib.load()
     B, N, K, ch = d_means.shape

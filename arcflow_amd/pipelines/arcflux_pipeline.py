@@ -7,6 +7,10 @@ What runs where: the denoising loop (arcflux_pipeline.py:457-510) is two C-ABI c
 Prompt encoding and VAE decode are the rows SURVEY 8f marks "next": pass ``prompt_embeds`` /
 ``pooled_prompt_embeds`` (or attach HF text encoders) and use ``output_type='latent'`` unless a decoder
 module is attached as ``pipe.vae``.
+
+Beyond the reference: ``__call__`` of both pipelines takes the keyword-only ``image`` / ``image_latents``, ``strength``, ``mask_image`` and
+``composite`` (image-to-image and inpainting); one more C-ABI call, ``afx_edit_blend``, forms the noised start and, with a
+mask, follows every step.  Without them the call is the text-to-image path unchanged.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import torch
 
 from .. import ops
 from ..engine import MMDiTEngine
-from ..schedule import FlowMatchEulerDiscreteScheduler, calculate_shift, retrieve_raw_timesteps
+from ..schedule import FlowMatchEulerDiscreteScheduler, calculate_shift, edit_raw_timesteps, mask_to_tokens, retrieve_raw_timesteps
 from .arcflow_loader import ArcFlowLoaderMixin
 
 POLICY_CLASSES = ('ArcFlow',)
@@ -114,8 +118,146 @@ class _PipelineBase(ArcFlowLoaderMixin):
         packed = noise.view(batch, 16, hp, 2, wp, 2).permute(0, 2, 4, 1, 3, 5).reshape(batch, hp * wp, 64)
         return packed.contiguous(), hp, wp
 
+    # image editing: image-to-image and inpainting ---------------------------------------------------------
+    @staticmethod
+    def _images01(image, name='image', channels=3) -> torch.Tensor:
+        """A torch [B, C, H, W] / [C, H, W], numpy [B, H, W, C] / [H, W, C], PIL image or list of PIL images in [0, 1] (PIL: 8 bit) ->
+        fp32 [B, C, H, W] in [0, 1].  With channels = 1 (a mask) the channel axis may be missing: [B, H, W] / [H, W]."""
+        import numpy as np
+
+        def pil(im):
+            return torch.from_numpy(np.asarray(im.convert('RGB' if channels == 3 else 'L'), dtype=np.float32) / 255.0)
+        if isinstance(image, (list, tuple)):
+            t = torch.stack([pil(im) for im in image])
+            t = t[:, None] if channels == 1 else t.permute(0, 3, 1, 2)
+        elif isinstance(image, torch.Tensor):
+            t = image
+            if channels == 1:
+                t = t[None, None] if t.dim() == 2 else (t[:, None] if t.dim() == 3 and t.shape[0] != 1 else t)
+            if t.dim() == 3:
+                t = t[None]
+        elif isinstance(image, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(image))
+            if channels == 1:
+                t = t[None, None] if t.dim() == 2 else (t[:, None] if t.dim() == 3 else t.permute(0, 3, 1, 2))
+            else:
+                t = (t[None] if t.dim() == 3 else t).permute(0, 3, 1, 2)
+        elif hasattr(image, 'convert'):
+            t = pil(image)
+            t = t[None, None] if channels == 1 else t.permute(2, 0, 1)[None]
+        else:
+            raise ValueError(f'`{name}`: a torch tensor, a numpy array, a PIL image or a list of PIL images, got {type(image).__name__}')
+        if t.dim() != 4 or t.shape[1] != channels:
+            raise ValueError(f'`{name}`: cannot read {tuple(t.shape)} as [B, {channels}, H, W]')
+        return t.to(torch.float32)
+
+    def _edit_inputs(self, image, image_latents, mask_image, strength, height, width):
+        """Host-side half of the edit arguments: -> (edit, height, width), ``edit`` None on the text-to-image path.  Normalises ``image`` and
+        ``mask_image`` to fp32 [B, C, H, W], takes ``height`` / ``width`` from them when not given; nothing is resized."""
+        if image is None and image_latents is None:
+            if mask_image is not None:
+                raise ValueError('`mask_image` needs `image` or `image_latents`')
+            return None, height, width
+        if image is not None and image_latents is not None:
+            raise ValueError('Cannot forward both `image` and `image_latents`.')
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f'`strength` must be in (0, 1], got {strength}')
+        img = None if image is None else self._images01(image)
+        mask = None if mask_image is None else self._images01(mask_image, 'mask_image', 1)
+        for t in (img, mask):
+            if t is not None:
+                height, width = height or t.shape[2], width or t.shape[3]
+        height = height or self.default_sample_size * self.vae_scale_factor
+        width = width or self.default_sample_size * self.vae_scale_factor
+        if height % 16 or width % 16:
+            raise ValueError(f'`height` and `width` have to be divisible by 16, got {height} x {width} (an edit resizes nothing)')
+        for t, name in ((img, 'image'), (mask, 'mask_image')):
+            if t is not None and tuple(t.shape[2:]) != (height, width):
+                raise ValueError(f'`{name}` is {t.shape[2]} x {t.shape[3]}, the call is {height} x {width}: an edit resizes nothing')
+        if image_latents is not None and (image_latents.dim() != 3 or tuple(image_latents.shape[1:]) != ((height // 16) * (width // 16), 64)):
+            raise ValueError(f'`image_latents`: need packed [B, {(height // 16) * (width // 16)}, 64] for {height} x {width}, '
+                             f'got {tuple(image_latents.shape)}')
+        return dict(image=img, image_latents=image_latents, mask=mask, strength=float(strength)), height, width
+
+    def _edit_prepare(self, edit, B, hp, wp):
+        """Device-side half: batch checks, the encode of ``image`` (posterior mode, packed), the mask per latent pixel."""
+        device = self._device
+        for name in ('image', 'image_latents', 'mask'):
+            t = edit[name]
+            if t is not None and t.shape[0] not in (1, B):
+                raise ValueError(f'`{"mask_image" if name == "mask" else name}` has batch {t.shape[0]}, the call has {B} (a batch of 1 broadcasts)')
+        if edit['image'] is not None:
+            encoder = getattr(self.vae, 'encoder', None)
+            if encoder is None:
+                raise RuntimeError('`image=` needs a VAE encoder (pipe.vae.encoder: a snapshot with encoder.* weights); without one pass '
+                                   '`image_latents=`, the packed latents of the image')
+            x0 = encoder.encode_images01(edit['image'], sample=False, packed=True)
+        else:
+            x0 = edit['image_latents'].to(device, torch.float32)
+        edit['x0'] = x0.expand(B, -1, -1).contiguous()
+        if edit['mask'] is not None:
+            edit['mask_tokens'] = mask_to_tokens(edit['mask'].to(device), hp, wp).expand(B, -1, -1).contiguous()
+        return edit
+
+    def _composite(self, image, edit, composite):
+        """Paste the original pixels back outside the mask: m decoded + (1 - m) original, in the decoder's range [-1, 1] and dtype."""
+        if not composite or edit is None or edit['image'] is None or edit['mask'] is None:
+            return image
+        m = edit['mask'].to(image.device, torch.float32)
+        orig = (edit['image'].to(image.device) * 2 - 1).to(image.dtype).to(torch.float32)
+        return (m * image.to(torch.float32) + (1 - m) * orig).to(image.dtype)
+
+    def _denoise_edit(self, noise, edit, num_inference_steps, total_substeps, timestep_ratio, fwd, callback_on_step_end,
+                      callback_on_step_end_tensor_inputs, prompt_embeds, prepare=None):
+        """``_denoise`` from a noised image: ``num_inference_steps`` student steps over the raw time [strength, 0], started on
+        (1 - sigma) x0 + sigma noise; with a mask, after every step the unmasked latent pixels are put back on the source's own
+        trajectory at the sigma the step landed on, with the same noise every time (afx_edit_blend: blend + the next forward's bf16 copy)."""
+        device = self._device
+        x0, mask = edit['x0'], edit.get('mask_tokens')
+        B = x0.shape[0]
+        if tuple(noise.shape) != tuple(x0.shape):
+            raise ValueError(f'`latents` (the start noise) is {tuple(noise.shape)}, the image latents are {tuple(x0.shape)}')
+        noise = noise.contiguous()
+        raw, per_step, total = edit_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio, edit['strength'])
+        timesteps = self._retrieve_timesteps(raw, device, x0.shape[1])
+        assert len(timesteps) == total
+        self._num_timesteps = total
+        self.scheduler.set_begin_index(0)
+        ntt = self.scheduler.config.num_train_timesteps
+        ts_host = timesteps.float().cpu().tolist()
+        starts = [sum(per_step[:i]) for i in range(num_inference_steps)]
+        prepared = bool(prepare([ts_host[j] / 1000.0 for j in starts])) if prepare is not None and not self.interrupt else False
+        latents, lat16 = ops.edit_blend(None, x0, noise, None, torch.full((B,), ts_host[0] / ntt, device=device, dtype=torch.float32))
+        tid = 0
+        for i in range(num_inference_steps):
+            if self.interrupt:
+                continue
+            t_src = ts_host[tid]
+            sigma_src = t_src / ntt
+            self._current_timestep = t_src
+            out = fwd(lat16 if lat16 is not None else latents.to(torch.bfloat16), torch.full((B,), t_src / 1000.0, device=device),
+                      prompt_embeds, i if prepared else None)
+            tid += per_step[i]
+            sigma_end = (ts_host[tid] / ntt) if tid < len(ts_host) else 0.0
+            latents = ops.arcflow_step(latents, out.means, out.logweights, out.loggammas, sigma_src, sigma_src, sigma_end, eps=1e-4)
+            lat16 = None
+            if mask is not None:
+                latents, lat16 = ops.edit_blend(latents, x0, noise if sigma_end > 0.0 else None, mask,
+                                                torch.full((B,), sigma_end, device=device, dtype=torch.float32), out=latents, out_bf16=lat16)
+            if callback_on_step_end is not None:
+                local = dict(latents=latents, prompt_embeds=prompt_embeds)
+                cb = callback_on_step_end(self, i, torch.tensor(t_src, device=device),
+                                          {k: local[k] for k in callback_on_step_end_tensor_inputs})
+                latents, lat16 = cb.pop('latents', latents), None          # the callback may have changed them: the kernel's bf16 copy is dropped
+                prompt_embeds = cb.pop('prompt_embeds', prompt_embeds)
+        self._current_timestep = None
+        return latents
+
     def _denoise(self, latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
-                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare=None):
+                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare=None, edit=None):
+        if edit is not None:
+            return self._denoise_edit(latents, edit, num_inference_steps, total_substeps, timestep_ratio, fwd, callback_on_step_end,
+                                      callback_on_step_end_tensor_inputs, prompt_embeds, prepare)
         device = self._device
         raw, per_step, total = retrieve_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio)
         timesteps = self._retrieve_timesteps(raw, device, latents.shape[1])
@@ -317,7 +459,14 @@ class ArcFluxPipeline(_PipelineBase):
                  ip_adapter_image_embeds=None, output_type: Optional[str] = 'pil', return_dict: bool = True,
                  joint_attention_kwargs: Optional[Dict[str, Any]] = None,
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
-                 callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512):
+                 callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
+                 image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
+                 composite: bool = True):
+        """Text-to-image by default.  ``image`` (or its packed latents ``image_latents``) starts the sampler from the image noised to
+        ``strength`` in (0, 1] instead of from pure noise (image-to-image); ``mask_image`` (1 = repaint) keeps the unmasked region on the
+        image's own trajectory (inpainting) and, with ``composite``, pastes the original pixels back there after decoding.  ``height`` /
+        ``width`` default to the image's size; nothing is resized.  ``latents`` / ``generator`` give the start noise as before."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -339,6 +488,8 @@ class ArcFluxPipeline(_PipelineBase):
                                                    num_images_per_prompt, max_sequence_length)
         B = batch_size * num_images_per_prompt
         latents, hp, wp = self._prepare_latents(B, height, width, generator, latents)
+        if edit is not None:
+            edit = self._edit_prepare(edit, B, hp, wp)
         guidance = torch.full((B,), guidance_scale, device=device, dtype=torch.float32) \
             if self.transformer.guidance_embeds else None
 
@@ -348,11 +499,12 @@ class ArcFluxPipeline(_PipelineBase):
         def prepare(sigmas):
             return self.transformer.prepare_steps(sigmas, pooled, guidance, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
-                                callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare)
-        return self._finish(latents, hp, wp, output_type, return_dict)
+                                callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare, edit=edit)
+        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite)
 
-    def _finish(self, latents, hp, wp, output_type, return_dict):
-        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``."""
+    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True):
+        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``.  An inpainting call
+        (``edit`` with an image and a mask) gets the original pixels pasted back outside the mask unless ``composite`` is off."""
         if output_type == 'latent':
             image = latents
         else:
@@ -365,7 +517,7 @@ class ArcFluxPipeline(_PipelineBase):
                 lat = self._unpack(latents, hp, wp)
                 lat = lat / self.vae.config.scaling_factor + self.vae.config.shift_factor
                 image = self.vae.decode(lat.to(next(self.vae.parameters()).dtype), return_dict=False)[0]
-            image = self._postprocess(image, output_type)
+            image = self._postprocess(self._composite(image, edit, composite), output_type)
         self.maybe_free_model_hooks()
         if not return_dict:
             return (image,)

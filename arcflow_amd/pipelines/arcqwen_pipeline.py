@@ -117,7 +117,12 @@ class ArcQwenImagePipeline(_PipelineBase):
                  prompt_embeds_mask: Optional[torch.Tensor] = None, output_type: Optional[str] = 'pil',
                  return_dict: bool = True, attention_kwargs: Optional[Dict[str, Any]] = None,
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
-                 callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512):
+                 callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
+                 image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
+                 composite: bool = True):
+        """Text-to-image by default; ``image`` / ``image_latents``, ``strength``, ``mask_image`` and ``composite`` as on
+        ``ArcFluxPipeline.__call__`` (image-to-image and inpainting)."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -139,6 +144,8 @@ class ArcQwenImagePipeline(_PipelineBase):
             prompt_embeds = prompt_embeds[:, :int(max(lens))]
         B = prompt_embeds.shape[0]
         latents, hp, wp = self._prepare_latents(B, height, width, generator, latents)
+        if edit is not None:
+            edit = self._edit_prepare(edit, B, hp, wp)
 
         def fwd(x, t, pe, prepared_step=None):
             return self.transformer(x, t, pe.to(device, torch.bfloat16), None, None, hp, wp, prepared_step=prepared_step)
@@ -146,11 +153,12 @@ class ArcQwenImagePipeline(_PipelineBase):
         def prepare(sigmas):
             return self.transformer.prepare_steps(sigmas, None, None, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
-                                callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare)
-        return self._finish(latents, hp, wp, output_type, return_dict)
+                                callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare, edit=edit)
+        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite)
 
-    def _finish(self, latents, hp, wp, output_type, return_dict):
-        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``."""
+    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True):
+        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``.  An inpainting call
+        (``edit`` with an image and a mask) gets the original pixels pasted back outside the mask unless ``composite`` is off."""
         device = self._execution_device
         if output_type == 'latent':
             image = latents
@@ -159,13 +167,13 @@ class ArcQwenImagePipeline(_PipelineBase):
                 raise RuntimeError("no VAE decoder attached: use output_type='latent' or set pipe.vae")
             from ..vae import AutoencoderKLQwenImageDecoder
             if isinstance(self.vae, AutoencoderKLQwenImageDecoder):   # HIP decoder: un-normalisation + unpack fused into its first kernel
-                image = self._postprocess(self.vae.decode_packed(latents, hp, wp), output_type)
+                image = self._postprocess(self._composite(self.vae.decode_packed(latents, hp, wp), edit, composite), output_type)
                 return (image,) if not return_dict else QwenImagePipelineOutput(images=image)
             lat = self._unpack(latents, hp, wp)[:, :, None]
             mean = torch.tensor(self.vae.config.latents_mean, device=device).view(1, -1, 1, 1, 1)
             std = torch.tensor(self.vae.config.latents_std, device=device).view(1, -1, 1, 1, 1)
             image = self.vae.decode((lat * std + mean).to(next(self.vae.parameters()).dtype), return_dict=False)[0][:, :, 0]
-            image = self._postprocess(image, output_type)
+            image = self._postprocess(self._composite(image, edit, composite), output_type)
         if not return_dict:
             return (image,)
         return QwenImagePipelineOutput(images=image)

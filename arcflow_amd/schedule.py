@@ -33,6 +33,37 @@ def retrieve_raw_timesteps(num_inference_steps: int, total_substeps: int, timest
     return times, per_step, sum(per_step)
 
 
+def edit_raw_timesteps(num_inference_steps: int, total_substeps: int, timestep_ratio: float, strength: float
+                       ) -> Tuple[List[float], List[int], int]:
+    """The raw grid of an edit (``image=`` / ``strength=`` on the pipelines): ``retrieve_raw_timesteps`` with every time multiplied by
+    ``strength`` in (0, 1].  The edit takes ``num_inference_steps`` full student steps over the raw time [strength, 0]; it does not walk a
+    truncated prefix of the text-to-image grid, which at 2 NFE could only express strength 0.5 or 1.  strength == 1.0 returns the lists of
+    ``retrieve_raw_timesteps`` themselves."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f'strength must be in (0, 1], got {strength}')
+    times, per_step, total = retrieve_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio)
+    if strength != 1.0:
+        times = [strength * t for t in times]
+    return times, per_step, total
+
+
+def mask_to_tokens(mask: torch.Tensor, hp: int, wp: int, reduce: str = 'max') -> torch.Tensor:
+    """An image-resolution mask [B, 1, H, W] or [B, H, W] with H = 16 hp, W = 16 wp -> [B, hp*wp, 4] fp32, the operand of
+    ``ops.edit_blend``: latent pixel (2r + ph, 2c + pw) of token r*wp + c, at index ph*2 + pw, takes the max (``reduce='max'``: any
+    repainted pixel repaints its latent pixel, a binary mask stays binary) or the mean (``'mean'``) of its 8 x 8 pixel block.  Once per
+    call, on whatever device the mask lives: plain torch."""
+    if reduce not in ('max', 'mean'):
+        raise ValueError(f"reduce: 'max' or 'mean', got {reduce!r}")
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 3 or tuple(mask.shape[1:]) != (16 * hp, 16 * wp):
+        raise ValueError(f'mask: need [B, 1, {16 * hp}, {16 * wp}] or [B, {16 * hp}, {16 * wp}], got {tuple(mask.shape)}')
+    blocks = mask.to(torch.float32).reshape(mask.shape[0], hp, 2, 8, wp, 2, 8)          # [B, r, ph, i, c, pw, j]
+    red = blocks.amax(dim=(3, 6)) if reduce == 'max' else blocks.mean(dim=(3, 6))      # [B, r, ph, c, pw]
+    return red.permute(0, 1, 3, 2, 4).reshape(mask.shape[0], hp * wp, 4).contiguous()
+
+
 def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
                    num_train_timesteps: int = 1000) -> List[float]:
     """sigma at the start of every student step plus the terminal 0, as the pipelines' ``__call__`` walks them: the raw sub-step grid

@@ -229,6 +229,24 @@ int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, con
 int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma,
                          const float* sigma_to, const float* m, const float* c_noise, const float* coef, float scale, float* x_out,
                          void* x_out_bf16, int32_t batch, int64_t n, int32_t max_blocks, void* stream);
+/* The blend of image editing (image-to-image start, inpainting) on the engine's packed token layout, in one launch: the source
+ * latents x0 diffused forward to sigma_to with the call's fixed noise, blended per latent pixel with the sampler's latents x, plus the
+ * bf16 copy the next forward reads.  Per element, in fp32, exactly:
+ *   om    = 1 - sigma_to[b]
+ *   known = noise ? fma(sigma_to[b], noise, om x0) : om x0
+ *   x_out = mask ? fma(m, x, (1 - m) known) : known                     m = mask[b, tok, e & 3] for element e of the token
+ *   x_out_bf16 = round-to-nearest-even of x_out
+ * so that, for finite inputs, m = 1 returns x, m = 0 returns known, sigma_to = 1 returns noise and sigma_to = 0 returns x0 bit for bit.
+ * x, x0, noise, x_out [batch, n_tok, ch] fp32, x_out_bf16 [batch, n_tok, ch] bf16, ch = 64 with channel = c*4 + ph*2 + pw; mask
+ * [batch, n_tok, 4] fp32 in [0, 1], one value per latent pixel of the 2 x 2 patch at index ph*2 + pw (1 = keep x, 0 = keep the source);
+ * sigma_to [batch] fp32.  mask NULL: everything is known (the image-to-image start: the noised source and its bf16 copy in one launch);
+ * x is then not read and may be NULL.  noise NULL: the noise term and its read are skipped (the final step, sigma_to = 0).  x_out may
+ * be x; x_out_bf16 may be NULL.  AFX_E_INVALID before any launch when x0, x_out or sigma_to is NULL, x is NULL with a mask, ch != 64,
+ * batch or n_tok < 1, a pointer is not 16-byte aligned, or an output overlaps another operand (other than x_out == x).  max_blocks: cap
+ * on the grid of the grid-stride loop (0 = the default, 2048).  Traffic at 1024 x 1024 (262144 elements per image): 4 + 4 + 4 B read and
+ * 4 + 2 B written per element, 16 B of mask per token: 18 B per element, about 4.7 MB per image and step. */
+int afx_edit_blend(const float* x, const float* x0, const float* noise, const float* mask, const float* sigma_to, float* x_out,
+                   void* x_out_bf16, int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks, void* stream);
 /* coef[b] = mean(bias pos) / max(mean(pos pos), 1e-6) over the n elements of sample b, bias = (pos - neg) (scale - 1) rounded to
  * fp32 as the step kernel computes it: the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25, dim = [1..]).
  * Deterministic: a number of work-groups per sample that depends on n alone, exact fp64 products, one slot of `ws` per
