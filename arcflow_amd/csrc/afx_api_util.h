@@ -13,3 +13,5 @@ int afx_fail(int code, const char* fmt, ...);
     hipError_t e_ = (expr);                                                                     \
     if (e_ != hipSuccess) return fail(AFX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+#define AFX_TRY(expr) do { const int rc_ = (expr); if (rc_ != AFX_OK) return rc_; } while (0)

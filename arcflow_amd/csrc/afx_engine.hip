@@ -1,4 +1,5 @@
-// C-ABI layer + MMDiT forward engine (see include/arcflow_hip.h for the contract).
+// The MMDiT forward engine behind the afx_ctx entry points (see include/arcflow_hip.h for the contract), and the library's error state.  The
+// stand-alone operators' entry points are in afx_ops_api.hip.
 //
 // The forward is a fixed launch plan over the kernels in afx_gemm / afx_attn / afx_elementwise:
 //   temb MLPs (gemv) -> ONE gemv over all stacked AdaLN modulation linears -> embedders (grouped GEMM)
@@ -21,12 +22,10 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/arcflow_hip.h"
-#include "afx_kernels.h"
+#include "afx_api_util.h"
+#include "afx_gemm_problem.h"
 
 using namespace afx;
-
-#include "afx_api_util.h"
 
 thread_local char afx_g_err[512] = "";
 
@@ -260,9 +259,14 @@ void stream_qk_epilogue(GemmProblem& p, const BlockShape& q, const float* qkn, i
 
 // the plain linear C [M, N] = A [M, K] . W^T + bias over the rows of lw from wrow0 on
 void linear_problem(GemmProblem& p, const uint16_t* A, int64_t lda, const LinW& lw, int64_t wrow0, uint16_t* C, int64_t ldc, int M, int N, int K) {
-  p = GemmProblem{};
-  p.A = A; p.lda = lda; p.W = lw.w + wrow0 * K; p.ldw = K; p.bias = lw.b ? lw.b + wrow0 : nullptr;
-  p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+  p = dense_problem(A, lda, lw.w + wrow0 * K, K, lw.b ? lw.b + wrow0 : nullptr, C, ldc, M, N, K);
+}
+
+// VT_PROJ: the V third of a k|v|q projection computed transposed -- A = the V rows of the weight, W = `keys` token rows -- into Vt at the keys' offset
+void vt_problem(GemmProblem& p, const BlockShape& q, const uint16_t* tokens, int64_t ldt, const LinW& lw, uint16_t* Vt, int keys) {
+  const int64_t D = q.D;
+  p = dense_problem(lw.w + D * D, D, tokens, ldt, lw.b ? lw.b + D : nullptr, Vt, q.S_pad, (int)D, keys, (int)D);
+  p.bias_rows = 1; p.w_perm16 = 1;
 }
 
 // the image (s = 0) or text (s = 1) rows of sample b in a per-stream linear over the joint token matrix
@@ -276,20 +280,13 @@ void stream_problem(GemmProblem& p, const BlockShape& q, const uint16_t* A, int6
 void kqv_problems(GemmBatch& gb, const BlockShape& q, const uint16_t* A, int64_t lda, const LinW& lw, uint16_t* C, int64_t ldc, int64_t row0g,
                   int rows, int b, int pos0, int period, const float* wq, const float* wk, bool with_v) {
   const int64_t D = q.D;
-  for (int part = 0; part < (with_v ? 3 : 2); ++part) {        // 0: k (weight rows 0..D), 1: q (2D..3D), 2: v^T (D..2D)
+  for (int part = 0; part < 2; ++part) {        // 0: k (weight rows 0..D), 1: q (2D..3D)
     GemmProblem& p = gb.p[gb.nprob++];
-    p = GemmProblem{};
-    p.K = (int)D; p.epi = EPI_NONE;
-    if (part < 2) {
-      const int64_t wrow = part == 0 ? 0 : 2 * D;
-      linear_problem(p, A + row0g * lda, lda, lw, wrow, C + row0g * ldc + wrow, ldc, rows, (int)D, (int)D);
-      set_qk_epilogue(p, q, part == 0 ? wk : wq, part == 0 ? wk : wq, pos0, period);     // a problem of its own: its columns are "region 0"
-    } else {
-      p.A = lw.w + D * D; p.lda = D; p.bias = lw.b ? lw.b + D : nullptr; p.bias_rows = 1;
-      p.W = A + row0g * lda; p.ldw = lda; p.w_perm16 = 1;
-      p.C = q.Vt + (int64_t)b * q.H * 128 * q.S_pad + pos0; p.ldc = q.S_pad; p.M = (int)D; p.N = rows;
-    }
+    const int64_t wrow = part == 0 ? 0 : 2 * D;
+    linear_problem(p, A + row0g * lda, lda, lw, wrow, C + row0g * ldc + wrow, ldc, rows, (int)D, (int)D);
+    set_qk_epilogue(p, q, part == 0 ? wk : wq, part == 0 ? wk : wq, pos0, period);     // a problem of its own: its columns are "region 0"
   }
+  if (with_v) vt_problem(gb.p[gb.nprob++], q, A + row0g * lda, lda, lw, q.Vt + (int64_t)b * q.H * 128 * q.S_pad + pos0, rows);      // v^T (D..2D)
 }
 
 // VT_PROJ, double block: sample b's image k, q, v^T + text k, q, v^T = 6 problems of one launch
@@ -316,13 +313,7 @@ void single_qkv_batch(GemmBatch& gb, int path, const BlockShape& q, const uint16
     GemmProblem& m = gb.p[gb.nprob++];
     linear_problem(m, A, lda, lw, 3 * D, F + 3 * D, ldf, R, (int)(4 * D), (int)D);
     m.epi = EPI_GELU; m.gelu_col0 = 0;
-    for (int b = 0; b < q.B; ++b) {
-      GemmProblem& v = gb.p[gb.nprob++];
-      v = GemmProblem{};
-      v.A = lw.w + D * D; v.lda = D; v.bias = lw.b ? lw.b + D : nullptr; v.bias_rows = 1;
-      v.W = A + (int64_t)b * q.S * lda; v.ldw = lda; v.w_perm16 = 1;
-      v.C = q.Vt + (int64_t)b * q.H * 128 * q.S_pad; v.ldc = q.S_pad; v.M = (int)D; v.N = q.S; v.K = (int)D; v.epi = EPI_NONE;
-    }
+    for (int b = 0; b < q.B; ++b) vt_problem(gb.p[gb.nprob++], q, A + (int64_t)b * q.S * lda, lda, lw, q.Vt + (int64_t)b * q.H * 128 * q.S_pad, q.S);
   } else if (path == AFX_QKV_QK_EPI) {
     set_qk_epilogue(f, q, qkn, qkn + 128, 0, q.S);
   }
@@ -337,8 +328,6 @@ hipError_t qkv_finish(int path, const BlockShape& q, uint16_t* F, int64_t ldf, c
     return launch_kv_prep(F, F + 2 * q.D, ldf, wk_txt, wk_img, wq_txt, wq_img, q.rope_cos, q.rope_sin, q.T, F + q.D, ldf, q.Vt, q.B, q.H, q.S, st);
   return hipSuccess;
 }
-
-#define AFX_TRY(expr) do { const int rc_ = (expr); if (rc_ != AFX_OK) return rc_; } while (0)
 
 // ---- conditioning: temb = t_mlp(sincos(1000 t)) [+ g_mlp(sincos(1000 g))] [+ p_mlp(pooled)] ------
 // ... of nsteps x B rows (step-major, then sample; t == nullptr: temb already holds the timestep part), then their SiLU and modulation vectors.
@@ -434,15 +423,15 @@ int fwd_resolve_fp8(Fwd& f) {
 void bind_fp8_operand(GemmProblem& p, const Fwd& f, ASrc src, int64_t row0, int K, const LinW& lw) {
   const Workspace& ws = f.ws;
   if (!f.c->fp8) return;
-  p.W = (const uint16_t*)lw.wq; p.fp8 = 1; p.w_scale = lw.wscale; p.lda = K;
+  p.W = (const uint16_t*)lw.wq; p.lda = K;
   if (!f.fp8.mx) {                                     // per-token scales: the pass in front of every GEMM wrote q8 / qs
-    p.A = (const uint16_t*)(ws.q8 + row0 * K); p.a_scale = ws.qs + row0;
+    p.A = (const uint16_t*)(ws.q8 + row0 * K); set_fp8(p, ws.qs + row0, lw.wscale);
   } else if (src == ASrc::Norm && f.fp8.norm_rows) {   // LayerNorm rows: one scale per row, the plain fp8 MFMA
-    p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.qs + row0;
+    p.A = (const uint16_t*)(ws.q8n + row0 * K); set_fp8(p, ws.qs + row0, lw.wscale);
   } else if (src == ASrc::Wide) {
-    p.A = (const uint16_t*)(ws.q8 + row0 * K); p.a_scale = ws.ones + row0; p.a_mx = ws.mxw + row0 * ws.ld_mxw; p.ld_mx = ws.ld_mxw;
+    p.A = (const uint16_t*)(ws.q8 + row0 * K); set_fp8(p, ws.ones + row0, lw.wscale, ws.mxw + row0 * ws.ld_mxw, ws.ld_mxw);
   } else {
-    p.A = (const uint16_t*)(ws.q8n + row0 * K); p.a_scale = ws.ones + row0; p.a_mx = ws.mxn + row0 * ws.ld_mxn; p.ld_mx = ws.ld_mxn;
+    p.A = (const uint16_t*)(ws.q8n + row0 * K); set_fp8(p, ws.ones + row0, lw.wscale, ws.mxn + row0 * ws.ld_mxn, ws.ld_mxn);
   }
 }
 // ... and the producer side (block-scaled mode): the epilogue of p stores its columns from col0 on as columns dst_col0.. of rows row0.. of
@@ -473,12 +462,9 @@ int stream_gemm(Fwd& f, const uint16_t* A, int64_t lda, int K, const LinW (&lw)[
       const int64_t row0 = (int64_t)b * f.bs.S + (s == 0 ? f.bs.T : 0);
       bind_fp8_operand(p, f, src, row0, K, lw[s]);
       if (wide_out) bind_fp8_producer(p, f, row0, Nout, 0, 0);
-      p.epi = epi; p.gelu_col0 = 0;
+      p.epi = epi;
       if (qkn != nullptr) stream_qk_epilogue(p, f.bs, qkn, s);          // [img_q, img_k, txt_q, txt_k][128]
-      if (epi == EPI_GATE_RES) {
-        p.gate = f.ws.mod + (int64_t)b * f.ldm + f.ml.dbl(blk, s, gate_chunk); p.ldg = 0; p.rows_per_batch = 1 << 30;
-        p.res = C + row0 * ldc; p.ldr = ldc;
-      }
+      if (epi == EPI_GATE_RES) set_epilogue(p, epi, 0, f.ws.mod + (int64_t)b * f.ldm + f.ml.dbl(blk, s, gate_chunk), 0, 1 << 30, C + row0 * ldc, ldc);
     }
   return fwd_gemm(f, gb);
 }
@@ -601,7 +587,7 @@ int fwd_single_block(Fwd& f, int i) {
   GemmBatch go{};
   GemmProblem& o = go.p[go.nprob++];
   linear_problem(o, ws.F + 2 * D, 7 * D, bw.out, 0, ws.X, D, (int)R, (int)D, (int)(5 * D));
-  o.epi = EPI_GATE_RES; o.gate = ws.mod + f.ml.sgl(i, 2); o.ldg = ldm; o.rows_per_batch = S; o.res = ws.X; o.ldr = D;
+  set_epilogue(o, EPI_GATE_RES, 0, ws.mod + f.ml.sgl(i, 2), ldm, S, ws.X, D);
   // mx: the attention output joins the mlp columns the projection's epilogue left in q8 (a pass of D columns unless the attention kernel wrote
   // them); per-token scales: the usual pass over all 5D columns.  Either way the operand is the wide one.
   if (mx && !o_fused) HIP_TRY(launch_quant_rows_mx8(ws.F + 2 * D, 7 * D, ws.q8, 5 * D, ws.mxw, ws.ld_mxw, (int)R, (int)D, f.st));
@@ -841,6 +827,51 @@ int afx_mmdit_use_prepared_step(afx_ctx* c, int32_t k) {
   return AFX_OK;
 }
 
+int afx_mmdit_import_tokens(afx_ctx* c, const void* src, int32_t batch, int32_t n_img, int32_t n_txt, void* stream) {
+  if (!c || !src || !c->ws || batch < 1 || n_img < 1 || n_txt < 0) return fail(AFX_E_INVALID, "bad argument to afx_mmdit_import_tokens");
+  Workspace ws = carve(c, c->ws, batch, n_img, n_txt);
+  if (ws.total > c->ws_bytes)
+    return fail(AFX_E_WORKSPACE, "afx_mmdit_import_tokens: shape (%d, %d, %d) needs %lld workspace bytes, have %lld", batch, n_img, n_txt,
+                (long long)ws.total, (long long)c->ws_bytes);
+  HIP_TRY(hipMemcpyAsync(ws.X, src, (size_t)batch * (n_img + n_txt) * c->D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return AFX_OK;
+}
+
+int afx_mmdit_export(afx_ctx* c, const char* what, void* dst, int32_t batch, int32_t n_img, int32_t n_txt, void* stream) {
+  if (!c || !what || !dst || !c->ws || batch < 1 || n_img < 1 || n_txt < 0) return fail(AFX_E_INVALID, "bad argument to afx_mmdit_export");
+  Workspace ws = carve(c, c->ws, batch, n_img, n_txt);
+  // the layout is a function of the shape: a shape the bound workspace was not sized for would read past it / from another layout
+  if (ws.total > c->ws_bytes)
+    return fail(AFX_E_WORKSPACE, "afx_mmdit_export: shape (%d, %d, %d) needs %lld workspace bytes, have %lld", batch, n_img, n_txt,
+                (long long)ws.total, (long long)c->ws_bytes);
+  const int64_t D = c->D;
+  ModLayout ml{D, c->d.num_double, c->d.num_single};
+  hipStream_t st = (hipStream_t)stream;
+  const std::string w(what);
+  if (w == "head_in") {            // [B*N, D] bf16: norm_out output = input of the velocity head
+    HIP_TRY(hipMemcpyAsync(dst, ws.Xn, (size_t)batch * n_img * D * 2, hipMemcpyDeviceToDevice, st));
+  } else if (w == "x_final") {     // [B*N, D] bf16: image tokens entering norm_out
+    for (int b = 0; b < batch; ++b)
+      HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)b * n_img * D * 2, ws.X + ((int64_t)b * (n_img + n_txt) + n_txt) * D,
+                             (size_t)n_img * D * 2, hipMemcpyDeviceToDevice, st));
+  } else if (w == "x_tokens") {    // [B*(T+N), D] bf16: the joint token matrix (after the embedders / after the last block)
+    HIP_TRY(hipMemcpyAsync(dst, ws.X, (size_t)batch * (n_img + n_txt) * D * 2, hipMemcpyDeviceToDevice, st));
+  } else if (w == "temb") {        // [B, D] f32: the summed conditioning embedding before SiLU
+    HIP_TRY(hipMemcpyAsync(dst, ws.temb, (size_t)batch * D * 4, hipMemcpyDeviceToDevice, st));
+  } else if (w == "silu_temb") {   // [B, D] f32
+    HIP_TRY(hipMemcpyAsync(dst, ws.semb, (size_t)batch * D * 4, hipMemcpyDeviceToDevice, st));
+  } else if (w == "mod_all") {     // [B, n_mod] f32: every AdaLN modulation vector of the network
+    HIP_TRY(hipMemcpyAsync(dst, ws.mod, (size_t)batch * c->n_mod * 4, hipMemcpyDeviceToDevice, st));
+  } else if (w == "mod_final") {   // [B, 2D] f32: (scale | shift) of norm_out
+    for (int b = 0; b < batch; ++b)
+      HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)b * 2 * D * 4, ws.mod + (int64_t)b * c->n_mod + ml.fin(0), (size_t)2 * D * 4,
+                             hipMemcpyDeviceToDevice, st));
+  } else {
+    return fail(AFX_E_INVALID, "afx_mmdit_export: unknown buffer '%s'", what);
+  }
+  return AFX_OK;
+}
+
 int afx_set_fp8_linear(afx_ctx* c, int32_t on) {
   if (!c) return fail(AFX_E_INVALID, "null ctx");
   if (on) {
@@ -901,304 +932,6 @@ int afx_profile_read(afx_ctx* ctx, int32_t klass, double* total_ms, int64_t* lau
   return AFX_OK;
 }
 
-int afx_arcflow_step(const float* x_in, const void* means, const void* logw, const void* logg, int32_t mix_dtype,
-                     float sigma_src, float sigma_start, float sigma_end, const float* sigma_vec, float eps,
-                     float* x_out, int32_t batch, int32_t n_tok, int32_t K, int32_t ch, int32_t pp, void* stream) {
-  if (!x_in || !means || !logw || !logg || !x_out) return fail(AFX_E_INVALID, "null argument to afx_arcflow_step");
-  if (mix_dtype != AFX_DT_BF16 && mix_dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "bad mix_dtype");
-  if (batch < 0 || n_tok < 0 || K < 1 || K > 32 || ch < 1 || pp < 1 || ch % pp != 0)
-    return fail(AFX_E_INVALID, "bad shape for afx_arcflow_step");
-  HIP_TRY(launch_arcflow_step(x_in, means, logw, logg, mix_dtype == AFX_DT_BF16, sigma_src, sigma_start, sigma_end,
-                              sigma_vec, eps, x_out, batch, n_tok, K, ch, pp, 0, nullptr, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_arcflow_step_dropout(const float* x_in, const void* means, const void* logw, const void* logg, int32_t mix_dtype,
-                             const float* sigma_vec, const uint8_t* drop_mask, float eps, float* x_out, int32_t batch,
-                             int32_t n_tok, int32_t K, int32_t ch, int32_t pp, void* stream) {
-  if (!x_in || !means || !logw || !logg || !x_out || !sigma_vec)
-    return fail(AFX_E_INVALID, "null argument to afx_arcflow_step_dropout");
-  if (mix_dtype != AFX_DT_BF16 && mix_dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "bad mix_dtype");
-  if (batch < 0 || n_tok < 0 || K < 1 || K > 32 || ch < 1 || pp < 1 || ch % pp != 0)
-    return fail(AFX_E_INVALID, "bad shape for afx_arcflow_step_dropout");
-  HIP_TRY(launch_arcflow_step(x_in, means, logw, logg, mix_dtype == AFX_DT_BF16, 0.f, 0.f, 0.f, sigma_vec, eps, x_out,
-                              batch, n_tok, K, ch, pp, 0, drop_mask, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_tn_f32out(const void* X, int64_t ldx, const void* Y, int64_t ldy, float* C, int64_t ldc, int32_t M, int32_t N1, int32_t N2,
-                         int32_t accumulate, void* stream) {
-  if (!X || !Y || !C) return fail(AFX_E_INVALID, "null argument to afx_linear_tn_f32out");
-  if (M < 0 || N1 < 0 || N2 < 0 || N1 % 8 || N2 % 8 || ldx % 8 || ldy % 8 || ldc % 4 || ldx < N1 || ldy < N2 || ldc < N2)
-    return fail(AFX_E_INVALID, "afx_linear_tn_f32out: need N1%%8==0, N2%%8==0, ldx/ldy%%8==0, ldc%%4==0, leading dimensions >= the widths");
-  if (((uintptr_t)X | (uintptr_t)Y | (uintptr_t)C) & 15) return fail(AFX_E_INVALID, "afx_linear_tn_f32out: operands must be 16-byte aligned");
-  HIP_TRY(launch_gemm_tn_f32((const uint16_t*)X, ldx, (const uint16_t*)Y, ldy, C, ldc, M, N1, N2, accumulate, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int64_t afx_linear_tn_ws_bytes(int32_t M, int32_t N1, int32_t N2) {
-  if (M < 0 || N1 < 0 || N2 < 0) return fail(AFX_E_INVALID, "bad shape to afx_linear_tn_ws_bytes");
-  return gemm_tn_ws_bytes(M, N1, N2);
-}
-
-int afx_linear_tn_f32out_ws(const void* X, int64_t ldx, const void* Y, int64_t ldy, float* C, int64_t ldc, int32_t M, int32_t N1, int32_t N2,
-                            int32_t accumulate, void* ws, void* stream) {
-  if (!X || !Y || !C) return fail(AFX_E_INVALID, "null argument to afx_linear_tn_f32out_ws");
-  if (M < 0 || N1 < 0 || N2 < 0 || N1 % 8 || N2 % 8 || ldx % 8 || ldy % 8 || ldc % 4 || ldx < N1 || ldy < N2 || ldc < N2)
-    return fail(AFX_E_INVALID, "afx_linear_tn_f32out_ws: need N1%%8==0, N2%%8==0, ldx/ldy%%8==0, ldc%%4==0, leading dimensions >= the widths");
-  if (((uintptr_t)X | (uintptr_t)Y | (uintptr_t)C | (uintptr_t)ws) & 15) return fail(AFX_E_INVALID, "afx_linear_tn_f32out_ws: operands must be 16-byte aligned");
-  if (!ws && gemm_tn_ws_bytes(M, N1, N2) > 0) return fail(AFX_E_INVALID, "afx_linear_tn_f32out_ws: this shape needs afx_linear_tn_ws_bytes() of workspace");
-  HIP_TRY(launch_gemm_tn_f32((const uint16_t*)X, ldx, (const uint16_t*)Y, ldy, C, ldc, M, N1, N2, accumulate, (hipStream_t)stream, (float*)ws));
-  return AFX_OK;
-}
-
-int afx_linear_bf16_f32out(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int32_t M,
-                           int32_t N, int32_t K, int32_t accumulate, void* stream) {
-  if (!A || !W || !C) return fail(AFX_E_INVALID, "null argument to afx_linear_bf16_f32out");
-  if (M < 0 || N < 0 || K <= 0 || K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 4)
-    return fail(AFX_E_INVALID, "afx_linear_bf16_f32out: need K%%64==0, N%%8==0, lda/ldw%%8==0, ldc%%4==0");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)A; p.lda = lda; p.W = (const uint16_t*)W; p.ldw = ldw; p.C = (uint16_t*)C; p.ldc = ldc;
-  p.M = M; p.N = N; p.K = K; p.epi = EPI_NONE; p.rows_per_batch = 1; p.out_f32 = accumulate ? 2 : 1;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_mmdit_import_tokens(afx_ctx* c, const void* src, int32_t batch, int32_t n_img, int32_t n_txt, void* stream) {
-  if (!c || !src || !c->ws || batch < 1 || n_img < 1 || n_txt < 0) return fail(AFX_E_INVALID, "bad argument to afx_mmdit_import_tokens");
-  Workspace ws = carve(c, c->ws, batch, n_img, n_txt);
-  if (ws.total > c->ws_bytes)
-    return fail(AFX_E_WORKSPACE, "afx_mmdit_import_tokens: shape (%d, %d, %d) needs %lld workspace bytes, have %lld", batch, n_img, n_txt,
-                (long long)ws.total, (long long)c->ws_bytes);
-  HIP_TRY(hipMemcpyAsync(ws.X, src, (size_t)batch * (n_img + n_txt) * c->D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_splitk_chunks(int32_t M, int32_t N, int32_t K, int32_t split_k) {
-  const int tiles = ((M + 255) / 256) * ((N + 255) / 256), nk = K / 64;
-  if (split_k <= 0) {                    // ~2 work-groups per CU (512 in flight), at least 4 K-tiles per chunk
-    split_k = (512 + tiles / 2) / tiles;
-    if (split_k > nk / 4) split_k = nk / 4;
-    if (split_k < 1) split_k = 1;
-  }
-  split_k = split_k < nk ? split_k : nk;
-  const int per = (nk + split_k - 1) / split_k;
-  return (nk + per - 1) / per;           // no empty chunk
-}
-
-int afx_linear_bf16_splitk(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, float* partials, int32_t M,
-                           int32_t N, int32_t K, int32_t split_k, void* stream) {
-  if (!A || !W || !partials) return fail(AFX_E_INVALID, "null argument to afx_linear_bf16_splitk");
-  if (M < 0 || N < 0 || K <= 0 || K % 64 || N % 8 || lda % 8 || ldw % 8 || split_k < 0)
-    return fail(AFX_E_INVALID, "afx_linear_bf16_splitk: need K%%64==0, N%%8==0, lda/ldw%%8==0, split_k >= 0");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)A; p.lda = lda; p.W = (const uint16_t*)W; p.ldw = ldw; p.bias = (const uint16_t*)bias; p.C = (uint16_t*)partials;
-  p.ldc = N; p.M = M; p.N = N; p.K = K; p.epi = EPI_NONE; p.rows_per_batch = 1; p.out_f32 = 3;
-  p.split_k = afx_linear_splitk_chunks(M, N, K, split_k);
-  p.split_stride = (int64_t)M * N;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_mmdit_export(afx_ctx* c, const char* what, void* dst, int32_t batch, int32_t n_img, int32_t n_txt, void* stream) {
-  if (!c || !what || !dst || !c->ws || batch < 1 || n_img < 1 || n_txt < 0) return fail(AFX_E_INVALID, "bad argument to afx_mmdit_export");
-  Workspace ws = carve(c, c->ws, batch, n_img, n_txt);
-  // the layout is a function of the shape: a shape the bound workspace was not sized for would read past it / from another layout
-  if (ws.total > c->ws_bytes)
-    return fail(AFX_E_WORKSPACE, "afx_mmdit_export: shape (%d, %d, %d) needs %lld workspace bytes, have %lld", batch, n_img, n_txt,
-                (long long)ws.total, (long long)c->ws_bytes);
-  const int64_t D = c->D;
-  ModLayout ml{D, c->d.num_double, c->d.num_single};
-  hipStream_t st = (hipStream_t)stream;
-  const std::string w(what);
-  if (w == "head_in") {            // [B*N, D] bf16: norm_out output = input of the velocity head
-    HIP_TRY(hipMemcpyAsync(dst, ws.Xn, (size_t)batch * n_img * D * 2, hipMemcpyDeviceToDevice, st));
-  } else if (w == "x_final") {     // [B*N, D] bf16: image tokens entering norm_out
-    for (int b = 0; b < batch; ++b)
-      HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)b * n_img * D * 2, ws.X + ((int64_t)b * (n_img + n_txt) + n_txt) * D,
-                             (size_t)n_img * D * 2, hipMemcpyDeviceToDevice, st));
-  } else if (w == "x_tokens") {    // [B*(T+N), D] bf16: the joint token matrix (after the embedders / after the last block)
-    HIP_TRY(hipMemcpyAsync(dst, ws.X, (size_t)batch * (n_img + n_txt) * D * 2, hipMemcpyDeviceToDevice, st));
-  } else if (w == "temb") {        // [B, D] f32: the summed conditioning embedding before SiLU
-    HIP_TRY(hipMemcpyAsync(dst, ws.temb, (size_t)batch * D * 4, hipMemcpyDeviceToDevice, st));
-  } else if (w == "silu_temb") {   // [B, D] f32
-    HIP_TRY(hipMemcpyAsync(dst, ws.semb, (size_t)batch * D * 4, hipMemcpyDeviceToDevice, st));
-  } else if (w == "mod_all") {     // [B, n_mod] f32: every AdaLN modulation vector of the network
-    HIP_TRY(hipMemcpyAsync(dst, ws.mod, (size_t)batch * c->n_mod * 4, hipMemcpyDeviceToDevice, st));
-  } else if (w == "mod_final") {   // [B, 2D] f32: (scale | shift) of norm_out
-    for (int b = 0; b < batch; ++b)
-      HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)b * 2 * D * 4, ws.mod + (int64_t)b * c->n_mod + ml.fin(0), (size_t)2 * D * 4,
-                             hipMemcpyDeviceToDevice, st));
-  } else {
-    return fail(AFX_E_INVALID, "afx_mmdit_export: unknown buffer '%s'", what);
-  }
-  return AFX_OK;
-}
-
-int afx_arcflow_velocity(const void* means, const void* logw, const void* logg, int32_t mix_dtype, float sigma_src,
-                         float sigma_t, const float* sigma_vec, float* u_out, int32_t batch, int32_t n_tok,
-                         int32_t K, int32_t ch, int32_t pp, void* stream) {
-  if (!means || !logw || !logg || !u_out) return fail(AFX_E_INVALID, "null argument to afx_arcflow_velocity");
-  if (mix_dtype != AFX_DT_BF16 && mix_dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "bad mix_dtype");
-  if (batch < 0 || n_tok < 0 || K < 1 || K > 32 || ch < 1 || pp < 1 || ch % pp != 0)
-    return fail(AFX_E_INVALID, "bad shape for afx_arcflow_velocity");
-  HIP_TRY(launch_arcflow_step(u_out, means, logw, logg, mix_dtype == AFX_DT_BF16, sigma_src, sigma_t, sigma_t,
-                              sigma_vec, 1e-4f, u_out, batch, n_tok, K, ch, pp, 1, nullptr, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                    int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
-                    int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, void* stream) {
-  return afx_linear_bf16_pre(A, lda, W, ldw, bias, C, ldc, M, N, K, epi, gelu_col0, gate, ldg, rows_per_batch, res, ldr, nullptr, 0,
-                             stream);
-}
-
-int afx_gemm_dropres_available(void) { return gemm_dropres_available() ? 1 : 0; }
-int afx_gemm_set_mode(int32_t impl, int32_t tile) {
-  gemm_set_mode(impl, tile);
-  return 0;
-}
-int afx_gemm_set_fp8_tile(int32_t tile) { return gemm_set_fp8_tile(tile); }
-int afx_attn_set_impl(int32_t impl) {
-  attn_set_impl(impl);
-  return 0;
-}
-int afx_attn_bwd_set_impl(int32_t impl) {
-  attn_bwd_set_impl(impl);
-  return 0;
-}
-
-int afx_linear_bf16_pre(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                        int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate,
-                        int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, const void* pre, int64_t ldp,
-                        void* stream) {
-  if (!A || !W || !C) return fail(AFX_E_INVALID, "null argument to afx_linear_bf16");
-  if (pre && ldp % 8) return fail(AFX_E_INVALID, "afx_linear_bf16_pre: ldp %% 8 == 0");
-  if (M < 0 || N < 0 || K <= 0 || K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8)
-    return fail(AFX_E_INVALID, "afx_linear_bf16: need K%%64==0, N%%8==0, strides%%8==0");
-  if (epi < 0 || epi > 2) return fail(AFX_E_INVALID, "bad epilogue");
-  if (epi == EPI_GATE_RES && (!res || ldr % 8 || (gate && rows_per_batch < 1)))
-    return fail(AFX_E_INVALID, "gated residual epilogue needs res (and rows_per_batch with a gate)");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)A; p.lda = lda; p.W = (const uint16_t*)W; p.ldw = ldw; p.bias = (const uint16_t*)bias;
-  p.C = (uint16_t*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epi; p.gelu_col0 = gelu_col0;
-  p.gate = gate; p.ldg = ldg; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.res = (const uint16_t*)res; p.ldr = ldr;
-  p.pre = (const uint16_t*)pre; p.ldp = ldp;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_bf16_dropres(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int32_t M, int32_t N, int32_t K,
-                            const void* res, int64_t ldr, float p, uint32_t seed, int64_t row0, void* stream) {
-  if (!A || !W || !C || !res) return fail(AFX_E_INVALID, "null argument to afx_linear_bf16_dropres");
-  if (M < 0 || N < 0 || K <= 0 || K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8 || ldr % 8 || !(p >= 0.f && p < 1.f))
-    return fail(AFX_E_INVALID, "afx_linear_bf16_dropres: need K%%64==0, N%%8==0, strides%%8==0, 0 <= p < 1");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& q = gb.p[0];
-  q = GemmProblem{};
-  q.A = (const uint16_t*)A; q.lda = lda; q.W = (const uint16_t*)W; q.ldw = ldw; q.C = (uint16_t*)C; q.ldc = ldc; q.M = M; q.N = N; q.K = K;
-  q.epi = EPI_GATE_RES; q.rows_per_batch = M > 0 ? M : 1; q.res = (const uint16_t*)res; q.ldr = ldr;
-  q.drop_on = 1; q.drop_thresh = (uint32_t)((double)p * 4294967296.0); q.drop_seed = seed; q.drop_inv_keep = 1.0f / (1.0f - p); q.drop_row0 = row0;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int64_t afx_attention_ws_bytes(int32_t batch, int32_t heads, int32_t S) {
-  if (batch < 1 || heads < 1 || S < 1) return fail(AFX_E_INVALID, "bad attention shape");
-  return (int64_t)batch * heads * 128 * attn_spad(S) * 2;
-}
-
-int afx_attention_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                       int64_t ldo, void* vt_ws, int32_t batch, int32_t heads, int32_t S, void* stream) {
-  if (!q || !k || !v || !o || !vt_ws) return fail(AFX_E_INVALID, "null argument to afx_attention_bf16");
-  if (batch < 1 || heads < 1 || S < 1 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4)
-    return fail(AFX_E_INVALID, "bad attention shape / stride");
-  HIP_TRY(launch_v_transpose((const uint16_t*)v, ldv, (uint16_t*)vt_ws, batch, heads, S, (hipStream_t)stream));
-  HIP_TRY(launch_attention((const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)vt_ws, (uint16_t*)o, ldo,
-                           batch, heads, S, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int64_t afx_attention_bwd_ws_bytes(int32_t batch, int32_t heads, int32_t S) {
-  if (batch < 1 || heads < 1 || S < 1) return fail(AFX_E_INVALID, "bad attention shape");
-  return attn_bwd_ws_bytes(batch, heads, S);
-}
-
-int afx_attention_fwd_lse_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                               int64_t ldo, float* lse, void* vt_ws, int32_t batch, int32_t heads, int32_t S, void* stream) {
-  if (!q || !k || !v || !o || !vt_ws || !lse) return fail(AFX_E_INVALID, "null argument to afx_attention_fwd_lse_bf16");
-  if (batch < 1 || heads < 1 || S < 1 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return fail(AFX_E_INVALID, "bad attention shape / stride");
-  HIP_TRY(launch_v_transpose((const uint16_t*)v, ldv, (uint16_t*)vt_ws, batch, heads, S, (hipStream_t)stream));
-  HIP_TRY(launch_attention((const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)vt_ws, (uint16_t*)o, ldo,
-                           batch, heads, S, (hipStream_t)stream, lse));
-  return AFX_OK;
-}
-
-int afx_attention_to_mx8(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o8, int64_t ldo8,
-                         void* mx, int64_t ld_mx, void* vt_ws, int32_t batch, int32_t heads, int32_t S, void* stream) {
-  if (!q || !k || !v || !o8 || !mx || !vt_ws) return fail(AFX_E_INVALID, "null argument to afx_attention_to_mx8");
-  if (batch < 1 || heads < 1 || S < 1 || ldq % 8 || ldk % 8 || ldv % 8 || ldo8 % 8 || ld_mx < heads) return fail(AFX_E_INVALID, "bad attention shape / stride");
-  if (!attention_v3_eligible(S)) return fail(AFX_E_INVALID, "afx_attention_to_mx8: S > 64 (the one-wave-per-SIMD kernel's epilogue)");
-  HIP_TRY(launch_v_transpose((const uint16_t*)v, ldv, (uint16_t*)vt_ws, batch, heads, S, (hipStream_t)stream));
-  const AttnMx8 m{(uint8_t*)o8, ldo8, (uint8_t*)mx, ld_mx};
-  bool fused = false;
-  HIP_TRY(launch_attention((const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)vt_ws, nullptr, 0, batch, heads, S, (hipStream_t)stream,
-                           nullptr, &m, &fused));
-  if (!fused) return fail(AFX_E_INVALID, "afx_attention_to_mx8: the one-wave-per-SIMD attention kernel is switched off (AFX_ATTN_IMPL)");
-  return AFX_OK;
-}
-
-int afx_attention_bwd_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
-                           int64_t ldo, const void* dout, int64_t lddo, const float* lse, void* dq, int64_t lddq, void* dk,
-                           int64_t lddk, void* dv, int64_t lddv, void* ws, int32_t batch, int32_t heads, int32_t S,
-                           void* stream) {
-  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !ws) return fail(AFX_E_INVALID, "null argument to afx_attention_bwd_bf16");
-  if (batch < 1 || heads < 1 || S < 1 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
-    return fail(AFX_E_INVALID, "bad attention backward shape / stride");
-  HIP_TRY(launch_attention_backward((const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv,
-                                    (const uint16_t*)o, ldo, (const uint16_t*)dout, lddo, lse, (uint16_t*)dq, lddq,
-                                    (uint16_t*)dk, lddk, (uint16_t*)dv, lddv, ws, batch, heads, S, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_norm_modulate_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t rows, int32_t D,
-                           const float* scale, const float* shift, int64_t ldmod, int32_t rows_per_batch, int32_t rms,
-                           void* stream) {
-  if (!x || !out || !scale || (!rms && !shift)) return fail(AFX_E_INVALID, "null argument to afx_norm_modulate_bf16");
-  if (rows < 0 || D < 8 || D % 8 || D > 4096 || ldx % 8 || ldo % 8) return fail(AFX_E_INVALID, "bad norm shape");
-  HIP_TRY(launch_norm_modulate((const uint16_t*)x, ldx, (uint16_t*)out, ldo, rows, D, scale, shift, ldmod,
-                               rows_per_batch, rms, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_qk_norm_rope_bf16(void* x, int64_t ldx, const float* w_txt, const float* w_img, const float* rope_cos,
-                          const float* rope_sin, int32_t batch, int32_t S, int32_t n_txt, int32_t heads, void* stream) {
-  if (!x || !w_txt || !w_img || !rope_cos || !rope_sin) return fail(AFX_E_INVALID, "null argument to afx_qk_norm_rope_bf16");
-  if (batch < 1 || S < 1 || heads < 1 || ldx % 8) return fail(AFX_E_INVALID, "bad qk_norm_rope shape");
-  HIP_TRY(launch_qk_norm_rope((uint16_t*)x, ldx, w_txt, w_img, rope_cos, rope_sin, batch, S, n_txt, heads,
-                              (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_gemv_bf16(const float* x, const void* W, const void* bias, float* y, int32_t B, int32_t N, int32_t K,
-                  int32_t act, int32_t accumulate, void* stream) {
-  if (!x || !W || !y) return fail(AFX_E_INVALID, "null argument to afx_gemv_bf16");
-  if (B < 1 || B > 8 || N < 1 || K < 8 || K % 8) return fail(AFX_E_INVALID, "bad gemv shape (B<=8, K%%8==0)");
-  HIP_TRY(launch_gemv(x, (const uint16_t*)W, (const uint16_t*)bias, y, B, N, K, act, accumulate, (hipStream_t)stream));
-  return AFX_OK;
-}
-
 int afx_qkv_operands(int32_t kind, const void* A, int64_t lda, const void* w_img, const void* b_img, const void* w_txt, const void* b_txt,
                      const float* qkn, const float* rope_cos, const float* rope_sin, int32_t B, int32_t N, int32_t T, int32_t heads,
                      int32_t path, void* F, int64_t ldf, void* Vt, void* stream) {
@@ -1224,17 +957,14 @@ int afx_qkv_operands(int32_t kind, const void* A, int64_t lda, const void* w_img
   const uint16_t* a = (const uint16_t*)A;
   uint16_t* f = (uint16_t*)F;
   if (single) {
-    LinW lw;
-    lw.w = (const uint16_t*)w_img; lw.b = (const uint16_t*)b_img;
+    const LinW lw{(const uint16_t*)w_img, (const uint16_t*)b_img};
     GemmBatch gb{};
     single_qkv_batch(gb, p, bs, a, lda, lw, f, ldf, qkn);
     HIP_TRY(launch_gemm(gb, st));
     HIP_TRY(qkv_finish(p, bs, f, ldf, qkn + 128, qkn + 128, qkn, qkn, st));
     return AFX_OK;
   }
-  LinW lw[2];
-  lw[0].w = (const uint16_t*)w_img; lw[0].b = (const uint16_t*)b_img;
-  lw[1].w = (const uint16_t*)w_txt; lw[1].b = (const uint16_t*)b_txt;
+  const LinW lw[2] = {{(const uint16_t*)w_img, (const uint16_t*)b_img}, {(const uint16_t*)w_txt, (const uint16_t*)b_txt}};
   if (p == AFX_QKV_VT_PROJ) {
     for (int b = 0; b < B; ++b) {
       GemmBatch gb{};
@@ -1252,44 +982,6 @@ int afx_qkv_operands(int32_t kind, const void* A, int64_t lda, const void* w_img
     }
   HIP_TRY(launch_gemm(gb, st));
   HIP_TRY(qkv_finish(p, bs, f, ldf, qkn + 3 * 128, qkn + 1 * 128, qkn + 2 * 128, qkn, st));
-  return AFX_OK;
-}
-
-// shared argument checks of the two AdaLN entry points below
-static int norm_joint_args(const char* fn, const void* x, int64_t ldx, int64_t ldo, int32_t rows, int32_t D, const float* scale, const float* shift,
-                           const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S, int32_t n_txt) {
-  if (!x || !scale || !shift || (!scale_txt) != (!shift_txt)) return fail(AFX_E_INVALID, "null argument to %s", fn);
-  if (rows < 0 || D < 8 || D % 8 || D > 4096 || ldx < D || ldx % 8 || ldo < D || ldo % 8 || ldmod < 0 || ldmod % 4 || S < 1 || n_txt < 0 ||
-      n_txt > S || (!scale_txt && n_txt != 0))
-    return fail(AFX_E_INVALID, "%s: need D %% 8 == 0, D <= 4096, ldx / ldo >= D and multiples of 8, ldmod %% 4 == 0, 0 <= n_txt <= S "
-                "(n_txt 0 without text vectors)", fn);
-  if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)scale_txt | (uintptr_t)shift_txt) & 15)
-    return fail(AFX_E_INVALID, "%s: operands must be 16-byte aligned", fn);
-  return AFX_OK;
-}
-
-int afx_norm_modulate_joint_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t rows, int32_t D, const float* scale,
-                                 const float* shift, const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S,
-                                 int32_t n_txt, void* stream) {
-  int r = norm_joint_args("afx_norm_modulate_joint_bf16", x, ldx, ldo, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt);
-  if (r != AFX_OK) return r;
-  if (!out || ((uintptr_t)out & 15)) return fail(AFX_E_INVALID, "afx_norm_modulate_joint_bf16: out null or not 16-byte aligned");
-  HIP_TRY(launch_norm_modulate_joint((const uint16_t*)x, ldx, (uint16_t*)out, ldo, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt,
-                                     (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_norm_modulate_mx8(const void* x, int64_t ldx, void* q8, int64_t ldq, void* mx, int64_t ld_mx, float* rowscale, int32_t rows, int32_t D,
-                          const float* scale, const float* shift, const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S,
-                          int32_t n_txt, int32_t* fused, void* stream) {
-  int r = norm_joint_args("afx_norm_modulate_mx8", x, ldx, ldq, rows, D, scale, shift, scale_txt, shift_txt, ldmod, S, n_txt);
-  if (r != AFX_OK) return r;
-  if (!q8 || !fused || ((uintptr_t)q8 & 7) || (!rowscale && (!mx || ld_mx < (D + 127) / 128 || ld_mx % 4)) || ((uintptr_t)rowscale & 3))
-    return fail(AFX_E_INVALID, "afx_norm_modulate_mx8: need q8 (8-byte aligned), fused, and rowscale or mx with ld_mx >= D / 128, ld_mx %% 4 == 0");
-  bool f = false;
-  HIP_TRY(launch_norm_modulate_mx8((const uint16_t*)x, ldx, (uint8_t*)q8, ldq, (uint8_t*)mx, ld_mx, rows, D, scale, shift, scale_txt, shift_txt,
-                                   ldmod, S, n_txt, (hipStream_t)stream, &f, rowscale));
-  *fused = f ? 1 : 0;
   return AFX_OK;
 }
 

@@ -316,101 +316,12 @@ int afx_rope_half_bf16(void* x, int64_t ldx, const float* cos_t, const float* si
   return AFX_OK;
 }
 
-int afx_quant_rows_fp8(const void* x, int64_t ldx, void* q, int64_t ldq, float* scale, int32_t rows, int32_t K, void* stream) {
-  if (!x || !q || !scale || rows < 1 || K % 8 || ldx % 8 || ldq % 8) return fail(AFX_E_INVALID, "bad argument to afx_quant_rows_fp8");
-  HIP_TRY(launch_quant_rows_fp8((const uint16_t*)x, ldx, (uint8_t*)q, ldq, scale, rows, K, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_fp8(const void* Aq, int64_t lda, const float* a_scale, const void* Wq, int64_t ldw, const float* w_scale, const void* bias,
-                   void* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t gelu_col0, const float* gate, int64_t ldg,
-                   int32_t rows_per_batch, const void* res, int64_t ldr, void* stream) {
-  if (!Aq || !Wq || !C || !a_scale || !w_scale) return fail(AFX_E_INVALID, "null argument to afx_linear_fp8");
-  if (M < 0 || N < 0 || K <= 0 || K % 128 || N % 8 || lda % 16 || ldw % 16 || ldc % 8 || epi < 0 || epi > 2)
-    return fail(AFX_E_INVALID, "afx_linear_fp8: need K%%128==0, N%%8==0, lda/ldw%%16==0, ldc%%8==0");
-  if (epi == EPI_GATE_RES && (!res || ldr % 8 || (gate && rows_per_batch < 1))) return fail(AFX_E_INVALID, "gated residual epilogue needs res");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)Aq; p.lda = lda; p.W = (const uint16_t*)Wq; p.ldw = ldw; p.bias = (const uint16_t*)bias;
-  p.C = (uint16_t*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epi; p.gelu_col0 = gelu_col0;
-  p.gate = gate; p.ldg = ldg; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.res = (const uint16_t*)res; p.ldr = ldr;
-  p.fp8 = 1; p.a_scale = a_scale; p.w_scale = w_scale;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_quant_rows_mx8(const void* x, int64_t ldx, void* q, int64_t ldq, void* mx, int64_t ld_mx, int32_t rows, int32_t K, void* stream) {
-  if (!x || !q || !mx || rows < 1 || K < 128 || K % 128 || ldx % 8 || ldq % 8 || ld_mx < K / 128)
-    return fail(AFX_E_INVALID, "afx_quant_rows_mx8: need K %% 128 == 0, ldx / ldq %% 8 == 0, ld_mx >= K / 128");
-  HIP_TRY(launch_quant_rows_mx8((const uint16_t*)x, ldx, (uint8_t*)q, ldq, (uint8_t*)mx, ld_mx, rows, K, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_fp8_mx(const void* Aq, int64_t lda, const void* a_mx, int64_t ld_mx, const float* a_scale, const void* Wq, int64_t ldw,
-                      const float* w_scale, const void* bias, void* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi,
-                      int32_t gelu_col0, const float* gate, int64_t ldg, int32_t rows_per_batch, const void* res, int64_t ldr, void* stream) {
-  if (!Aq || !a_mx || !Wq || !C || !a_scale || !w_scale) return fail(AFX_E_INVALID, "null argument to afx_linear_fp8_mx");
-  if (M < 0 || N < 0 || K < 512 || K % 512 || N % 8 || lda % 16 || ldw % 16 || ldc % 8 || ld_mx % 4 || ld_mx < K / 128 || epi < 0 || epi > 2)
-    return fail(AFX_E_INVALID, "afx_linear_fp8_mx: need K%%512==0, N%%8==0, lda/ldw%%16==0, ldc%%8==0, ld_mx%%4==0");
-  if (epi == EPI_GATE_RES && (!res || ldr % 8 || (gate && rows_per_batch < 1))) return fail(AFX_E_INVALID, "gated residual epilogue needs res");
-  if (!gemm_fp8_mx_ok(M, N, K)) return fail(AFX_E_INVALID, "afx_linear_fp8_mx: the block-scaled kernel is switched off (AFX_FP8_V3 / AFX_GEMM_IMPL)");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)Aq; p.lda = lda; p.W = (const uint16_t*)Wq; p.ldw = ldw; p.bias = (const uint16_t*)bias;
-  p.C = (uint16_t*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epi; p.gelu_col0 = gelu_col0;
-  p.gate = gate; p.ldg = ldg; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.res = (const uint16_t*)res; p.ldr = ldr;
-  p.fp8 = 1; p.a_scale = a_scale; p.w_scale = w_scale; p.a_mx = (const uint8_t*)a_mx; p.ld_mx = ld_mx;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_linear_fp8_to_mx8(const void* Aq, int64_t lda, const void* a_mx, int64_t ld_mx, const float* a_scale, const void* Wq, int64_t ldw,
-                          const float* w_scale, const void* bias, void* C, int64_t ldc, void* c8, int64_t ldc8, void* c_mx, int64_t ld_cmx,
-                          int32_t c8_col0, int32_t M, int32_t N, int32_t K, int32_t gelu, void* stream) {
-  if (!Aq || !Wq || !c8 || !c_mx || !a_scale || !w_scale || (c8_col0 > 0 && !C)) return fail(AFX_E_INVALID, "null argument to afx_linear_fp8_to_mx8");
-  if (M < 0 || N < 0 || K < 256 || K % 128 || N % 8 || lda % 16 || ldw % 16 || ldc % 8 || ldc8 % 8 || c8_col0 < 0 || c8_col0 % 128 || c8_col0 >= N ||
-      ld_cmx < (N - c8_col0 + 127) / 128 || (a_mx && (K % 512 || ld_mx % 4 || ld_mx < K / 128)))
-    return fail(AFX_E_INVALID, "afx_linear_fp8_to_mx8: need K%%128==0 (K%%512==0 with block-scaled A), c8_col0%%128==0, ldc8%%8==0");
-  // (the producer epilogue lives in the one-wave-per-SIMD fp8 kernel: the same switches as the block-scaled consumer; K % 512 only binds with a_mx)
-  if (!gemm_fp8_mx_ok(M, N, a_mx ? K : 512)) return fail(AFX_E_INVALID, "afx_linear_fp8_to_mx8: the one-wave-per-SIMD fp8 kernel is switched off");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)Aq; p.lda = lda; p.W = (const uint16_t*)Wq; p.ldw = ldw; p.bias = (const uint16_t*)bias;
-  p.C = (uint16_t*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = gelu ? EPI_GELU : EPI_NONE; p.gelu_col0 = gelu ? c8_col0 : 0;
-  p.rows_per_batch = 1;
-  p.fp8 = 1; p.a_scale = a_scale; p.w_scale = w_scale; p.a_mx = (const uint8_t*)a_mx; p.ld_mx = ld_mx;
-  p.c8 = (uint8_t*)c8; p.ldc8 = ldc8; p.c_mx = (uint8_t*)c_mx; p.ld_cmx = ld_cmx; p.c8_col0 = c8_col0;
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
-  return AFX_OK;
-}
-
 int afx_finish_f32_bf16(const float* partials, int32_t nslab, const void* res, int64_t ldr, void* out, int64_t ldo, int64_t M, int32_t N,
                         void* stream) {
   if (!partials || !out || M < 1 || N % 8 || nslab < 1 || ldo % 8 || (res && ldr % 8)) return fail(AFX_E_INVALID, "bad argument to afx_finish_f32_bf16");
   hipLaunchKernelGGL(finish_f32_kernel, dim3(tblocks(M * (N >> 3))), dim3(256), 0, (hipStream_t)stream, partials, nslab, (const bf16_t*)res,
                      ldr, (bf16_t*)out, ldo, M, N);
   HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int64_t afx_attention_ext_ws_bytes(int32_t B, int32_t Hkv, int32_t S, int32_t head_dim) {
-  return (int64_t)B * Hkv * head_dim * attn_spad(S) * 2;
-}
-
-int afx_attention_ext_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
-                           void* ws, int32_t B, int32_t H, int32_t Hkv, int32_t S, int32_t head_dim, float scale, int32_t causal,
-                           const float* bias, void* stream) {
-  if (!q || !k || !v || !o || !ws || B < 1 || S < 1 || H < 1 || Hkv < 1 || H % Hkv || (head_dim != 64 && head_dim != 128) ||
-      ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || !(scale > 0.f))
-    return fail(AFX_E_INVALID, "afx_attention_ext_bf16: head_dim 64 or 128, H %% Hkv == 0, strides %% 8 == 0, scale > 0");
-  HIP_TRY(launch_attention_ext((const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)ws, (uint16_t*)o,
-                               ldo, B, H, Hkv, S, head_dim, scale, causal, bias, (hipStream_t)stream));
   return AFX_OK;
 }
 

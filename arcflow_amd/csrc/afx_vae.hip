@@ -11,7 +11,7 @@
 
 #include "afx_api_util.h"
 #include "afx_common.h"
-#include "afx_kernels.h"
+#include "afx_gemm_problem.h"
 
 namespace afx {
 
@@ -437,17 +437,10 @@ static int conv3x3_impl(const void* x, const void* w, const void* bias, void* y,
   // (guard band of the shifted taps).  w: [Cout][3][3][Cin] bf16 (tap-major K).  Cin % 64 == 0, Cout % 8 == 0.
   if (!x || !w || !y || H < 1 || W < 1 || Cin < 64 || Cin % 64 || Cout < 8 || Cout % 8)
     return fail(AFX_E_INVALID, "afx_conv3x3_bf16: need Cin %% 64 == 0, Cout %% 8 == 0");
-  GemmBatch gb{};
-  gb.nprob = 1;
-  GemmProblem& p = gb.p[0];
-  p = GemmProblem{};
-  p.A = (const uint16_t*)x; p.lda = Cin; p.W = (const uint16_t*)w; p.ldw = 9 * (int64_t)Cin; p.bias = (const uint16_t*)bias;
-  p.C = (uint16_t*)y; p.ldc = Cout; p.M = (H + 2) * (W + 2); p.N = Cout; p.K = 9 * Cin;
+  GemmProblem p = dense_problem(x, Cin, w, 9 * (int64_t)Cin, bias, y, Cout, (H + 2) * (W + 2), Cout, 9 * Cin);
   p.rows_per_batch = 1 << 30;
   p.conv_cin_tiles = Cin / 64; p.conv_wp = W + 2; p.conv_hp = H + 2;
-  if (res != nullptr) {          // y = res + conv(x): residual epilogue with a unit gate
-    p.epi = EPI_GATE_RES; p.gate = nullptr; p.ldg = 0; p.res = (const uint16_t*)res; p.ldr = Cout;
-  }
+  if (res != nullptr) set_epilogue(p, EPI_GATE_RES, 0, nullptr, 0, 1 << 30, res, Cout);      // y = res + conv(x): residual epilogue with a unit gate
   if (gn_stats != nullptr) {   // GroupNorm sums of y from the epilogue (one-wave-per-SIMD kernel only): [GN_SLOTS][groups][2] doubles, zeroed here
     const int gs = groups > 0 && Cout % groups == 0 ? Cout / groups : 0;
     if (groups < 1 || groups > 64 || gs < 4 || gs % 4 || (gs > 8 && gs % 8) || Cout > 128 || !gemm_conv_stats_available())
@@ -455,7 +448,7 @@ static int conv3x3_impl(const void* x, const void* w, const void* bias, void* y,
     HIP_TRY(hipMemsetAsync(gn_stats, 0, sizeof(double) * 2 * groups * GN_SLOTS, (hipStream_t)stream));
     p.gn_stats = gn_stats; p.gn_gs = Cout / groups; p.gn_groups = groups;
   }
-  HIP_TRY(launch_gemm(gb, (hipStream_t)stream));
+  HIP_TRY(launch_single(p, (hipStream_t)stream));
   return AFX_OK;
 }
 
@@ -482,9 +475,7 @@ int afx_upconv3x3_bf16(const void* x, const void* w4, const void* bias, void* y,
   gb.nprob = 4;
   for (int ph = 0; ph < 4; ++ph) {
     GemmProblem& p = gb.p[ph];
-    p = GemmProblem{};
-    p.A = (const uint16_t*)x; p.lda = Cin; p.W = (const uint16_t*)w4 + (int64_t)ph * Cout * 4 * Cin; p.ldw = 4 * (int64_t)Cin; p.bias = (const uint16_t*)bias;
-    p.C = (uint16_t*)y; p.ldc = Cout; p.M = (H + 2) * (W + 2); p.N = Cout; p.K = 4 * Cin;
+    p = dense_problem(x, Cin, (const uint16_t*)w4 + (int64_t)ph * Cout * 4 * Cin, 4 * (int64_t)Cin, bias, y, Cout, (H + 2) * (W + 2), Cout, 4 * Cin);
     p.rows_per_batch = 1 << 30;
     p.conv_cin_tiles = Cin / 64; p.conv_wp = W + 2; p.conv_hp = H + 2;
     p.up_phase = 1 + ph;

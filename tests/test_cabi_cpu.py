@@ -271,6 +271,37 @@ def test_forward_operand_entry_points_validate_before_launch(lib):
     assert fused.value == 7 and b'afx_norm_modulate_mx8' in lib.afx_last_error()
 
 
+def test_linear_entry_points_refuse_by_their_own_name(lib):
+    """Each afx_linear_* GEMM entry and both afx_linear_tn_f32out* refuse a null operand, a K one element off its multiple (64 bf16, 128 fp8,
+    512 block-scaled; the TN product has no K rule: its width N1, a multiple of 8, stands in) and a leading dimension one element off its
+    multiple with AFX_E_INVALID, and afx_last_error() names the entry that was called.  Every call carries exactly one defect and fake but
+    aligned pointers: validation returns before any launch."""
+    from arcflow_amd import _lib
+    p = lambda: C.c_void_p(1 << 20)         # noqa: E731
+    M, N = 264, 136
+    entries = {      # name -> (K, call(A, K, lda)); ldw stays at the good K
+        'afx_linear_bf16': (128, lambda A, K, lda: lib.afx_linear_bf16(A, lda, p(), 128, p(), p(), N, M, N, K, 0, 0, None, 0, 1, None, 0, None)),
+        'afx_linear_bf16_pre': (128, lambda A, K, lda: lib.afx_linear_bf16_pre(A, lda, p(), 128, p(), p(), N, M, N, K, 0, 0, None, 0, 1, None, 0,
+                                                                                  p(), N, None)),
+        'afx_linear_bf16_f32out': (128, lambda A, K, lda: lib.afx_linear_bf16_f32out(A, lda, p(), 128, p(), N, M, N, K, 0, None)),
+        'afx_linear_bf16_splitk': (128, lambda A, K, lda: lib.afx_linear_bf16_splitk(A, lda, p(), 128, p(), p(), M, N, K, 0, None)),
+        'afx_linear_bf16_dropres': (128, lambda A, K, lda: lib.afx_linear_bf16_dropres(A, lda, p(), 128, p(), N, M, N, K, p(), N, 0.05, 1, 0, None)),
+        'afx_linear_fp8': (128, lambda A, K, lda: lib.afx_linear_fp8(A, lda, p(), p(), 128, p(), p(), p(), N, M, N, K, 0, 0, None, 0, 1, None, 0,
+                                                                        None)),
+        'afx_linear_fp8_mx': (512, lambda A, K, lda: lib.afx_linear_fp8_mx(A, lda, p(), 4, p(), p(), 512, p(), p(), p(), N, M, N, K, 0, 0, None, 0, 1,
+                                                                              None, 0, None)),
+        'afx_linear_fp8_to_mx8': (512, lambda A, K, lda: lib.afx_linear_fp8_to_mx8(A, lda, p(), 4, p(), p(), 512, p(), p(), p(), N, p(), N, p(), 4, 0,
+                                                                                      M, N, K, 0, None)),
+        'afx_linear_tn_f32out': (128, lambda X, N1, ldx: lib.afx_linear_tn_f32out(X, ldx, p(), N, p(), N, M, N1, N, 0, None)),
+        'afx_linear_tn_f32out_ws': (128, lambda X, N1, ldx: lib.afx_linear_tn_f32out_ws(X, ldx, p(), N, p(), N, M, N1, N, 0, None, None)),
+    }
+    assert set(entries) == {n for n in _lib.PROTOTYPES if n.startswith('afx_linear_') and not n.endswith(('_ws_bytes', '_chunks'))}
+    for name, (K, call) in entries.items():
+        for defect, args in (('null operand', (None, K, K)), ('K + 1', (p(), K + 1, K + 8 if '_tn_' in name else K)), ('lda + 1', (p(), K, K + 1))):
+            assert call(*args) == _lib.AFX_E_INVALID, (name, defect)
+            assert name.encode() in lib.afx_last_error() and (name + '_').encode() not in lib.afx_last_error(), (name, defect, lib.afx_last_error())
+
+
 def test_schedule_matches_oracle_and_golden(golden):
     from arcflow_amd.schedule import FlowMatchEulerDiscreteScheduler, retrieve_raw_timesteps
     from oracle import arcflow_ref as R

@@ -31,7 +31,7 @@ import math
 
 import pytest
 import torch
-from bf16_parity import U32, check_bf16, gelu64, proj64
+from bf16_parity import U32, check_bf16, check_f32, gelu64, proj64
 
 pytestmark = pytest.mark.gpu
 
@@ -163,6 +163,67 @@ def test_linear_vs_fp64_every_mode(ops, cid, M, K, N, epi, opt):
     # teeth: the per-element bound against the reference without the last K column fails
     yd = y - a[:, K - 1].double()[:, None] * w[:, K - 1].double()[None, :]
     _teeth(out, ref, _epi_ref(yd, e, epi, col0, gate_rows, r)[0], fl, cid)
+
+
+# The two linear entry points no Python wrapper calls (ops.linear goes through afx_linear_bf16_pre, ops.linear_tn_f32out through the _ws entry),
+# straight through the C ABI at the smallest shape that spans a tile edge and leaves a ragged row tile.
+EDGE_M, EDGE_N, EDGE_K = 264, 136, 128
+
+
+def test_afx_linear_bf16_entry_vs_fp64(ops):
+    """afx_linear_bf16 itself (bias, no epilogue) in all eight GEMM modes: the bound and the equal share of the cases above, then the teeth check."""
+    from arcflow_amd import _lib
+    lib = _lib.load()
+    M, N, K = EDGE_M, EDGE_N, EDGE_K
+    g = _gen(M * 7 + K * 3 + N)
+    a = (torch.randn(M, K, generator=g, device='cuda') * 1.2 + 0.1).bfloat16()
+    w = (torch.randn(N, K, generator=g, device='cuda') * K ** -0.5).bfloat16()
+    b = (torch.randn(N, generator=g, device='cuda') * 0.2).bfloat16()
+    ref, fl = proj64(a, w, b)
+    buf, out = _guarded(M, N)
+    try:
+        for mode in GEMM_MODES:
+            ops.set_gemm_mode(*mode)
+            out.fill_(SENT)
+            _lib.check(lib.afx_linear_bf16(ops._p(a), a.stride(0), ops._p(w), w.stride(0), ops._p(b), ops._p(out), out.stride(0), M, N, K, 0, 0, None, 0, 1,
+                                           None, 0, ops._s()))
+            torch.cuda.synchronize()
+            what = f'afx_linear_bf16 {M}x{N}x{K} mode={mode}'
+            _unchanged(buf, M, N, what)
+            check_bf16(out, ref, floor=fl, what=what)
+    finally:
+        ops.set_gemm_mode(3, 0)
+    _teeth(out, ref, ref - a[:, K - 1].double()[:, None] * w[:, K - 1].double()[None, :], fl, 'afx_linear_bf16')
+
+
+def test_afx_linear_tn_f32out_entry_vs_fp64(ops):
+    """afx_linear_tn_f32out itself (no workspace: one work-group per tile): C [N, K] = X^T Y over M tokens, X [M, N], Y [M, K].  The output is fp32, so the
+    bound is the product's floor F of the cases above (proj64 over the M-deep sum) plus the fp32 rounding of the stored value, 2^-24 |y|, where
+    those cases allow one bf16 ulp; then the accumulate mode with the add's rounding on top, and the bound against a reference without the last
+    token fails."""
+    from arcflow_amd import _lib
+    lib = _lib.load()
+    M, N1, N2 = EDGE_M, EDGE_N, EDGE_K
+    g = _gen(M * 7 + N2 * 3 + N1)
+    x = (torch.randn(M, N1 + 64, generator=g, device='cuda') * 1.2 + 0.1).bfloat16()[:, 32:32 + N1]      # views: row stride != width
+    y = (torch.randn(M, N2 + 8, generator=g, device='cuda') * M ** -0.5).bfloat16()[:, 8:8 + N2]
+    ref, fl = proj64(x.T, y.T, None)
+    buf = torch.full((N1 + 16, N2 + 128), SENT, dtype=torch.float32, device='cuda')
+    out = buf[8:8 + N1, 64:64 + N2]
+
+    def run(accumulate):
+        _lib.check(lib.afx_linear_tn_f32out(ops._p(x), x.stride(0), ops._p(y), y.stride(0), ops._p(out), out.stride(0), M, N1, N2, accumulate, ops._s()))
+        torch.cuda.synchronize()
+        _unchanged(buf, N1, N2, f'afx_linear_tn_f32out accumulate={accumulate}')
+    run(0)
+    bound = fl + U32 * ref.abs()
+    check_f32(out, ref, bound, what='afx_linear_tn_f32out')
+    with pytest.raises(AssertionError, match='beyond the bound'):
+        check_f32(out, ref - x[M - 1].double()[:, None] * y[M - 1].double()[None, :], bound, what='afx_linear_tn_f32out: last token dropped')
+    c0 = torch.randn(N1, N2, generator=g, device='cuda')
+    out.copy_(c0)
+    run(1)
+    check_f32(out, c0.double() + ref, bound + U32 * (c0.double() + ref).abs(), what='afx_linear_tn_f32out accumulate')
 
 
 # ------------------------------------------------------------------------------------------------ fp8
