@@ -64,13 +64,6 @@ __global__ __launch_bounds__(256) void edit_blend_kernel(const float* x, const f
 
 using namespace afx;
 
-// [a, a + an) and [b, b + bn) share a byte (a null range shares nothing)
-static inline bool ranges_overlap(const void* a, int64_t an, const void* b, int64_t bn) {
-  if (a == nullptr || b == nullptr) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + (uintptr_t)bn && pb < pa + (uintptr_t)an;
-}
-
 extern "C" {
 
 int afx_edit_blend(const float* x, const float* x0, const float* noise, const float* mask, const float* sigma_to, float* x_out,

@@ -9,6 +9,8 @@
 //     an fp32 operand drawn by torch, so that a torch.Generator reproduces the run.  Traffic at 1024 x 1024 (4096 tokens x 64
 //     channels = 262144 elements per image): 4 (x) + 2 (pos) + 2 (neg) + 4 (z) B read and 4 (x') + 2 (bf16 x') B written per
 //     element = 18 B, about 4.7 MB per image and step.
+//   * teacher_edit_step_kernel<SDE>: either step + the inpainting blend of afx_edit.hip at the sigma the step lands on + the bf16 copy,
+//     in one pass of the same shape (teacher image-to-image / inpainting); formula and traffic at the kernel.
 //   * cfg_ortho_partial_kernel / cfg_ortho_finish_kernel: the per-sample projection coefficient of orthogonal guidance,
 //     mean(bias pos) / max(mean(pos pos), 1e-6) over all n elements of a sample.  A fixed number of work-groups per sample
 //     (a function of n alone), every product exact in fp64, one workspace slot per work-group, the slots added in index order
@@ -100,6 +102,85 @@ __global__ __launch_bounds__(256) void teacher_sde_step_kernel(const float* x, c
       float mix = mb * eps;
       if (noise != nullptr) mix = mix + cn * (e < 4 ? z0[e & 3] : z1[e & 3]);
       o[e] = alpha_to * clean + sg_to * mix;
+    }
+    const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
+    *reinterpret_cast<f32x4_t*>(x_out + c * 8 + 4) = o1;
+    *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
+  }
+}
+
+// The step of teacher image editing (image-to-image / inpainting with the many-step sampler): the Euler (SDE = false) or FlowSDE
+// (SDE = true) update with the CFG combine, written as the two kernels above write it and rounded to fp32, then the re-imposition of
+// the known region at the sigma the step lands on, in edit_blend_kernel's own forms (afx_edit.hip):
+//   x'    = the step above                                              (fp32)
+//   om    = 1 - sigma_to[b]
+//   known = noise0 ? fma(sigma_to[b], noise0, om x0) : om x0
+//   x_out = fma(m, x', (1 - m) known)                                   m = mask[b, tok, e & 3], 1 = repaint, 0 = keep the source
+// so that the outputs are, bit for bit, those of the step kernel followed by edit_blend_kernel on its result.  One chunk = 8 consecutive
+// elements of one token (64 channels per token), one 16-byte load of the token's mask row per chunk as in edit_blend_kernel.  Traffic
+// per element at 1024 x 1024: 4 (x) + 2 (pos) + 2 (neg) [+ 4 (z), SDE] + 4 (x0) + 4 (noise0) B read, 16 B of mask per token (0.25 B), 4 (x') +
+// 2 (bf16 x') B written = 22.25 B (SDE 26.25 B); the two launches it replaces move 14 (18) + 18.25 B: the fused step saves the fp32
+// write and re-read of x', the first bf16 copy (10 B per element) and a launch.
+template <bool SDE>
+__global__ __launch_bounds__(256) void teacher_edit_step_kernel(const float* x, const bf16_t* __restrict__ pos, const bf16_t* __restrict__ neg,
+                                                                const float* __restrict__ noise, const float* __restrict__ sigma,
+                                                                const float* __restrict__ sigma_to, const float* __restrict__ m,
+                                                                const float* __restrict__ c_noise, const float* __restrict__ coef, float scale,
+                                                                const float* __restrict__ x0, const float* __restrict__ noise0,
+                                                                const float* __restrict__ mask, float* x_out, bf16_t* __restrict__ x_bf16,
+                                                                int64_t chunks_per_sample, int64_t chunks) {
+  const float sm1 = scale - 1.0f;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += stride) {
+    const int64_t b = c / chunks_per_sample;
+    const float sg = sigma[b], sg_to = sigma_to[b];
+    const float cf = coef != nullptr ? coef[b] : 0.f;
+    float p[8], q[8], o[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(pos + c * 8), p);
+    if (neg != nullptr) unpack8(*reinterpret_cast<const u32x4_t*>(neg + c * 8), q);
+    const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(x + c * 8);        // (x_out may be x: every load precedes every store)
+    const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(x + c * 8 + 4);
+    const f32x4_t a0 = *reinterpret_cast<const f32x4_t*>(x0 + c * 8);
+    const f32x4_t a1 = *reinterpret_cast<const f32x4_t*>(x0 + c * 8 + 4);
+    const f32x4_t mk = *reinterpret_cast<const f32x4_t*>(mask + (c >> 3) * 4);
+    f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = z0, n0 = z0, n1 = z0;
+    if (SDE && noise != nullptr) {
+      z0 = *reinterpret_cast<const f32x4_t*>(noise + c * 8);
+      z1 = *reinterpret_cast<const f32x4_t*>(noise + c * 8 + 4);
+    }
+    if (noise0 != nullptr) {
+      n0 = *reinterpret_cast<const f32x4_t*>(noise0 + c * 8);
+      n1 = *reinterpret_cast<const f32x4_t*>(noise0 + c * 8 + 4);
+    }
+    if constexpr (SDE) {            // teacher_sde_step_kernel's update
+      const float mb = m[b], cn = c_noise[b];
+      const float alpha = 1.0f - sg, alpha_to = 1.0f - sg_to;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float u = cfg_velocity(p, q, e, neg != nullptr, coef != nullptr, sm1, cf);
+        const float xe = e < 4 ? v0[e & 3] : v1[e & 3];
+        const float clean = xe - sg * u;
+        const float eps = xe + alpha * u;
+        float mix = mb * eps;
+        if (noise != nullptr) mix = mix + cn * (e < 4 ? z0[e & 3] : z1[e & 3]);
+        o[e] = alpha_to * clean + sg_to * mix;
+      }
+    } else {                        // teacher_euler_step_kernel's update
+      const float dt = sg_to - sg;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float u = cfg_velocity(p, q, e, neg != nullptr, coef != nullptr, sm1, cf);
+        o[e] = (e < 4 ? v0[e & 3] : v1[e & 3]) + u * dt;
+      }
+    }
+    const float om = 1.0f - sg_to;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {   // edit_blend_kernel's blend, on the step's fp32 result
+      float known = om * (e < 4 ? a0[e & 3] : a1[e & 3]);
+      if (noise0 != nullptr) known = __builtin_fmaf(sg_to, e < 4 ? n0[e & 3] : n1[e & 3], known);
+      const float mm = mk[e & 3];
+      o[e] = __builtin_fmaf(mm, o[e], (1.0f - mm) * known);
     }
     const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
     *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
@@ -278,6 +359,78 @@ int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const
                      noise, sigma, sigma_to, m, c_noise, coef, scale, x_out, (bf16_t*)x_out_bf16, cps, chunks);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
+}
+
+}  // extern "C"
+
+// Both edit-step entries: the refusals (before any launch), then mask == NULL -> the plain step entry itself, else the fused kernel.
+// sde = false: the Euler step (noise, m, c_noise are NULL and unused).
+static int edit_step(const char* name, bool sde, const float* x, const void* pos, const void* neg, const float* noise, const float* sigma,
+                     const float* sigma_to, const float* m, const float* c_noise, const float* coef, float scale, const float* x0,
+                     const float* noise0, const float* mask, float* x_out, void* x_out_bf16, int32_t batch, int32_t n_tok, int32_t ch,
+                     int32_t max_blocks, void* stream) {
+  if (!x || !pos || !sigma || !sigma_to || (sde && (!m || !c_noise)) || !x0 || !x_out || !x_out_bf16)
+    return fail(AFX_E_INVALID, "null argument to %s (only neg, noise, coef, noise0 and mask may be NULL)", name);
+  if (ch != 64) return fail(AFX_E_INVALID, "%s: ch must be 64 (16 latent channels x the 2 x 2 patch), got %d", name, (int)ch);
+  if (batch < 1 || n_tok < 1 || max_blocks < 0)
+    return fail(AFX_E_INVALID, "bad argument to %s (batch and n_tok must be >= 1, max_blocks >= 0)", name);
+  if (((uintptr_t)x & 15) || ((uintptr_t)pos & 15) || ((uintptr_t)neg & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)x0 & 15) ||
+      ((uintptr_t)noise0 & 15) || ((uintptr_t)mask & 15) || ((uintptr_t)x_out & 15) || ((uintptr_t)x_out_bf16 & 15))
+    return fail(AFX_E_INVALID, "%s: x, pos, neg, noise, x0, noise0, mask, x_out and x_out_bf16 must be 16-byte aligned", name);
+  const int64_t elems = (int64_t)batch * n_tok * 64;
+  const int64_t fbytes = elems * 4, hbytes = elems * 2, mbytes = (int64_t)batch * n_tok * 16, sbytes = (int64_t)batch * 4;
+  // every lane reads its own 8 elements before it writes them, so x_out == x is safe; any other overlap lets one lane's store
+  // land in another lane's load
+  const void* fin[] = {x, noise, x0, noise0};
+  const void* sin[] = {sigma, sigma_to, m, c_noise, coef};
+  bool out_hit = x != x_out && ranges_overlap(x_out, fbytes, x, fbytes), bf_hit = false;
+  for (int i = 0; i < 4; ++i) {
+    if (i > 0) out_hit = out_hit || ranges_overlap(x_out, fbytes, fin[i], fbytes);
+    bf_hit = bf_hit || ranges_overlap(x_out_bf16, hbytes, fin[i], fbytes);
+  }
+  for (const void* s : sin) {
+    out_hit = out_hit || ranges_overlap(x_out, fbytes, s, sbytes);
+    bf_hit = bf_hit || ranges_overlap(x_out_bf16, hbytes, s, sbytes);
+  }
+  out_hit = out_hit || ranges_overlap(x_out, fbytes, pos, hbytes) || ranges_overlap(x_out, fbytes, neg, hbytes) ||
+            ranges_overlap(x_out, fbytes, mask, mbytes) || ranges_overlap(x_out, fbytes, x_out_bf16, hbytes);
+  bf_hit = bf_hit || ranges_overlap(x_out_bf16, hbytes, pos, hbytes) || ranges_overlap(x_out_bf16, hbytes, neg, hbytes) ||
+           ranges_overlap(x_out_bf16, hbytes, mask, mbytes);
+  if (out_hit) return fail(AFX_E_INVALID, "%s: x_out overlaps another operand (only x_out == x is allowed)", name);
+  if (bf_hit) return fail(AFX_E_INVALID, "%s: x_out_bf16 overlaps an input", name);
+  const int64_t n = (int64_t)n_tok * 64;
+  if (mask == nullptr)            // nothing to re-impose: the plain step, the very kernel the plain sampler runs
+    return sde ? afx_teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, scale, x_out, x_out_bf16, batch, n, max_blocks, stream)
+               : afx_teacher_euler_step(x, pos, neg, sigma, sigma_to, coef, scale, x_out, x_out_bf16, batch, n, max_blocks, stream);
+  const int64_t cps = n / 8, chunks = cps * batch;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;          // as afx_teacher_euler_step: 8 work-groups per CU
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
+  if (sde)
+    hipLaunchKernelGGL(teacher_edit_step_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos, (const bf16_t*)neg,
+                       noise, sigma, sigma_to, m, c_noise, coef, scale, x0, noise0, mask, x_out, (bf16_t*)x_out_bf16, cps, chunks);
+  else
+    hipLaunchKernelGGL(teacher_edit_step_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos, (const bf16_t*)neg,
+                       (const float*)nullptr, sigma, sigma_to, (const float*)nullptr, (const float*)nullptr, coef, scale, x0, noise0, mask, x_out,
+                       (bf16_t*)x_out_bf16, cps, chunks);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" {
+
+int afx_teacher_edit_step(const float* x, const void* pos, const void* neg, const float* sigma, const float* sigma_to, const float* coef,
+                          float scale, const float* x0, const float* noise0, const float* mask, float* x_out, void* x_out_bf16,
+                          int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks, void* stream) {
+  return edit_step("afx_teacher_edit_step", false, x, pos, neg, nullptr, sigma, sigma_to, nullptr, nullptr, coef, scale, x0, noise0, mask, x_out,
+                   x_out_bf16, batch, n_tok, ch, max_blocks, stream);
+}
+
+int afx_teacher_sde_edit_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma, const float* sigma_to,
+                              const float* m, const float* c_noise, const float* coef, float scale, const float* x0, const float* noise0,
+                              const float* mask, float* x_out, void* x_out_bf16, int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks,
+                              void* stream) {
+  return edit_step("afx_teacher_sde_edit_step", true, x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, scale, x0, noise0, mask, x_out,
+                   x_out_bf16, batch, n_tok, ch, max_blocks, stream);
 }
 
 int64_t afx_cfg_ortho_ws_bytes(int32_t batch, int64_t n) {

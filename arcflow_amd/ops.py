@@ -605,6 +605,59 @@ def edit_blend(x, x0, noise, mask, sigma_to, out: Optional[torch.Tensor] = None,
     return out, out_bf16
 
 
+def _edit_step_operands(x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16):
+    """The operands both edit steps share, checked: -> (x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch)."""
+    if x.dim() != 3:
+        raise ValueError(f'x: need packed tokens [B, N, 64], got {tuple(x.shape)}')
+    B, N, ch = x.shape
+    x = _packed(x, torch.float32, x.shape, 'x')
+    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
+    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
+    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
+    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    x0 = _packed(x0, torch.float32, x.shape, 'x0')
+    noise0 = None if noise0 is None else _packed(noise0, torch.float32, x.shape, 'noise0')
+    mask = None if mask is None else _packed(mask, torch.float32, (B, N, 4), 'mask')
+    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
+    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    return x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch
+
+
+def teacher_edit_step(x, pos, neg, sigma, sigma_to, x0, noise0, mask, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
+    """One Euler step of teacher image editing in one launch (afx_teacher_edit_step): teacher_euler_step's x', then with
+    known = (1 - sigma_to[b]) x0 + sigma_to[b] noise0 the blend mask x' + (1 - mask) known of edit_blend -> (fp32 latents, their bf16
+    rounding), bit for bit teacher_euler_step followed by edit_blend.  x, x0, noise0 (None: no noise term, the step landing on
+    sigma_to = 0) [B, N, 64] fp32 packed tokens; mask [B, N, 4] fp32 in [0, 1], 1 = repaint (None: the plain step, the same kernel as
+    teacher_euler_step); the other operands as for teacher_euler_step.  out may be x (in place).  Nothing is copied or cast."""
+    lib = _lib.load()
+    _gpu(x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16)
+    x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch = _edit_step_operands(
+        x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16)
+    _lib.check(lib.afx_teacher_edit_step(_p(x), _p(pos), _p(neg), _p(sigma), _p(sigma_to), _p(coef), scale, _p(x0), _p(noise0), _p(mask),
+                                         _p(out), _p(out_bf16), B, N, ch, max_blocks, _s()))
+    return out, out_bf16
+
+
+def teacher_sde_edit_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, x0, noise0, mask, scale: float = 1.0,
+                          coef: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None,
+                          max_blocks: int = 0):
+    """One FlowSDE step of teacher image editing in one launch (afx_teacher_sde_edit_step): teacher_sde_step's x' with the step's draw
+    ``noise``, then edit_blend's blend with the START noise ``noise0`` as in teacher_edit_step -> (fp32 latents, their bf16 rounding),
+    bit for bit teacher_sde_step followed by edit_blend.  Operands as for teacher_sde_step and teacher_edit_step."""
+    lib = _lib.load()
+    _gpu(x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, x0, noise0, mask, out, out_bf16)
+    x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch = _edit_step_operands(
+        x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16)
+    noise = None if noise is None else _packed(noise, torch.float32, x.shape, 'noise')
+    m = _packed(m, torch.float32, (B,), 'm')
+    c_noise = _packed(c_noise, torch.float32, (B,), 'c_noise')
+    _lib.check(lib.afx_teacher_sde_edit_step(_p(x), _p(pos), _p(neg), _p(noise), _p(sigma), _p(sigma_to), _p(m), _p(c_noise), _p(coef), scale,
+                                             _p(x0), _p(noise0), _p(mask), _p(out), _p(out_bf16), B, N, ch, max_blocks, _s()))
+    return out, out_bf16
+
+
 def head_grad(d_means, d_logw, d_logg, logw_out, ldy: int):
     lib = _lib.load()
     B, N, K, ch = d_means.shape

@@ -317,16 +317,24 @@ class _PipelineBase(ArcFlowLoaderMixin):
                     terminal_sigma=c.get('shift_terminal') or None)
 
     def _sample_teacher(self, cond, batch, height, width, num_inference_steps, guidance_scale, true_cfg_scale, generator, latents,
-                        guidance_interval, orthogonal_guidance, sampler='FlowEulerODE', h=None):
+                        guidance_interval, orthogonal_guidance, sampler='FlowEulerODE', h=None, edit=None):
+        """-> (latents, hp, wp, edit).  ``edit`` (from ``_edit_inputs``; None: from pure noise) is prepared as ``__call__`` prepares it and
+        reaches TeacherSampler as ``x0`` / ``mask`` / ``strength``; ``latents`` / ``generator`` give the start noise either way."""
         from ..teacher import TeacherSampler
         engine = self._teacher_engine()
         latents, hp, wp = self._prepare_latents(batch, height, width, generator, latents)
         cond = dict(cond, hp=hp, wp=wp)
+        kw = {}
+        if edit is not None:
+            edit = self._edit_prepare(edit, batch, hp, wp)
+            if tuple(latents.shape) != tuple(edit['x0'].shape):
+                raise ValueError(f'`latents` (the start noise) is {tuple(latents.shape)}, the image latents are {tuple(edit["x0"].shape)}')
+            kw = dict(x0=edit['x0'], mask=edit.get('mask_tokens'), strength=edit['strength'])
         sampler = TeacherSampler(engine, num_inference_steps, guidance_scale=true_cfg_scale, distilled_guidance=guidance_scale,
                                  guidance_interval=guidance_interval, orthogonal_guidance=orthogonal_guidance, tokens_as_seq_len=True,
                                  sampler=sampler, **({} if h is None else dict(h=h)), **self._euler_scheduler_kwargs())
         self._num_timesteps = num_inference_steps
-        return sampler(cond, latents, generator=generator), hp, wp          # (the generator's stream continues from the start noise into FlowSDE's step draws)
+        return sampler(cond, latents, generator=generator, **kw), hp, wp, edit          # (the generator's stream continues from the start noise into FlowSDE's step draws)
 
     def _unpack(self, latents, hp, wp):
         b = latents.shape[0]
@@ -533,7 +541,8 @@ class ArcFluxPipeline(_PipelineBase):
                        negative_pooled_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = 'pil',
                        return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
-                       h: Optional[Union[float, str]] = None):
+                       h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
+                       strength: float = 1.0, mask_image=None, composite: bool = True):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
@@ -542,7 +551,16 @@ class ArcFluxPipeline(_PipelineBase):
         after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's
         own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
         transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the
-        adapter weights of ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s."""
+        adapter weights of ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.
+
+        ``image`` / ``image_latents``, ``strength``, ``mask_image`` and ``composite`` are ``__call__``'s, validated and prepared by the
+        same code: the teacher's image-to-image and inpainting, the many-step reference for the student's edits.  Unlike the student
+        (which takes all its steps over [strength, 0]) the teacher walks a SUFFIX of its ``num_inference_steps`` schedule: t_start =
+        int(max(n - min(n strength, n), 0)), start on the image noised to sigmas[t_start], steps t_start .. n - 1 run
+        (``schedule.truncate_by_strength``); with a mask every step also puts the unmasked latent pixels back on the image's own
+        trajectory with the start noise (fused into the step kernel, ``afx_teacher_edit_step``).  These follow diffusers' img2img /
+        inpaint pipelines as recalled; the reference has no image-conditioned sampling and nothing pins them."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -561,6 +579,6 @@ class ArcFluxPipeline(_PipelineBase):
             if ne.shape[0] != pe.shape[0]:
                 raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
             cond.update(negative_prompt_embeds=ne, negative_pooled=npooled)
-        out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
-                                           generator, latents, guidance_interval, orthogonal_guidance, sampler, h)
-        return self._finish(out, hp, wp, output_type, return_dict)
+        out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
+                                                 generator, latents, guidance_interval, orthogonal_guidance, sampler, h, edit)
+        return self._finish(out, hp, wp, output_type, return_dict, edit, composite)

@@ -197,7 +197,8 @@ class ArcQwenImagePipeline(_PipelineBase):
                        negative_prompt_embeds_mask: Optional[torch.Tensor] = None, output_type: Optional[str] = 'pil',
                        return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
-                       h: Optional[Union[float, str]] = None):
+                       h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
+                       strength: float = 1.0, mask_image=None, composite: bool = True):
         """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
         ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
@@ -205,7 +206,10 @@ class ArcQwenImagePipeline(_PipelineBase):
         noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator`` after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a
         teacher engine is built once from the kept base weights, which holds a SECOND copy of the transformer on the GPU
         (Qwen-Image: about 41 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the adapter weights of
-        ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s."""
+        ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.  ``image`` / ``image_latents``,
+        ``strength``, ``mask_image`` and ``composite``: the teacher's image-to-image and inpainting, as on
+        ``ArcFluxPipeline.sample_teacher`` (a suffix of the schedule chosen by ``strength``; unpinned semantics)."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -226,6 +230,6 @@ class ArcQwenImagePipeline(_PipelineBase):
             if ne.shape[0] != pe.shape[0]:
                 raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
             cond['negative_prompt_embeds'] = ne
-        out, hp, wp = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
-                                           latents, guidance_interval, orthogonal_guidance, sampler, h)
-        return self._finish(out, hp, wp, output_type, return_dict)
+        out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
+                                                 latents, guidance_interval, orthogonal_guidance, sampler, h, edit)
+        return self._finish(out, hp, wp, output_type, return_dict, edit, composite)

@@ -48,6 +48,27 @@ def edit_raw_timesteps(num_inference_steps: int, total_substeps: int, timestep_r
     return times, per_step, total
 
 
+def truncate_by_strength(sigmas: torch.Tensor, strength: float) -> Tuple[int, torch.Tensor]:
+    """The schedule of a many-step edit (``sample_teacher(image=..., strength=...)``, TeacherSampler with ``x0``): a suffix of the
+    sampler's FULL schedule ``sigmas`` [n + 1] (trailing 0; shift / dynamic shifting already applied for all n steps), as the
+    image-to-image pipelines of diffusers truncate theirs (as recalled; unpinned):
+
+        init = min(n * strength, n),   t_start = int(max(n - init, 0)),   steps t_start .. n - 1 run
+
+    -> (t_start, sigmas[t_start:]): the edit starts from the source noised to ``sigmas[t_start]``.  ``strength`` must lie in (0, 1];
+    1.0 keeps all n steps, and a strength so small that no step is left raises like one outside the interval."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f'strength must be in (0, 1], got {strength}')
+    n = int(sigmas.numel()) - 1
+    if n < 1:
+        raise ValueError('sigmas: need at least one step (two entries)')
+    t_start = int(max(n - min(n * strength, n), 0))
+    if t_start >= n:
+        raise ValueError(f'strength {strength} leaves none of the {n} steps to run')
+    return t_start, sigmas[t_start:]
+
+
 def mask_to_tokens(mask: torch.Tensor, hp: int, wp: int, reduce: str = 'max') -> torch.Tensor:
     """An image-resolution mask [B, 1, H, W] or [B, H, W] with H = 16 hp, W = 16 wp -> [B, hp*wp, 4] fp32, the operand of
     ``ops.edit_blend``: latent pixel (2r + ph, 2c + pw) of token r*wp + c, at index ph*2 + pw, takes the max (``reduce='max'``: any

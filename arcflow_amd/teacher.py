@@ -8,6 +8,12 @@ orthogonal guidance (``afx_cfg_ortho_coef``, orthogonal only) and ONE step kerne
 ``afx_teacher_sde_step``) that combines the two bf16 velocities, advances the fp32 latents in place and writes the bf16 copy the next
 forward reads.  No torch arithmetic runs inside the loop -- with FlowSDE, nothing but the step's N(0, 1) draw, which stays torch's so
 that a ``torch.Generator`` reproduces a run; the latents never leave the packed token layout.
+
+Image editing (``x0=``, ``mask=``, ``strength=``): the same loop over a suffix of the schedule, started on the source
+latents noised to the suffix's first sigma (``afx_edit_blend``); with a mask the step kernel is ``afx_teacher_edit_step`` /
+``afx_teacher_sde_edit_step``, which also puts the kept region back on the source's own trajectory at the sigma the step lands on --
+still one launch per step.  The reference has no image-conditioned sampling: these semantics follow the image-to-image / inpainting
+pipelines of diffusers as recalled and are not pinned by a fixture.
 """
 from __future__ import annotations
 
@@ -17,13 +23,14 @@ import torch
 
 from . import ops
 from .engine import MMDiTEngine
-from .schedule import FlowEulerODEScheduler, FlowSDEScheduler
+from .schedule import FlowEulerODEScheduler, FlowSDEScheduler, truncate_by_strength
 
 SAMPLERS = {'FlowEulerODE': FlowEulerODEScheduler, 'FlowSDE': FlowSDEScheduler}
 
 
 class TeacherSampler:
-    """``sampler(cond, noise, generator=None, step_noise=None) -> latents``: noise / latents [B, N, C] fp32 packed tokens.
+    """``sampler(cond, noise, generator=None, step_noise=None, x0=None, mask=None, strength=1.0) -> latents``: noise / latents
+    [B, N, C] fp32 packed tokens.
 
     engine: a ``teacher_head=True`` MMDiTEngine.
     cond: ``prompt_embeds`` [B, T, joint] (+ ``pooled`` for FLUX), ``hp``, ``wp``, and for true CFG ``negative_prompt_embeds``
@@ -39,7 +46,17 @@ class TeacherSampler:
     sampler: 'FlowEulerODE' (the default) or 'FlowSDE', the scheduler class as the reference's ``test_cfg['sampler']`` names it;
     FlowSDE's ``h`` (a float or 'inf') travels in scheduler_kwargs.  With FlowSDE every step takes a fresh N(0, 1) draw of the latents'
     shape: from ``generator`` (one torch.randn per step, also on the steps whose draw is not read, so that the generator advances as in
-    the reference), or from ``step_noise`` [num_steps, B, N, C].  With FlowEulerODE both are accepted and ignored."""
+    the reference), or from ``step_noise`` [num_steps, B, N, C].  With FlowEulerODE both are accepted and ignored.
+
+    Editing.  ``x0`` [B, N, 64] fp32, the packed latents of a source image, starts the roll from the image instead of from noise:
+    with ``sigmas`` the full schedule of ``num_steps`` = n steps, ``schedule.truncate_by_strength`` gives t_start = int(max(n -
+    min(n strength, n), 0)); the roll starts on (1 - s) x0 + s noise, s = sigmas[t_start] (at s = 1 that is ``noise`` itself), and runs
+    the steps t_start .. n - 1.  ``strength`` in (0, 1]; 1.0 runs all n steps.  ``mask`` [B, N, 4] fp32 in [0, 1] (one value per latent
+    pixel of the 2 x 2 patch, ``schedule.mask_to_tokens``; 1 = repaint, 0 = keep) needs ``x0``: after every step sigma -> sigma_to the
+    kept region is set to (1 - sigma_to) x0 + sigma_to noise with the START noise (never a FlowSDE draw), so after the last step
+    (sigma_to = 0) it is x0 bit for bit.  With FlowSDE one draw is made for every step that RUNS and none for the skipped ones: a
+    generator advances n - t_start times, and ``step_noise`` is [n - t_start, B, N, C].  Guidance interval, orthogonal guidance, the
+    prepared-step chunks and the micro-batches work as without an edit."""
 
     def __init__(self, engine: MMDiTEngine, num_steps: int = 28, guidance_scale: float = 1.0, distilled_guidance: Optional[float] = None,
                  guidance_interval: Optional[Sequence[float]] = None, orthogonal_guidance: bool = False,
@@ -73,9 +90,12 @@ class TeacherSampler:
     # ------------------------------------------------------------------ one step
     def step(self, x: torch.Tensor, x_bf16: torch.Tensor, cond: Dict[str, Any], sigma: torch.Tensor, sigma_to: torch.Tensor,
              active: bool, prepared_step: Optional[int] = None, scratch: Optional[dict] = None, m: Optional[torch.Tensor] = None,
-             c_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None) -> None:
+             c_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None,
+             noise0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> None:
         """Advance x (fp32, in place) and x_bf16 (its rounding, in place) from sigma [B] to sigma_to [B].  FlowSDE: m, c_noise [B]
-        (FlowSDEScheduler.coefficients) and the step's draw ``noise`` like x (None: no noise term on this step)."""
+        (FlowSDEScheduler.coefficients) and the step's draw ``noise`` like x (None: no noise term on this step).  Inpainting: with
+        ``mask`` [B, N, 4] the fused edit step re-imposes (1 - sigma_to) x0 + sigma_to noise0 where the mask is 0 (``noise0`` None on
+        the step landing on sigma_to = 0); without a mask the plain step runs."""
         eng = self.engine
         B = x.shape[0]
         s = scratch if scratch is not None else {}
@@ -97,7 +117,13 @@ class TeacherSampler:
         if self.sampler == 'FlowSDE':
             if m is None or c_noise is None:
                 raise ValueError('a FlowSDE step needs m and c_noise (FlowSDEScheduler.coefficients)')
-            ops.teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+            if mask is not None:
+                ops.teacher_sde_edit_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, x0, noise0, mask, self.guidance_scale, coef,
+                                          out=x, out_bf16=x_bf16)
+            else:
+                ops.teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+        elif mask is not None:
+            ops.teacher_edit_step(x, pos, neg, sigma, sigma_to, x0, noise0, mask, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
         else:
             ops.teacher_euler_step(x, pos, neg, sigma, sigma_to, self.guidance_scale, coef, out=x, out_bf16=x_bf16)
 
@@ -114,7 +140,8 @@ class TeacherSampler:
         return torch.randn(tuple(shape), device=gdev, dtype=torch.float32, generator=generator).to(dev)
 
     # ------------------------------------------------------------------ the loop
-    def _roll(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _roll(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None,
+              x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, t_start: int = 0) -> torch.Tensor:
         eng = self.engine
         B, N, _ = noise.shape
         hp, wp = cond['hp'], cond['wp']
@@ -132,31 +159,42 @@ class TeacherSampler:
             reads_noise = ((co[:, 1] * co[:, 3]) != 0).tolist()               # sigma_to c_noise = 0 (always so on the final step): the kernel gets no noise
             if step_noise is not None:
                 step_noise = step_noise.to(dev, torch.float32).contiguous()
-        x = noise.to(dev, torch.float32).clone().contiguous()
-        xb = x.to(torch.bfloat16)
+        if x0 is None:
+            x = noise.to(dev, torch.float32).clone().contiguous()
+            xb = x.to(torch.bfloat16)
+        else:
+            # the source noised to the first sigma that runs (at sigma = 1: the noise itself, bit for bit) and its bf16 copy, one launch
+            noise = noise.to(dev, torch.float32).contiguous()
+            x0 = x0.to(dev, torch.float32).contiguous()
+            mask = None if mask is None else mask.to(dev, torch.float32).contiguous()
+            x, xb = ops.edit_blend(None, x0, noise, None, sig[t_start].clone())      # (a row of sig need not be 16-byte aligned)
+            lands_on_zero = (sigmas[1:] == 0).tolist()                       # the step whose sigma_to is 0 reads no start noise
         T = cond['prompt_embeds'].shape[1]
         if any(active):
             T = max(T, cond['negative_prompt_embeds'].shape[1])
         eng._workspace(B, N, T)           # sized for both prompts up front: a workspace that grows mid-loop would drop the prepared steps
-        chunk = min(max(8 // B, 1), self.num_steps) if self.prepare_steps else 0
+        chunk = min(max(8 // B, 1), self.num_steps - t_start) if self.prepare_steps else 0
         scratch: dict = {}
         g = None
         if eng.guidance_embeds and self.distilled_guidance is not None:
             g = scratch['guidance'] = torch.full((B,), float(self.distilled_guidance), dtype=torch.float32, device=dev)
         prepared = False
-        for i in range(self.num_steps):
-            if chunk > 1 and i % chunk == 0:
+        for i in range(t_start, self.num_steps):
+            j = i - t_start                                                   # the steps that run are counted from the first one that does
+            if chunk > 1 and j % chunk == 0:
                 prepared = eng.prepare_steps(sig[i:min(i + chunk, self.num_steps)], cond.get('pooled'), g, B, N, T)
-            prep = (i % chunk) if (chunk > 1 and prepared) else None
+            prep = (j % chunk) if (chunk > 1 and prepared) else None
+            edit = {} if mask is None else dict(x0=x0, noise0=None if lands_on_zero[i] else noise, mask=mask)
             if sde:
-                z = step_noise[i] if step_noise is not None else self._draw(x.shape, generator)
-                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, m_rows[i], c_rows[i], z if reads_noise[i] else None)
+                z = step_noise[j] if step_noise is not None else self._draw(x.shape, generator)
+                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, m_rows[i], c_rows[i], z if reads_noise[i] else None, **edit)
             else:
-                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch)
+                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, **edit)
         return x
 
     @torch.no_grad()
-    def __call__(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, cond: Dict[str, Any], noise: torch.Tensor, generator=None, step_noise: Optional[torch.Tensor] = None,
+                 x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, strength: float = 1.0) -> torch.Tensor:
         if noise.dim() != 3:
             raise ValueError(f'noise: need packed tokens [B, N, C], got {tuple(noise.shape)}')
         if noise.shape[1] != cond['hp'] * cond['wp']:
@@ -164,21 +202,35 @@ class TeacherSampler:
         if self.guidance_scale > 1.0 and 'negative_prompt_embeds' not in cond:
             raise ValueError('guidance_scale > 1 (true CFG) needs cond["negative_prompt_embeds"]')
         B = noise.shape[0]
+        t_start = 0
+        if x0 is None:
+            if mask is not None:
+                raise ValueError('mask needs x0 (the packed latents of the image whose unmasked region is kept)')
+            if float(strength) != 1.0:
+                raise ValueError('strength needs x0 (without a source image the roll starts from pure noise)')
+        else:
+            if tuple(x0.shape) != tuple(noise.shape) or noise.shape[2] != 64:
+                raise ValueError(f'x0: need packed source latents like noise, [B, N, 64]; got {tuple(x0.shape)} for noise {tuple(noise.shape)}')
+            if mask is not None and tuple(mask.shape) != (B, noise.shape[1], 4):
+                raise ValueError(f'mask: need [B, N, 4] = {(B, noise.shape[1], 4)} (schedule.mask_to_tokens), got {tuple(mask.shape)}')
+            t_start = truncate_by_strength(self.schedule(cond['hp'], cond['wp'])[0], strength)[0]
+        n_run = self.num_steps - t_start
         if self.sampler != 'FlowSDE':
             generator = step_noise = None
         elif step_noise is not None:
-            if tuple(step_noise.shape) != (self.num_steps,) + tuple(noise.shape):
-                raise ValueError(f'step_noise: need [num_steps, B, N, C] = {(self.num_steps,) + tuple(noise.shape)}, got {tuple(step_noise.shape)}')
+            if tuple(step_noise.shape) != (n_run,) + tuple(noise.shape):
+                raise ValueError(f'step_noise: need [steps that run, B, N, C] = {(n_run,) + tuple(noise.shape)}, got {tuple(step_noise.shape)}')
         elif B > 4:
             # the whole batch's draws first, step by step as a single roll would make them: the result does not depend on the micro-batch split
-            step_noise = torch.stack([self._draw(noise.shape, generator) for _ in range(self.num_steps)])
+            step_noise = torch.stack([self._draw(noise.shape, generator) for _ in range(n_run)])
         if B <= 4:
-            return self._roll(cond, noise, generator, step_noise)
+            return self._roll(cond, noise, generator, step_noise, x0, mask, t_start)
         # the engine's prepared steps hold at most 4 samples: larger batches run as micro-batches of 4 (per-sample results are the same)
         outs: List[torch.Tensor] = []
         for a in range(0, B, 4):
             mb = {k: (v[a:a + 4] if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == B else v) for k, v in cond.items()}
-            outs.append(self._roll(mb, noise[a:a + 4], None, None if step_noise is None else step_noise[:, a:a + 4]))
+            outs.append(self._roll(mb, noise[a:a + 4], None, None if step_noise is None else step_noise[:, a:a + 4],
+                                   None if x0 is None else x0[a:a + 4], None if mask is None else mask[a:a + 4], t_start))
         return torch.cat(outs)
 
 

@@ -310,14 +310,15 @@ class ArcFlowDistiller:
     @torch.no_grad()
     def sample_teacher(self, cond, noise, num_steps: int = 28, guidance_scale: Optional[float] = None,
                        distilled_guidance: Optional[float] = None, sampler: str = 'FlowEulerODE', h=None, generator=None,
-                       step_noise=None, **sampler_kwargs):
+                       step_noise=None, x0=None, mask=None, strength: float = 1.0, **sampler_kwargs):
         """Roll the frozen teacher from ``noise`` [B, N, C] (packed tokens, fp32) to latents with the Euler ODE sampler
         (arcflow_amd.teacher.TeacherSampler; GaussianFlow.forward_test in the reference) on this distiller's teacher context -- no
         new weights.  Defaults are _teacher_u's: true CFG ``cfg.teacher_guidance_scale`` (needs cond['negative_prompt_embeds'] when
         > 1), guidance embedding ``cfg.teacher_guidance`` (else ``cfg.guidance``), time shift ``cfg.shift``.  Further keywords
         (guidance_interval, orthogonal_guidance, terminal_sigma ...) go to TeacherSampler.  sampler='FlowSDE': the stochastic
         sampler with noise strength ``h`` (a float, default 1.0, or 'inf'), its per-step draws from ``generator`` or from
-        ``step_noise`` [num_steps, B, N, C]."""
+        ``step_noise`` [num_steps, B, N, C].  ``x0`` [B, N, 64] (packed latents of a source image), ``mask`` [B, N, 4] and ``strength``
+        are TeacherSampler's image-to-image / inpainting arguments, passed through."""
         from ..teacher import TeacherSampler
         c = self.cfg
         if guidance_scale is None:
@@ -328,7 +329,8 @@ class ArcFlowDistiller:
         if h is not None:
             sampler_kwargs['h'] = h
         return TeacherSampler(self.teacher, num_steps, guidance_scale=guidance_scale, distilled_guidance=distilled_guidance,
-                              sampler=sampler, **sampler_kwargs)(cond, noise, generator=generator, step_noise=step_noise)
+                              sampler=sampler, **sampler_kwargs)(cond, noise, generator=generator, step_noise=step_noise, x0=x0, mask=mask,
+                                                                 strength=strength)
 
     # ------------------------------------------------------------------ evaluation: the student's own samples
     def _exchange_ema(self, scratch: torch.Tensor) -> None:

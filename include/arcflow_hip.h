@@ -247,6 +247,32 @@ int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const
  * 4 + 2 B written per element, 16 B of mask per token: 18 B per element, about 4.7 MB per image and step. */
 int afx_edit_blend(const float* x, const float* x0, const float* noise, const float* mask, const float* sigma_to, float* x_out,
                    void* x_out_bf16, int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks, void* stream);
+/* One step of teacher image editing (image-to-image / inpainting with the many-step sampler): afx_teacher_euler_step /
+ * afx_teacher_sde_step and the re-imposition of the known region at the sigma the step lands on, in one launch.  Per element, in fp32:
+ *   x'    = the Euler / FlowSDE update with the CFG combine, exactly as afx_teacher_euler_step / afx_teacher_sde_step compute it
+ *   om    = 1 - sigma_to[b]
+ *   known = noise0 ? fma(sigma_to[b], noise0, om x0) : om x0
+ *   x_out = fma(m, x', (1 - m) known)                                 m = mask[b, tok, e & 3] for element e of the token
+ *   x_out_bf16 = round-to-nearest-even of x_out
+ * so x_out and x_out_bf16 are, bit for bit, those of the step entry followed by afx_edit_blend(x', x0, noise0, mask, sigma_to): m = 1
+ * returns the plain step, m = 0 returns known, and m = 0 with sigma_to = 0 returns x0 (finite inputs).  x0 [batch, n_tok, ch] fp32: the
+ * packed source latents; noise0 [batch, n_tok, ch] fp32: the START noise of the edit on every step (never the FlowSDE draw `noise`), NULL on
+ * the step whose sigma_to is 0 (the term and its read are skipped); mask [batch, n_tok, 4] fp32 in [0, 1] as for afx_edit_blend (1 =
+ * repaint, 0 = keep the source), NULL: nothing is re-imposed and the call IS the plain step entry (same kernel, same bits; x0 and noise0
+ * are then not read).  Every other operand as for the step entries with n = n_tok * ch.  These semantics follow the image-to-image /
+ * inpainting pipelines of diffusers as recalled; the reference has no image-conditioned sampling, so no fixture pins them.
+ * AFX_E_INVALID before any launch when a required pointer is NULL (all but neg, noise, coef, noise0, mask), ch != 64, batch or n_tok < 1,
+ * max_blocks < 0, a tensor is not 16-byte aligned, or an output overlaps another operand (other than x_out == x).  max_blocks: cap on
+ * the grid of the grid-stride loop (0 = the default, 2048).  Traffic at 1024 x 1024 (262144 elements per image): 4 + 2 + 2 + 4 + 4 B read
+ * (+ 4 B of `noise` for FlowSDE), 16 B of mask per token, 4 + 2 B written: 22.25 B per element (26.25 B), about 5.8 MB (6.9 MB) per image
+ * and step.  The two launches it replaces move 14 (18) + 18.25 B: fused saves one fp32 write + read of x', one bf16 write and a launch. */
+int afx_teacher_edit_step(const float* x, const void* pos, const void* neg, const float* sigma, const float* sigma_to, const float* coef,
+                          float scale, const float* x0, const float* noise0, const float* mask, float* x_out, void* x_out_bf16,
+                          int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks, void* stream);
+int afx_teacher_sde_edit_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma, const float* sigma_to,
+                              const float* m, const float* c_noise, const float* coef, float scale, const float* x0, const float* noise0,
+                              const float* mask, float* x_out, void* x_out_bf16, int32_t batch, int32_t n_tok, int32_t ch, int32_t max_blocks,
+                              void* stream);
 /* coef[b] = mean(bias pos) / max(mean(pos pos), 1e-6) over the n elements of sample b, bias = (pos - neg) (scale - 1) rounded to
  * fp32 as the step kernel computes it: the projection coefficient of orthogonal guidance (gaussian_flow.py:21-25, dim = [1..]).
  * Deterministic: a number of work-groups per sample that depends on n alone, exact fp64 products, one slot of `ws` per

@@ -8,6 +8,12 @@ own trajectory and the original pixels are pasted back after decoding.  Nothing 
     python tools/edit_image.py --family flux --snapshot /path/to/FLUX.1-dev --adapter /path/to/arcflow --image in.png --mask mask.png \\
         --prompt "a red door" --strength 0.8 --out out.png
 
+``--teacher`` also (or, without ``--adapter``, only) produces the TEACHER's edit of the same source, noise and mask through
+``pipe.sample_teacher(image=..., strength=..., mask_image=...)`` in ``--steps`` steps, written beside ``--out`` as ``<out>.teacher<ext>``;
+with both, the latents of the two edits are scored against each other with ``afx_sample_score`` (student = a, teacher = b): mse, rel-L2 and
+cosine per sample.  The teacher walks the last ``strength`` share of its schedule, the student all its steps over [strength, 0]; both
+start from the same noise draw (``--seed``).
+
 ``--synthetic``: random-init weights of a reduced architecture, random prompt embeddings and a random image in latent space
 (``image_latents=``; no snapshot, no VAE): writes the edited packed latents to ``--out`` with torch.save, for trying the path end to end.
 """
@@ -38,6 +44,20 @@ def synthetic_pipeline(family: str, device='cuda', seed: int = 0):
     return pipe, cond
 
 
+def score_latents(student: torch.Tensor, teacher: torch.Tensor):
+    """Packed latents [B, N, 64] of the two edits -> {'latent_mse' | 'latent_rel_l2' | 'latent_cosine': per-sample list} (afx_sample_score)."""
+    from arcflow_amd import ops
+    from arcflow_amd.train.evaluate import metrics_from_sums
+    a, b = student.to('cuda', torch.float32).contiguous(), teacher.to('cuda', torch.float32).contiguous()
+    m = metrics_from_sums(ops.sample_score(a, b), a[0].numel())
+    return {'latent_' + k: m[k].tolist() for k in ('mse', 'rel_l2', 'cosine')}
+
+
+def _teacher_path(out: str) -> str:
+    root, ext = os.path.splitext(out)
+    return root + '.teacher' + ext
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--family', choices=['flux', 'qwen'], required=True)
@@ -52,6 +72,10 @@ def main(argv=None):
     ap.add_argument('--out', required=True)
     ap.add_argument('--synthetic', action='store_true', help='reduced random-init student, random embeddings, a random image in latent space')
     ap.add_argument('--size', type=int, nargs=2, default=[256, 256], help='--synthetic: height width')
+    ap.add_argument('--teacher', action='store_true', help='also write the teacher\'s edit (sample_teacher) and score the student\'s against it')
+    ap.add_argument('--steps', type=int, default=28, help='--teacher: steps of the full schedule (the last `strength` share of them runs)')
+    ap.add_argument('--true-cfg-scale', type=float, default=1.0, help='--teacher: true classifier-free guidance against --negative-prompt when > 1')
+    ap.add_argument('--negative-prompt', default='')
     args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(args.seed)
     kw = dict(strength=args.strength, num_inference_steps=args.nfe, timestep_ratio=1.0 if args.nfe == 2 else 0.5, generator=gen)
@@ -67,6 +91,22 @@ def main(argv=None):
         out = pipe(image_latents=x0, mask_image=mask, height=h, width=w, output_type='latent', **cond, **kw).images
         torch.save(out.cpu(), args.out)
         print(f'wrote edited latents {tuple(out.shape)} to {args.out}  (|out - source| rel-L2 {((out.cpu() - x0).norm() / x0.norm()).item():.3f})')
+        if args.teacher:
+            from arcflow_amd import MMDiTEngine
+            from arcflow_amd.weights import random_packed
+            eng = pipe.transformer
+            nd, ns = (1, 1) if args.family == 'flux' else (2, 0)
+            joint, pooled = (128, 64) if args.family == 'flux' else (192, 768)
+            pipe._teacher = MMDiTEngine(args.family, nd, ns, heads=2, joint_dim=joint, pooled_dim=pooled, teacher_head=True, device=eng.device)
+            pipe._teacher.bind_packed(random_packed(args.family, nd, ns, eng.device, heads=2, joint_dim=joint, pooled_dim=pooled, seed=args.seed,
+                                                    teacher=True))
+            tea = pipe.sample_teacher(image_latents=x0, mask_image=mask, height=h, width=w, output_type='latent', strength=args.strength,
+                                      num_inference_steps=args.steps, true_cfg_scale=1.0, generator=torch.Generator().manual_seed(args.seed),
+                                      **cond).images
+            torch.save(tea.cpu(), _teacher_path(args.out))
+            scores = score_latents(out, tea)
+            print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}; student vs teacher: {scores}')
+            return out, tea, scores
         return out
     if not args.snapshot or not args.image:
         raise SystemExit('--snapshot and --image are required (or pass --synthetic)')
@@ -77,9 +117,25 @@ def main(argv=None):
         pipe.load_arcflow_adapter(args.adapter)
     image = Image.open(args.image)
     mask = Image.open(args.mask) if args.mask else None
-    out = pipe(prompt=args.prompt, image=image, mask_image=mask, **kw).images[0]
-    out.save(args.out)
-    print(f'wrote {args.out} ({out.size[0]} x {out.size[1]})')
+    student = pipe.transformer is not None and not pipe.transformer.teacher_head
+    if not student and not args.teacher:
+        raise SystemExit('no ArcFlow student loaded: pass --adapter, or --teacher for the base model\'s own edit')
+    out = lat = None
+    if student:
+        lat = pipe(prompt=args.prompt, image=image, mask_image=mask, output_type='latent', **kw).images
+        out = pipe(prompt=args.prompt, image=image, mask_image=mask, **dict(kw, generator=torch.Generator().manual_seed(args.seed))).images[0]
+        out.save(args.out)
+        print(f'wrote {args.out} ({out.size[0]} x {out.size[1]})')
+    if args.teacher:
+        tkw = dict(prompt=args.prompt, image=image, mask_image=mask, strength=args.strength, num_inference_steps=args.steps,
+                   true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt if args.true_cfg_scale > 1.0 else None)
+        tlat = pipe.sample_teacher(output_type='latent', generator=torch.Generator().manual_seed(args.seed), **tkw).images
+        tea = pipe.sample_teacher(generator=torch.Generator().manual_seed(args.seed), **tkw).images[0]
+        tea.save(_teacher_path(args.out))
+        print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}')
+        if student:
+            print(f'student vs teacher: {score_latents(lat, tlat)}')
+        out = tea if out is None else out
     return out
 
 

@@ -8,6 +8,12 @@ classifier-free guidance (arcflow_amd.teacher.TeacherSampler; GaussianFlow.forwa
     python tools/sample_teacher.py --family flux --snapshot /path/to/FLUX.1-dev --prompts prompts.txt --cache-dir data/teacher_flux
     python tools/train.py examples/flux_distill_data_2nfe.py --transformer-dir /path/to/FLUX.1-dev/transformer --data-dir data/teacher_flux
 
+``--image`` (+ ``--mask``, white = repaint; ``--strength``) conditions every sample on one source image: the teacher's image-to-image /
+inpainting (TeacherSampler ``x0`` / ``mask`` / ``strength``), so that edit-conditioned teacher latents can be cached too.  The image is
+encoded by the snapshot's VAE encoder and must match every record's ``latent_size`` (8 pixels per latent pixel; nothing is resized).  A
+``.pt`` file is read with torch.load instead: a tensor [16, H, W] (or [1, 16, H, W]) of latents for ``--image``, [H, W] in [0, 1] at
+latent resolution for ``--mask`` -- which is all ``--synthetic`` can take, having no VAE.
+
 ``--synthetic``: random-init weights of a reduced architecture and random prompt embeddings (no snapshot, no text encoders): writes
 ``--count`` complete records, for trying the data path end to end.
 """
@@ -29,11 +35,54 @@ def unpack(latents: torch.Tensor, hp: int, wp: int) -> torch.Tensor:
     return latents.view(b, hp, wp, 16, 2, 2).permute(0, 3, 1, 4, 2, 5).reshape(b, 16, 2 * hp, 2 * wp)
 
 
-def add_teacher_latents(sampler, cache_dir: str, negative=None, seed: int = 0, dtype=torch.float16, device='cuda'):
+def pack(latents: torch.Tensor) -> torch.Tensor:
+    """[B, 16, 2 hp, 2 wp] latents -> [B, hp wp, 64] packed tokens: the inverse of ``unpack``."""
+    b, c, h, w = latents.shape
+    return latents.view(b, c, h // 2, 2, w // 2, 2).permute(0, 2, 4, 1, 3, 5).reshape(b, (h // 2) * (w // 2), c * 4).contiguous()
+
+
+def load_edit(image: str, mask=None, encoder=None, device='cuda'):
+    """``--image`` / ``--mask`` -> dict(x0 [1, N, 64] packed fp32 latents, mask [1, N, 4] or None, size (16, H, W)).  ``.pt`` files hold
+    latent-space tensors; anything else is an image file, which needs ``encoder`` (pipe.vae.encoder)."""
+    from arcflow_amd.schedule import mask_to_tokens
+    if image.endswith('.pt'):
+        lat = torch.load(image).to(torch.float32)
+        lat = lat[None] if lat.dim() == 3 else lat
+        if lat.dim() != 4 or lat.shape[1] != 16 or lat.shape[2] % 2 or lat.shape[3] % 2:
+            raise SystemExit(f'--image {image}: need latents [16, H, W] with even H, W, got {tuple(lat.shape)}')
+        x0 = pack(lat).to(device)
+        _, _, h, w = lat.shape
+    else:
+        if encoder is None:
+            raise SystemExit('--image needs a snapshot whose vae/ holds encoder weights (or a .pt file of latents)')
+        from PIL import Image
+        from arcflow_amd.pipelines import ArcFluxPipeline
+        img = ArcFluxPipeline._images01(Image.open(image))
+        if img.shape[2] % 16 or img.shape[3] % 16:
+            raise SystemExit(f'--image {image}: sides must be multiples of 16, got {img.shape[2]} x {img.shape[3]}')
+        x0 = encoder.encode_images01(img, sample=False, packed=True).to(torch.float32)
+        h, w = img.shape[2] // 8, img.shape[3] // 8
+    tokens = None
+    if mask is not None:
+        if mask.endswith('.pt'):
+            m = torch.load(mask).to(torch.float32).reshape(1, h, w)
+            tokens = m.view(1, h // 2, 2, w // 2, 2).permute(0, 1, 3, 2, 4).reshape(1, (h // 2) * (w // 2), 4).contiguous().to(device)
+        else:
+            from PIL import Image
+            from arcflow_amd.pipelines import ArcFluxPipeline
+            m = ArcFluxPipeline._images01(Image.open(mask), 'mask', 1)
+            if tuple(m.shape[2:]) != (8 * h, 8 * w):
+                raise SystemExit(f'--mask {mask} is {m.shape[2]} x {m.shape[3]}, the image is {8 * h} x {8 * w}')
+            tokens = mask_to_tokens(m.to(device), h // 2, w // 2)
+    return dict(x0=x0, mask=tokens, size=(16, h, w))
+
+
+def add_teacher_latents(sampler, cache_dir: str, negative=None, seed: int = 0, dtype=torch.float16, device='cuda', edit=None,
+                        strength: float = 1.0):
     """sampler(cond, noise [1, N, 64]) -> packed latents.  Every record of ``cache_dir`` is sampled at its own ``latent_size`` from
     noise seeded with ``seed + index`` (the same generator goes on to the step draws of a stochastic sampler) and rewritten with
     ``latents``.  negative: prompt_embed_kwargs of the negative prompt (true
-    CFG).  Returns {file name: the fp32 latents [16, H, W] before the cast to ``dtype``}."""
+    CFG).  edit (``load_edit``): every record is an edit of that one source image at ``strength``.  Returns {file name: the fp32 latents [16, H, W] before the cast to ``dtype``}."""
     from arcflow_amd.train import data
     ds = data.PromptEmbedCache(cache_dir)
     done = {}
@@ -45,7 +94,12 @@ def add_teacher_latents(sampler, cache_dir: str, negative=None, seed: int = 0, d
         _, h, w = item['latent_size']
         gen = torch.Generator().manual_seed(seed + i)
         noise = torch.randn(1, cond['hp'] * cond['wp'], 64, generator=gen).to(device)
-        lat = unpack(sampler(cond, noise, generator=gen), cond['hp'], cond['wp'])[0].float().cpu()
+        kw = {}
+        if edit is not None:
+            if tuple(edit['size']) != (16, h, w):
+                raise SystemExit(f'{fn}: latent_size {tuple(item["latent_size"])} but --image gives {edit["size"]}')
+            kw = dict(x0=edit['x0'], mask=edit['mask'], strength=strength)
+        lat = unpack(sampler(cond, noise, generator=gen, **kw), cond['hp'], cond['wp'])[0].float().cpu()
         assert tuple(lat.shape) == (16, h, w)
         path = os.path.join(cache_dir, fn)
         rec = read_record(path)
@@ -100,6 +154,9 @@ def main(argv=None):
     ap.add_argument('--sampler', choices=['FlowEulerODE', 'FlowSDE'], default='FlowEulerODE')
     ap.add_argument('--h', type=lambda v: v if v == 'inf' else float(v), default=None,
                     help='--sampler FlowSDE: noise strength, a float (0 = the ODE; default 1.0) or inf (re-noise the clean prediction completely)')
+    ap.add_argument('--image', help='source image of an edit (sides multiples of 16), or a .pt file of its latents [16, H, W]')
+    ap.add_argument('--mask', help='inpainting mask of --image: an image of its size (white = repaint), or a .pt file [H, W] in [0, 1] per latent pixel')
+    ap.add_argument('--strength', type=float, default=1.0, help='--image: in (0, 1], the share of the --steps schedule that runs (1 = all of it)')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--max-sequence-length', type=int, default=512)
     args = ap.parse_args(argv)
@@ -107,6 +164,9 @@ def main(argv=None):
     from arcflow_amd.train import data
     dev = 'cuda'
     negative = None
+    encoder = None
+    if args.mask and not args.image:
+        raise SystemExit('--mask needs --image')
     if args.synthetic:
         engine, joint, pooled = synthetic_engine(args.family, dev, args.seed)
         if not os.path.isdir(args.cache_dir) or not os.listdir(args.cache_dir):
@@ -122,6 +182,7 @@ def main(argv=None):
         from arcflow_amd.pipelines import ArcFluxPipeline, ArcQwenImagePipeline
         pipe = (ArcFluxPipeline if args.family == 'flux' else ArcQwenImagePipeline).from_pretrained(args.snapshot)
         engine = pipe._teacher_engine()
+        encoder = getattr(pipe.vae, 'encoder', None)
         if args.prompts:
             from arcflow_amd.train.prompts import PromptEncoder, write_cache
             enc = PromptEncoder(args.family, pipe, max_sequence_length=args.max_sequence_length)
@@ -139,7 +200,8 @@ def main(argv=None):
     sampler = TeacherSampler(engine, args.steps, guidance_scale=args.true_cfg_scale, distilled_guidance=args.guidance_scale,
                              guidance_interval=args.guidance_interval, orthogonal_guidance=args.orthogonal_guidance, shift=args.shift,
                              sampler=args.sampler, **({} if args.h is None else dict(h=args.h)))
-    done = add_teacher_latents(sampler, args.cache_dir, negative, args.seed, device=dev)
+    edit = load_edit(args.image, args.mask, encoder, dev) if args.image else None
+    done = add_teacher_latents(sampler, args.cache_dir, negative, args.seed, device=dev, edit=edit, strength=args.strength)
     print(f'wrote teacher latents into {len(done)} records of {args.cache_dir}')
     return done
 
