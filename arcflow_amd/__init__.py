@@ -7,7 +7,7 @@ integrator run as hand-written HIP kernels behind the C ABI in include/arcflow_h
 __version__ = '0.1.0'
 
 from .engine import ArcFlowModelOutput, MMDiTEngine  # noqa: F401
-from .schedule import (FlowEulerODEScheduler, FlowMatchEulerDiscreteScheduler, FlowSDEScheduler, edit_raw_timesteps, mask_to_tokens,  # noqa: F401
+from .schedule import (FlowEulerODEScheduler, FlowMatchEulerDiscreteScheduler, FlowSDEScheduler, FlowUniPCScheduler, edit_raw_timesteps, mask_to_tokens,  # noqa: F401
                        retrieve_raw_timesteps)
 from .teacher import TeacherSampler, sampler_kwargs_from_test_cfg  # noqa: F401
 

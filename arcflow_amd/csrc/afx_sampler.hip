@@ -9,6 +9,9 @@
 //     an fp32 operand drawn by torch, so that a torch.Generator reproduces the run.  Traffic at 1024 x 1024 (4096 tokens x 64
 //     channels = 262144 elements per image): 4 (x) + 2 (pos) + 2 (neg) + 4 (z) B read and 4 (x') + 2 (bf16 x') B written per
 //     element = 18 B, about 4.7 MB per image and step.
+//   * teacher_unipc_step_kernel: the same combine + one predictor-corrector step of the UniPC multistep solver (FlowUniPCScheduler) + the bf16
+//     copy + the solver's state (the corrected sample, the clean-sample prediction into the host's history ring), in one pass of the same
+//     shape; the host hands over one fp32 weight per operand.  Formula, fma order and traffic at the kernel.
 //   * teacher_edit_step_kernel<SDE>: either step + the inpainting blend of afx_edit.hip at the sigma the step lands on + the bf16 copy,
 //     in one pass of the same shape (teacher image-to-image / inpainting); formula and traffic at the kernel.
 //   * cfg_ortho_partial_kernel / cfg_ortho_finish_kernel: the per-sample projection coefficient of orthogonal guidance,
@@ -107,6 +110,81 @@ __global__ __launch_bounds__(256) void teacher_sde_step_kernel(const float* x, c
     *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
     *reinterpret_cast<f32x4_t*>(x_out + c * 8 + 4) = o1;
     *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
+  }
+}
+
+AFX_DEV void load8(const float* p, float (&v)[8]) {
+  const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p), b = *reinterpret_cast<const f32x4_t*>(p + 4);
+  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
+AFX_DEV void store8(float* p, const float (&v)[8]) {
+  const f32x4_t a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
+  *reinterpret_cast<f32x4_t*>(p) = a;
+  *reinterpret_cast<f32x4_t*>(p + 4) = b;
+}
+
+// One step of the UniPC multistep sampler (FlowUniPCScheduler: the solver behind the reference's FlowAdapterScheduler on its default base
+// scheduler; the arithmetic is diffusers' as recalled, DESIGN.md 6.1 "Multistep sampling") on the same chunks, with the same CFG combine.  The
+// predictor and the corrector are linear in their operands, and the host (FlowUniPCScheduler.coefficients, fp64) hands over one fp32 weight
+// per operand and sample, w[r * batch + b], rows
+//   0 s | 1 c_last  2 c_mt  3 c_1  4 c_2  5 c_3 | 6 p_xc  7 p_mt  8 p_1  9 p_2
+// Per element, in this order, every product-sum one fused multiply-add (a rounding each):
+//   u      = cfg_velocity
+//   m_t    = fma(-s, u, x)                                                          the clean-sample prediction, from the uncorrected x
+//   x_c    = fma(c_mt, m_t, fma(c_3, h3, fma(c_2, h2, fma(c_1, h1, c_last last))))  last == nullptr (first step of a roll): x_c = x
+//   x_next = fma(p_mt, m_t, fma(p_2, h2, fma(p_1, h1, p_xc x_c)))
+// h1, h2, h3 = the clean-sample predictions of one, two, three steps ago; a nullptr one is neither read nor multiplied (its fma is skipped).
+// On the step that lands on sigma 0 the weights are p_xc = 0, p_mt = 1, p_1 = p_2 = 0: x_next = m_t bit for bit (finite operands).
+// Writes x_next (x_out, may be x) and its bf16 copy, x_c (last_out, may be last) and m_t (hist_out, may be one of h1 / h2 / h3: the host
+// rotates a ring of solver_order buffers and overwrites the oldest).  A lane loads all of its 8 elements of every operand before it stores
+// any, and no two lanes share an element, so these aliases are safe; the operands that may alias carry no __restrict__.
+// Traffic per element at order 2 past the warm-up: 4 (x) + 2 (pos) + 2 (neg) + 4 (last) + 4 (h1) + 4 (h2) = 20 B read and 4 (x') + 2 (bf16 x') +
+// 4 (x_c) + 4 (m_t) = 14 B written: 34 B, about 8.9 MB per 1024 x 1024 image and step (order 3: 38 B; the Euler step moves 14 B).
+__global__ __launch_bounds__(256) void teacher_unipc_step_kernel(const float* x, const bf16_t* __restrict__ pos, const bf16_t* __restrict__ neg,
+                                                                 const float* __restrict__ w, const float* last, const float* h1, const float* h2,
+                                                                 const float* h3, const float* __restrict__ coef, float scale, float* x_out,
+                                                                 bf16_t* __restrict__ x_bf16, float* last_out, float* hist_out, int64_t batch,
+                                                                 int64_t chunks_per_sample, int64_t chunks) {
+  const float sm1 = scale - 1.0f;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += stride) {
+    const int64_t b = c / chunks_per_sample;
+    float wv[10];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) wv[r] = w[r * batch + b];
+    const float cf = coef != nullptr ? coef[b] : 0.f;
+    float p[8], q[8], v[8], l[8], a1[8], a2[8], a3[8], o[8], xc[8], mt[8];
+    unpack8(*reinterpret_cast<const u32x4_t*>(pos + c * 8), p);
+    if (neg != nullptr) unpack8(*reinterpret_cast<const u32x4_t*>(neg + c * 8), q);
+    load8(x + c * 8, v);
+    if (last != nullptr) load8(last + c * 8, l);
+    if (h1 != nullptr) load8(h1 + c * 8, a1);
+    if (h2 != nullptr) load8(h2 + c * 8, a2);
+    if (h3 != nullptr) load8(h3 + c * 8, a3);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float u = cfg_velocity(p, q, e, neg != nullptr, coef != nullptr, sm1, cf);
+      const float m = __builtin_fmaf(-wv[0], u, v[e]);
+      float cx = v[e];
+      if (last != nullptr) {
+        cx = wv[1] * l[e];
+        if (h1 != nullptr) cx = __builtin_fmaf(wv[3], a1[e], cx);
+        if (h2 != nullptr) cx = __builtin_fmaf(wv[4], a2[e], cx);
+        if (h3 != nullptr) cx = __builtin_fmaf(wv[5], a3[e], cx);
+        cx = __builtin_fmaf(wv[2], m, cx);
+      }
+      float nx = wv[6] * cx;
+      if (h1 != nullptr) nx = __builtin_fmaf(wv[8], a1[e], nx);
+      if (h2 != nullptr) nx = __builtin_fmaf(wv[9], a2[e], nx);
+      o[e] = __builtin_fmaf(wv[7], m, nx);
+      xc[e] = cx;
+      mt[e] = m;
+    }
+    store8(x_out + c * 8, o);
+    *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
+    store8(last_out + c * 8, xc);
+    store8(hist_out + c * 8, mt);
   }
 }
 
@@ -357,6 +435,47 @@ int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const
   const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
   hipLaunchKernelGGL(teacher_sde_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos, (const bf16_t*)neg,
                      noise, sigma, sigma_to, m, c_noise, coef, scale, x_out, (bf16_t*)x_out_bf16, cps, chunks);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_teacher_unipc_step(const float* x, const void* pos, const void* neg, const float* w, const float* last, const float* h1,
+                           const float* h2, const float* h3, const float* coef, float scale, float* x_out, void* x_out_bf16, float* last_out,
+                           float* hist_out, int32_t batch, int64_t n, int32_t max_blocks, void* stream) {
+  if (!x || !pos || !w || !x_out || !x_out_bf16 || !last_out || !hist_out)
+    return fail(AFX_E_INVALID, "null argument to afx_teacher_unipc_step (only neg, last, h1, h2, h3 and coef may be NULL)");
+  if ((last && !h1) || (h2 && !h1) || (h3 && !h2))
+    return fail(AFX_E_INVALID, "afx_teacher_unipc_step: the corrector (last) needs h1, h2 needs h1 and h3 needs h2");
+  if (batch < 0 || n < 64 || n % 64 || max_blocks < 0)
+    return fail(AFX_E_INVALID, "bad argument to afx_teacher_unipc_step (n = tokens x channels must be a positive multiple of 64)");
+  if (((uintptr_t)x & 15) || ((uintptr_t)pos & 15) || ((uintptr_t)neg & 15) || ((uintptr_t)last & 15) || ((uintptr_t)h1 & 15) ||
+      ((uintptr_t)h2 & 15) || ((uintptr_t)h3 & 15) || ((uintptr_t)x_out & 15) || ((uintptr_t)x_out_bf16 & 15) || ((uintptr_t)last_out & 15) ||
+      ((uintptr_t)hist_out & 15))
+    return fail(AFX_E_INVALID, "afx_teacher_unipc_step: x, pos, neg, last, h1, h2, h3, x_out, x_out_bf16, last_out and hist_out must be 16-byte aligned");
+  if (batch == 0) return AFX_OK;
+  // a lane reads its own 8 elements of every operand before it writes them, so an output may BE the input it replaces (x_out == x,
+  // last_out == last, hist_out == one history slot); any other overlap lets one lane's store land in another lane's load
+  const int64_t fbytes = (int64_t)batch * n * 4, hbytes = (int64_t)batch * n * 2, wbytes = (int64_t)batch * 10 * 4, cbytes = (int64_t)batch * 4;
+  const void* fin[] = {x, last, h1, h2, h3};
+  struct { const void* p; int64_t bytes; const void* may; const char* name; } outs[] = {
+      {x_out, fbytes, x, "x_out"}, {x_out_bf16, hbytes, nullptr, "x_out_bf16"}, {last_out, fbytes, last, "last_out"}, {hist_out, fbytes, nullptr, "hist_out"}};
+  for (int k = 0; k < 4; ++k) {
+    bool hit = ranges_overlap(outs[k].p, outs[k].bytes, pos, hbytes) || ranges_overlap(outs[k].p, outs[k].bytes, neg, hbytes) ||
+               ranges_overlap(outs[k].p, outs[k].bytes, w, wbytes) || ranges_overlap(outs[k].p, outs[k].bytes, coef, cbytes);
+    for (int i = 0; i < 5; ++i) {
+      const bool same = outs[k].p == fin[i] && (fin[i] == outs[k].may || (k == 3 && i >= 2));      // hist_out: h1, h2 or h3 itself
+      hit = hit || (!same && ranges_overlap(outs[k].p, outs[k].bytes, fin[i], fbytes));
+    }
+    for (int j = 0; j < k; ++j) hit = hit || ranges_overlap(outs[k].p, outs[k].bytes, outs[j].p, outs[j].bytes);
+    if (hit)
+      return fail(AFX_E_INVALID, "afx_teacher_unipc_step: %s overlaps another operand (only x_out == x, last_out == last and hist_out == h1, h2 or h3 are allowed)",
+                  outs[k].name);
+  }
+  const int64_t cps = n / 8, chunks = cps * batch;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;          // as afx_teacher_euler_step: 8 work-groups per CU
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
+  hipLaunchKernelGGL(teacher_unipc_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)pos, (const bf16_t*)neg, w, last,
+                     h1, h2, h3, coef, scale, x_out, (bf16_t*)x_out_bf16, last_out, hist_out, (int64_t)batch, cps, chunks);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

@@ -573,6 +573,38 @@ def teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, scale: flo
     return out, out_bf16
 
 
+def teacher_unipc_step(x, pos, neg, w, last, hist, last_out, hist_out, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
+    """One step of the teacher's UniPC multistep sampler (FlowUniPCScheduler) in one launch (afx_teacher_unipc_step): with u as
+    teacher_euler_step forms it and the per-sample weights w [10, B] fp32 (``FlowUniPCScheduler.coefficients(i).row()``: s | c_last, c_mt,
+    c_1, c_2, c_3 | p_xc, p_mt, p_1, p_2), m_t = x - s u; x_c = c_last last + c_1 h1 + c_2 h2 + c_3 h3 + c_mt m_t (last None: x_c = x);
+    x_next = p_xc x_c + p_1 h1 + p_2 h2 + p_mt m_t -> (fp32 x_next, its bf16 rounding); x_c is written to last_out and m_t to hist_out.
+    x, last (None: no corrector) and the up to three tensors of ``hist`` (m_t of one, two, three steps ago; only those given are read)
+    [B, ...] fp32; pos, neg (None: no guidance) bf16 of the same shape; coef (None: not orthogonal) [B] fp32.  out may be x, last_out may
+    be last, hist_out may be one of ``hist``.  numel / B must be a multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
+    lib = _lib.load()
+    hist = list(hist or ())
+    if len(hist) > 3:
+        raise ValueError(f'hist: at most three past predictions, got {len(hist)}')
+    _gpu(x, pos, neg, w, last, *hist, last_out, hist_out, coef, out, out_bf16)
+    B = x.shape[0]
+    n = x[0].numel() if B else 0
+    x = _packed(x, torch.float32, x.shape, 'x')
+    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
+    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    w = _packed(w, torch.float32, (10, B), 'w')
+    last = None if last is None else _packed(last, torch.float32, x.shape, 'last')
+    hist = [_packed(h, torch.float32, x.shape, f'hist[{k}]') for k, h in enumerate(hist)] + [None] * (3 - len(hist))
+    last_out = _packed(last_out, torch.float32, x.shape, 'last_out')
+    hist_out = _packed(hist_out, torch.float32, x.shape, 'hist_out')
+    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
+    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    _lib.check(lib.afx_teacher_unipc_step(_p(x), _p(pos), _p(neg), _p(w), _p(last), _p(hist[0]), _p(hist[1]), _p(hist[2]), _p(coef), scale,
+                                          _p(out), _p(out_bf16), _p(last_out), _p(hist_out), B, n, max_blocks, _s()))
+    return out, out_bf16
+
+
 def edit_blend(x, x0, noise, mask, sigma_to, out: Optional[torch.Tensor] = None, out_bf16=None, max_blocks: int = 0):
     """The blend of image editing in one launch (afx_edit_blend): with known = (1 - sigma_to[b]) x0 + sigma_to[b] noise, the source
     latents diffused to sigma_to, mask x + (1 - mask) known -> (fp32 latents, their bf16 rounding).

@@ -317,7 +317,7 @@ class _PipelineBase(ArcFlowLoaderMixin):
                     terminal_sigma=c.get('shift_terminal') or None)
 
     def _sample_teacher(self, cond, batch, height, width, num_inference_steps, guidance_scale, true_cfg_scale, generator, latents,
-                        guidance_interval, orthogonal_guidance, sampler='FlowEulerODE', h=None, edit=None):
+                        guidance_interval, orthogonal_guidance, sampler='FlowEulerODE', h=None, edit=None, solver_order=None, solver_type=None):
         """-> (latents, hp, wp, edit).  ``edit`` (from ``_edit_inputs``; None: from pure noise) is prepared as ``__call__`` prepares it and
         reaches TeacherSampler as ``x0`` / ``mask`` / ``strength``; ``latents`` / ``generator`` give the start noise either way."""
         from ..teacher import TeacherSampler
@@ -330,9 +330,10 @@ class _PipelineBase(ArcFlowLoaderMixin):
             if tuple(latents.shape) != tuple(edit['x0'].shape):
                 raise ValueError(f'`latents` (the start noise) is {tuple(latents.shape)}, the image latents are {tuple(edit["x0"].shape)}')
             kw = dict(x0=edit['x0'], mask=edit.get('mask_tokens'), strength=edit['strength'])
+        solver = {k: v for k, v in dict(h=h, solver_order=solver_order, solver_type=solver_type).items() if v is not None}       # the scheduler refuses a keyword that is not its own
         sampler = TeacherSampler(engine, num_inference_steps, guidance_scale=true_cfg_scale, distilled_guidance=guidance_scale,
                                  guidance_interval=guidance_interval, orthogonal_guidance=orthogonal_guidance, tokens_as_seq_len=True,
-                                 sampler=sampler, **({} if h is None else dict(h=h)), **self._euler_scheduler_kwargs())
+                                 sampler=sampler, **solver, **self._euler_scheduler_kwargs())
         self._num_timesteps = num_inference_steps
         return sampler(cond, latents, generator=generator, **kw), hp, wp, edit          # (the generator's stream continues from the start noise into FlowSDE's step draws)
 
@@ -542,14 +543,16 @@ class ArcFluxPipeline(_PipelineBase):
                        return_dict: bool = True, guidance_interval=None, orthogonal_guidance: bool = False,
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
-                       strength: float = 1.0, mask_image=None, composite: bool = True):
+                       strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
+                       solver_type: Optional[str] = None):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
         t = 1000 sigma limits it, ``orthogonal_guidance`` projects it).  ``sampler='FlowSDE'`` takes the stochastic steps of
         FlowSDEScheduler instead, with noise strength ``h`` (a float, default 1.0, or 'inf'); their draws come from ``generator``
-        after the start noise.  Works before ``load_arcflow_adapter()`` on the pipeline's
-        own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
+        after the start noise.  ``sampler='UniPC'`` takes the multistep predictor-corrector steps of FlowUniPCScheduler
+        (``solver_order`` 1 / 2 (default) / 3, ``solver_type`` 'bh1' / 'bh2'; no ``mask_image`` with it).  Works before
+        ``load_arcflow_adapter()`` on the pipeline's own engine; afterwards a teacher engine is built once from the kept base weights, which holds a SECOND copy of the
         transformer on the GPU (FLUX.1-dev: about 24 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the
         adapter weights of ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.
 
@@ -580,5 +583,5 @@ class ArcFluxPipeline(_PipelineBase):
                 raise ValueError(f'{ne.shape[0]} negative prompts for {pe.shape[0]} prompts')
             cond.update(negative_prompt_embeds=ne, negative_pooled=npooled)
         out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
-                                                 generator, latents, guidance_interval, orthogonal_guidance, sampler, h, edit)
+                                                 generator, latents, guidance_interval, orthogonal_guidance, sampler, h, edit, solver_order, solver_type)
         return self._finish(out, hp, wp, output_type, return_dict, edit, composite)

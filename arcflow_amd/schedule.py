@@ -8,7 +8,7 @@ Host-side float arithmetic only (128 numbers per image) -- nothing here runs on 
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -332,6 +332,174 @@ class FlowSDEScheduler(_FlowSchedulerTables):
         if noise is None:
             noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
         prev_sample = (alpha_to * x0 + sigma_to * (m * epsilon + c_noise * noise)).to(ori_dtype)
+        self._step_index += 1
+        if not return_dict:
+            return (prev_sample,)
+        return _Config(prev_sample=prev_sample)
+
+
+class UniPCStep(NamedTuple):
+    """The scalars of one UniPC step (FlowUniPCScheduler.coefficients), fp64: with m_t = x - sigma u,
+        x_c    = corrector . (last_sample, m_t, m[-1], m[-2], m[-3])          (corrector None: x_c = x, the first step of a roll)
+        x_next = predictor . (x_c, m_t, m[-1], m[-2])
+    m[-k] the x0-prediction of k steps ago.  A history term beyond the step's order has weight 0.0 and is not read."""
+    sigma: float
+    corrector: Optional[Tuple[float, float, float, float, float]]
+    predictor: Tuple[float, float, float, float]
+    corrector_order: int
+    predictor_order: int
+
+    def row(self) -> List[float]:
+        """The ten values afx_teacher_unipc_step takes per sample: sigma, the corrector's five (zeros without one), the predictor's four."""
+        return [self.sigma, *(self.corrector or (0.0,) * 5), *self.predictor]
+
+
+class FlowUniPCScheduler(_FlowSchedulerTables):
+    """The reference's adapter scheduler (lakonlab/models/diffusions/schedulers/flow_adapter.py, ``sampler='FlowAdapter'`` in a ``test_cfg``)
+    on its default ``base_scheduler='UniPCMultistep'``, without diffusers: the tables of FlowEulerODEScheduler, ``base_sigmas`` =
+    ``sigmas.clamp(max=1 - eps)`` for the solver (flow_adapter.py:148), and UniPC (predictor + corrector, x0-prediction, flow sigmas,
+    ``lower_order_final``, final sigma 0) of order ``solver_order`` in {1, 2, 3} with ``solver_type`` 'bh1' / 'bh2'.
+
+    The multistep arithmetic is diffusers' ``UniPCMultistepScheduler`` AS RECALLED (DESIGN.md 6.1 "Multistep sampling" writes it out): no
+    fixture pins it -- parity unpinned.  With s the clamped sigmas, alpha = 1 - s, lambda = log alpha - log s, step i does
+    m_t = x - s_i u; for i past the first step of the roll the corrector re-evaluates x with m_t; then the predictor advances to s_{i+1}.
+    Both are linear in (last_sample | x, m_t, past m's): ``coefficients(i)`` evaluates their weights in fp64 on the host, which is what
+    ``step()`` applies in torch and the fused kernel (afx_teacher_unipc_step) per element."""
+    _DEFAULTS = dict(FlowEulerODEScheduler._DEFAULTS, solver_order=2, solver_type='bh2', eps=1e-4)
+
+    def __init__(self, num_train_timesteps: int = 1000, **kwargs: Any):
+        super().__init__(num_train_timesteps, **kwargs)
+        c = self.config
+        if isinstance(c.solver_order, bool) or c.solver_order not in (1, 2, 3):
+            raise ValueError(f'solver_order: one of 1, 2, 3, got {c.solver_order!r}')
+        if c.solver_type not in ('bh1', 'bh2'):
+            raise ValueError(f"solver_type: 'bh1' or 'bh2', got {c.solver_type!r}")
+        if not 0.0 < float(c.eps) < 1.0:
+            raise ValueError(f'eps must lie in (0, 1), got {c.eps!r}')
+        self.base_sigmas = self.sigmas.clamp(max=1 - c.eps)
+        self._reset()
+
+    def _reset(self):
+        self.model_outputs: List[torch.Tensor] = []          # past x0-predictions, oldest first, at most solver_order of them
+        self.last_sample: Optional[torch.Tensor] = None
+        self.lower_order_nums = 0
+        self.this_order: Optional[int] = None
+        self._first_index: Optional[int] = None              # the step the current roll began with
+
+    def set_timesteps(self, num_inference_steps: int, seq_len=None, device=None):
+        ts = super().set_timesteps(num_inference_steps, seq_len=seq_len, device=device)
+        self.base_sigmas = self.sigmas.clamp(max=1 - self.config.eps)
+        self._reset()
+        return ts
+
+    def orders(self, i: int, begin: int = 0) -> Tuple[int, int]:
+        """-> (corrector order, predictor order) of step i in a roll that began at step ``begin`` with an empty history; corrector order 0
+        = no corrector (i == begin).  The predictor's is diffusers' ``this_order`` = min(solver_order, n - i, lower_order_nums + 1) with
+        lower_order_nums = min(i - begin, solver_order); the corrector's is the previous step's ``this_order``."""
+        n, so, j = self.num_inference_steps, self.config.solver_order, i - begin
+        if not 0 <= begin <= i < n:
+            raise ValueError(f'step {i} of a roll from step {begin} of {n}')
+        return (min(so, n - i + 1, j) if j > 0 else 0), min(so, n - i, min(j, so) + 1)
+
+    def _rho(self, order: int, rks: List[float], hh: float, predictor: bool) -> Tuple[List[float], float, float]:
+        """-> (rho over rks, h phi_1, B) of one UniPC update with hh = -h, finite.  rks = [r_1 .. r_{order-1}, 1]."""
+        h_phi_1 = math.expm1(hh)
+        B = h_phi_1 if self.config.solver_type == 'bh2' else hh
+        phi, f, b = h_phi_1 / hh - 1.0, 1.0, []
+        for j in range(1, order + 1):
+            b.append(phi * f / B)
+            f *= j + 1
+            phi = phi / hh - 1.0 / f
+        R = [[r ** j for r in rks] for j in range(order)]
+        if predictor:                                       # the last column (r = 1, the point not yet evaluated) is the corrector's
+            if order == 1:
+                rho: List[float] = []
+            elif order == 2:
+                rho = [0.5]
+            else:
+                rho = np.linalg.solve(np.array(R, dtype=np.float64)[:-1, :-1], np.array(b[:-1], dtype=np.float64)).tolist()
+        else:
+            rho = [0.5] if order == 1 else np.linalg.solve(np.array(R, dtype=np.float64), np.array(b, dtype=np.float64)).tolist()
+        return rho, h_phi_1, B
+
+    def coefficients(self, i: int, begin: Optional[int] = None) -> UniPCStep:
+        """The flattened scalars of step i, in fp64 from the fp32 table ``base_sigmas``; ``begin``: the first step of the roll (default: the
+        one ``step()`` began with, else 0), where the history is empty.  Needs ``set_timesteps()``.
+
+        Flattening: each D_k = (m[-(k+1)] - m0) / r_k puts rho_k / r_k on m[-(k+1)] and takes the same from m0, so with
+        a = alpha(s_to), g_k = rho_k / r_k:
+          corrector (s_to = s_i, m0 = m[-1]):  last_sample: s_i / s_{i-1};  m_t: -a B rho_last;  m[-(k+1)]: -a B g_k;
+                                               m[-1]: -a h phi_1 + a B (sum_k g_k + rho_last)
+          predictor (s_to = s_{i+1}, m0 = m_t): x_c: s_{i+1} / s_i;  m[-k]: -a B g_k;  m_t: -a h phi_1 + a B sum_k g_k
+        The step landing on sigma 0 has h = +inf: order 1 (lower_order_final), expm1(-inf) = -1, so x_next = 0 x_c + 1 m_t exactly."""
+        if begin is None:
+            begin = self._first_index if self._first_index is not None else 0
+        oc, op = self.orders(i, begin)
+        s = [float(v) for v in self.base_sigmas.double().tolist()]
+        lam = [math.log1p(-v) - math.log(v) if v > 0.0 else math.inf for v in s]
+
+        def ratios(order: int, base: int, h: float) -> List[float]:
+            return [(lam[base - k] - lam[base]) / h for k in range(1, order)] + [1.0]
+
+        corrector = None
+        if oc:
+            h = lam[i] - lam[i - 1]
+            if not (h > 0.0 and math.isfinite(h)):
+                raise ValueError(f'UniPC needs strictly decreasing sigmas in (0, 1): sigma[{i - 1}] = {s[i - 1]}, sigma[{i}] = {s[i]} (after the clamp to 1 - eps)')
+            rks = ratios(oc, i - 1, h)
+            rho, h_phi_1, B = self._rho(oc, rks, -h, predictor=False)
+            a = 1.0 - s[i]
+            g = [rho[k] / rks[k] for k in range(oc - 1)]
+            w = [s[i] / s[i - 1], -a * B * rho[-1], -a * h_phi_1 + a * B * (sum(g) + rho[-1])] + [-a * B * gk for gk in g]
+            corrector = tuple(w + [0.0] * (5 - len(w)))
+        if s[i + 1] == 0.0:
+            if op != 1:
+                raise ValueError('a step onto sigma 0 that is not the last step of the schedule')
+            predictor = (0.0, 1.0, 0.0, 0.0)
+        else:
+            h = lam[i + 1] - lam[i]
+            if not (h > 0.0 and math.isfinite(h)):
+                raise ValueError(f'UniPC needs strictly decreasing sigmas in (0, 1): sigma[{i}] = {s[i]}, sigma[{i + 1}] = {s[i + 1]} (after the clamp to 1 - eps)')
+            rks = ratios(op, i, h)
+            rho, h_phi_1, B = self._rho(op, rks, -h, predictor=True)
+            a = 1.0 - s[i + 1]
+            g = [rho[k] / rks[k] for k in range(op - 1)]
+            w = [s[i + 1] / s[i], -a * h_phi_1 + a * B * sum(g)] + [-a * B * gk for gk in g]
+            predictor = tuple(w + [0.0] * (4 - len(w)))
+        return UniPCStep(s[i], corrector, predictor, oc, op)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None, return_dict: bool = True,
+             prediction_type: str = 'u'):
+        """One UniPC step in fp32 with the weights of ``coefficients()`` rounded to fp32, cast back to model_output's dtype.  The first
+        ``step()`` after ``set_timesteps()`` begins a roll: an empty history, at ``begin_index`` or at ``timestep``'s index."""
+        i = self._begin_step(timestep, prediction_type)
+        if self._first_index is None:
+            self._first_index = i
+        ori_dtype = model_output.dtype
+        x = sample.to(torch.float32)
+        u = model_output.to(torch.float32)
+        co = self.coefficients(i)
+        m_t = x - torch.tensor(co.sigma, dtype=torch.float32) * u
+        hist = self.model_outputs[::-1]                                  # hist[k - 1] = m[-k]
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)             # noqa: E731
+        if co.corrector is not None:
+            cl, cm, *ch = co.corrector
+            x_c = f32(cl) * self.last_sample
+            for k in range(co.corrector_order):
+                x_c = x_c + f32(ch[k]) * hist[k]
+            x_c = x_c + f32(cm) * m_t
+        else:
+            x_c = x
+        px, pm, *ph = co.predictor
+        prev = f32(px) * x_c
+        for k in range(co.predictor_order - 1):
+            prev = prev + f32(ph[k]) * hist[k]
+        prev_sample = (prev + f32(pm) * m_t).to(ori_dtype)
+        self.model_outputs = (self.model_outputs + [m_t])[-self.config.solver_order:]
+        self.last_sample = x_c
+        self.this_order = co.predictor_order
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
         self._step_index += 1
         if not return_dict:
             return (prev_sample,)

@@ -1,11 +1,12 @@
 """Teacher sampling: the loop with true classifier-free guidance that the reference runs in ``GaussianFlow.forward_test``
 (lakonlab/models/diffusions/gaussian_flow.py:149-222) with one of its own schedulers, chosen by name as ``test_cfg['sampler']`` does:
-``FlowEulerODEScheduler`` (schedulers/flow_euler_ode.py, the default) or the stochastic ``FlowSDEScheduler`` (schedulers/flow_sde.py)
--- what the student is judged against, and a source of latents for the data mode.
+``FlowEulerODEScheduler`` (schedulers/flow_euler_ode.py, the default), the stochastic ``FlowSDEScheduler`` (schedulers/flow_sde.py) or,
+as ``'UniPC'``, the multistep solver behind ``FlowAdapterScheduler`` (schedulers/flow_adapter.py on its default base scheduler;
+``schedule.FlowUniPCScheduler``) -- what the student is judged against, and a source of latents for the data mode.
 
 Per step: the positive teacher forward, the negative one when guidance is active on that step, the projection coefficient of
 orthogonal guidance (``afx_cfg_ortho_coef``, orthogonal only) and ONE step kernel (``afx_teacher_euler_step`` /
-``afx_teacher_sde_step``) that combines the two bf16 velocities, advances the fp32 latents in place and writes the bf16 copy the next
+``afx_teacher_sde_step`` / ``afx_teacher_unipc_step``) that combines the two bf16 velocities, advances the fp32 latents in place and writes the bf16 copy the next
 forward reads.  No torch arithmetic runs inside the loop -- with FlowSDE, nothing but the step's N(0, 1) draw, which stays torch's so
 that a ``torch.Generator`` reproduces a run; the latents never leave the packed token layout.
 
@@ -23,9 +24,9 @@ import torch
 
 from . import ops
 from .engine import MMDiTEngine
-from .schedule import FlowEulerODEScheduler, FlowSDEScheduler, truncate_by_strength
+from .schedule import FlowEulerODEScheduler, FlowSDEScheduler, FlowUniPCScheduler, truncate_by_strength
 
-SAMPLERS = {'FlowEulerODE': FlowEulerODEScheduler, 'FlowSDE': FlowSDEScheduler}
+SAMPLERS = {'FlowEulerODE': FlowEulerODEScheduler, 'FlowSDE': FlowSDEScheduler, 'UniPC': FlowUniPCScheduler}
 
 
 class TeacherSampler:
@@ -46,7 +47,10 @@ class TeacherSampler:
     sampler: 'FlowEulerODE' (the default) or 'FlowSDE', the scheduler class as the reference's ``test_cfg['sampler']`` names it;
     FlowSDE's ``h`` (a float or 'inf') travels in scheduler_kwargs.  With FlowSDE every step takes a fresh N(0, 1) draw of the latents'
     shape: from ``generator`` (one torch.randn per step, also on the steps whose draw is not read, so that the generator advances as in
-    the reference), or from ``step_noise`` [num_steps, B, N, C].  With FlowEulerODE both are accepted and ignored.
+    the reference), or from ``step_noise`` [num_steps, B, N, C].  With FlowEulerODE and UniPC both are accepted and ignored.
+    'UniPC': the predictor-corrector multistep solver of FlowUniPCScheduler (``solver_order`` 1 / 2 (default) / 3, ``solver_type`` 'bh1' /
+    'bh2', ``eps`` in scheduler_kwargs), one forward (pair) per step like the others; the step kernel afx_teacher_unipc_step also keeps
+    the solver's state -- the corrected sample and a ring of ``solver_order`` past clean-sample predictions, allocated once per roll.
 
     Editing.  ``x0`` [B, N, 64] fp32, the packed latents of a source image, starts the roll from the image instead of from noise:
     with ``sigmas`` the full schedule of ``num_steps`` = n steps, ``schedule.truncate_by_strength`` gives t_start = int(max(n -
@@ -56,7 +60,9 @@ class TeacherSampler:
     kept region is set to (1 - sigma_to) x0 + sigma_to noise with the START noise (never a FlowSDE draw), so after the last step
     (sigma_to = 0) it is x0 bit for bit.  With FlowSDE one draw is made for every step that RUNS and none for the skipped ones: a
     generator advances n - t_start times, and ``step_noise`` is [n - t_start, B, N, C].  Guidance interval, orthogonal guidance, the
-    prepared-step chunks and the micro-batches work as without an edit."""
+    prepared-step chunks and the micro-batches work as without an edit.  With UniPC a ``strength`` < 1 roll starts its suffix on an
+    empty history (first order, then warming up), and ``mask`` is refused: re-imposing the kept region after a step would invalidate the
+    history the next step extrapolates from, so inpainting stays with FlowEulerODE and FlowSDE."""
 
     def __init__(self, engine: MMDiTEngine, num_steps: int = 28, guidance_scale: float = 1.0, distilled_guidance: Optional[float] = None,
                  guidance_interval: Optional[Sequence[float]] = None, orthogonal_guidance: bool = False,
@@ -67,7 +73,8 @@ class TeacherSampler:
         if num_steps < 1:
             raise ValueError('num_steps must be >= 1')
         if sampler not in SAMPLERS:
-            raise ValueError(f'sampler: one of {sorted(SAMPLERS)}, got {sampler!r}')
+            hint = " (the adapter's default base scheduler, UniPCMultistep, is sampler='UniPC' here)" if sampler == 'FlowAdapter' else ''
+            raise ValueError(f'sampler: one of {sorted(SAMPLERS)}, got {sampler!r}{hint}')
         self.engine, self.num_steps = engine, int(num_steps)
         self.guidance_scale, self.distilled_guidance = float(guidance_scale), distilled_guidance
         self.guidance_interval = None if guidance_interval is None else (float(guidance_interval[0]), float(guidance_interval[1]))
@@ -91,11 +98,12 @@ class TeacherSampler:
     def step(self, x: torch.Tensor, x_bf16: torch.Tensor, cond: Dict[str, Any], sigma: torch.Tensor, sigma_to: torch.Tensor,
              active: bool, prepared_step: Optional[int] = None, scratch: Optional[dict] = None, m: Optional[torch.Tensor] = None,
              c_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None,
-             noise0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> None:
+             noise0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, unipc: Optional[Dict[str, Any]] = None) -> None:
         """Advance x (fp32, in place) and x_bf16 (its rounding, in place) from sigma [B] to sigma_to [B].  FlowSDE: m, c_noise [B]
         (FlowSDEScheduler.coefficients) and the step's draw ``noise`` like x (None: no noise term on this step).  Inpainting: with
         ``mask`` [B, N, 4] the fused edit step re-imposes (1 - sigma_to) x0 + sigma_to noise0 where the mask is 0 (``noise0`` None on
-        the step landing on sigma_to = 0); without a mask the plain step runs."""
+        the step landing on sigma_to = 0); without a mask the plain step runs.  UniPC: ``unipc`` = the step's operands for
+        ops.teacher_unipc_step (w, last, hist, last_out, hist_out); sigma_to is not read (the weights carry it)."""
         eng = self.engine
         B = x.shape[0]
         s = scratch if scratch is not None else {}
@@ -114,7 +122,14 @@ class TeacherSampler:
                     s['coef'] = torch.empty(B, dtype=torch.float32, device=x.device)
                     s['ws'] = ops.cfg_ortho_ws(B, x[0].numel(), x.device)
                 coef = ops.cfg_ortho_coef(pos, neg, self.guidance_scale, out=s['coef'], ws=s['ws'])
-        if self.sampler == 'FlowSDE':
+        if self.sampler == 'UniPC':
+            if unipc is None:
+                raise ValueError('a UniPC step needs its weights and state buffers (FlowUniPCScheduler.coefficients)')
+            if mask is not None:
+                raise ValueError("mask: not with sampler='UniPC' (inpainting stays with FlowEulerODE and FlowSDE)")
+            ops.teacher_unipc_step(x, pos, neg, unipc['w'], unipc['last'], unipc['hist'], unipc['last_out'], unipc['hist_out'],
+                                   self.guidance_scale, coef, out=x, out_bf16=x_bf16)
+        elif self.sampler == 'FlowSDE':
             if m is None or c_noise is None:
                 raise ValueError('a FlowSDE step needs m and c_noise (FlowSDEScheduler.coefficients)')
             if mask is not None:
@@ -159,6 +174,13 @@ class TeacherSampler:
             reads_noise = ((co[:, 1] * co[:, 3]) != 0).tolist()               # sigma_to c_noise = 0 (always so on the final step): the kernel gets no noise
             if step_noise is not None:
                 step_noise = step_noise.to(dev, torch.float32).contiguous()
+        multistep = self.sampler == 'UniPC'
+        if multistep:
+            # the solver's per-step weights, once (the history is empty at t_start): rows [num_steps, 10, B]
+            so = self.scheduler.config.solver_order
+            steps = {i: self.scheduler.coefficients(i, t_start) for i in range(t_start, self.num_steps)}
+            rows = torch.tensor([steps[i].row() if i in steps else [0.0] * 10 for i in range(self.num_steps)], dtype=torch.float64)
+            w_rows = rows.to(torch.float32)[:, :, None].expand(-1, -1, B).contiguous().to(dev)
         if x0 is None:
             x = noise.to(dev, torch.float32).clone().contiguous()
             xb = x.to(torch.bfloat16)
@@ -178,6 +200,9 @@ class TeacherSampler:
         g = None
         if eng.guidance_embeds and self.distilled_guidance is not None:
             g = scratch['guidance'] = torch.full((B,), float(self.distilled_guidance), dtype=torch.float32, device=dev)
+        if multistep:
+            last_sample = torch.empty_like(x)
+            ring = [torch.empty_like(x) for _ in range(so)]                   # slot j % so receives the clean-sample prediction of the j-th step that runs
         prepared = False
         for i in range(t_start, self.num_steps):
             j = i - t_start                                                   # the steps that run are counted from the first one that does
@@ -185,7 +210,13 @@ class TeacherSampler:
                 prepared = eng.prepare_steps(sig[i:min(i + chunk, self.num_steps)], cond.get('pooled'), g, B, N, T)
             prep = (j % chunk) if (chunk > 1 and prepared) else None
             edit = {} if mask is None else dict(x0=x0, noise0=None if lands_on_zero[i] else noise, mask=mask)
-            if sde:
+            if multistep:
+                # m[-k] lives in slot (j - k) % so; only the terms the step's orders reach are handed over (the oldest may be the slot written)
+                reach = max(steps[i].corrector_order, steps[i].predictor_order - 1)
+                ms = dict(w=w_rows[i], last=last_sample if j > 0 else None, hist=[ring[(j - k) % so] for k in range(1, reach + 1)],
+                          last_out=last_sample, hist_out=ring[j % so])
+                self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, unipc=ms)
+            elif sde:
                 z = step_noise[j] if step_noise is not None else self._draw(x.shape, generator)
                 self.step(x, xb, cond, sig[i], sig[i + 1], active[i], prep, scratch, m_rows[i], c_rows[i], z if reads_noise[i] else None, **edit)
             else:
@@ -203,6 +234,9 @@ class TeacherSampler:
             raise ValueError('guidance_scale > 1 (true CFG) needs cond["negative_prompt_embeds"]')
         B = noise.shape[0]
         t_start = 0
+        if mask is not None and self.sampler == 'UniPC':
+            raise ValueError("mask: not with sampler='UniPC' -- re-imposing the kept region after each step invalidates the multistep history; "
+                             "inpaint with sampler='FlowEulerODE' or 'FlowSDE'")
         if x0 is None:
             if mask is not None:
                 raise ValueError('mask needs x0 (the packed latents of the image whose unmasked region is kept)')
@@ -239,7 +273,11 @@ _SHIFT_KEYS = ('shift', 'use_dynamic_shifting', 'base_seq_len', 'max_seq_len', '
 _TIMESTEP_SAMPLER_DEFAULTS = dict(shift=1.0, use_dynamic_shifting=False, base_seq_len=256, max_seq_len=4096, base_logshift=0.5, max_logshift=1.15)
 
 
-def sampler_kwargs_from_test_cfg(test_cfg: Optional[Dict[str, Any]] = None, timestep_sampler: Any = None, num_timesteps: int = 1000) -> Dict[str, Any]:
+_ADAPTER_BASE = 'UniPCMultistep'          # FlowAdapterScheduler's default base_scheduler, the one built here (sampler='UniPC')
+
+
+def sampler_kwargs_from_test_cfg(test_cfg: Optional[Dict[str, Any]] = None, timestep_sampler: Any = None, num_timesteps: int = 1000,
+                                 allow_adapter: bool = False) -> Dict[str, Any]:
     """A reference ``test_cfg`` (what ``GaussianFlow.forward_test`` reads, gaussian_flow.py:157-181) -> the keyword arguments of
     ``TeacherSampler(engine, **kwargs)``.
 
@@ -249,12 +287,21 @@ def sampler_kwargs_from_test_cfg(test_cfg: Optional[Dict[str, Any]] = None, time
     with these attributes or as its config dict (a key it leaves out has ContinuousTimeStepSampler's default) -- exactly as
     gaussian_flow.py:167-171 fills them.  ``num_timesteps`` of the test_cfg is the number of sampling steps (default: the model's
     ``num_timesteps``, the argument here, which is also the scheduler's ``num_train_timesteps``).  A sampler this project does
-    not have (FlowAdapter, any diffusers scheduler) raises ValueError."""
+    not have (any diffusers scheduler) raises ValueError, and so does 'FlowAdapter' unless ``allow_adapter``: then a test_cfg with
+    sampler 'FlowAdapter' whose ``sampler_kwargs['base_scheduler']`` is 'UniPCMultistep' or absent (the adapter's default) maps to
+    ``sampler='UniPC'`` with its solver_order, solver_type, eps and the shift family; any other base_scheduler (the DPM-Solver, DEIS, SA and
+    Euler families) raises ValueError naming it."""
     cfg = dict(test_cfg or {})
     name = cfg.get('sampler', 'FlowEulerODE')
-    if name not in SAMPLERS:
-        raise ValueError(f'test_cfg sampler {name!r} is not available here: one of {sorted(SAMPLERS)} (FlowAdapter and the diffusers schedulers are not built)')
     kw = dict(cfg.get('sampler_kwargs') or {})
+    if name == 'FlowAdapter' and allow_adapter:
+        base = kw.pop('base_scheduler', _ADAPTER_BASE)
+        if base != _ADAPTER_BASE:
+            raise ValueError(f'test_cfg sampler FlowAdapter with base_scheduler {base!r}: only {_ADAPTER_BASE!r} (the default) is built here')
+        name = 'UniPC'
+    elif name not in SAMPLERS:
+        raise ValueError(f"test_cfg sampler {name!r} is not available here: one of {sorted(SAMPLERS)}, or FlowAdapter on its "
+                         f"{_ADAPTER_BASE} base scheduler with allow_adapter=True (TeacherSampler's sampler='UniPC'); the other diffusers schedulers are not built")
     unknown = set(kw) - set(SAMPLERS[name]._DEFAULTS)
     if unknown:
         raise TypeError(f'{name}Scheduler takes no {sorted(unknown)}')

@@ -318,7 +318,8 @@ class ArcFlowDistiller:
         (guidance_interval, orthogonal_guidance, terminal_sigma ...) go to TeacherSampler.  sampler='FlowSDE': the stochastic
         sampler with noise strength ``h`` (a float, default 1.0, or 'inf'), its per-step draws from ``generator`` or from
         ``step_noise`` [num_steps, B, N, C].  ``x0`` [B, N, 64] (packed latents of a source image), ``mask`` [B, N, 4] and ``strength``
-        are TeacherSampler's image-to-image / inpainting arguments, passed through."""
+        are TeacherSampler's image-to-image / inpainting arguments, passed through.  sampler='UniPC': the multistep solver of
+        FlowUniPCScheduler; its ``solver_order`` (1 / 2 / 3) and ``solver_type`` ('bh1' / 'bh2') travel with the further keywords."""
         from ..teacher import TeacherSampler
         c = self.cfg
         if guidance_scale is None:

@@ -229,6 +229,29 @@ int afx_teacher_euler_step(const float* x, const void* pos, const void* neg, con
 int afx_teacher_sde_step(const float* x, const void* pos, const void* neg, const float* noise, const float* sigma,
                          const float* sigma_to, const float* m, const float* c_noise, const float* coef, float scale, float* x_out,
                          void* x_out_bf16, int32_t batch, int64_t n, int32_t max_blocks, void* stream);
+/* One step of the teacher's UniPC multistep sampler (FlowUniPCScheduler: the predictor-corrector solver behind the reference's
+ * FlowAdapterScheduler on its default base scheduler, schedulers/flow_adapter.py; the multistep arithmetic is diffusers' as recalled and
+ * no fixture pins it) with the same operands, layout and CFG combine as afx_teacher_euler_step, in one launch.  The host evaluates the
+ * solver's scalars in fp64 (FlowUniPCScheduler.coefficients) and passes one fp32 weight per operand and sample, w [10, batch], rows
+ *   0 s | 1 c_last  2 c_mt  3 c_1  4 c_2  5 c_3 | 6 p_xc  7 p_mt  8 p_1  9 p_2.
+ * Per element, in fp32, every product-sum one fused multiply-add in exactly this order:
+ *   u      = pos + (pos - neg) (scale - 1) - coef[b] pos          exactly as afx_teacher_euler_step forms it
+ *   m_t    = fma(-s, u, x)                                         the clean-sample prediction x - s u
+ *   x_c    = fma(c_mt, m_t, fma(c_3, h3, fma(c_2, h2, fma(c_1, h1, c_last last))))      the corrector; last NULL: x_c = x
+ *   x_next = fma(p_mt, m_t, fma(p_2, h2, fma(p_1, h1, p_xc x_c)))                        the predictor
+ * last [batch, n] fp32: the corrected sample the previous step wrote (NULL on the first step of a roll: no corrector); h1, h2, h3
+ * [batch, n] fp32: the m_t of one, two and three steps ago, NULL when the step's orders do not reach them -- a NULL operand is neither
+ * read nor multiplied.  last needs h1, h2 needs h1, h3 needs h2.  Outputs: x_out = x_next (may be x), x_out_bf16 = its
+ * round-to-nearest-even bf16 copy, last_out = x_c (may be last), hist_out = m_t (may be h1, h2 or h3 itself: the caller rotates a ring
+ * of solver_order buffers and overwrites the oldest).  With p_xc = 0, p_mt = 1, p_1 = p_2 = 0 (the step that lands on sigma 0)
+ * x_next = m_t bit for bit for finite operands.  AFX_E_INVALID before any launch when a required pointer is NULL (all but neg, last,
+ * h1, h2, h3, coef), n is not a positive multiple of 64, batch or max_blocks < 0, a tensor is not 16-byte aligned, or an output
+ * overlaps another operand other than by the three aliases above.  max_blocks: cap on the grid of the grid-stride loop (0 = the
+ * default, 2048).  Traffic at 1024 x 1024 (262144 elements per image) at order 2: 4 + 2 + 2 + 4 + 4 + 4 = 20 B read and 4 + 2 + 4 + 4 =
+ * 14 B written per element, about 8.9 MB per image and step. */
+int afx_teacher_unipc_step(const float* x, const void* pos, const void* neg, const float* w, const float* last, const float* h1,
+                           const float* h2, const float* h3, const float* coef, float scale, float* x_out, void* x_out_bf16, float* last_out,
+                           float* hist_out, int32_t batch, int64_t n, int32_t max_blocks, void* stream);
 /* The blend of image editing (image-to-image start, inpainting) on the engine's packed token layout, in one launch: the source
  * latents x0 diffused forward to sigma_to with the call's fixed noise, blended per latent pixel with the sampler's latents x, plus the
  * bf16 copy the next forward reads.  Per element, in fp32, exactly:

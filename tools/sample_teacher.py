@@ -151,7 +151,9 @@ def main(argv=None):
     ap.add_argument('--guidance-interval', type=float, nargs=2, default=None)
     ap.add_argument('--orthogonal-guidance', action='store_true')
     ap.add_argument('--shift', type=float, default=3.2)
-    ap.add_argument('--sampler', choices=['FlowEulerODE', 'FlowSDE'], default='FlowEulerODE')
+    ap.add_argument('--sampler', choices=['FlowEulerODE', 'FlowSDE', 'UniPC'], default='FlowEulerODE')
+    ap.add_argument('--solver-order', type=int, choices=[1, 2, 3], default=None, help='--sampler UniPC: order of the multistep solver (default 2)')
+    ap.add_argument('--solver-type', choices=['bh1', 'bh2'], default=None, help='--sampler UniPC: the B(h) of the solver (default bh2)')
     ap.add_argument('--h', type=lambda v: v if v == 'inf' else float(v), default=None,
                     help='--sampler FlowSDE: noise strength, a float (0 = the ODE; default 1.0) or inf (re-noise the clean prediction completely)')
     ap.add_argument('--image', help='source image of an edit (sides multiples of 16), or a .pt file of its latents [16, H, W]')
@@ -167,6 +169,8 @@ def main(argv=None):
     encoder = None
     if args.mask and not args.image:
         raise SystemExit('--mask needs --image')
+    if args.mask and args.sampler == 'UniPC':
+        raise SystemExit('--mask: not with --sampler UniPC (inpainting stays with FlowEulerODE and FlowSDE)')
     if args.synthetic:
         engine, joint, pooled = synthetic_engine(args.family, dev, args.seed)
         if not os.path.isdir(args.cache_dir) or not os.listdir(args.cache_dir):
@@ -199,7 +203,8 @@ def main(argv=None):
         raise SystemExit('--true-cfg-scale > 1 needs --negative-prompt (with --prompts) or --negative-prompt-embeds')
     sampler = TeacherSampler(engine, args.steps, guidance_scale=args.true_cfg_scale, distilled_guidance=args.guidance_scale,
                              guidance_interval=args.guidance_interval, orthogonal_guidance=args.orthogonal_guidance, shift=args.shift,
-                             sampler=args.sampler, **({} if args.h is None else dict(h=args.h)))
+                             sampler=args.sampler,
+                             **{k: v for k, v in dict(h=args.h, solver_order=args.solver_order, solver_type=args.solver_type).items() if v is not None})
     edit = load_edit(args.image, args.mask, encoder, dev) if args.image else None
     done = add_teacher_latents(sampler, args.cache_dir, negative, args.seed, device=dev, edit=edit, strength=args.strength)
     print(f'wrote teacher latents into {len(done)} records of {args.cache_dir}')

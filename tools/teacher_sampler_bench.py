@@ -12,6 +12,10 @@ against the two launches it replaces (afx_teacher_euler_step / afx_teacher_sde_s
 interleaved in every round, at least 21 rounds, with the bytes per element and the GB/s of each; and a 28-step inpainting roll
 (TeacherSampler with x0 and a mask) beside the plain roll.
 
+``--sampler UniPC`` measures the multistep sampler instead (DESIGN.md 6.1 "Multistep sampling"): the fused UniPC step
+(afx_teacher_unipc_step at order 2 past the warm-up: 34 B per element, in place, history ring rotated) beside the Euler step (14 B) at B = 1 and 4,
+interleaved in every round, with the GB/s of each; and a ``--steps`` UniPC teacher image beside the Euler one.
+
     python tools/teacher_sampler_bench.py --out profiles/teacher_sampler_bench.json
 """
 import argparse
@@ -101,6 +105,67 @@ def edit_bench(args, emit):
         emit(dict(what='teacher_image_1024', variant=k, steps=args.steps, ms_median=statistics.median(v), ms_min=min(v), ms_max=max(v), rounds=len(v)))
 
 
+def unipc_bench(args, emit):
+    """The fused UniPC step beside the Euler step, and a UniPC roll beside the Euler roll."""
+    from arcflow_amd import FlowUniPCScheduler, MMDiTEngine, TeacherSampler, ops
+    from arcflow_amd.weights import random_packed
+    dev = 'cuda'
+    g = torch.Generator(device=dev).manual_seed(0)
+    N, C, T = 4096, 64, 512
+    rounds = max(args.rounds, 21)
+    sch = FlowUniPCScheduler(1000, shift=3.2, solver_order=args.solver_order)
+    sch.set_timesteps(args.steps)
+    i = min(args.steps // 2, args.steps - 2)                     # a step past the warm-up and before the order drops again
+    co = sch.coefficients(i)
+    reach = max(co.corrector_order, co.predictor_order - 1)
+    nbytes = dict(euler=14.0, unipc=4 + 2 + 2 + 4 + 4 * reach + 4 + 2 + 4 + 4)
+    for B in (1, 4):
+        x = torch.randn(B, N, C, generator=g, device=dev)
+        pos = torch.randn(B, N, C, generator=g, device=dev).bfloat16()
+        neg = torch.randn(B, N, C, generator=g, device=dev).bfloat16()
+        last = torch.randn(B, N, C, generator=g, device=dev)
+        ring = [torch.randn(B, N, C, generator=g, device=dev) for _ in range(max(reach, 1))]
+        w = torch.tensor(co.row(), dtype=torch.float64).float()[:, None].expand(-1, B).contiguous().to(dev)
+        sig, sig_to = torch.full((B,), 0.7, device=dev), torch.full((B,), 0.65, device=dev)
+        xo, xb = torch.empty_like(x), torch.empty(B, N, C, dtype=torch.bfloat16, device=dev)
+
+        def euler():
+            ops.teacher_euler_step(x, pos, neg, sig, sig_to, 4.0, None, out=xo, out_bf16=xb)
+
+        def unipc():                                               # as the roll calls it: the state in place, the oldest slot overwritten
+            ops.teacher_unipc_step(x, pos, neg, w, last, ring[:reach], last, ring[reach - 1], 4.0, None, out=xo, out_bf16=xb)
+
+        variants = dict(euler=euler, unipc=unipc)
+        samples = {k: [] for k in variants}
+        for r in range(args.warmup + rounds):
+            for k, fn in variants.items():                 # interleaved: every round times every variant
+                t = timed(fn, 50)
+                if r >= args.warmup:
+                    samples[k].append(t)
+        for k, v in samples.items():
+            med = statistics.median(v)
+            emit(dict(what='teacher_unipc_step', variant=k, shape=[B, N, C], solver_order=args.solver_order, us_median=1e3 * med, us_min=1e3 * min(v),
+                      us_max=1e3 * max(v), bytes_per_element=nbytes[k], gb_per_s=nbytes[k] * B * N * C / (med * 1e-3) / 1e9, rounds=len(v), reps_per_round=50))
+    if args.skip_image:
+        return
+    B = 1
+    eng = MMDiTEngine('flux', 19, 38, teacher_head=True)
+    eng.bind_packed(random_packed('flux', 19, 38, dev, teacher=True))
+    cond = dict(prompt_embeds=(torch.randn(B, T, 4096, generator=g, device=dev) * 0.5).bfloat16(),
+                pooled=(torch.randn(B, 768, generator=g, device=dev) * 0.5).bfloat16(), hp=64, wp=64)
+    noise = torch.randn(B, N, C, generator=g, device=dev)
+    runs = dict(euler=TeacherSampler(eng, args.steps, guidance_scale=1.0, distilled_guidance=3.5, shift=3.2),
+                unipc=TeacherSampler(eng, args.steps, guidance_scale=1.0, distilled_guidance=3.5, shift=3.2, sampler='UniPC', solver_order=args.solver_order))
+    samples = {k: [] for k in runs}
+    for r in range(1 + 5):
+        for k, s in runs.items():
+            t = timed(lambda: s(cond, noise), 1)
+            if r >= 1:
+                samples[k].append(t)
+    for k, v in samples.items():
+        emit(dict(what='teacher_image_1024', variant=k, steps=args.steps, ms_median=statistics.median(v), ms_min=min(v), ms_max=max(v), rounds=len(v)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out')
@@ -109,6 +174,8 @@ def main():
     ap.add_argument('--steps', type=int, default=28)
     ap.add_argument('--skip-image', action='store_true')
     ap.add_argument('--edit', action='store_true', help='measure the fused edit step against the two-launch composition, and an inpainting roll')
+    ap.add_argument('--sampler', choices=['FlowEulerODE', 'UniPC'], default='FlowEulerODE', help='UniPC: measure the multistep step and roll beside the Euler ones')
+    ap.add_argument('--solver-order', type=int, choices=[1, 2, 3], default=2)
     args = ap.parse_args()
     from arcflow_amd import MMDiTEngine, TeacherSampler, ops
     from arcflow_amd.weights import random_packed
@@ -121,8 +188,8 @@ def main():
         lines.append(rec)
         print(json.dumps(rec), flush=True)
 
-    if args.edit:
-        edit_bench(args, emit)
+    if args.edit or args.sampler == 'UniPC':
+        (edit_bench if args.edit else unipc_bench)(args, emit)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, 'w') as f:
