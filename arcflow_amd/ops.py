@@ -167,13 +167,19 @@ def attention_to_mx8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out=None
 def norm_modulate(x: torch.Tensor, scale: torch.Tensor, shift: Optional[torch.Tensor], rows_per_batch: int = 0,
                   rms: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [R,D] bf16; AdaLN: scale/shift [B,D] f32 (row r uses batch r // rows_per_batch);
-    rms=True: x * rsqrt(mean x^2 + 1e-6) * scale[D]."""
+    rms=True: x * rsqrt(mean x^2 + 1e-6) * scale[D].  Two fp32 [B,D] column views of one stacked modulation tensor (unit inner stride, the
+    same row stride, 16-byte aligned rows) are read in place, as the forward's single blocks read them; anything else is copied."""
     lib = _lib.load()
     R, D = x.shape
     if out is None:
         out = torch.empty(R, D, dtype=torch.bfloat16, device=x.device)
-    scale = _cuda(scale, torch.float32)
-    shift = None if shift is None else _cuda(shift, torch.float32)
+    _gpu(scale, shift)
+    in_place = not rms and shift is not None and all(
+        v.dim() == 2 and v.dtype == torch.float32 and v.stride(1) == 1 and v.stride(0) % 4 == 0 and v.data_ptr() % 16 == 0
+        for v in (scale, shift)) and scale.stride(0) == shift.stride(0)
+    if not in_place:
+        scale = _cuda(scale, torch.float32)
+        shift = None if shift is None else _cuda(shift, torch.float32)
     ldm = 0 if rms or scale.dim() == 1 else scale.stride(0)
     _lib.check(lib.afx_norm_modulate_bf16(_p(x), x.stride(0), _p(out), out.stride(0), R, D, _p(scale), _p(shift), ldm,
                                           rows_per_batch if rows_per_batch > 0 else max(R, 1), int(rms), _s()))

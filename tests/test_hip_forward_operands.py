@@ -245,13 +245,17 @@ def _silu64(x):
 def _sincos64(t, cast):
     """sincos_kernel's documented casts: FLUX (cast 1) feeds bf16(bf16(t) * 1000) to the sinusoid.  The angle is formed in fp32 as the kernel
     forms it (frequency expf(-ln(1e4) i / 128), then the product), its cos / sin in fp64.  Bound: cos / sin in fp32 (2 u) and one fp32 ulp of
-    the frequency between the device's expf and torch's (2 u |a| through the product)."""
-    assert cast == 1
+    the frequency between the device's expf and torch's (2 u |a| through the product).  Qwen (cast 2) rounds t alone to bf16; the x 1000 is
+    the sinusoid's own scale in fp32: a = 1000 * (bf16(t) * f), two fp32 products in the kernel's order (same bound)."""
+    assert cast in (1, 2)
     tb = t.bfloat16().float()
-    x = (tb * 1000).bfloat16().float()
     i = torch.arange(128, device=t.device, dtype=torch.float32)
     f = torch.exp(torch.tensor(-9.210340371976184, dtype=torch.float32, device=t.device) * i / 128.0)
-    a = (x[:, None] * f[None]).double()
+    if cast == 1:
+        x = (tb * 1000).bfloat16().float()
+        a = (x[:, None] * f[None]).double()
+    else:
+        a = (1000.0 * (tb[:, None] * f[None])).double()
     return torch.cat([torch.cos(a), torch.sin(a)], 1), torch.cat([2 * a.abs() + 2] * 2, 1) * U32
 
 
@@ -363,3 +367,76 @@ def test_conditioning_chain_full_width(ops):
     assert eng.prepare_steps(ts, pooled, gd, batch=B, n_img=N, n_txt=T)
     for k in range(4):
         check_all(exported(k), ts[k], f'prepared step {k}: ')
+
+
+def test_conditioning_chain_full_width_qwen(ops):
+    """The Qwen twin: temb = t_mlp(sincos(t)) alone -- sincos_kernel cast mode 2, no guidance and no pooled branch -- SiLU and the stacked
+    modulation GEMV of a Qwen engine with one block at D = 3072 (n_mod = 14 D rows), then afx_mmdit_prepare_steps with B x nsteps = 8 rows.
+    t = 0.7619 is moved visibly by the bf16 rounding (to 0.76171875), t = 0 gives cos 1 / sin 0 exactly.  _gemv64 and its bound unchanged."""
+    from arcflow_amd import MMDiTEngine, _lib
+    nd, B, J = 1, 2, 3584
+    eng = MMDiTEngine('qwen', nd, 0, joint_dim=J)
+    n_mod = eng.n_mod
+    assert n_mod == 14 * D
+    g = _gen(2025)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, generator=g, device='cuda') * sc).bfloat16()     # noqa: E731
+    cond = {'temb.t.l1': (D, 256), 'temb.t.l2': (D, D), 'mod': (n_mod, D)}
+    packed = {}
+    for n, (o, i) in cond.items():
+        packed[n + '.weight'] = rnd(o, i, sc=i ** -0.5)
+        packed[n + '.bias'] = rnd(o, sc=0.1)
+    # the trunk's weights take no part in stage 1's conditioning: one zero buffer behind all of them
+    trunk = {'x_in': (D, 64), 'ctx_in': (D, J), 'head': (1152, D)}
+    for i in range(nd):
+        for s in ('img', 'txt'):
+            trunk.update({f'd{i}.{s}_qkv': (3 * D, D), f'd{i}.{s}_out': (D, D), f'd{i}.{s}_mlp1': (4 * D, D), f'd{i}.{s}_mlp2': (D, 4 * D)})
+    zero = torch.zeros(4 * D * D, dtype=torch.bfloat16, device='cuda')
+    for n, (o, i) in trunk.items():
+        packed[n + '.weight'] = zero[:o * i].view(o, i)
+        packed[n + '.bias'] = zero[:o]
+    zf = torch.ones(J, device='cuda')
+    for i in range(nd):
+        packed[f'd{i}.qknorm'] = zf[:512].view(4, 128)
+    packed['txt_norm.weight'] = zf
+    eng.bind_packed(packed)
+    N, T = 16, 8
+    x = torch.zeros(B, N, 64, dtype=torch.bfloat16, device='cuda')
+    ctx = torch.zeros(B, T, J, dtype=torch.bfloat16, device='cuda')
+    W = {n: (packed[n + '.weight'], packed[n + '.bias']) for n in cond}
+
+    def check_all(got, t, what):
+        sc_t, e_t = _sincos64(t, 2)
+        h, eh = _gemv64(sc_t, e_t, *W['temb.t.l1'], act=True)
+        temb, et = _gemv64(h, eh, *W['temb.t.l2'])
+        _assert_within(got[0], temb, et, f'{what}temb')
+        # SiLU of the engine's own temb: x / (1 + __expf(-x)) in fp32, a few ulp
+        _assert_within(got[1], _silu64(got[0].double()), 4 * U32 * got[0].double().abs() + 1e-30, f'{what}silu_temb')
+        # the stacked modulation GEMV on the engine's own SiLU output (exact fp32 inputs: the summation bound alone)
+        semb = got[1].double()
+        for r0 in range(0, n_mod, 16384):
+            mod, emod = _gemv64(semb, 0 * semb, W['mod'][0][r0:r0 + 16384], W['mod'][1][r0:r0 + 16384])
+            _assert_within(got[2][:, r0:r0 + 16384], mod, emod, f'{what}mod_all rows {r0}..')
+
+    def exported(t, k=None):
+        if k is not None:
+            _lib.check(eng.lib.afx_mmdit_use_prepared_step(eng._ctx, k))
+        eng(x, t, ctx, None, None, 4, 4, stage=1)
+        outs = [torch.empty(B, D, device='cuda'), torch.empty(B, D, device='cuda'), torch.empty(B, n_mod, device='cuda')]
+        for name, o in zip(('temb', 'silu_temb', 'mod_all'), outs):
+            eng.export(name, o, B, N, T)
+        torch.cuda.synchronize()
+        return outs
+
+    t0 = torch.tensor([0.7619, 0.0], device='cuda')
+    assert t0.bfloat16().float()[0].item() == 0.76171875
+    got = exported(t0)
+    check_all(got, t0, '')
+    # cast mode 2 is what ran: the FLUX cast (bf16(bf16(t) * 1000) = 760.0 against 761.71875) gives another embedding
+    sc1, e1 = _sincos64(t0, 1)
+    h, eh = _gemv64(sc1, e1, *W['temb.t.l1'], act=True)
+    temb1, et1 = _gemv64(h, eh, *W['temb.t.l2'])
+    assert bool(((got[0].double() - temb1).abs() > et1)[0].any()), 'temb: the bound cannot tell cast mode 1 from cast mode 2'
+    ts = torch.tensor([[1.0, 0.9], [0.7619, 0.45], [0.3, 0.2], [0.1, 0.0]], device='cuda')
+    assert eng.prepare_steps(ts, None, None, batch=B, n_img=N, n_txt=T)
+    for k in range(4):
+        check_all(exported(ts[k], k), ts[k], f'prepared step {k}: ')
