@@ -22,7 +22,12 @@
 //     student against teacher samples), sum (a-b)^2, sum a^2, sum b^2, sum a b over the n elements of a sample, on the coefficient's
 //     reduction scheme: the same fixed partition, elements widened to fp64 (after the optional image-range transform in fp32), one slot
 //     of 4 doubles per work-group, the slots added in index order by the second launch.  16 B per lane and operand: 8 bf16 or 4 fp32.
+//   * image_ssim_partial_kernel / image_ssim_finish_kernel: per-sample sum of the structural similarity of two image batches over
+//     every valid 11 x 11 Gaussian window (training-time evaluation, decoded images), fp64 throughout: one work-group and one slot per
+//     tile of windows, the slots added in a fixed order by the second launch.  Scheme and LDS use at the kernel.
 #include <algorithm>
+#include <climits>
+#include <cmath>
 
 #include "afx_api_util.h"
 #include "afx_common.h"
@@ -391,6 +396,102 @@ __global__ __launch_bounds__(64) void sample_score_finish_kernel(const double* _
   out[i] = v;
 }
 
+// ---- SSIM of two image batches (Wang et al. 2004: 11-tap Gaussian window, sigma 1.5, "valid" windows only) -----------------------------
+// One work-group = a tile of SSIM_TW x SSIM_TH windows of one (sample, channel) plane.  The (SSIM_TW + 10) x (SSIM_TH + 10) inputs of both
+// images are staged in LDS as the fp32 values the transform leaves (widening is exact, so they are widened where they are read); the
+// horizontal 11-tap pass of a, b, a a, a b, b b goes to LDS as fp64; the vertical pass, the ratio and the sums are fp64 in registers.
+// Positions past the right / bottom edge of the image are staged as zeros and their windows are not counted.
+constexpr int SSIM_TAPS = 11, SSIM_TW = 32, SSIM_TH = 16;
+constexpr int SSIM_IW = SSIM_TW + SSIM_TAPS - 1, SSIM_IH = SSIM_TH + SSIM_TAPS - 1;          // 42 x 26 staged inputs per image
+
+struct ssim_taps_t { double g[SSIM_TAPS]; };          // the normalised 1-D window, built in fp64 by the host
+
+// The ratio of one window.  The three central moments come from the same sequence of operations (multiply, subtract: contraction is
+// off, or the compiler would fuse some products into the additions and not others), so a == b gives num == den bit for bit and 1.0.
+AFX_DEV double ssim_ratio(double mu_a, double mu_b, double e_aa, double e_ab, double e_bb, double c1, double c2) {
+#pragma clang fp contract(off)
+  const double p_aa = mu_a * mu_a, p_ab = mu_a * mu_b, p_bb = mu_b * mu_b;
+  const double s_aa = e_aa - p_aa, s_ab = e_ab - p_ab, s_bb = e_bb - p_bb;
+  const double num = (2.0 * p_ab + c1) * (2.0 * s_ab + c2);
+  const double den = ((p_aa + p_bb) + c1) * ((s_aa + s_bb) + c2);
+  return num / den;
+}
+
+// grid (C tiles, B), tiles = tiles_x tiles_y: work-group (ch tiles + tile) of sample s writes ws[s gridDim.x + blockIdx.x] = the sum
+// of ssim over the valid windows of its tile.
+template <bool BF16>
+__global__ __launch_bounds__(256) void image_ssim_partial_kernel(const void* __restrict__ a, const void* __restrict__ b, int transform,
+                                                                 ssim_taps_t taps, double c1, double c2, double* __restrict__ ws, int H,
+                                                                 int W, int tiles_x, int tiles) {
+  __shared__ float sa[SSIM_IH][SSIM_IW + 1], sb[SSIM_IH][SSIM_IW + 1];
+  __shared__ double hq[5][SSIM_IH][SSIM_TW];
+  __shared__ double red[4];
+  const int tile = blockIdx.x % tiles, ch = blockIdx.x / tiles, C = gridDim.x / tiles;
+  const int x0 = (tile % tiles_x) * SSIM_TW, y0 = (tile / tiles_x) * SSIM_TH;
+  const int64_t base = ((int64_t)blockIdx.y * C + ch) * H * W;
+  for (int i = threadIdx.x; i < SSIM_IH * SSIM_IW; i += 256) {
+    const int r = i / SSIM_IW, c = i % SSIM_IW;
+    const int y = y0 + r, x = x0 + c;
+    float p = 0.f, q = 0.f;
+    if (y < H && x < W) {
+      const int64_t at = base + (int64_t)y * W + x;
+      if constexpr (BF16) {
+        p = bf16_to_f32(reinterpret_cast<const bf16_t*>(a)[at]);
+        q = bf16_to_f32(reinterpret_cast<const bf16_t*>(b)[at]);
+      } else {
+        p = reinterpret_cast<const float*>(a)[at];
+        q = reinterpret_cast<const float*>(b)[at];
+      }
+      if (transform) { p = unit_range(p); q = unit_range(q); }
+    }
+    sa[r][c] = p;
+    sb[r][c] = q;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SSIM_IH * SSIM_TW; i += 256) {          // horizontal pass: x x, x y, y y are exact in fp64
+    const int r = i / SSIM_TW, c = i % SSIM_TW;
+    double h[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SSIM_TAPS; ++j) {
+      const double x = (double)sa[r][c + j], y = (double)sb[r][c + j], g = taps.g[j];
+      h[0] = fma(g, x, h[0]);
+      h[1] = fma(g, y, h[1]);
+      h[2] = fma(g, x * x, h[2]);
+      h[3] = fma(g, x * y, h[3]);
+      h[4] = fma(g, y * y, h[4]);
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) hq[k][r][c] = h[k];
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < SSIM_TH * SSIM_TW; i += 256) {          // vertical pass, ratio; a lane adds its windows in index order
+    const int r = i / SSIM_TW, c = i % SSIM_TW;
+    if (y0 + r >= H - (SSIM_TAPS - 1) || x0 + c >= W - (SSIM_TAPS - 1)) continue;
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SSIM_TAPS; ++j) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[k] = fma(taps.g[j], hq[k][r + j][c], v[k]);
+    }
+    acc += ssim_ratio(v[0], v[1], v[2], v[3], v[4], c1, c2);
+  }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one wave per sample: lane l adds the slots l, l + 64, ... of its sample in index order, then the 64 lanes are added by the shuffle
+// tree -- an order that depends on `parts` alone
+__global__ __launch_bounds__(64) void image_ssim_finish_kernel(const double* __restrict__ ws, double* __restrict__ out, int parts) {
+  const int64_t s = blockIdx.x;
+  double v = 0.0;
+  for (int w = threadIdx.x; w < parts; w += 64) v += ws[s * parts + w];
+  v = wave_sum_f64(v);
+  if (threadIdx.x == 0) out[s] = v;
+}
+
 }  // namespace afx
 
 using namespace afx;
@@ -604,6 +705,58 @@ int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transf
   else
     hipLaunchKernelGGL(sample_score_partial_kernel<false>, dim3(parts, batch), dim3(256), 0, st, a, b, (int)transform, (double*)ws, ups, upw);
   hipLaunchKernelGGL(sample_score_finish_kernel, dim3((batch * 4 + 63) / 64), dim3(64), 0, st, (const double*)ws, out, batch, parts);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+// work-groups (= workspace slots) per sample of the SSIM pass: one per tile of windows and channel -- a function of the shape alone
+static inline int64_t ssim_parts(int32_t C, int32_t H, int32_t W, int* tiles_x, int* tiles) {
+  const int64_t tx = ((int64_t)W - (SSIM_TAPS - 1) + SSIM_TW - 1) / SSIM_TW, ty = ((int64_t)H - (SSIM_TAPS - 1) + SSIM_TH - 1) / SSIM_TH;
+  if (tiles_x) *tiles_x = (int)tx;
+  if (tiles) *tiles = (int)std::min<int64_t>(tx * ty, INT32_MAX);
+  return tx * ty * C;
+}
+
+int64_t afx_image_ssim_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W) {
+  if (batch < 1 || C < 1 || H < SSIM_TAPS || W < SSIM_TAPS) return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_image_ssim_ws_bytes (batch and C at least 1, H and W at least 11)");
+  const int64_t parts = ssim_parts(C, H, W, nullptr, nullptr);
+  if (parts > INT32_MAX) return (int64_t)fail(AFX_E_INVALID, "afx_image_ssim_ws_bytes: more than 2^31 - 1 tiles per sample");
+  return (int64_t)batch * parts * (int64_t)sizeof(double);
+}
+
+int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transform, double data_range, double* out, void* ws,
+                   int64_t ws_bytes, int32_t batch, int32_t C, int32_t H, int32_t W, void* stream) {
+  if (!a || !b || !out || !ws) return fail(AFX_E_INVALID, "null argument to afx_image_ssim");
+  if (dtype != AFX_DT_BF16 && dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "afx_image_ssim: dtype must be AFX_DT_BF16 or AFX_DT_F32");
+  if (transform != 0 && transform != 1) return fail(AFX_E_INVALID, "afx_image_ssim: transform must be 0 or 1");
+  if (!(data_range > 0.0) || data_range > 1e150) return fail(AFX_E_INVALID, "afx_image_ssim: data_range must be positive (and finite)");
+  if (batch < 1 || batch > 65535 || C < 1) return fail(AFX_E_INVALID, "bad argument to afx_image_ssim (1 <= batch <= 65535, C >= 1)");
+  if (H < SSIM_TAPS || W < SSIM_TAPS) return fail(AFX_E_INVALID, "afx_image_ssim: H and W must be at least 11 (one window)");
+  const bool bf16 = dtype == AFX_DT_BF16;
+  if (((uintptr_t)a & (bf16 ? 1 : 3)) || ((uintptr_t)b & (bf16 ? 1 : 3)) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7))
+    return fail(AFX_E_INVALID, "afx_image_ssim: a and b must be aligned to their element, out and ws 8-byte aligned");
+  int tiles_x = 0, tiles = 0;
+  const int64_t parts = ssim_parts(C, H, W, &tiles_x, &tiles);
+  if (parts > INT32_MAX) return fail(AFX_E_INVALID, "afx_image_ssim: more than 2^31 - 1 tiles per sample");
+  if (ws_bytes < (int64_t)batch * parts * (int64_t)sizeof(double))
+    return fail(AFX_E_INVALID, "afx_image_ssim: workspace smaller than afx_image_ssim_ws_bytes()");
+  ssim_taps_t taps;
+  double sum = 0.0;
+  for (int i = 0; i < SSIM_TAPS; ++i) {
+    const double d = (double)(i - SSIM_TAPS / 2);
+    taps.g[i] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
+    sum += taps.g[i];
+  }
+  for (int i = 0; i < SSIM_TAPS; ++i) taps.g[i] /= sum;
+  const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16)
+    hipLaunchKernelGGL(image_ssim_partial_kernel<true>, dim3((unsigned)parts, batch), dim3(256), 0, st, a, b, (int)transform, taps, c1, c2,
+                       (double*)ws, (int)H, (int)W, tiles_x, tiles);
+  else
+    hipLaunchKernelGGL(image_ssim_partial_kernel<false>, dim3((unsigned)parts, batch), dim3(256), 0, st, a, b, (int)transform, taps, c1, c2,
+                       (double*)ws, (int)H, (int)W, tiles_x, tiles);
+  hipLaunchKernelGGL(image_ssim_finish_kernel, dim3(batch), dim3(64), 0, st, (const double*)ws, out, (int)parts);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

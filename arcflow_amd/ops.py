@@ -528,6 +528,42 @@ def sample_score(a, b, transform: bool = False, out: Optional[torch.Tensor] = No
     return out
 
 
+def image_ssim_ws(batch: int, channels: int, height: int, width: int, device='cuda') -> torch.Tensor:
+    """Workspace of image_ssim for [batch, channels, height, width] operands (afx_image_ssim_ws_bytes): one fp64 partial sum per work-group."""
+    need = _lib.load().afx_image_ssim_ws_bytes(batch, channels, height, width)
+    if need < 0:
+        _lib.check(int(need))
+    return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+
+def image_ssim(a, b, transform: bool = False, data_range: float = 1.0, out: Optional[torch.Tensor] = None,
+               ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B] float64 = per sample, the SUM of the structural similarity (11 x 11 Gaussian window, sigma 1.5, valid windows only) over the C
+    channels and (H - 10)(W - 10) windows of a, b [B, C, H, W] (afx_image_ssim); the mean SSIM is the sum / (C (H - 10)(W - 10)).
+    a, b both fp32 or both bf16, contiguous NCHW, H, W >= 11.  transform: score clamp(v / 2 + 0.5, 0, 1) (fp32) of both operands, the
+    [0, 1] image range.  data_range: L of c1 = (0.01 L)^2, c2 = (0.03 L)^2.  Elements are widened to fp64 and everything after is fp64;
+    bit-reproducible (fixed partition, fixed order of the sum).  Nothing is copied or cast: a wrong dtype, device, layout or rank raises.
+    out / ws: reuse buffers (ops.image_ssim_ws)."""
+    lib = _lib.load()
+    _gpu(a, b, out, ws)
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
+    if a.dim() != 4:
+        raise ValueError(f'a: need [B, C, H, W], got {tuple(a.shape)}')
+    B, Cn, H, W = a.shape
+    a = _packed(a, a.dtype, a.shape, 'a')
+    b = _packed(b, a.dtype, a.shape, 'b')
+    out = torch.empty(B, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B,), 'out')
+    if ws is None:
+        ws = image_ssim_ws(B, Cn, H, W, a.device)
+    elif not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.image_ssim_ws)')
+    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    _lib.check(lib.afx_image_ssim(_p(a), _p(b), dt, int(bool(transform)), float(data_range), _p(out), _p(ws), ws.numel() * ws.element_size(),
+                                  B, Cn, H, W, _s()))
+    return out
+
+
 def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
     """One step of the teacher's Euler ODE sampler in one launch (afx_teacher_euler_step):

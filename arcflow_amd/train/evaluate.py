@@ -10,6 +10,8 @@ scoring pass.
 What is scored: the packed latents (what the distillation loss acts on; no decoder needed) and, with a VAE decoder, the decoded images
 in the [0, 1] range of the reference's ``val_step``.  The per-sample sums come from ONE kernel, ``afx_sample_score`` (fp64
 accumulation, fixed partition, ordered second pass: bit-reproducible); ``metrics_from_sums`` turns them into numbers on the host.
+MSE and PSNR are per-pixel; the decoded images are also scored structurally, by ``afx_image_ssim`` (the 11 x 11 Gaussian-window SSIM
+in fp64, the same reduction scheme) and ``ssim_from_sums``.
 The student's sampling semantics are the pipelines' ``__call__`` (``ArcFlowDistiller.sample_student``); ``temperature`` plays no part.
 """
 from __future__ import annotations
@@ -23,7 +25,8 @@ import torch
 from .. import ops
 
 LATENT_KEYS = ('latent_mse', 'latent_rel_l2', 'latent_cosine')
-IMAGE_KEYS = ('image_psnr', 'image_mse')
+IMAGE_KEYS = ('image_psnr', 'image_mse', 'image_ssim')
+SSIM_WINDOW = 11          # the taps of afx_image_ssim's Gaussian window: the smallest image side it scores
 
 
 def metrics_from_sums(sums, n: int, data_range: Optional[float] = None) -> Dict[str, torch.Tensor]:
@@ -43,9 +46,19 @@ def metrics_from_sums(sums, n: int, data_range: Optional[float] = None) -> Dict[
     return out
 
 
+def ssim_from_sums(sums, channels: int, height: int, width: int) -> torch.Tensor:
+    """sums [B] = afx_image_ssim's per-sample sum of the window ratios over ``channels`` planes of ``height`` x ``width`` -> the mean SSIM
+    per sample, fp64 CPU [B]: sums / (channels (height - 10)(width - 10)), the number of windows that lie inside the image."""
+    if channels < 1 or height < SSIM_WINDOW or width < SSIM_WINDOW:
+        raise ValueError(f'ssim_from_sums: no {SSIM_WINDOW} x {SSIM_WINDOW} window fits {channels} x {height} x {width}')
+    s = torch.as_tensor(sums).detach().to('cpu', torch.float64).reshape(-1)
+    return s / float(channels * (height - SSIM_WINDOW + 1) * (width - SSIM_WINDOW + 1))
+
+
 class Evaluator:
     """``evaluate() -> dict``: per-sample lists ``latent_mse``, ``latent_rel_l2``, ``latent_cosine`` (+ ``image_psnr``, ``image_mse`` with a
-    ``vae``), their means as ``<key>_mean``, ``iteration`` and ``seconds`` (HIP events around the call).
+    ``vae``, + ``image_ssim`` where the decoded images are [B, C, H, W] with H, W >= 11), their means as ``<key>_mean``, ``iteration`` and
+    ``seconds`` (HIP events around the call).
 
     distiller: an ArcFlowDistiller.  conds: a list of per-batch condition dicts as ``train_step`` takes them.  seed: condition i draws its
     start noise from ``torch.Generator(device).manual_seed(seed + i)``, once.  teacher_steps / teacher_kwargs: ``sample_teacher``'s
@@ -83,6 +96,7 @@ class Evaluator:
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         lat_sums, img_sums = [], []            # (sums [B, 4] on the device, elements per sample) per condition
+        ssim_sums = []                         # (sums [B] on the device, C, H, W) per condition -- only where a window fits the decoded images
         with d.ema_weights() if self.use_ema else contextlib.nullcontext():
             for i, c in enumerate(self.conds):
                 t_lat, t_img = self._teacher(i)
@@ -91,6 +105,8 @@ class Evaluator:
                 if self.vae is not None:
                     s_img = self.vae.decode_packed(s_lat, c['hp'], c['wp']).contiguous()
                     img_sums.append((ops.sample_score(s_img, t_img, transform=True), s_img[0].numel()))
+                    if s_img.dim() == 4 and min(s_img.shape[2:]) >= SSIM_WINDOW:
+                        ssim_sums.append((ops.image_ssim(s_img, t_img, transform=True, data_range=1.0), *s_img.shape[1:]))
         end.record()
         end.synchronize()
         out: Dict[str, Any] = dict(iteration=int(d.iteration))
@@ -99,8 +115,10 @@ class Evaluator:
             out[key] = [v for m in lat for v in m[key[len('latent_'):]].tolist()]
         if self.vae is not None:
             img = [metrics_from_sums(s, n, data_range=1.0) for s, n in img_sums]
-            for key in IMAGE_KEYS:
+            for key in ('image_psnr', 'image_mse'):
                 out[key] = [v for m in img for v in m[key[len('image_'):]].tolist()]
+            if len(ssim_sums) == len(self.conds):          # every condition's images took a window (a stand-in decoder of another shape: no key)
+                out['image_ssim'] = [v for s, ch, h, w in ssim_sums for v in ssim_from_sums(s, ch, h, w).tolist()]
         for key in [k for k in out if k != 'iteration']:
             out[key + '_mean'] = math.fsum(out[key]) / len(out[key])
         out['seconds'] = start.elapsed_time(end) / 1000.0

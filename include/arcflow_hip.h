@@ -318,6 +318,28 @@ int afx_cfg_ortho_coef(const void* pos, const void* neg, float scale, float* coe
 int64_t afx_sample_score_ws_bytes(int32_t batch, int64_t n);
 int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transform, double* out, void* ws, int64_t ws_bytes,
                      int32_t batch, int64_t n, void* stream);
+/* Structural similarity of two image batches (training-time evaluation: decoded student images a against teacher images b), Wang et al.
+ * 2004 in the common "Gaussian, valid" form:
+ *   out[s] = sum over the C channels and the (H - 10)(W - 10) windows of each of
+ *            (2 mu_a mu_b + c1)(2 s_ab + c2) / ((mu_a^2 + mu_b^2 + c1)(s_aa + s_bb + c2)),        as fp64;
+ * the mean SSIM of sample s is out[s] / (C (H - 10)(W - 10)).  The window is g g^T with g[i] = exp(-(i - 5)^2 / (2 1.5^2)), i = 0..10,
+ * normalised to sum 1 in fp64; only windows that lie fully inside the image count.  mu are the weighted means, s_aa = E[a^2] - mu_a^2,
+ * s_bb likewise, s_ab = E[a b] - mu_a mu_b (weighted, biased); c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2.
+ * a, b [batch, C, H, W] contiguous, both `dtype` (AFX_DT_BF16 or AFX_DT_F32), aligned to their element; H, W >= 11; batch, C >= 1.
+ * transform as in afx_sample_score: 0 the values as they are, 1 clamp(v / 2 + 0.5, 0, 1) in fp32 first.  Every element is widened to
+ * fp64 after the transform; both 11-tap passes, the moments and the ratio are fp64, and the three second moments are formed by the same
+ * sequence of operations: a == b gives exactly 1.0 per window, i.e. out[s] == C (H - 10)(W - 10).  The values are expected in (about)
+ * [0, data_range]: the denominators are positive then.
+ * Deterministic on the scheme of afx_sample_score: one work-group per tile of 32 x 16 windows and channel (a function of the shape
+ * alone), one fp64 slot of `ws` per work-group, the slots of a sample added in a fixed order by a second launch (lane l of one wave adds
+ * the slots l, l + 64, ... in index order, then the 64 lanes by the shuffle tree); no atomics, bit-reproducible.
+ * ws: afx_image_ssim_ws_bytes(batch, C, H, W) = 8 batch C ceil((H - 10) / 16) ceil((W - 10) / 32) bytes, 8-byte aligned, private to the
+ * call until it completes.  Traffic: every element of a and b is read once from memory (and up to 42 x 26 / (32 x 16) = 2.1 times through the
+ * caches: a tile reads its 10-wide apron), 8 B written per tile: 25.2 MB per decoded 3 x 1024 x 1024 fp32 image pair (12.6 MB in bf16), 49 KB
+ * of slots. */
+int64_t afx_image_ssim_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
+int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transform, double data_range, double* out, void* ws,
+                   int64_t ws_bytes, int32_t batch, int32_t C, int32_t H, int32_t W, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,

@@ -11,7 +11,8 @@ own trajectory and the original pixels are pasted back after decoding.  Nothing 
 ``--teacher`` also (or, without ``--adapter``, only) produces the TEACHER's edit of the same source, noise and mask through
 ``pipe.sample_teacher(image=..., strength=..., mask_image=...)`` in ``--steps`` steps, written beside ``--out`` as ``<out>.teacher<ext>``;
 with both, the latents of the two edits are scored against each other with ``afx_sample_score`` (student = a, teacher = b): mse, rel-L2 and
-cosine per sample.  The teacher walks the last ``strength`` share of its schedule, the student all its steps over [strength, 0]; both
+cosine per sample, and the two decoded edits as written (8 bits per channel, / 255) with ``afx_sample_score`` and ``afx_image_ssim``:
+``image_psnr`` and ``image_ssim``.  The teacher walks the last ``strength`` share of its schedule, the student all its steps over [strength, 0]; both
 start from the same noise draw (``--seed``).
 
 ``--synthetic``: random-init weights of a reduced architecture, random prompt embeddings and a random image in latent space
@@ -51,6 +52,20 @@ def score_latents(student: torch.Tensor, teacher: torch.Tensor):
     a, b = student.to('cuda', torch.float32).contiguous(), teacher.to('cuda', torch.float32).contiguous()
     m = metrics_from_sums(ops.sample_score(a, b), a[0].numel())
     return {'latent_' + k: m[k].tolist() for k in ('mse', 'rel_l2', 'cosine')}
+
+
+def score_images(student, teacher):
+    """The two decoded edits as written (PIL images of one size, 8 bits per channel) -> {'image_psnr' | 'image_ssim': per-sample list} on
+    their values / 255 (afx_sample_score, afx_image_ssim; data range 1)."""
+    import numpy as np
+    from arcflow_amd import ops
+    from arcflow_amd.train.evaluate import metrics_from_sums, ssim_from_sums
+
+    def planes(im):
+        return torch.from_numpy(np.asarray(im.convert('RGB'), dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous().cuda()
+    a, b = planes(student), planes(teacher)
+    m = metrics_from_sums(ops.sample_score(a, b), a[0].numel(), data_range=1.0)
+    return {'image_psnr': m['psnr'].tolist(), 'image_ssim': ssim_from_sums(ops.image_ssim(a, b), *a.shape[1:]).tolist()}
 
 
 def _teacher_path(out: str) -> str:
@@ -134,7 +149,7 @@ def main(argv=None):
         tea.save(_teacher_path(args.out))
         print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}')
         if student:
-            print(f'student vs teacher: {score_latents(lat, tlat)}')
+            print(f'student vs teacher: {dict(score_latents(lat, tlat), **score_images(out, tea))}')
         out = tea if out is None else out
     return out
 

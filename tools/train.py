@@ -47,7 +47,24 @@ def parse_args(argv=None):
                                             "'config' for the config's eval_interval (default: off)")
     ap.add_argument('--eval-batches', type=int, help='evaluate on the first K batches of the data source (default: eval_cfg.num_batches, 1)')
     ap.add_argument('--eval-teacher-steps', type=int, help='steps of the teacher ODE the student is scored against (default: eval_cfg.teacher_steps, 28)')
+    ap.add_argument('--vae-dir', help='local diffusers vae/ directory (config.json + safetensors) of the config\'s family: the evaluation also decodes '
+                                      'both sample sets and reports image_mse, image_psnr and image_ssim (needs --eval-interval)')
     return ap.parse_args(argv)
+
+
+def load_vae_decoder(family: str, path: str, device):
+    """The HIP decoder of ``family`` from a local ``vae/`` directory, built the way the pipelines' ``from_pretrained`` builds it."""
+    from arcflow_amd.pipelines.arcflux_pipeline import load_transformer_dir
+    if not os.path.isfile(os.path.join(path, 'config.json')):
+        raise SystemExit(f'--vae-dir: {path}/config.json not found: pass the vae/ directory of a local FLUX.1-dev / Qwen-Image snapshot')
+    vcfg, vsd = load_transformer_dir(path)
+    if family == 'flux':
+        from arcflow_amd.vae import AutoencoderKLDecoder
+        return AutoencoderKLDecoder(vsd, tuple(vcfg.get('block_out_channels', (128, 256, 512, 512))), vcfg.get('norm_num_groups', 32),
+                                    vcfg.get('layers_per_block', 2), vcfg.get('scaling_factor', 0.3611), vcfg.get('shift_factor', 0.1159), device=device)
+    from arcflow_amd.vae import AutoencoderKLQwenImageDecoder
+    return AutoencoderKLQwenImageDecoder(vsd, vcfg['latents_mean'], vcfg['latents_std'], tuple(vcfg.get('dim_mult', (1, 2, 4, 4))),
+                                         vcfg.get('num_res_blocks', 2), vcfg.get('z_dim', 16), device=device)
 
 
 def eval_interval(args, run) -> int:
@@ -82,6 +99,8 @@ def main(argv=None):
     # the host driver only supports dmabuf IPC: must be in the environment BEFORE the first torch.cuda call initialises the HIP / HSA runtime
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     args = parse_args(argv)
+    if args.vae_dir and args.eval_interval is None:
+        raise SystemExit('--vae-dir decodes the evaluation samples: it needs --eval-interval')
     from arcflow_amd.train import ArcFlowDistiller, checkpoint, config, data
     cfg = config.apply_options(config.load_config(args.config), _options(args.cfg_options))
     family, eng, dc, run = config.distill_setup(cfg)
@@ -134,6 +153,8 @@ def main(argv=None):
     B = run['samples_per_gpu']
     loader = None
     n_eval = eval_interval(args, run)
+    if args.vae_dir and n_eval == 0:
+        raise SystemExit('--vae-dir decodes the evaluation samples: it needs an --eval-interval above 0')
     ecfg = dict(run['eval_cfg'])
     if args.eval_batches is not None:
         ecfg['num_batches'] = args.eval_batches
@@ -206,8 +227,9 @@ def main(argv=None):
             print(f"[eval] test_cfg.distilled_guidance_scale = {tcfg['distilled_guidance_scale']} differs from the training value {dc.guidance}: "
                   'the student is evaluated with the guidance it is trained with', flush=True)
         eval_conds = [{k: v for k, v in c.items() if k != 'latents'} for c in eval_conds]
+        vae = load_vae_decoder(family, args.vae_dir, dev) if args.vae_dir else None          # with a decoder: the image metrics too
         evaluator = Evaluator(dist_, eval_conds, seed=ecfg['seed'], teacher_steps=ecfg['teacher_steps'], nfe=tcfg['nfe'],
-                              timestep_ratio=tcfg['timestep_ratio'], use_ema=ecfg['use_ema'])
+                              timestep_ratio=tcfg['timestep_ratio'], use_ema=ecfg['use_ema'], vae=vae)
         eval_dir = args.work_dir or run['work_dir'] or ckpt_dir
         os.makedirs(eval_dir, exist_ok=True)
         eval_path = os.path.join(eval_dir, 'eval.jsonl')
