@@ -6,6 +6,7 @@ No fallback: every function launches a HIP kernel or raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -562,6 +563,110 @@ def image_ssim(a, b, transform: bool = False, data_range: float = 1.0, out: Opti
     _lib.check(lib.afx_image_ssim(_p(a), _p(b), dt, int(bool(transform)), float(data_range), _p(out), _p(ws), ws.numel() * ws.element_size(),
                                   B, Cn, H, W, _s()))
     return out
+
+
+_FILTERS = {'lanczos3': 'AFX_FILTER_LANCZOS3', 'triangle': 'AFX_FILTER_TRIANGLE'}
+
+
+def _axis_table(n_in: int, n_out: int, filt: int, b0: float, b1: float, sigma: float):
+    """One axis' table from afx_resample_table (a host function: no GPU is touched): (start [n_out] int32, count [n_out] int32,
+    w [n_out, taps] float32) on the CPU.  The C function's refusals (bad size, box, sigma, too many taps) are raised as ValueError."""
+    lib = _lib.load()
+    taps = lib.afx_resample_table(n_in, n_out, filt, b0, b1, sigma, None, None, None, _lib.AFX_RESAMPLE_MAX_TAPS)
+    if taps < 0:
+        raise ValueError(lib.afx_last_error().decode())
+    start = torch.empty(n_out, dtype=torch.int32)
+    count = torch.empty(n_out, dtype=torch.int32)
+    w = torch.empty(n_out, taps, dtype=torch.float32)
+    rc = lib.afx_resample_table(n_in, n_out, filt, b0, b1, sigma, _p(start), _p(count), _p(w), taps)
+    if rc != taps:
+        _lib.check(rc if rc < 0 else _lib.AFX_E_INVALID)
+    return start, count, w
+
+
+def resample_tables(n_in: int, n_out: int, filter: str = 'lanczos3', box=None):
+    """(start, count, w) of one axis of Pillow's ``Image.resize(..., box=)``: output i is sum_k w[i, k] in[start[i] + k], k < count[i].
+    ``box`` = (b0, b1) in source pixels (fractional allowed; default the whole axis).  Built in fp64, weights rounded to fp32 once; CPU
+    tensors, no GPU needed.  A ratio that needs more than AFX_RESAMPLE_MAX_TAPS taps (Lanczos-3: beyond about 21x down) raises."""
+    if filter not in _FILTERS:
+        raise ValueError(f"filter: 'lanczos3' or 'triangle', got {filter!r}")
+    b0, b1 = (0.0, float(n_in)) if box is None else (float(box[0]), float(box[1]))
+    return _axis_table(int(n_in), int(n_out), getattr(_lib, _FILTERS[filter]), b0, b1, 0.0)
+
+
+def gaussian_tables(n: int, sigma: float):
+    """(start, count, w) of a Gaussian blur along an axis of ``n`` pixels: taps exp(-d^2 / (2 sigma^2)) for |d| <= ceil(3 sigma), windows
+    clipped at the border and renormalised (every row of w sums to 1).  CPU tensors."""
+    return _axis_table(int(n), int(n), _lib.AFX_FILTER_GAUSSIAN, 0.0, float(n), float(sigma))
+
+
+@functools.lru_cache(maxsize=64)
+def _device_table(n_in: int, n_out: int, filt: int, b0: float, b1: float, sigma: float, device: str):
+    """``_axis_table`` on the GPU, kept for the next call of the same geometry.  The cache holds at most 64 tables for the life of the
+    process (a table is n_out (taps + 2) 4 bytes: 0.4 MB for 1024 outputs of a 4x Lanczos-3 downscale).  A table is uploaded on the
+    stream that is current at its first use and that stream is waited for here, once per table, so a later call on ANY stream reads a
+    finished upload."""
+    tabs = tuple(t.to(device) for t in _axis_table(n_in, n_out, filt, b0, b1, sigma))
+    torch.cuda.current_stream(tabs[0].device).synchronize()
+    return tabs
+
+
+def _resample_source(src: torch.Tensor, name: str):
+    """-> (B, C, H, W) of a source as afx_image_resample reads it: uint8 [B, H, W, C] or float32 [B, C, H, W], C 1 or 3, non-empty."""
+    _gpu(src, name=name)
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f'{name}: need uint8 [B, H, W, C] or float32 [B, C, H, W], got {tuple(src.shape)} {src.dtype}')
+    B, Cn, H, W = (src.shape[0], src.shape[3], src.shape[1], src.shape[2]) if src.dtype == torch.uint8 else src.shape
+    if Cn not in (1, 3) or min(B, H, W) < 1:
+        raise ValueError(f'{name}: need 1 or 3 channels and a non-empty image, got {tuple(src.shape)} '
+                         f'({"B, H, W, C" if src.dtype == torch.uint8 else "B, C, H, W"})')
+    return int(B), int(Cn), int(H), int(W)
+
+
+def _resample(src: torch.Tensor, dims, out_h: int, out_w: int, tab_h, tab_w, clamp: bool) -> torch.Tensor:
+    """afx_image_resample on a checked source (``dims`` from ``_resample_source``) with the device tables ``tab_w`` (W axis) and ``tab_h``
+    (H axis) of ``_device_table``: (start, count, w)."""
+    B, Cn, H, W = dims
+    src = src.contiguous()
+    lib = _lib.load()
+    need = lib.afx_image_resample_ws_bytes(B, Cn, H, out_w)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=src.device)
+    dst = torch.empty(B, Cn, out_h, out_w, dtype=torch.float32, device=src.device)
+    _lib.check(lib.afx_image_resample(_p(src), int(src.dtype == torch.uint8), B, Cn, H, W, _p(tab_w[0]), _p(tab_w[1]), _p(tab_w[2]),
+                                      tab_w[2].shape[1], _p(tab_h[0]), _p(tab_h[1]), _p(tab_h[2]), tab_h[2].shape[1], _p(dst), out_h, out_w,
+                                      int(bool(clamp)), _p(ws), need, _s()))
+    return dst
+
+
+def image_resample(src: torch.Tensor, out_h: int, out_w: int, filter: str = 'lanczos3', box=None, clamp: bool = True) -> torch.Tensor:
+    """Pillow's ``Image.resize((out_w, out_h), filter, box)`` on the GPU (afx_image_resample): src uint8 [B, H, W, C] (read as x / 255, so
+    3 B per pixel cross the bus) or float32 [B, C, H, W], C 1 or 3 -> float32 [B, C, out_h, out_w].  ``box`` = (left, upper, right, lower)
+    in source pixels, fractional allowed (default the whole image); ``clamp`` to [0, 1] (Lanczos overshoots).  Separable, horizontal
+    pass first, fp32 accumulation; a same-size call without a box returns the source's values exactly."""
+    if filter not in _FILTERS:
+        raise ValueError(f"filter: 'lanczos3' or 'triangle', got {filter!r}")
+    dims = _resample_source(src, 'src')
+    H, W = dims[2:]
+    left, upper, right, lower = (0.0, 0.0, float(W), float(H)) if box is None else (float(v) for v in box)
+    filt, dev = getattr(_lib, _FILTERS[filter]), str(src.device)
+    tab_w = _device_table(W, int(out_w), filt, left, right, 0.0, dev)
+    tab_h = _device_table(H, int(out_h), filt, upper, lower, 0.0, dev)
+    return _resample(src, dims, int(out_h), int(out_w), tab_h, tab_w, clamp)
+
+
+def mask_feather(mask: torch.Tensor, sigma: float) -> torch.Tensor:
+    """Gaussian feathering of a float32 [B, C, H, W] mask (C 1 or 3) with ``sigma`` in pixels, on the table-driven resampling kernel
+    (ops.gaussian_tables on both axes: border windows are clipped and renormalised), clamped to [0, 1]."""
+    if mask.dtype != torch.float32:
+        raise ValueError(f'mask: need float32 [B, C, H, W], got {tuple(mask.shape)} {mask.dtype}')
+    dims = _resample_source(mask, 'mask')
+    H, W = dims[2:]
+    dev = str(mask.device)
+    tab_w = _device_table(W, W, _lib.AFX_FILTER_GAUSSIAN, 0.0, float(W), float(sigma), dev)
+    tab_h = _device_table(H, H, _lib.AFX_FILTER_GAUSSIAN, 0.0, float(H), float(sigma), dev)
+    return _resample(mask, dims, H, W, tab_h, tab_w, True)
 
 
 def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: Optional[torch.Tensor] = None,

@@ -151,17 +151,106 @@ class _PipelineBase(ArcFlowLoaderMixin):
             raise ValueError(f'`{name}`: cannot read {tuple(t.shape)} as [B, {channels}, H, W]')
         return t.to(torch.float32)
 
-    def _edit_inputs(self, image, image_latents, mask_image, strength, height, width):
+    @staticmethod
+    def _default_side(n: int) -> int:
+        """The call's side for a source side of ``n`` pixels under ``resize``: the nearest multiple of 16 (ties up), at least 16."""
+        return max(16, 16 * ((int(n) + 8) // 16))
+
+    @staticmethod
+    def _crop_box(src_h: int, src_w: int, height: int, width: int):
+        """(left, upper, right, lower) of the largest centred window of a ``src_h`` x ``src_w`` image with the aspect ratio ``width`` :
+        ``height``, in source pixels; fractional.  An image that already has that ratio gives the whole image."""
+        if src_w * height > src_h * width:                  # the source is wider: full height, centred columns
+            cw = src_h * width / height
+            return ((src_w - cw) / 2, 0.0, (src_w + cw) / 2, float(src_h))
+        if src_w * height < src_h * width:
+            ch = src_w * height / width
+            return (0.0, (src_h - ch) / 2, float(src_w), (src_h + ch) / 2)
+        return (0.0, 0.0, float(src_w), float(src_h))
+
+    def _resize_source(self, image, name, channels) -> torch.Tensor:
+        """``image`` on the GPU as ops.image_resample reads it: PIL images and uint8 numpy arrays as uint8 [B, H, W, C] (read as x / 255, 3 B per
+        pixel over the bus), everything else as ``_images01`` gives it, fp32 [B, C, H, W].  NOTE the one difference to ``resize=None``: there
+        ``_images01`` takes a uint8 numpy array as values already in [0, 1], undivided; here it is 8-bit pixels.  A uint8 torch tensor raises."""
+        import numpy as np
+        mode = 'RGB' if channels == 3 else 'L'
+        if isinstance(image, (list, tuple)) and len(image) and all(hasattr(im, 'convert') for im in image):
+            arr = np.stack([np.array(im.convert(mode), dtype=np.uint8) for im in image])
+            arr = arr[..., None] if channels == 1 else arr
+        elif hasattr(image, 'convert'):
+            arr = np.array(image.convert(mode), dtype=np.uint8)[None]
+            arr = arr[..., None] if channels == 1 else arr
+        elif isinstance(image, np.ndarray) and image.dtype == np.uint8:
+            arr = image
+            if channels == 1:
+                arr = arr[None, ..., None] if arr.ndim == 2 else (arr[..., None] if arr.ndim == 3 else arr)
+            elif arr.ndim == 3:
+                arr = arr[None]
+            if arr.ndim != 4 or arr.shape[3] != channels:
+                raise ValueError(f'`{name}`: cannot read uint8 {tuple(image.shape)} as [B, H, W, {channels}]')
+        elif isinstance(image, torch.Tensor) and image.dtype == torch.uint8:
+            # [B, C, H, W] bytes read undivided (as resize=None reads them) would saturate in the clamp, and a byte tensor's layout is ambiguous
+            raise ValueError(f'`{name}`: with `resize`, pass 8-bit pixels as a PIL image or a uint8 numpy array [B, H, W, {channels}] (read as x / 255); '
+                             f'a torch tensor must be floating point in [0, 1], got uint8 {tuple(image.shape)}')
+        else:
+            return self._images01(image, name, channels).to(self._device).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(self._device)
+
+    def _edit_inputs_resized(self, image, image_latents, mask_image, height, width, resize):
+        """The ``resize`` branch of ``_edit_inputs``: -> (img, mask, height, width) with img / mask fp32 [B, C, height, width] on the GPU."""
+        if resize not in ('stretch', 'crop'):
+            raise ValueError(f"`resize`: None, 'stretch' or 'crop', got {resize!r}")
+        if image_latents is not None and mask_image is None:
+            raise ValueError('`resize` with `image_latents` and no `mask_image` has nothing to resize: latents are not resampled')
+        if (height and height % 16) or (width and width % 16):
+            raise ValueError(f'`height` and `width` have to be divisible by 16, got {height} x {width}')
+        srcs = [None if image is None else self._resize_source(image, 'image', 3),
+                None if mask_image is None else self._resize_source(mask_image, 'mask_image', 1)]
+        sizes = [None if t is None else ((t.shape[1], t.shape[2]) if t.dtype == torch.uint8 else (t.shape[2], t.shape[3])) for t in srcs]
+        for hw in sizes:
+            if hw is not None:
+                height, width = height or self._default_side(hw[0]), width or self._default_side(hw[1])
+        out = []
+        for t, hw, filt in zip(srcs, sizes, ('lanczos3', 'triangle')):
+            box = None if t is None or resize == 'stretch' else self._crop_box(hw[0], hw[1], height, width)
+            out.append(None if t is None else ops.image_resample(t, height, width, filt, box, clamp=True))
+        return out[0], out[1], height, width
+
+    def _edit_inputs(self, image, image_latents, mask_image, strength, height, width, resize=None, mask_blur=0.0):
         """Host-side half of the edit arguments: -> (edit, height, width), ``edit`` None on the text-to-image path.  Normalises ``image`` and
-        ``mask_image`` to fp32 [B, C, H, W], takes ``height`` / ``width`` from them when not given; nothing is resized."""
+        ``mask_image`` to fp32 [B, C, H, W], takes ``height`` / ``width`` from them when not given.  ``resize`` None: nothing is resized, an
+        input of another size raises.  'stretch' / 'crop': both are resampled to the call's size on the GPU (ops.image_resample: the image
+        with Lanczos-3, the mask with the triangle filter, soft values kept), 'crop' from the largest centred window of the call's aspect
+        ratio; ``height`` / ``width`` then default to the source's sides rounded to multiples of 16.  ``mask_blur`` > 0: the
+        image-resolution mask is feathered by a Gaussian of that sigma in output pixels (ops.mask_feather) after any resize."""
+        mask_blur = float(mask_blur)
+        if not 0.0 <= mask_blur < float('inf'):
+            raise ValueError(f'`mask_blur` must be a finite sigma >= 0, got {mask_blur}')
         if image is None and image_latents is None:
             if mask_image is not None:
                 raise ValueError('`mask_image` needs `image` or `image_latents`')
+            if resize is not None or mask_blur:
+                raise ValueError('`resize` and `mask_blur` need `image` (or `image_latents` with a `mask_image`)')
             return None, height, width
         if image is not None and image_latents is not None:
             raise ValueError('Cannot forward both `image` and `image_latents`.')
         if not 0.0 < float(strength) <= 1.0:
             raise ValueError(f'`strength` must be in (0, 1], got {strength}')
+        if mask_blur and mask_image is None:
+            raise ValueError('`mask_blur` needs a `mask_image`')
+        if resize is not None:
+            img, mask, height, width = self._edit_inputs_resized(image, image_latents, mask_image, height, width, resize)
+        else:
+            img, mask, height, width = self._edit_inputs_as_given(image, mask_image, height, width)
+        if mask_blur:
+            mask = ops.mask_feather(mask.to(self._device), mask_blur)
+        if image_latents is not None and (image_latents.dim() != 3 or tuple(image_latents.shape[1:]) != ((height // 16) * (width // 16), 64)):
+            raise ValueError(f'`image_latents`: need packed [B, {(height // 16) * (width // 16)}, 64] for {height} x {width}, '
+                             f'got {tuple(image_latents.shape)}')
+        return dict(image=img, image_latents=image_latents, mask=mask, strength=float(strength)), height, width
+
+    def _edit_inputs_as_given(self, image, mask_image, height, width):
+        """The ``resize=None`` branch of ``_edit_inputs``: -> (img, mask, height, width); every input must have the call's size."""
         img = None if image is None else self._images01(image)
         mask = None if mask_image is None else self._images01(mask_image, 'mask_image', 1)
         for t in (img, mask):
@@ -174,10 +263,7 @@ class _PipelineBase(ArcFlowLoaderMixin):
         for t, name in ((img, 'image'), (mask, 'mask_image')):
             if t is not None and tuple(t.shape[2:]) != (height, width):
                 raise ValueError(f'`{name}` is {t.shape[2]} x {t.shape[3]}, the call is {height} x {width}: an edit resizes nothing')
-        if image_latents is not None and (image_latents.dim() != 3 or tuple(image_latents.shape[1:]) != ((height // 16) * (width // 16), 64)):
-            raise ValueError(f'`image_latents`: need packed [B, {(height // 16) * (width // 16)}, 64] for {height} x {width}, '
-                             f'got {tuple(image_latents.shape)}')
-        return dict(image=img, image_latents=image_latents, mask=mask, strength=float(strength)), height, width
+        return img, mask, height, width
 
     def _edit_prepare(self, edit, B, hp, wp):
         """Device-side half: batch checks, the encode of ``image`` (posterior mode, packed), the mask per latent pixel."""
@@ -470,12 +556,17 @@ class ArcFluxPipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True):
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0):
         """Text-to-image by default.  ``image`` (or its packed latents ``image_latents``) starts the sampler from the image noised to
         ``strength`` in (0, 1] instead of from pure noise (image-to-image); ``mask_image`` (1 = repaint) keeps the unmasked region on the
         image's own trajectory (inpainting) and, with ``composite``, pastes the original pixels back there after decoding.  ``height`` /
-        ``width`` default to the image's size; nothing is resized.  ``latents`` / ``generator`` give the start noise as before."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
+        ``width`` default to the image's size.  ``resize`` None: nothing is resized and an input of another size raises; 'stretch' / 'crop':
+        ``image`` (Lanczos-3) and ``mask_image`` (triangle filter, soft values kept) are resampled to the call's size on the GPU, 'crop' from
+        the largest centred window of the call's aspect ratio, PIL and uint8 numpy inputs uploaded as uint8; ``height`` / ``width`` then
+        default to the image's sides rounded to multiples of 16.  With ``resize`` a uint8 numpy array is 8-bit pixels, read as x / 255
+        (with ``resize=None`` it is taken, as before, as values already in [0, 1]); a uint8 torch tensor raises with ``resize``.  ``mask_blur``: sigma in output pixels of a Gaussian feather of the mask
+        (0 = none), which feeds the latent blend and the composite alike.  ``latents`` / ``generator`` give the start noise as before."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -544,7 +635,7 @@ class ArcFluxPipeline(_PipelineBase):
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
-                       solver_type: Optional[str] = None):
+                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
@@ -562,8 +653,9 @@ class ArcFluxPipeline(_PipelineBase):
         int(max(n - min(n strength, n), 0)), start on the image noised to sigmas[t_start], steps t_start .. n - 1 run
         (``schedule.truncate_by_strength``); with a mask every step also puts the unmasked latent pixels back on the image's own
         trajectory with the start noise (fused into the step kernel, ``afx_teacher_edit_step``).  These follow diffusers' img2img /
-        inpaint pipelines as recalled; the reference has no image-conditioned sampling and nothing pins them."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
+        inpaint pipelines as recalled; the reference has no image-conditioned sampling and nothing pins them.  ``resize``
+        and ``mask_blur`` are ``__call__``'s too: the device resize of ``image`` / ``mask_image`` and the Gaussian feather of the mask."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)

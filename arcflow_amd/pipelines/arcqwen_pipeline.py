@@ -119,10 +119,11 @@ class ArcQwenImagePipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True):
-        """Text-to-image by default; ``image`` / ``image_latents``, ``strength``, ``mask_image`` and ``composite`` as on
-        ``ArcFluxPipeline.__call__`` (image-to-image and inpainting)."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0):
+        """Text-to-image by default; ``image`` / ``image_latents``, ``strength``, ``mask_image``, ``composite``, ``resize`` and ``mask_blur``
+        as on ``ArcFluxPipeline.__call__`` (image-to-image and inpainting; ``resize='stretch'|'crop'`` resamples inputs of any size on the GPU,
+        ``mask_blur`` feathers the mask)."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -199,7 +200,7 @@ class ArcQwenImagePipeline(_PipelineBase):
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
-                       solver_type: Optional[str] = None):
+                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0):
         """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
         ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
@@ -210,8 +211,9 @@ class ArcQwenImagePipeline(_PipelineBase):
         (Qwen-Image: about 41 GB in bf16) next to the student.  Style LoRAs (``load_lora_weights``) and the adapter weights of
         ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.  ``image`` / ``image_latents``,
         ``strength``, ``mask_image`` and ``composite``: the teacher's image-to-image and inpainting, as on
-        ``ArcFluxPipeline.sample_teacher`` (a suffix of the schedule chosen by ``strength``; unpinned semantics)."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width)
+        ``ArcFluxPipeline.sample_teacher`` (a suffix of the schedule chosen by ``strength``; unpinned semantics); ``resize`` and
+        ``mask_blur`` as on ``ArcFluxPipeline.__call__``."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:

@@ -340,6 +340,40 @@ int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transf
 int64_t afx_image_ssim_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
 int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transform, double data_range, double* out, void* ws,
                    int64_t ws_bytes, int32_t batch, int32_t C, int32_t H, int32_t W, void* stream);
+/* Image resampling for the edit pipelines: resize, crop and Gaussian mask feathering are one table-driven separable operation,
+ *   out[i] = sum_{k < count[i]} w[i, k] in[start[i] + k]        per axis, horizontally first, then vertically, fp32 fma in tap order.
+ * afx_resample_table is a HOST function on HOST arrays (no GPU needed): it builds one axis' table in fp64, rounds the weights to fp32 once
+ * and returns the tap count (the largest count[i]), or a negative AFX_E_* code.  start, count [n_out] int32, w [n_out, max_taps] fp32 with
+ * row stride max_taps (entries past count[i] are written as 0); all three NULL only asks for the tap count.
+ *   AFX_FILTER_LANCZOS3 (a = 3) / AFX_FILTER_TRIANGLE (a = 1): the rule of Pillow's Image.resize(size, resample, box) along one axis with
+ *   box [b0, b1) in source pixels, 0 <= b0 < b1 <= n_in, fractional allowed:
+ *     scale = (b1 - b0) / n_out, fs = max(scale, 1), support = a fs, c = b0 + (i + 0.5) scale,
+ *     lo = max(0, int(c - support + 0.5)), hi = min(n_in, int(c + support + 0.5)), w_k = f((k + lo - c + 0.5) / fs) / sum.
+ *   sin(pi x) / (pi x) is taken as exactly 0 at the non-zero integers, so a same-size table is exactly the identity.  sigma is ignored.
+ *   AFX_FILTER_GAUSSIAN: n_out == n_in, b0 / b1 ignored, taps exp(-d^2 / (2 sigma^2)) for |d| <= ceil(3 sigma), the window clipped at the
+ *   border and renormalised there (an edge pixel is a weighted mean of the pixels that exist; nothing is padded or reflected).
+ * AFX_E_UNSUPPORTED when a window needs more than AFX_RESAMPLE_MAX_TAPS taps (a 16x Lanczos-3 downscale takes 95), AFX_E_INVALID when it
+ * needs more than max_taps, for a bad size, filter, box or sigma (sigma and sigma^2 must be positive and finite), for weights whose sum is zero
+ * or not finite, or when only some of start / count / w are NULL.
+ * afx_image_resample: src uint8 [batch, H_in, W_in, C] (src_u8 = 1; a byte x is read as the IEEE fp32 quotient float(x) / 255.0f) or fp32
+ * [batch, C, H_in, W_in] (src_u8 = 0), C 1 or 3; dst fp32 [batch, C, H_out, W_out]; h_* the table of the W axis (n_out = W_out, row stride
+ * h_taps), v_* that of the H axis (n_out = H_out, row stride v_taps), all DEVICE pointers; clamp 1: dst is clamped to [0, 1] (Lanczos
+ * overshoots).  ws: afx_image_resample_ws_bytes(batch, C, H_in, W_out) = 4 batch C H_in W_out bytes, the fp32 horizontal result, private to
+ * the call until it completes.  Two launches.  Every source index is clamped into the source and count[i] is capped at the row stride
+ * before any load: a bad table gives wrong pixels, never a read outside src.  AFX_E_INVALID before any launch for a NULL src, dst or
+ * table, C outside {1, 3}, a size < 1, taps outside [1, AFX_RESAMPLE_MAX_TAPS], a misaligned pointer (4 bytes; a uint8 src: none), or dst
+ * or ws overlapping the source, a table or each other; AFX_E_WORKSPACE for a NULL or short ws. */
+#define AFX_RESAMPLE_MAX_TAPS 128
+#define AFX_FILTER_LANCZOS3 0
+#define AFX_FILTER_TRIANGLE 1
+#define AFX_FILTER_GAUSSIAN 2
+int afx_resample_table(int32_t n_in, int32_t n_out, int32_t filter, double b0, double b1, double sigma, int32_t* start, int32_t* count,
+                       float* w, int32_t max_taps);
+int64_t afx_image_resample_ws_bytes(int32_t batch, int32_t C, int32_t H_in, int32_t W_out);
+int afx_image_resample(const void* src, int32_t src_u8, int32_t batch, int32_t C, int32_t H_in, int32_t W_in, const int32_t* h_start,
+                       const int32_t* h_count, const float* h_w, int32_t h_taps, const int32_t* v_start, const int32_t* v_count,
+                       const float* v_w, int32_t v_taps, float* dst, int32_t H_out, int32_t W_out, int32_t clamp, void* ws,
+                       int64_t ws_bytes, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,

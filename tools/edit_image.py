@@ -78,7 +78,7 @@ def main(argv=None):
     ap.add_argument('--family', choices=['flux', 'qwen'], required=True)
     ap.add_argument('--snapshot', help='local FLUX.1-dev / Qwen-Image snapshot (transformer/, vae/ with encoder weights, text encoders)')
     ap.add_argument('--adapter', help='ArcFlow adapter directory (load_arcflow_adapter)')
-    ap.add_argument('--image', help='the image to edit (sides multiples of 16)')
+    ap.add_argument('--image', help='the image to edit (sides multiples of 16, or any size with --resize)')
     ap.add_argument('--mask', help='inpainting mask, same size: white = repaint, black = keep')
     ap.add_argument('--prompt', default='')
     ap.add_argument('--strength', type=float, default=0.8, help='in (0, 1]: 1 starts from pure noise, small values stay close to the image')
@@ -91,6 +91,12 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=28, help='--teacher: steps of the full schedule (the last `strength` share of them runs)')
     ap.add_argument('--true-cfg-scale', type=float, default=1.0, help='--teacher: true classifier-free guidance against --negative-prompt when > 1')
     ap.add_argument('--negative-prompt', default='')
+    ap.add_argument('--resize', choices=['stretch', 'crop'], help='resample --image and --mask to the call\'s size on the GPU (Lanczos-3; the mask '
+                    'with the triangle filter): stretch the whole image, or crop the largest centred window of the target aspect ratio.  Without it '
+                    'the image must already have the size, a multiple of 16')
+    ap.add_argument('--mask-blur', type=float, default=0.0, help='sigma in output pixels of a Gaussian feather of the mask (0 = none)')
+    ap.add_argument('--height', type=int, help='with --resize: the output height (default: the image\'s, rounded to a multiple of 16)')
+    ap.add_argument('--width', type=int, help='with --resize: the output width')
     args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(args.seed)
     kw = dict(strength=args.strength, num_inference_steps=args.nfe, timestep_ratio=1.0 if args.nfe == 2 else 0.5, generator=gen)
@@ -103,7 +109,8 @@ def main(argv=None):
         if args.mask:
             from PIL import Image
             mask = Image.open(args.mask)
-        out = pipe(image_latents=x0, mask_image=mask, height=h, width=w, output_type='latent', **cond, **kw).images
+        mkw = dict(resize=args.resize, mask_blur=args.mask_blur) if mask is not None else {}        # latents are not resampled: only a mask is
+        out = pipe(image_latents=x0, mask_image=mask, height=h, width=w, output_type='latent', **cond, **kw, **mkw).images
         torch.save(out.cpu(), args.out)
         print(f'wrote edited latents {tuple(out.shape)} to {args.out}  (|out - source| rel-L2 {((out.cpu() - x0).norm() / x0.norm()).item():.3f})')
         if args.teacher:
@@ -117,7 +124,7 @@ def main(argv=None):
                                                     teacher=True))
             tea = pipe.sample_teacher(image_latents=x0, mask_image=mask, height=h, width=w, output_type='latent', strength=args.strength,
                                       num_inference_steps=args.steps, true_cfg_scale=1.0, generator=torch.Generator().manual_seed(args.seed),
-                                      **cond).images
+                                      **cond, **mkw).images
             torch.save(tea.cpu(), _teacher_path(args.out))
             scores = score_latents(out, tea)
             print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}; student vs teacher: {scores}')
@@ -136,6 +143,9 @@ def main(argv=None):
     if not student and not args.teacher:
         raise SystemExit('no ArcFlow student loaded: pass --adapter, or --teacher for the base model\'s own edit')
     out = lat = None
+    if (args.height or args.width) and not args.resize:
+        raise SystemExit('--height / --width need --resize (without it the call has the image\'s size)')
+    kw.update(resize=args.resize, mask_blur=args.mask_blur if mask is not None else 0.0, height=args.height, width=args.width)
     if student:
         lat = pipe(prompt=args.prompt, image=image, mask_image=mask, output_type='latent', **kw).images
         out = pipe(prompt=args.prompt, image=image, mask_image=mask, **dict(kw, generator=torch.Generator().manual_seed(args.seed))).images[0]
@@ -143,7 +153,8 @@ def main(argv=None):
         print(f'wrote {args.out} ({out.size[0]} x {out.size[1]})')
     if args.teacher:
         tkw = dict(prompt=args.prompt, image=image, mask_image=mask, strength=args.strength, num_inference_steps=args.steps,
-                   true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt if args.true_cfg_scale > 1.0 else None)
+                   true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt if args.true_cfg_scale > 1.0 else None,
+                   resize=kw['resize'], mask_blur=kw['mask_blur'], height=args.height, width=args.width)
         tlat = pipe.sample_teacher(output_type='latent', generator=torch.Generator().manual_seed(args.seed), **tkw).images
         tea = pipe.sample_teacher(generator=torch.Generator().manual_seed(args.seed), **tkw).images[0]
         tea.save(_teacher_path(args.out))
