@@ -25,6 +25,8 @@
 //   * image_ssim_partial_kernel / image_ssim_finish_kernel: per-sample sum of the structural similarity of two image batches over
 //     every valid 11 x 11 Gaussian window (training-time evaluation, decoded images), fp64 throughout: one work-group and one slot per
 //     tile of windows, the slots added in a fixed order by the second launch.  Scheme and LDS use at the kernel.
+//   * sample_score_masked_* / image_ssim_masked_*: the two scoring passes weighted by an edit's mask, a repainted (weight m) and a kept
+//     (weight 1 - m) set of sums each, on the same partitions and the same ordered second launches.  Weight maps and LDS use at the kernels.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -396,6 +398,96 @@ __global__ __launch_bounds__(64) void sample_score_finish_kernel(const double* _
   out[i] = v;
 }
 
+// The masked agreement sums (training-time evaluation of edits: how the student repaints the masked region against the teacher).  A sample
+// is viewed as [G, P, R] and the mask as [P, Q], Q | R: element i takes the weight m[(i / R) % P, i % Q]  (i % R % Q == i % Q).  Packed
+// latents [N, 64] with the [N, 4] operand of edit_blend_kernel: G = 1, P = N, R = 64, Q = 4 -- element e of token t reads m[t, e & 3], that
+// kernel's map.  Decoded images [C, H, W] with a [1, H, W] mask: G = C, P = H W, R = Q = 1.
+// grid (parts, B), the partition of sample_score_partial_kernel: work-group w of sample s owns the units [w upw, min((w + 1) upw,
+// units_per_sample)) and writes ws[(s parts + w) 10 + 5 g + {0..4}] = sum w, sum w d^2, sum w a^2, sum w b^2, sum w a b, region g = 0
+// with w = m (repainted), g = 1 with w = 1 - m formed in fp64 (kept).  d, the squares and the product are sample_score_partial_kernel's
+// (x x, y y, x y exact); the square of d takes its weight on one factor, fma(w d, d, acc), so that w = 1 is that kernel's own
+// fma(d, d, acc) bit for bit; contraction is off and every multiply-add is written out, so the compiler fuses nothing else.
+// A lane keeps (p, r, q) = ((i / R) % P, i % R, i % Q) of its unit's first element and moves it by 256 units per round with adds and
+// compares: three divisions per lane, none in the loop.  The mask is read 4 B per element through the caches (0.0625 B per element from
+// memory in the latent form, 4 / C B in the image form).
+template <bool BF16>
+__global__ __launch_bounds__(256) void sample_score_masked_partial_kernel(const void* __restrict__ a, const void* __restrict__ b,
+                                                                          const float* __restrict__ mask, int transform, double* __restrict__ ws,
+                                                                          int64_t units_per_sample, int64_t upw, int64_t mask_stride, uint32_t P,
+                                                                          uint32_t R, uint32_t Q) {
+#pragma clang fp contract(off)
+  constexpr int E = BF16 ? 8 : 4;
+  __shared__ double red[4][10];
+  const int64_t s = blockIdx.y;
+  const int64_t begin = (int64_t)blockIdx.x * upw;
+  const int64_t end = begin + upw < units_per_sample ? begin + upw : units_per_sample;
+  const int64_t base = s * units_per_sample;
+  const float* __restrict__ mrow = mask + s * mask_stride;
+  const uint32_t first = (uint32_t)(begin + threadIdx.x) * E;          // n < 2^31 (checked by the entry): an index fits 32 bits
+  uint32_t p0 = (first / R) % P, r0 = first % R, q0 = first % Q;
+  const uint32_t step = 256 * E, sp = (step / R) % P, sr = step % R, sq = step % Q;
+  double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t u = begin + threadIdx.x; u < end; u += 256) {
+    float f[E], h[E];
+    load_unit<BF16>(a, base + u, f);
+    load_unit<BF16>(b, base + u, h);
+    uint32_t p = p0, r = r0, q = q0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const double w = (double)mrow[p * Q + q], k = 1.0 - w;
+      const double x = (double)(transform ? unit_range(f[e]) : f[e]);
+      const double y = (double)(transform ? unit_range(h[e]) : h[e]);
+      const double d = x - y, xx = x * x, yy = y * y, xy = x * y;
+      acc[0] += w;
+      acc[1] = fma(w * d, d, acc[1]);
+      acc[2] = fma(w, xx, acc[2]);
+      acc[3] = fma(w, yy, acc[3]);
+      acc[4] = fma(w, xy, acc[4]);
+      acc[5] += k;
+      acc[6] = fma(k * d, d, acc[6]);
+      acc[7] = fma(k, xx, acc[7]);
+      acc[8] = fma(k, yy, acc[8]);
+      acc[9] = fma(k, xy, acc[9]);
+      q = q + 1 == Q ? 0 : q + 1;
+      if (++r == R) {
+        r = 0;
+        p = p + 1 == P ? 0 : p + 1;
+      }
+    }
+    q0 += sq;
+    if (q0 >= Q) q0 -= Q;
+    r0 += sr;
+    p0 += sp;
+    if (r0 >= R) {
+      r0 -= R;
+      ++p0;
+    }
+    if (p0 >= P) p0 -= P;          // sp < P and one carry: p0 < 2 P
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const double v = wave_sum_f64(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 10) {      // an empty work-group (upw rounded up) writes zeros: every slot the finish reads is written
+    const int k = threadIdx.x;
+    ws[(s * gridDim.x + blockIdx.x) * 10 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// one lane per (sample, region, sum): out[s][g][k] = the slots of sample s added in index order
+__global__ __launch_bounds__(64) void sample_score_masked_finish_kernel(const double* __restrict__ ws, double* __restrict__ out, int batch,
+                                                                        int parts) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= batch * 10) return;
+  const int s = i / 10, k = i % 10;
+  double v = 0.0;
+  for (int w = 0; w < parts; ++w) v += ws[((int64_t)s * parts + w) * 10 + k];
+  out[i] = v;
+}
+
 // ---- SSIM of two image batches (Wang et al. 2004: 11-tap Gaussian window, sigma 1.5, "valid" windows only) -----------------------------
 // One work-group = a tile of SSIM_TW x SSIM_TH windows of one (sample, channel) plane.  The (SSIM_TW + 10) x (SSIM_TH + 10) inputs of both
 // images are staged in LDS as the fp32 values the transform leaves (widening is exact, so they are widened where they are read); the
@@ -490,6 +582,108 @@ __global__ __launch_bounds__(64) void image_ssim_finish_kernel(const double* __r
   for (int w = threadIdx.x; w < parts; w += 64) v += ws[s * parts + w];
   v = wave_sum_f64(v);
   if (threadIdx.x == 0) out[s] = v;
+}
+
+// ---- the same SSIM, every window weighted by the mask it covers (training-time evaluation of edits) ---------------------------------------
+// image_ssim_partial_kernel with the mask [Bm, 1, H, W] (fp32, shared by the channels) as a sixth quantity: staged beside the two images,
+// taken through the same horizontal and vertical 11-tap passes.  A window's weight w is the Gaussian-weighted mean of the mask over the
+// window's own 11 x 11 support, clamped to [0, 1] in fp64 (the taps sum to 1 within a few ulp); the ratio is ssim_ratio() on the same five
+// moments formed by the same fma chains, so a == b still gives exactly 1.0 per window and then sum w ssim == sum w bit for bit.
+// Work-group (ch tiles + tile) of sample s writes ws[(s gridDim.x + blockIdx.x) 4 + {0..3}] = sum w ssim, sum w, sum (1 - w) ssim, sum (1 - w)
+// over the valid windows of its tile.
+// LDS: 3 x 26 x 43 x 4 B staged inputs + 6 x 26 x 32 x 8 B horizontal sums + 128 B = 53480 B, 53504 B as laid out (52.3 KB); the sixth
+// plane costs 4472 + 6656 = 11128 B over image_ssim_partial_kernel's 42272 B (+ 96 B for four sums per wave).  Three work-groups still fit
+// the CU's 160 KB (3 x 53504 = 160512 <= 163840), the occupancy the unmasked kernel has (3 by LDS there too), so the mask needs no pass
+// of its own.  138 VGPRs (3 waves per SIMD: the same three work-groups), no scratch; the unmasked kernel has 114.
+template <bool BF16>
+__global__ __launch_bounds__(256) void image_ssim_masked_partial_kernel(const void* __restrict__ a, const void* __restrict__ b,
+                                                                        const float* __restrict__ mask, int transform, ssim_taps_t taps, double c1,
+                                                                        double c2, double* __restrict__ ws, int H, int W, int tiles_x, int tiles,
+                                                                        int64_t mask_stride) {
+  __shared__ float sa[SSIM_IH][SSIM_IW + 1], sb[SSIM_IH][SSIM_IW + 1], sm[SSIM_IH][SSIM_IW + 1];
+  __shared__ double hq[6][SSIM_IH][SSIM_TW];
+  __shared__ double red[4][4];
+  const int tile = blockIdx.x % tiles, ch = blockIdx.x / tiles, C = gridDim.x / tiles;
+  const int x0 = (tile % tiles_x) * SSIM_TW, y0 = (tile / tiles_x) * SSIM_TH;
+  const int64_t base = ((int64_t)blockIdx.y * C + ch) * H * W;
+  const float* __restrict__ mplane = mask + (int64_t)blockIdx.y * mask_stride;
+  for (int i = threadIdx.x; i < SSIM_IH * SSIM_IW; i += 256) {
+    const int r = i / SSIM_IW, c = i % SSIM_IW;
+    const int y = y0 + r, x = x0 + c;
+    float p = 0.f, q = 0.f, m = 0.f;
+    if (y < H && x < W) {
+      const int64_t at = base + (int64_t)y * W + x;
+      if constexpr (BF16) {
+        p = bf16_to_f32(reinterpret_cast<const bf16_t*>(a)[at]);
+        q = bf16_to_f32(reinterpret_cast<const bf16_t*>(b)[at]);
+      } else {
+        p = reinterpret_cast<const float*>(a)[at];
+        q = reinterpret_cast<const float*>(b)[at];
+      }
+      if (transform) { p = unit_range(p); q = unit_range(q); }
+      m = mplane[(int64_t)y * W + x];
+    }
+    sa[r][c] = p;
+    sb[r][c] = q;
+    sm[r][c] = m;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SSIM_IH * SSIM_TW; i += 256) {          // horizontal pass: the five of image_ssim_partial_kernel, and the mask
+    const int r = i / SSIM_TW, c = i % SSIM_TW;
+    double h[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SSIM_TAPS; ++j) {
+      const double x = (double)sa[r][c + j], y = (double)sb[r][c + j], g = taps.g[j];
+      h[0] = fma(g, x, h[0]);
+      h[1] = fma(g, y, h[1]);
+      h[2] = fma(g, x * x, h[2]);
+      h[3] = fma(g, x * y, h[3]);
+      h[4] = fma(g, y * y, h[4]);
+      h[5] = fma(g, (double)sm[r][c + j], h[5]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) hq[k][r][c] = h[k];
+  }
+  __syncthreads();
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < SSIM_TH * SSIM_TW; i += 256) {          // vertical pass, ratio, weight; a lane adds its windows in index order
+    const int r = i / SSIM_TW, c = i % SSIM_TW;
+    if (y0 + r >= H - (SSIM_TAPS - 1) || x0 + c >= W - (SSIM_TAPS - 1)) continue;
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SSIM_TAPS; ++j) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) v[k] = fma(taps.g[j], hq[k][r + j][c], v[k]);
+    }
+    const double ratio = ssim_ratio(v[0], v[1], v[2], v[3], v[4], c1, c2);
+    const double w = fmin(fmax(v[5], 0.0), 1.0), k = 1.0 - w;
+    acc[0] = fma(w, ratio, acc[0]);
+    acc[1] += w;
+    acc[2] = fma(k, ratio, acc[2]);
+    acc[3] += k;
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double v = wave_sum_f64(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    ws[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// one wave per (sample, sum): image_ssim_finish_kernel's order -- lane l adds the slots l, l + 64, ... of its sample in index order, then the
+// 64 lanes are added by the shuffle tree
+__global__ __launch_bounds__(64) void image_ssim_masked_finish_kernel(const double* __restrict__ ws, double* __restrict__ out, int parts) {
+  const int64_t s = blockIdx.x;
+  const int k = blockIdx.y;
+  double v = 0.0;
+  for (int w = threadIdx.x; w < parts; w += 64) v += ws[(s * parts + w) * 4 + k];
+  v = wave_sum_f64(v);
+  if (threadIdx.x == 0) out[s * 4 + k] = v;
 }
 
 }  // namespace afx
@@ -717,6 +911,19 @@ static inline int64_t ssim_parts(int32_t C, int32_t H, int32_t W, int* tiles_x, 
   return tx * ty * C;
 }
 
+// g[i] = exp(-(i - 5)^2 / (2 1.5^2)), normalised to sum 1, in fp64 on the host: the one window of both SSIM entries
+static inline ssim_taps_t ssim_window() {
+  ssim_taps_t taps;
+  double sum = 0.0;
+  for (int i = 0; i < SSIM_TAPS; ++i) {
+    const double d = (double)(i - SSIM_TAPS / 2);
+    taps.g[i] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
+    sum += taps.g[i];
+  }
+  for (int i = 0; i < SSIM_TAPS; ++i) taps.g[i] /= sum;
+  return taps;
+}
+
 int64_t afx_image_ssim_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W) {
   if (batch < 1 || C < 1 || H < SSIM_TAPS || W < SSIM_TAPS) return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_image_ssim_ws_bytes (batch and C at least 1, H and W at least 11)");
   const int64_t parts = ssim_parts(C, H, W, nullptr, nullptr);
@@ -740,14 +947,7 @@ int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transfor
   if (parts > INT32_MAX) return fail(AFX_E_INVALID, "afx_image_ssim: more than 2^31 - 1 tiles per sample");
   if (ws_bytes < (int64_t)batch * parts * (int64_t)sizeof(double))
     return fail(AFX_E_INVALID, "afx_image_ssim: workspace smaller than afx_image_ssim_ws_bytes()");
-  ssim_taps_t taps;
-  double sum = 0.0;
-  for (int i = 0; i < SSIM_TAPS; ++i) {
-    const double d = (double)(i - SSIM_TAPS / 2);
-    taps.g[i] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
-    sum += taps.g[i];
-  }
-  for (int i = 0; i < SSIM_TAPS; ++i) taps.g[i] /= sum;
+  const ssim_taps_t taps = ssim_window();
   const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
   hipStream_t st = (hipStream_t)stream;
   if (bf16)
@@ -757,6 +957,88 @@ int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transfor
     hipLaunchKernelGGL(image_ssim_partial_kernel<false>, dim3((unsigned)parts, batch), dim3(256), 0, st, a, b, (int)transform, taps, c1, c2,
                        (double*)ws, (int)H, (int)W, tiles_x, tiles);
   hipLaunchKernelGGL(image_ssim_finish_kernel, dim3(batch), dim3(64), 0, st, (const double*)ws, out, (int)parts);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int64_t afx_sample_score_masked_ws_bytes(int32_t batch, int64_t n) {
+  if (batch < 0 || n < 64 || n % 64 || n > INT32_MAX) return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_sample_score_masked_ws_bytes (n must be a positive multiple of 64 below 2^31)");
+  return (int64_t)batch * ortho_parts(n) * 10 * (int64_t)sizeof(double);
+}
+
+int afx_sample_score_masked(const void* a, const void* b, const float* mask, int32_t dtype, int32_t transform, double* out, void* ws,
+                            int64_t ws_bytes, int32_t batch, int32_t mask_batch, int32_t G, int32_t P, int32_t R, int32_t Q, void* stream) {
+  if (!a || !b || !mask || !out || !ws) return fail(AFX_E_INVALID, "null argument to afx_sample_score_masked");
+  if (dtype != AFX_DT_BF16 && dtype != AFX_DT_F32)
+    return fail(AFX_E_INVALID, "afx_sample_score_masked: dtype must be AFX_DT_BF16 or AFX_DT_F32");
+  if (transform != 0 && transform != 1) return fail(AFX_E_INVALID, "afx_sample_score_masked: transform must be 0 or 1");
+  if (batch < 0 || batch > 65535 || G < 1 || P < 1 || R < 1 || Q < 1)
+    return fail(AFX_E_INVALID, "bad argument to afx_sample_score_masked (0 <= batch <= 65535; G, P, R, Q >= 1)");
+  if (R % Q) return fail(AFX_E_INVALID, "afx_sample_score_masked: Q = %d must divide R = %d", (int)Q, (int)R);
+  if (mask_batch != 1 && mask_batch != batch)
+    return fail(AFX_E_INVALID, "afx_sample_score_masked: mask_batch must be 1 or batch = %d, got %d", (int)batch, (int)mask_batch);
+  const int64_t pr = (int64_t)P * R;
+  if (pr > INT32_MAX || pr * G > INT32_MAX || (pr * G) % 64)
+    return fail(AFX_E_INVALID, "bad argument to afx_sample_score_masked (n = G P R elements per sample must be a multiple of 64 below 2^31)");
+  const int64_t n = pr * G;
+  if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)mask & 3) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7))
+    return fail(AFX_E_INVALID, "afx_sample_score_masked: a and b must be 16-byte aligned, mask 4-byte, out and ws 8-byte aligned");
+  const int parts = ortho_parts(n);
+  if (ws_bytes < (int64_t)batch * parts * 10 * (int64_t)sizeof(double))
+    return fail(AFX_E_INVALID, "afx_sample_score_masked: workspace smaller than afx_sample_score_masked_ws_bytes()");
+  if (batch == 0) return AFX_OK;
+  const bool bf16 = dtype == AFX_DT_BF16;
+  const int64_t ups = n / (bf16 ? 8 : 4), upw = (ups + parts - 1) / parts;          // the partition of afx_sample_score
+  const int64_t mstride = mask_batch == 1 ? 0 : (int64_t)P * Q;
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16)
+    hipLaunchKernelGGL(sample_score_masked_partial_kernel<true>, dim3(parts, batch), dim3(256), 0, st, a, b, mask, (int)transform, (double*)ws,
+                       ups, upw, mstride, (uint32_t)P, (uint32_t)R, (uint32_t)Q);
+  else
+    hipLaunchKernelGGL(sample_score_masked_partial_kernel<false>, dim3(parts, batch), dim3(256), 0, st, a, b, mask, (int)transform, (double*)ws,
+                       ups, upw, mstride, (uint32_t)P, (uint32_t)R, (uint32_t)Q);
+  hipLaunchKernelGGL(sample_score_masked_finish_kernel, dim3((batch * 10 + 63) / 64), dim3(64), 0, st, (const double*)ws, out, batch, parts);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int64_t afx_image_ssim_masked_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W) {
+  if (batch < 1 || C < 1 || H < SSIM_TAPS || W < SSIM_TAPS)
+    return (int64_t)fail(AFX_E_INVALID, "bad argument to afx_image_ssim_masked_ws_bytes (batch and C at least 1, H and W at least 11)");
+  const int64_t parts = ssim_parts(C, H, W, nullptr, nullptr);
+  if (parts > INT32_MAX) return (int64_t)fail(AFX_E_INVALID, "afx_image_ssim_masked_ws_bytes: more than 2^31 - 1 tiles per sample");
+  return (int64_t)batch * parts * 4 * (int64_t)sizeof(double);
+}
+
+int afx_image_ssim_masked(const void* a, const void* b, const float* mask, int32_t dtype, int32_t transform, double data_range, double* out,
+                          void* ws, int64_t ws_bytes, int32_t batch, int32_t mask_batch, int32_t C, int32_t H, int32_t W, void* stream) {
+  if (!a || !b || !mask || !out || !ws) return fail(AFX_E_INVALID, "null argument to afx_image_ssim_masked");
+  if (dtype != AFX_DT_BF16 && dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "afx_image_ssim_masked: dtype must be AFX_DT_BF16 or AFX_DT_F32");
+  if (transform != 0 && transform != 1) return fail(AFX_E_INVALID, "afx_image_ssim_masked: transform must be 0 or 1");
+  if (!(data_range > 0.0) || data_range > 1e150) return fail(AFX_E_INVALID, "afx_image_ssim_masked: data_range must be positive (and finite)");
+  if (batch < 1 || batch > 65535 || C < 1) return fail(AFX_E_INVALID, "bad argument to afx_image_ssim_masked (1 <= batch <= 65535, C >= 1)");
+  if (mask_batch != 1 && mask_batch != batch)
+    return fail(AFX_E_INVALID, "afx_image_ssim_masked: mask_batch must be 1 or batch = %d, got %d", (int)batch, (int)mask_batch);
+  if (H < SSIM_TAPS || W < SSIM_TAPS) return fail(AFX_E_INVALID, "afx_image_ssim_masked: H and W must be at least 11 (one window)");
+  const bool bf16 = dtype == AFX_DT_BF16;
+  if (((uintptr_t)a & (bf16 ? 1 : 3)) || ((uintptr_t)b & (bf16 ? 1 : 3)) || ((uintptr_t)mask & 3) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7))
+    return fail(AFX_E_INVALID, "afx_image_ssim_masked: a, b and mask must be aligned to their element, out and ws 8-byte aligned");
+  int tiles_x = 0, tiles = 0;
+  const int64_t parts = ssim_parts(C, H, W, &tiles_x, &tiles);
+  if (parts > INT32_MAX) return fail(AFX_E_INVALID, "afx_image_ssim_masked: more than 2^31 - 1 tiles per sample");
+  if (ws_bytes < (int64_t)batch * parts * 4 * (int64_t)sizeof(double))
+    return fail(AFX_E_INVALID, "afx_image_ssim_masked: workspace smaller than afx_image_ssim_masked_ws_bytes()");
+  const ssim_taps_t taps = ssim_window();
+  const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+  const int64_t mstride = mask_batch == 1 ? 0 : (int64_t)H * W;
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16)
+    hipLaunchKernelGGL(image_ssim_masked_partial_kernel<true>, dim3((unsigned)parts, batch), dim3(256), 0, st, a, b, mask, (int)transform, taps, c1,
+                       c2, (double*)ws, (int)H, (int)W, tiles_x, tiles, mstride);
+  else
+    hipLaunchKernelGGL(image_ssim_masked_partial_kernel<false>, dim3((unsigned)parts, batch), dim3(256), 0, st, a, b, mask, (int)transform, taps, c1,
+                       c2, (double*)ws, (int)H, (int)W, tiles_x, tiles, mstride);
+  hipLaunchKernelGGL(image_ssim_masked_finish_kernel, dim3(batch, 4), dim3(64), 0, st, (const double*)ws, out, (int)parts);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

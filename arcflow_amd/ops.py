@@ -565,6 +565,92 @@ def image_ssim(a, b, transform: bool = False, data_range: float = 1.0, out: Opti
     return out
 
 
+def _score_mask_view(a, mask):
+    """(G, P, R, Q) of afx_sample_score_masked for operands a [B, ...] and a mask: packed tokens [B, N, 64] with [Bm, N, 4] (the operand of
+    edit_blend), or images [B, C, H, W] with [Bm, 1, H, W]."""
+    if a.dim() == 3 and mask.dim() == 3 and mask.shape[1] == a.shape[1] and mask.shape[2] >= 1 and a.shape[2] % mask.shape[2] == 0:
+        return 1, a.shape[1], a.shape[2], mask.shape[2]
+    if a.dim() == 4 and mask.dim() == 4 and mask.shape[1] == 1 and tuple(mask.shape[2:]) == tuple(a.shape[2:]):
+        return a.shape[1], a.shape[2] * a.shape[3], 1, 1
+    raise ValueError(f'mask: need [B or 1, N, Q] (Q dividing C) for a [B, N, C], or [B or 1, 1, H, W] for a [B, C, H, W]; got {tuple(mask.shape)} '
+                     f'for a {tuple(a.shape)}')
+
+
+def sample_score_masked_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
+    """Workspace of sample_score_masked for [batch, n] operands (afx_sample_score_masked_ws_bytes): fp64 partial sums, 10 per work-group."""
+    need = _lib.load().afx_sample_score_masked_ws_bytes(batch, n)
+    if need < 0:
+        _lib.check(int(need))
+    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+
+
+def sample_score_masked(a, b, mask, transform: bool = False, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, 2, 5] float64 = per sample and region (sum w, sum w (a-b)^2, sum w a^2, sum w b^2, sum w a b): region 0 the repainted one,
+    w = mask, region 1 the kept one, w = 1 - mask (afx_sample_score_masked).  a, b as sample_score takes them, either packed tokens
+    [B, N, 64] with the [B or 1, N, 4] fp32 mask of edit_blend / schedule.mask_to_tokens, or images [B, C, H, W] with a [B or 1, 1, H, W]
+    fp32 mask; a mask batch of 1 is shared.  Bit-reproducible; with mask = 1 region 0's last four sums are sample_score's bit for bit.
+    Nothing is copied or cast: a wrong dtype or layout raises.  out / ws: reuse buffers (ops.sample_score_masked_ws)."""
+    lib = _lib.load()
+    _gpu(a, b, mask, out, ws)
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
+    G, Pn, R, Q = _score_mask_view(a, mask)
+    B = a.shape[0]
+    n = a[0].numel() if B else 0
+    a = _packed(a, a.dtype, a.shape, 'a')
+    b = _packed(b, a.dtype, a.shape, 'b')
+    Bm = mask.shape[0]
+    mask = _packed(mask, torch.float32, mask.shape, 'mask')
+    out = torch.empty(B, 2, 5, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 2, 5), 'out')
+    if ws is None:
+        ws = sample_score_masked_ws(B, n, a.device)
+    elif not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.sample_score_masked_ws)')
+    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    _lib.check(lib.afx_sample_score_masked(_p(a), _p(b), _p(mask), dt, int(bool(transform)), _p(out), _p(ws), ws.numel() * ws.element_size(),
+                                           B, Bm, G, Pn, R, Q, _s()))
+    return out
+
+
+def image_ssim_masked_ws(batch: int, channels: int, height: int, width: int, device='cuda') -> torch.Tensor:
+    """Workspace of image_ssim_masked (afx_image_ssim_masked_ws_bytes): four fp64 partial sums per work-group."""
+    need = _lib.load().afx_image_ssim_masked_ws_bytes(batch, channels, height, width)
+    if need < 0:
+        _lib.check(int(need))
+    return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+
+def image_ssim_masked(a, b, mask, transform: bool = False, data_range: float = 1.0, out: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, 4] float64 = per sample (sum w ssim, sum w, sum (1 - w) ssim, sum (1 - w)) over the C channels and (H - 10)(W - 10) windows of
+    a, b [B, C, H, W] (afx_image_ssim_masked): image_ssim's window SSIM, every window weighted by w = the Gaussian-weighted mean of
+    mask [B or 1, 1, H, W] (fp32, in [0, 1]) over the window's own support.  [:, 0] / [:, 1] is the mean SSIM of the repainted region,
+    [:, 2] / [:, 3] that of the kept region.  transform, data_range, dtypes and layout as image_ssim; bit-reproducible.  Nothing is
+    copied or cast: a wrong dtype, device, layout or rank raises.  out / ws: reuse buffers (ops.image_ssim_masked_ws)."""
+    lib = _lib.load()
+    _gpu(a, b, mask, out, ws)
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
+    if a.dim() != 4:
+        raise ValueError(f'a: need [B, C, H, W], got {tuple(a.shape)}')
+    B, Cn, H, W = a.shape
+    if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, H, W):
+        raise ValueError(f'mask: need [B or 1, 1, {H}, {W}], got {tuple(mask.shape)}')
+    a = _packed(a, a.dtype, a.shape, 'a')
+    b = _packed(b, a.dtype, a.shape, 'b')
+    Bm = mask.shape[0]
+    mask = _packed(mask, torch.float32, mask.shape, 'mask')
+    out = torch.empty(B, 4, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 4), 'out')
+    if ws is None:
+        ws = image_ssim_masked_ws(B, Cn, H, W, a.device)
+    elif not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.image_ssim_masked_ws)')
+    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    _lib.check(lib.afx_image_ssim_masked(_p(a), _p(b), _p(mask), dt, int(bool(transform)), float(data_range), _p(out), _p(ws),
+                                         ws.numel() * ws.element_size(), B, Bm, Cn, H, W, _s()))
+    return out
+
+
 _FILTERS = {'lanczos3': 'AFX_FILTER_LANCZOS3', 'triangle': 'AFX_FILTER_TRIANGLE'}
 
 

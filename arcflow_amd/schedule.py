@@ -101,6 +101,22 @@ def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep
     return out + [0.0]
 
 
+def student_edit_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
+                        strength: float = 1.0, num_train_timesteps: int = 1000) -> List[float]:
+    """``student_sigmas`` of an edit, as the pipelines' ``_denoise_edit`` walks them: the raw grid of ``edit_raw_timesteps`` (every raw time
+    multiplied by ``strength`` in (0, 1]) through the same static shift in fp32, every step reading the first sub-step of its segment, plus
+    the terminal 0.  The first entry is the sigma the source is noised to.  strength == 1.0 returns ``student_sigmas``' list."""
+    raw, per_step, total = edit_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio, strength)
+    sch = FlowMatchEulerDiscreteScheduler(num_train_timesteps=num_train_timesteps, shift=shift, use_dynamic_shifting=False)
+    ts = sch.set_timesteps(sigmas=raw).float().tolist()
+    out, tid = [], 0
+    for n in per_step:
+        out.append(ts[tid] / num_train_timesteps)
+        tid += n
+    assert tid == total == len(ts)
+    return out + [0.0]
+
+
 class _Config(dict):
     """dict with attribute access, like diffusers' FrozenDict configs."""
     __getattr__ = dict.get

@@ -15,6 +15,9 @@ from .distill import DistillConfig
 _FAMILY = {'ArcFluxTransformer2DModel': 'flux', 'ArcQwenImageTransformer2DModel': 'qwen'}
 # this project's own key (absent from the reference's configs): how the training-time evaluation samples -- evaluate.Evaluator
 EVAL_CFG_DEFAULTS = dict(num_batches=1, seed=0, teacher_steps=28, use_ema=True)
+# further eval_cfg keys, present in run['eval_cfg'] only where the config sets them (a config without them reads as before): score an edit
+# too -- edit_mask None | 'box' (the centred rectangle of half the side) | 'left' (the left half), edit_strength in (0, 1]
+EVAL_CFG_EDIT_DEFAULTS = dict(edit_mask=None, edit_strength=0.8)
 _MODE = {'ArcFlowImitationDataFree': 'data_free', 'ArcFlowImitation': 'data'}        # diffusion.type -> DistillConfig.mode (arcflow.py:275,339)
 
 
@@ -107,10 +110,14 @@ def distill_setup(cfg: Dict[str, Any]) -> Tuple[str, Dict[str, Any], DistillConf
     # evaluation (latent_diffusion_text_image.py:108-170 val_step): the reference's eval_interval + test_cfg, and the optional eval_cfg of this project
     test_cfg = dict(cfg.get('test_cfg') or {})
     eval_cfg = dict(EVAL_CFG_DEFAULTS)
-    unknown = set(cfg.get('eval_cfg') or {}) - set(eval_cfg)
+    unknown = set(cfg.get('eval_cfg') or {}) - set(eval_cfg) - set(EVAL_CFG_EDIT_DEFAULTS)
     if unknown:
-        raise ValueError(f'eval_cfg: unknown keys {sorted(unknown)} (known: {sorted(eval_cfg)})')
+        raise ValueError(f'eval_cfg: unknown keys {sorted(unknown)} (known: {sorted(set(eval_cfg) | set(EVAL_CFG_EDIT_DEFAULTS))})')
     eval_cfg.update(cfg.get('eval_cfg') or {})
+    if eval_cfg.get('edit_mask') not in (None, 'box', 'left'):
+        raise ValueError(f"eval_cfg: edit_mask must be None, 'box' or 'left', got {eval_cfg['edit_mask']!r}")
+    if not 0.0 < float(eval_cfg.get('edit_strength', EVAL_CFG_EDIT_DEFAULTS['edit_strength'])) <= 1.0:
+        raise ValueError(f"eval_cfg: edit_strength must be in (0, 1], got {eval_cfg['edit_strength']!r}")
     run = dict(name=cfg.get('name', 'arcflow'), total_iters=cfg.get('total_iters', 10000),
                samples_per_gpu=cfg.get('data', {}).get('train_dataloader', {}).get('samples_per_gpu', 1),
                save_interval=ck.get('interval', 500), ckpt_dir=os.path.join(ck.get('out_dir', 'checkpoints/'), cfg.get('name', 'arcflow')),

@@ -359,30 +359,58 @@ class ArcFlowDistiller:
             del scratch
 
     @torch.no_grad()
-    def sample_student(self, cond, noise, nfe: Optional[int] = None, timestep_ratio: Optional[float] = None, ema: bool = False):
+    def sample_student(self, cond, noise, nfe: Optional[int] = None, timestep_ratio: Optional[float] = None, ema: bool = False,
+                       x0=None, mask=None, strength: float = 1.0):
         """Roll the student from ``noise`` [B, N, C] (packed tokens) to latents [B, N, C] fp32 as the pipelines' ``__call__`` does: ``nfe``
         forwards of the merged engine (student_forward: W + B A of the live adapters, no dropout), each followed by the analytic step
         ``ops.arcflow_step`` to the next step's sigma (schedule.student_sigmas with cfg.shift / cfg.total_substeps; defaults cfg.nfe,
-        cfg.timestep_ratio).  ema=True: on the EMA weights (ema_weights()).  B > 4 runs as micro-batches of 4, as TeacherSampler does."""
-        from ..schedule import student_sigmas
+        cfg.timestep_ratio).  ema=True: on the EMA weights (ema_weights()).  B > 4 runs as micro-batches of 4, as TeacherSampler does.
+
+        ``x0`` [B, N, 64] (packed latents of a source image, fp32): an edit, with the semantics of the pipelines' ``_denoise_edit`` -- start
+        on (1 - sigma_0) x0 + sigma_0 noise (``ops.edit_blend``), ``nfe`` steps over ``schedule.student_edit_sigmas(..., strength)``, and with
+        ``mask`` [B or 1, N, 4] (1 = repaint: ``schedule.mask_to_tokens``) after every step the kept latent pixels are put back on the
+        source's trajectory at the sigma the step landed on, with the same noise every time and none at sigma 0; the next forward reads the
+        blend kernel's bf16 copy.  Without ``x0`` the text-to-image path above runs unchanged; ``mask`` or a ``strength`` other than 1 raise."""
+        from ..schedule import student_edit_sigmas, student_sigmas
+        if x0 is None and mask is not None:
+            raise ValueError('mask: inpainting needs the source latents x0')
+        if x0 is None and float(strength) != 1.0:
+            raise ValueError(f'strength = {strength}: only an edit (x0=...) takes a strength other than 1')
         if ema:
             with self.ema_weights():
-                return self.sample_student(cond, noise, nfe, timestep_ratio)
+                return self.sample_student(cond, noise, nfe, timestep_ratio, x0=x0, mask=mask, strength=strength)
         c = self.cfg
         nfe = c.nfe if nfe is None else int(nfe)
         ratio = c.timestep_ratio if timestep_ratio is None else float(timestep_ratio)
         if noise.dim() != 3 or noise.shape[1] != cond['hp'] * cond['wp'] or noise.shape[2] != self.C:
             raise ValueError(f"noise: need packed tokens [B, {cond['hp'] * cond['wp']}, {self.C}], got {tuple(noise.shape)}")
-        sig = student_sigmas(nfe, c.total_substeps, ratio, c.shift)
         B = noise.shape[0]
+        if x0 is None:
+            sig = student_sigmas(nfe, c.total_substeps, ratio, c.shift)
+        else:
+            sig = student_edit_sigmas(nfe, c.total_substeps, ratio, c.shift, strength)
+            if tuple(x0.shape) != tuple(noise.shape):
+                raise ValueError(f'x0: the source latents are {tuple(x0.shape)}, the start noise is {tuple(noise.shape)}')
+            if mask is not None and (mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (noise.shape[1], 4)):
+                raise ValueError(f'mask: need [{B} or 1, {noise.shape[1]}, 4] (schedule.mask_to_tokens), got {tuple(mask.shape)}')
         outs = []
         for a in range(0, B, 4):
             b = min(a + 4, B)
             cc = cond if B <= 4 else {k: (v[a:b] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B else v) for k, v in cond.items()}
             x = noise[a:b].to(self.device, torch.float32).contiguous()
+            x16 = None
+            if x0 is not None:
+                z, src = x, x0[a:b].to(self.device, torch.float32).contiguous()
+                mk = None if mask is None else (mask if mask.shape[0] == 1 else mask[a:b]).to(self.device, torch.float32).expand(b - a, -1, -1).contiguous()
+                x, x16 = ops.edit_blend(None, src, z, None, torch.full((b - a,), sig[0], dtype=torch.float32, device=self.device))
             for i in range(nfe):
-                out = self.student_forward(x, torch.full((b - a,), sig[i], dtype=torch.float32, device=self.device), cc)
+                sigma = torch.full((b - a,), sig[i], dtype=torch.float32, device=self.device)
+                out = self.student_forward(x, sigma, cc) if x16 is None else self._student(x, sigma, cc, x_bf16=x16)
                 x = ops.arcflow_step(x, out.means, out.logweights, out.loggammas, sig[i], sig[i], sig[i + 1], eps=c.eps)
+                x16 = None
+                if x0 is not None and mk is not None:
+                    x, x16 = ops.edit_blend(x, src, z if sig[i + 1] > 0.0 else None, mk,
+                                            torch.full((b - a,), sig[i + 1], dtype=torch.float32, device=self.device), out=x)
             outs.append(x)
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 

@@ -340,6 +340,35 @@ int afx_sample_score(const void* a, const void* b, int32_t dtype, int32_t transf
 int64_t afx_image_ssim_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
 int afx_image_ssim(const void* a, const void* b, int32_t dtype, int32_t transform, double data_range, double* out, void* ws,
                    int64_t ws_bytes, int32_t batch, int32_t C, int32_t H, int32_t W, void* stream);
+/* afx_sample_score weighted by an edit's mask (training-time evaluation of edits: does the student repaint the masked region the way the
+ * teacher does?).  a, b [batch, n] as afx_sample_score takes them, n = G P R, viewed as [batch, G, P, R]; mask [mask_batch, P, Q] fp32
+ * weights in [0, 1], mask_batch 1 (shared by the batch) or batch, Q a divisor of R: element (s, g, p, r) takes the weight
+ * m[s, p, r % Q].  Packed latents [batch, N, 64] with the [batch, N, 4] mask of afx_edit_blend: G = 1, P = N, R = 64, Q = 4 (element e
+ * of a token reads m[token, e & 3], that kernel's map).  Decoded images [batch, C, H, W] with a [batch, 1, H, W] mask: G = C, P = H W,
+ * R = Q = 1.
+ *   out[s][0] = { sum w, sum w (a-b)^2, sum w a^2, sum w b^2, sum w a b },  w = m          the repainted region
+ *   out[s][1] = the same with w = 1 - m (formed in fp64)                                   the kept region
+ * out [batch, 2, 5] fp64.  transform as in afx_sample_score.  w is widened to fp64; the difference, the squares and the product are
+ * afx_sample_score's, then weighted; the partition is afx_sample_score's, min(64, ceil(n / 8192)) work-groups per sample, one slot of
+ * 10 doubles each, added in index order by a second launch: no atomics, bit-reproducible, and with m = 1 everywhere out[s][0][1..4]
+ * equals afx_sample_score's out[s] bit for bit while out[s][1] is exactly 0.
+ * n a positive multiple of 64 below 2^31; a, b 16-byte aligned, mask 4-byte, out and ws 8-byte.  ws: afx_sample_score_masked_ws_bytes(
+ * batch, n) bytes, private to the call until it completes.  Every refusal precedes the first launch: out is untouched then. */
+int64_t afx_sample_score_masked_ws_bytes(int32_t batch, int64_t n);
+int afx_sample_score_masked(const void* a, const void* b, const float* mask, int32_t dtype, int32_t transform, double* out, void* ws,
+                            int64_t ws_bytes, int32_t batch, int32_t mask_batch, int32_t G, int32_t P, int32_t R, int32_t Q, void* stream);
+/* afx_image_ssim weighted by an edit's mask.  a, b, dtype, transform, data_range, the window and the ratio are afx_image_ssim's (a == b
+ * gives exactly 1.0 per window).  mask [mask_batch, 1, H, W] fp32 in [0, 1], mask_batch 1 or batch, shared by the C channels.  The
+ * weight w of a window is the Gaussian-weighted mean of the mask over the window's own 11 x 11 support (the same two 11-tap passes),
+ * clamped to [0, 1] in fp64.
+ *   out[s] = { sum w ssim, sum w, sum (1 - w) ssim, sum (1 - w) }  over the C channels and the (H - 10)(W - 10) windows of each, fp64:
+ * out[s][0] / out[s][1] is the mean SSIM of the repainted region, out[s][2] / out[s][3] that of the kept region.
+ * Deterministic on the scheme of afx_image_ssim: the same tiles, one slot of 4 doubles of `ws` per work-group, each sum added in that
+ * entry's fixed order by a second launch.  ws: afx_image_ssim_masked_ws_bytes(batch, C, H, W) = 4 x afx_image_ssim_ws_bytes bytes,
+ * 8-byte aligned, private to the call until it completes.  Every refusal precedes the first launch: out is untouched then. */
+int64_t afx_image_ssim_masked_ws_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
+int afx_image_ssim_masked(const void* a, const void* b, const float* mask, int32_t dtype, int32_t transform, double data_range, double* out,
+                          void* ws, int64_t ws_bytes, int32_t batch, int32_t mask_batch, int32_t C, int32_t H, int32_t W, void* stream);
 /* Image resampling for the edit pipelines: resize, crop and Gaussian mask feathering are one table-driven separable operation,
  *   out[i] = sum_{k < count[i]} w[i, k] in[start[i] + k]        per axis, horizontally first, then vertically, fp32 fma in tap order.
  * afx_resample_table is a HOST function on HOST arrays (no GPU needed): it builds one axis' table in fp64, rounds the weights to fp32 once

@@ -12,7 +12,8 @@ own trajectory and the original pixels are pasted back after decoding.  Nothing 
 ``pipe.sample_teacher(image=..., strength=..., mask_image=...)`` in ``--steps`` steps, written beside ``--out`` as ``<out>.teacher<ext>``;
 with both, the latents of the two edits are scored against each other with ``afx_sample_score`` (student = a, teacher = b): mse, rel-L2 and
 cosine per sample, and the two decoded edits as written (8 bits per channel, / 255) with ``afx_sample_score`` and ``afx_image_ssim``:
-``image_psnr`` and ``image_ssim``.  The teacher walks the last ``strength`` share of its schedule, the student all its steps over [strength, 0]; both
+``image_psnr`` and ``image_ssim``, and with ``--mask`` the same two weighted by the mask, ``repaint_image_psnr`` and ``repaint_image_ssim``
+(``afx_sample_score_masked``, ``afx_image_ssim_masked``).  The teacher walks the last ``strength`` share of its schedule, the student all its steps over [strength, 0]; both
 start from the same noise draw (``--seed``).
 
 ``--synthetic``: random-init weights of a reduced architecture, random prompt embeddings and a random image in latent space
@@ -54,18 +55,29 @@ def score_latents(student: torch.Tensor, teacher: torch.Tensor):
     return {'latent_' + k: m[k].tolist() for k in ('mse', 'rel_l2', 'cosine')}
 
 
-def score_images(student, teacher):
+def score_images(student, teacher, mask=None):
     """The two decoded edits as written (PIL images of one size, 8 bits per channel) -> {'image_psnr' | 'image_ssim': per-sample list} on
-    their values / 255 (afx_sample_score, afx_image_ssim; data range 1)."""
+    their values / 255 (afx_sample_score, afx_image_ssim; data range 1).  With ``mask`` (a PIL image, white = repaint; the mask file as
+    given, its grey values / 255, stretched to the edits' size when it differs -- not the pipeline's feathered copy) also
+    'repaint_image_psnr' | 'repaint_image_ssim': the same two scores weighted by the mask (afx_sample_score_masked,
+    afx_image_ssim_masked).  The whole-image scores are dominated by the kept region, which both edits paste back from the source."""
     import numpy as np
     from arcflow_amd import ops
-    from arcflow_amd.train.evaluate import metrics_from_sums, ssim_from_sums
+    from arcflow_amd.train.evaluate import masked_metrics_from_sums, masked_ssim_from_sums, metrics_from_sums, ssim_from_sums
 
     def planes(im):
         return torch.from_numpy(np.asarray(im.convert('RGB'), dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous().cuda()
     a, b = planes(student), planes(teacher)
     m = metrics_from_sums(ops.sample_score(a, b), a[0].numel(), data_range=1.0)
-    return {'image_psnr': m['psnr'].tolist(), 'image_ssim': ssim_from_sums(ops.image_ssim(a, b), *a.shape[1:]).tolist()}
+    out = {'image_psnr': m['psnr'].tolist(), 'image_ssim': ssim_from_sums(ops.image_ssim(a, b), *a.shape[1:]).tolist()}
+    if mask is not None:
+        grey = mask.convert('L')
+        if grey.size != student.size:
+            grey = grey.resize(student.size, 2)          # 2 = bilinear
+        w = torch.from_numpy(np.asarray(grey, dtype=np.float32) / 255.0)[None, None].contiguous().cuda()
+        out['repaint_image_psnr'] = masked_metrics_from_sums(ops.sample_score_masked(a, b, w), data_range=1.0)[0]['psnr'].tolist()
+        out['repaint_image_ssim'] = masked_ssim_from_sums(ops.image_ssim_masked(a, b, w))[0].tolist()
+    return out
 
 
 def _teacher_path(out: str) -> str:
@@ -160,7 +172,7 @@ def main(argv=None):
         tea.save(_teacher_path(args.out))
         print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}')
         if student:
-            print(f'student vs teacher: {dict(score_latents(lat, tlat), **score_images(out, tea))}')
+            print(f'student vs teacher: {dict(score_latents(lat, tlat), **score_images(out, tea, mask))}')
         out = tea if out is None else out
     return out
 

@@ -49,6 +49,10 @@ def parse_args(argv=None):
     ap.add_argument('--eval-teacher-steps', type=int, help='steps of the teacher ODE the student is scored against (default: eval_cfg.teacher_steps, 28)')
     ap.add_argument('--vae-dir', help='local diffusers vae/ directory (config.json + safetensors) of the config\'s family: the evaluation also decodes '
                                       'both sample sets and reports image_mse, image_psnr and image_ssim (needs --eval-interval)')
+    ap.add_argument('--eval-edits', choices=['box', 'left'], help='the evaluation also scores an inpainting edit of every condition, student against '
+                                                                  "teacher, weighted by the mask: 'box' repaints the centred rectangle of half the side, 'left' the "
+                                                                  'left half (default: eval_cfg.edit_mask, off; needs --eval-interval)')
+    ap.add_argument('--eval-edit-strength', type=float, help='strength of the scored edit, in (0, 1] (default: eval_cfg.edit_strength, 0.8; needs --eval-interval)')
     return ap.parse_args(argv)
 
 
@@ -101,6 +105,10 @@ def main(argv=None):
     args = parse_args(argv)
     if args.vae_dir and args.eval_interval is None:
         raise SystemExit('--vae-dir decodes the evaluation samples: it needs --eval-interval')
+    if (args.eval_edits or args.eval_edit_strength is not None) and args.eval_interval is None:
+        raise SystemExit('--eval-edits / --eval-edit-strength score an edit inside the evaluation: they need --eval-interval')
+    if args.eval_edit_strength is not None and not 0.0 < args.eval_edit_strength <= 1.0:
+        raise SystemExit(f'--eval-edit-strength must be in (0, 1], got {args.eval_edit_strength}')
     from arcflow_amd.train import ArcFlowDistiller, checkpoint, config, data
     cfg = config.apply_options(config.load_config(args.config), _options(args.cfg_options))
     family, eng, dc, run = config.distill_setup(cfg)
@@ -160,6 +168,12 @@ def main(argv=None):
         ecfg['num_batches'] = args.eval_batches
     if args.eval_teacher_steps is not None:
         ecfg['teacher_steps'] = args.eval_teacher_steps
+    if args.eval_edits is not None:
+        ecfg['edit_mask'] = args.eval_edits
+    if args.eval_edit_strength is not None:
+        ecfg['edit_strength'] = args.eval_edit_strength
+    if (args.eval_edits or args.eval_edit_strength is not None) and n_eval == 0:
+        raise SystemExit('--eval-edits / --eval-edit-strength score an edit inside the evaluation: they need an --eval-interval above 0')
     eval_conds = None                  # rank 0, evaluation on: the first num_batches batches of the data source, drawn apart from the training order
     want_eval = n_eval > 0 and rank == 0
     if n_eval > 0 and ecfg['num_batches'] < 1:
@@ -229,7 +243,8 @@ def main(argv=None):
         eval_conds = [{k: v for k, v in c.items() if k != 'latents'} for c in eval_conds]
         vae = load_vae_decoder(family, args.vae_dir, dev) if args.vae_dir else None          # with a decoder: the image metrics too
         evaluator = Evaluator(dist_, eval_conds, seed=ecfg['seed'], teacher_steps=ecfg['teacher_steps'], nfe=tcfg['nfe'],
-                              timestep_ratio=tcfg['timestep_ratio'], use_ema=ecfg['use_ema'], vae=vae)
+                              timestep_ratio=tcfg['timestep_ratio'], use_ema=ecfg['use_ema'], vae=vae,
+                              edits=dict(mask=ecfg['edit_mask'], strength=ecfg.get('edit_strength', 0.8)) if ecfg.get('edit_mask') else None)
         eval_dir = args.work_dir or run['work_dir'] or ckpt_dir
         os.makedirs(eval_dir, exist_ok=True)
         eval_path = os.path.join(eval_dir, 'eval.jsonl')
