@@ -1,6 +1,10 @@
-// Error plumbing shared by the extern "C" translation units.
+// Error plumbing and entry helpers shared by the extern "C" translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <initializer_list>
 
 #include "../../include/arcflow_hip.h"
 
@@ -21,4 +25,32 @@ static inline bool ranges_overlap(const void* a, int64_t an, const void* b, int6
   if (a == nullptr || b == nullptr) return false;
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
   return pa < pb + (uintptr_t)bn && pb < pa + (uintptr_t)an;
+}
+
+// one of the pointers (NULL ones pass) is not 16-byte aligned
+static inline bool misaligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return (bits & 15) != 0;
+}
+
+// Launch of a streaming step kernel (the teacher-sampler steps, afx_sampler.hip, and the edit blend, afx_edit.hip): one lane per chunk of
+// 8 consecutive elements, 256 lanes per work-group, grid-stride over `batch` samples of n elements; the kernel's last two parameters are
+// (chunks_per_sample, chunks).  max_blocks > 0 caps the grid; the default cap of 2048 is 8 work-groups per CU (256 CUs), which hide the
+// load latency of a streaming pass -- more only add launch work.
+template <typename... P, typename... A>
+static int launch_step(void (*kernel)(P...), int32_t batch, int64_t n, int32_t max_blocks, void* stream, A... args) {
+  const int64_t cps = n / 8, chunks = cps * batch;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, args..., cps, chunks);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+// The value of a *_ws_bytes entry: `batch` samples x `parts` slots of K doubles, or the refusal (negative) by the entry's name.
+static inline int64_t ws_bytes_or_fail(const char* name, bool bad, const char* rule, int32_t batch, int64_t parts, int K) {
+  if (bad) return (int64_t)fail(AFX_E_INVALID, "bad argument to %s%s", name, rule);
+  if (parts > INT32_MAX) return (int64_t)fail(AFX_E_INVALID, "%s: more than 2^31 - 1 tiles per sample", name);
+  return (int64_t)batch * parts * K * (int64_t)sizeof(double);
 }

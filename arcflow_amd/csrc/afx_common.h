@@ -55,6 +55,40 @@ AFX_DEV u32x4_t pack8(const float (&f)[8]) {
   return w;
 }
 
+// 8 consecutive fp32 values as two 16-byte words (p 16-byte aligned)
+AFX_DEV void load8(const float* p, float (&v)[8]) {
+  const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p), b = *reinterpret_cast<const f32x4_t*>(p + 4);
+  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
+AFX_DEV void store8(float* p, const float (&v)[8]) {
+  const f32x4_t a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
+  *reinterpret_cast<f32x4_t*>(p) = a;
+  *reinterpret_cast<f32x4_t*>(p + 4) = b;
+}
+
+// The known-region blend of image editing on one chunk of 8 consecutive elements of a token (edit_blend_kernel, afx_edit.hip, and the
+// fused teacher_edit_step_kernel, afx_sampler.hip: one function, so the two agree bit for bit):
+//   known = has_noise ? fma(sigma_to, noise, om x0) : om x0,   om = 1 - sigma_to
+//   o     = has_mask ? fma(m, x, (1 - m) known) : known,       m = mk[e & 3], the token's mask row
+// noise is read only with has_noise, x and mk only with has_mask; o may be x.  m = 1 returns x, m = 0 known, sigma_to = 1 noise and
+// sigma_to = 0 x0 bit for bit (finite inputs): each multiplies the other term by an exact 0 and the kept term by an exact 1.
+AFX_DEV void edit_blend8(const float (&x)[8], const float (&x0)[8], const float (&noise)[8], const f32x4_t& mk, bool has_noise, bool has_mask,
+                         float sigma_to, float (&o)[8]) {
+  const float om = 1.0f - sigma_to;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float known = om * x0[e];
+    if (has_noise) known = __builtin_fmaf(sigma_to, noise[e], known);
+    if (has_mask) {
+      const float m = mk[e & 3];
+      o[e] = __builtin_fmaf(m, x[e], (1.0f - m) * known);
+    } else {
+      o[e] = known;
+    }
+  }
+}
+
 // ---- block-scaled fp8 (MX layout, E8M0 scale bytes; afx_text.hip quant_rows_mx8_kernel and the fused producers) -------------------------
 // biased exponent b of the power-of-two scale of a block with absolute maximum amax: the smallest 2^(b - 127) with amax <= 448 * 2^(b - 127)
 AFX_DEV int mx_exp(float amax) {

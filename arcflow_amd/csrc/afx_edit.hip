@@ -5,6 +5,7 @@
 //       om    = 1 - sigma_to[b]
 //       known = noise ? fma(sigma_to[b], noise, om x0) : om x0
 //       x_out = mask ? fma(m, x, (1 - m) known) : known
+//     (edit_blend8, afx_common.h: the function the fused teacher_edit_step_kernel of afx_sampler.hip calls too)
 //     A token is 64 channels = 16 latent channels x the 2 x 2 patch, channel = c*4 + ph*2 + pw, and the mask holds one value per
 //     latent pixel of the patch: element e of a token reads mask[b, tok, e & 3].  A chunk of 8 consecutive elements starts at a
 //     multiple of 8, so its elements read mask values 0 1 2 3 0 1 2 3: one 16-byte load of the token's mask row per chunk.
@@ -14,8 +15,6 @@
 //     = 18 B, about 4.7 MB per image and step.
 //   The products are written so that m = 1 returns x, m = 0 returns known, sigma_to = 1 returns noise and sigma_to = 0 returns x0
 //   bit for bit (finite inputs): each of them multiplies the other term by an exact 0 and the kept term by an exact 1.
-#include <algorithm>
-
 #include "afx_api_util.h"
 #include "afx_common.h"
 
@@ -29,33 +28,16 @@ __global__ __launch_bounds__(256) void edit_blend_kernel(const float* x, const f
   for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += stride) {
     const int64_t b = c / chunks_per_sample;
     const float sg = sigma_to[b];
-    const float om = 1.0f - sg;
-    const f32x4_t a0 = *reinterpret_cast<const f32x4_t*>(x0 + c * 8);
-    const f32x4_t a1 = *reinterpret_cast<const f32x4_t*>(x0 + c * 8 + 4);
-    f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = z0, v0 = z0, v1 = z0, mk = z0;
-    if (noise != nullptr) {
-      z0 = *reinterpret_cast<const f32x4_t*>(noise + c * 8);
-      z1 = *reinterpret_cast<const f32x4_t*>(noise + c * 8 + 4);
-    }
+    float a[8], z[8], v[8], o[8];
+    f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
+    load8(x0 + c * 8, a);
+    if (noise != nullptr) load8(noise + c * 8, z);
     if (mask != nullptr) {
-      v0 = *reinterpret_cast<const f32x4_t*>(x + c * 8);          // (x_out may be x: every load precedes every store)
-      v1 = *reinterpret_cast<const f32x4_t*>(x + c * 8 + 4);
+      load8(x + c * 8, v);          // (x_out may be x: every load precedes every store)
       mk = *reinterpret_cast<const f32x4_t*>(mask + (c >> 3) * 4);
     }
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float known = om * (e < 4 ? a0[e & 3] : a1[e & 3]);
-      if (noise != nullptr) known = __builtin_fmaf(sg, e < 4 ? z0[e & 3] : z1[e & 3], known);
-      o[e] = known;
-      if (mask != nullptr) {
-        const float m = mk[e & 3];
-        o[e] = __builtin_fmaf(m, e < 4 ? v0[e & 3] : v1[e & 3], (1.0f - m) * known);
-      }
-    }
-    const f32x4_t o0 = {o[0], o[1], o[2], o[3]}, o1 = {o[4], o[5], o[6], o[7]};
-    *reinterpret_cast<f32x4_t*>(x_out + c * 8) = o0;
-    *reinterpret_cast<f32x4_t*>(x_out + c * 8 + 4) = o1;
+    edit_blend8(v, a, z, mk, noise != nullptr, mask != nullptr, sg, o);
+    store8(x_out + c * 8, o);
     if (x_bf16 != nullptr) *reinterpret_cast<u32x4_t*>(x_bf16 + c * 8) = pack8(o);
   }
 }
@@ -73,8 +55,7 @@ int afx_edit_blend(const float* x, const float* x0, const float* noise, const fl
   if (ch != 64) return fail(AFX_E_INVALID, "afx_edit_blend: ch must be 64 (16 latent channels x the 2 x 2 patch), got %d", (int)ch);
   if (batch < 1 || n_tok < 1 || max_blocks < 0)
     return fail(AFX_E_INVALID, "bad argument to afx_edit_blend (batch and n_tok must be >= 1, max_blocks >= 0)");
-  if (((uintptr_t)x & 15) || ((uintptr_t)x0 & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)mask & 15) || ((uintptr_t)sigma_to & 15) ||
-      ((uintptr_t)x_out & 15) || ((uintptr_t)x_out_bf16 & 15))
+  if (misaligned16({x, x0, noise, mask, sigma_to, x_out, x_out_bf16}))
     return fail(AFX_E_INVALID, "afx_edit_blend: x, x0, noise, mask, sigma_to, x_out and x_out_bf16 must be 16-byte aligned");
   const int64_t elems = (int64_t)batch * n_tok * 64;
   const int64_t fbytes = elems * 4, hbytes = elems * 2, mbytes = (int64_t)batch * n_tok * 16, sbytes = (int64_t)batch * 4;
@@ -88,13 +69,8 @@ int afx_edit_blend(const float* x, const float* x0, const float* noise, const fl
       ranges_overlap(x_out_bf16, hbytes, noise, fbytes) || ranges_overlap(x_out_bf16, hbytes, mask, mbytes) ||
       ranges_overlap(x_out_bf16, hbytes, sigma_to, sbytes))
     return fail(AFX_E_INVALID, "afx_edit_blend: x_out_bf16 overlaps an input");
-  const int64_t cps = (int64_t)n_tok * 8, chunks = cps * batch;
-  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;          // as afx_teacher_euler_step: 8 work-groups per CU
-  const unsigned grid = (unsigned)std::min<int64_t>((chunks + 255) / 256, cap);
-  hipLaunchKernelGGL(edit_blend_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, mask != nullptr ? x : nullptr, x0, noise, mask,
-                     sigma_to, x_out, (bf16_t*)x_out_bf16, cps, chunks);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
+  return launch_step(edit_blend_kernel, batch, (int64_t)n_tok * 64, max_blocks, stream, mask != nullptr ? x : nullptr, x0, noise, mask, sigma_to,
+                     x_out, (bf16_t*)x_out_bf16);
 }
 
 }  // extern "C"

@@ -471,12 +471,17 @@ def _packed(t: torch.Tensor, dtype, shape, name: str) -> torch.Tensor:
     return t
 
 
-def cfg_ortho_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
-    """Workspace of cfg_ortho_coef for [batch, n] velocities (afx_cfg_ortho_ws_bytes): fp64 partial sums, one pair per work-group."""
-    need = _lib.load().afx_cfg_ortho_ws_bytes(batch, n)
+def _ws(lib_fn, *args, device, min_one: bool) -> torch.Tensor:
+    """The float64 workspace of lib_fn(*args) bytes (a *_ws_bytes entry; its refusal raises).  min_one: one element where no bytes are needed."""
+    need = lib_fn(*args)
     if need < 0:
         _lib.check(int(need))
-    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+    return torch.empty(max(need // 8, 1) if min_one else need // 8, dtype=torch.float64, device=device)
+
+
+def cfg_ortho_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
+    """Workspace of cfg_ortho_coef for [batch, n] velocities (afx_cfg_ortho_ws_bytes): fp64 partial sums, one pair per work-group."""
+    return _ws(_lib.load().afx_cfg_ortho_ws_bytes, batch, n, device=device, min_one=True)
 
 
 def cfg_ortho_coef(pos, neg, scale: float, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -498,12 +503,25 @@ def cfg_ortho_coef(pos, neg, scale: float, out: Optional[torch.Tensor] = None, w
     return out
 
 
+def _score_operands(a, b, out, out_shape, ws, ws_fn, *ws_args):
+    """The operands every scorer shares, checked: -> (a, b, out, ws, dt).  a, b both fp32 or both bf16, contiguous, of one shape; out
+    [B, *out_shape] float64 (allocated when None); ws from ws_fn(B, *ws_args, device), one of the *_ws functions below, when None."""
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
+    B = a.shape[0]
+    a = _packed(a, a.dtype, a.shape, 'a')
+    b = _packed(b, a.dtype, a.shape, 'b')
+    out = torch.empty(B, *out_shape, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, *out_shape), 'out')
+    if ws is None:
+        ws = ws_fn(B, *ws_args, a.device)
+    elif not ws.is_contiguous():
+        raise ValueError(f'ws: need a contiguous GPU buffer (ops.{ws_fn.__name__})')
+    return a, b, out, ws, _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+
+
 def sample_score_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
     """Workspace of sample_score for [batch, n] operands (afx_sample_score_ws_bytes): fp64 partial sums, 4 per work-group."""
-    need = _lib.load().afx_sample_score_ws_bytes(batch, n)
-    if need < 0:
-        _lib.check(int(need))
-    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+    return _ws(_lib.load().afx_sample_score_ws_bytes, batch, n, device=device, min_one=True)
 
 
 def sample_score(a, b, transform: bool = False, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -513,28 +531,16 @@ def sample_score(a, b, transform: bool = False, out: Optional[torch.Tensor] = No
     Nothing is copied or cast: a wrong dtype or layout raises.  out / ws: reuse buffers (ops.sample_score_ws)."""
     lib = _lib.load()
     _gpu(a, b, out, ws)
-    if a.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
     B = a.shape[0]
     n = a[0].numel() if B else 0
-    a = _packed(a, a.dtype, a.shape, 'a')
-    b = _packed(b, a.dtype, a.shape, 'b')
-    out = torch.empty(B, 4, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 4), 'out')
-    if ws is None:
-        ws = sample_score_ws(B, n, a.device)
-    elif not ws.is_contiguous():
-        raise ValueError('ws: need a contiguous GPU buffer (ops.sample_score_ws)')
-    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    a, b, out, ws, dt = _score_operands(a, b, out, (4,), ws, sample_score_ws, n)
     _lib.check(lib.afx_sample_score(_p(a), _p(b), dt, int(bool(transform)), _p(out), _p(ws), ws.numel() * ws.element_size(), B, n, _s()))
     return out
 
 
 def image_ssim_ws(batch: int, channels: int, height: int, width: int, device='cuda') -> torch.Tensor:
     """Workspace of image_ssim for [batch, channels, height, width] operands (afx_image_ssim_ws_bytes): one fp64 partial sum per work-group."""
-    need = _lib.load().afx_image_ssim_ws_bytes(batch, channels, height, width)
-    if need < 0:
-        _lib.check(int(need))
-    return torch.empty(need // 8, dtype=torch.float64, device=device)
+    return _ws(_lib.load().afx_image_ssim_ws_bytes, batch, channels, height, width, device=device, min_one=False)
 
 
 def image_ssim(a, b, transform: bool = False, data_range: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -547,19 +553,10 @@ def image_ssim(a, b, transform: bool = False, data_range: float = 1.0, out: Opti
     out / ws: reuse buffers (ops.image_ssim_ws)."""
     lib = _lib.load()
     _gpu(a, b, out, ws)
-    if a.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
     if a.dim() != 4:
         raise ValueError(f'a: need [B, C, H, W], got {tuple(a.shape)}')
     B, Cn, H, W = a.shape
-    a = _packed(a, a.dtype, a.shape, 'a')
-    b = _packed(b, a.dtype, a.shape, 'b')
-    out = torch.empty(B, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B,), 'out')
-    if ws is None:
-        ws = image_ssim_ws(B, Cn, H, W, a.device)
-    elif not ws.is_contiguous():
-        raise ValueError('ws: need a contiguous GPU buffer (ops.image_ssim_ws)')
-    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    a, b, out, ws, dt = _score_operands(a, b, out, (), ws, image_ssim_ws, Cn, H, W)
     _lib.check(lib.afx_image_ssim(_p(a), _p(b), dt, int(bool(transform)), float(data_range), _p(out), _p(ws), ws.numel() * ws.element_size(),
                                   B, Cn, H, W, _s()))
     return out
@@ -578,10 +575,7 @@ def _score_mask_view(a, mask):
 
 def sample_score_masked_ws(batch: int, n: int, device='cuda') -> torch.Tensor:
     """Workspace of sample_score_masked for [batch, n] operands (afx_sample_score_masked_ws_bytes): fp64 partial sums, 10 per work-group."""
-    need = _lib.load().afx_sample_score_masked_ws_bytes(batch, n)
-    if need < 0:
-        _lib.check(int(need))
-    return torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+    return _ws(_lib.load().afx_sample_score_masked_ws_bytes, batch, n, device=device, min_one=True)
 
 
 def sample_score_masked(a, b, mask, transform: bool = False, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -592,32 +586,18 @@ def sample_score_masked(a, b, mask, transform: bool = False, out: Optional[torch
     Nothing is copied or cast: a wrong dtype or layout raises.  out / ws: reuse buffers (ops.sample_score_masked_ws)."""
     lib = _lib.load()
     _gpu(a, b, mask, out, ws)
-    if a.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
     G, Pn, R, Q = _score_mask_view(a, mask)
-    B = a.shape[0]
-    n = a[0].numel() if B else 0
-    a = _packed(a, a.dtype, a.shape, 'a')
-    b = _packed(b, a.dtype, a.shape, 'b')
-    Bm = mask.shape[0]
     mask = _packed(mask, torch.float32, mask.shape, 'mask')
-    out = torch.empty(B, 2, 5, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 2, 5), 'out')
-    if ws is None:
-        ws = sample_score_masked_ws(B, n, a.device)
-    elif not ws.is_contiguous():
-        raise ValueError('ws: need a contiguous GPU buffer (ops.sample_score_masked_ws)')
-    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    B = a.shape[0]
+    a, b, out, ws, dt = _score_operands(a, b, out, (2, 5), ws, sample_score_masked_ws, a[0].numel() if B else 0)
     _lib.check(lib.afx_sample_score_masked(_p(a), _p(b), _p(mask), dt, int(bool(transform)), _p(out), _p(ws), ws.numel() * ws.element_size(),
-                                           B, Bm, G, Pn, R, Q, _s()))
+                                           B, mask.shape[0], G, Pn, R, Q, _s()))
     return out
 
 
 def image_ssim_masked_ws(batch: int, channels: int, height: int, width: int, device='cuda') -> torch.Tensor:
     """Workspace of image_ssim_masked (afx_image_ssim_masked_ws_bytes): four fp64 partial sums per work-group."""
-    need = _lib.load().afx_image_ssim_masked_ws_bytes(batch, channels, height, width)
-    if need < 0:
-        _lib.check(int(need))
-    return torch.empty(need // 8, dtype=torch.float64, device=device)
+    return _ws(_lib.load().afx_image_ssim_masked_ws_bytes, batch, channels, height, width, device=device, min_one=False)
 
 
 def image_ssim_masked(a, b, mask, transform: bool = False, data_range: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -629,25 +609,15 @@ def image_ssim_masked(a, b, mask, transform: bool = False, data_range: float = 1
     copied or cast: a wrong dtype, device, layout or rank raises.  out / ws: reuse buffers (ops.image_ssim_masked_ws)."""
     lib = _lib.load()
     _gpu(a, b, mask, out, ws)
-    if a.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f'a: need float32 or bfloat16, got {a.dtype}')
     if a.dim() != 4:
         raise ValueError(f'a: need [B, C, H, W], got {tuple(a.shape)}')
     B, Cn, H, W = a.shape
     if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, H, W):
         raise ValueError(f'mask: need [B or 1, 1, {H}, {W}], got {tuple(mask.shape)}')
-    a = _packed(a, a.dtype, a.shape, 'a')
-    b = _packed(b, a.dtype, a.shape, 'b')
-    Bm = mask.shape[0]
     mask = _packed(mask, torch.float32, mask.shape, 'mask')
-    out = torch.empty(B, 4, dtype=torch.float64, device=a.device) if out is None else _packed(out, torch.float64, (B, 4), 'out')
-    if ws is None:
-        ws = image_ssim_masked_ws(B, Cn, H, W, a.device)
-    elif not ws.is_contiguous():
-        raise ValueError('ws: need a contiguous GPU buffer (ops.image_ssim_masked_ws)')
-    dt = _lib.AFX_DT_BF16 if a.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    a, b, out, ws, dt = _score_operands(a, b, out, (4,), ws, image_ssim_masked_ws, Cn, H, W)
     _lib.check(lib.afx_image_ssim_masked(_p(a), _p(b), _p(mask), dt, int(bool(transform)), float(data_range), _p(out), _p(ws),
-                                         ws.numel() * ws.element_size(), B, Bm, Cn, H, W, _s()))
+                                         ws.numel() * ws.element_size(), B, mask.shape[0], Cn, H, W, _s()))
     return out
 
 
@@ -755,6 +725,27 @@ def mask_feather(mask: torch.Tensor, sigma: float) -> torch.Tensor:
     return _resample(mask, dims, H, W, tab_h, tab_w, True)
 
 
+def _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
+    """The operands every teacher step shares, checked: -> (x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n), out and out_bf16
+    allocated when None.  sigma and sigma_to may be None (the UniPC step takes its weights instead)."""
+    B = x.shape[0]
+    x = _packed(x, torch.float32, x.shape, 'x')
+    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
+    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    sigma = None if sigma is None else _packed(sigma, torch.float32, (B,), 'sigma')
+    sigma_to = None if sigma_to is None else _packed(sigma_to, torch.float32, (B,), 'sigma_to')
+    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
+    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    return x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, x[0].numel() if B else 0
+
+
+def _sde_operands(x, noise, m, c_noise):
+    """What the FlowSDE steps take beside _step_operands, checked against x: -> (noise, m, c_noise)."""
+    noise = None if noise is None else _packed(noise, torch.float32, x.shape, 'noise')
+    return noise, _packed(m, torch.float32, (x.shape[0],), 'm'), _packed(c_noise, torch.float32, (x.shape[0],), 'c_noise')
+
+
 def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, max_blocks: int = 0):
     """One step of the teacher's Euler ODE sampler in one launch (afx_teacher_euler_step):
@@ -763,16 +754,7 @@ def teacher_euler_step(x, pos, neg, sigma, sigma_to, scale: float = 1.0, coef: O
     out may be x (in place).  numel / B must be a multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
     lib = _lib.load()
     _gpu(x, pos, neg, sigma, sigma_to, coef, out, out_bf16)
-    B = x.shape[0]
-    n = x[0].numel() if B else 0
-    x = _packed(x, torch.float32, x.shape, 'x')
-    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
-    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
-    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
-    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
-    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
-    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
-    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n = _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16)
     _lib.check(lib.afx_teacher_euler_step(_p(x), _p(pos), _p(neg), _p(sigma), _p(sigma_to), _p(coef), scale, _p(out), _p(out_bf16), B, n,
                                           max_blocks, _s()))
     return out, out_bf16
@@ -788,19 +770,8 @@ def teacher_sde_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, scale: flo
     multiple of 64.  Nothing is copied or cast: a wrong dtype or layout raises."""
     lib = _lib.load()
     _gpu(x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, out, out_bf16)
-    B = x.shape[0]
-    n = x[0].numel() if B else 0
-    x = _packed(x, torch.float32, x.shape, 'x')
-    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
-    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
-    noise = None if noise is None else _packed(noise, torch.float32, x.shape, 'noise')
-    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
-    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
-    m = _packed(m, torch.float32, (B,), 'm')
-    c_noise = _packed(c_noise, torch.float32, (B,), 'c_noise')
-    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
-    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
-    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
+    x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n = _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16)
+    noise, m, c_noise = _sde_operands(x, noise, m, c_noise)
     _lib.check(lib.afx_teacher_sde_step(_p(x), _p(pos), _p(neg), _p(noise), _p(sigma), _p(sigma_to), _p(m), _p(c_noise), _p(coef), scale,
                                         _p(out), _p(out_bf16), B, n, max_blocks, _s()))
     return out, out_bf16
@@ -820,19 +791,12 @@ def teacher_unipc_step(x, pos, neg, w, last, hist, last_out, hist_out, scale: fl
     if len(hist) > 3:
         raise ValueError(f'hist: at most three past predictions, got {len(hist)}')
     _gpu(x, pos, neg, w, last, *hist, last_out, hist_out, coef, out, out_bf16)
-    B = x.shape[0]
-    n = x[0].numel() if B else 0
-    x = _packed(x, torch.float32, x.shape, 'x')
-    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
-    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
+    x, pos, neg, _, _, coef, out, out_bf16, B, n = _step_operands(x, pos, neg, None, None, coef, out, out_bf16)
     w = _packed(w, torch.float32, (10, B), 'w')
     last = None if last is None else _packed(last, torch.float32, x.shape, 'last')
     hist = [_packed(h, torch.float32, x.shape, f'hist[{k}]') for k, h in enumerate(hist)] + [None] * (3 - len(hist))
     last_out = _packed(last_out, torch.float32, x.shape, 'last_out')
     hist_out = _packed(hist_out, torch.float32, x.shape, 'hist_out')
-    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
-    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
-    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
     _lib.check(lib.afx_teacher_unipc_step(_p(x), _p(pos), _p(neg), _p(w), _p(last), _p(hist[0]), _p(hist[1]), _p(hist[2]), _p(coef), scale,
                                           _p(out), _p(out_bf16), _p(last_out), _p(hist_out), B, n, max_blocks, _s()))
     return out, out_bf16
@@ -871,21 +835,15 @@ def edit_blend(x, x0, noise, mask, sigma_to, out: Optional[torch.Tensor] = None,
 
 
 def _edit_step_operands(x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16):
-    """The operands both edit steps share, checked: -> (x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch)."""
+    """_step_operands for the edit steps, x packed tokens [B, N, 64], with their x0, noise0 and mask, checked:
+    -> (x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch)."""
     if x.dim() != 3:
         raise ValueError(f'x: need packed tokens [B, N, 64], got {tuple(x.shape)}')
     B, N, ch = x.shape
-    x = _packed(x, torch.float32, x.shape, 'x')
-    pos = _packed(pos, torch.bfloat16, x.shape, 'pos')
-    neg = None if neg is None else _packed(neg, torch.bfloat16, x.shape, 'neg')
-    sigma = _packed(sigma, torch.float32, (B,), 'sigma')
-    sigma_to = _packed(sigma_to, torch.float32, (B,), 'sigma_to')
-    coef = None if coef is None else _packed(coef, torch.float32, (B,), 'coef')
+    x, pos, neg, sigma, sigma_to, coef, out, out_bf16, _, _ = _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16)
     x0 = _packed(x0, torch.float32, x.shape, 'x0')
     noise0 = None if noise0 is None else _packed(noise0, torch.float32, x.shape, 'noise0')
     mask = None if mask is None else _packed(mask, torch.float32, (B, N, 4), 'mask')
-    out = torch.empty_like(x) if out is None else _packed(out, torch.float32, x.shape, 'out')
-    out_bf16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out_bf16 is None else _packed(out_bf16, torch.bfloat16, x.shape, 'out_bf16')
     return x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch
 
 
@@ -915,9 +873,7 @@ def teacher_sde_edit_step(x, pos, neg, noise, sigma, sigma_to, m, c_noise, x0, n
     _gpu(x, pos, neg, noise, sigma, sigma_to, m, c_noise, coef, x0, noise0, mask, out, out_bf16)
     x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16, B, N, ch = _edit_step_operands(
         x, pos, neg, sigma, sigma_to, coef, x0, noise0, mask, out, out_bf16)
-    noise = None if noise is None else _packed(noise, torch.float32, x.shape, 'noise')
-    m = _packed(m, torch.float32, (B,), 'm')
-    c_noise = _packed(c_noise, torch.float32, (B,), 'c_noise')
+    noise, m, c_noise = _sde_operands(x, noise, m, c_noise)
     _lib.check(lib.afx_teacher_sde_edit_step(_p(x), _p(pos), _p(neg), _p(noise), _p(sigma), _p(sigma_to), _p(m), _p(c_noise), _p(coef), scale,
                                              _p(x0), _p(noise0), _p(mask), _p(out), _p(out_bf16), B, N, ch, max_blocks, _s()))
     return out, out_bf16
