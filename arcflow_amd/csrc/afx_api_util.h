@@ -48,6 +48,31 @@ static int launch_step(void (*kernel)(P...), int32_t batch, int64_t n, int32_t m
   return AFX_OK;
 }
 
+// work-groups of 256 lanes that cover n units of work
+static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Launch of a kernel with one lane per unit of work: n units on blocks_for(n) work-groups of 256; n == 0 launches nothing.
+template <typename... P, typename... A>
+static int launch_flat(void (*kernel)(P...), int64_t n, void* stream, A... args) {
+  if (n == 0) return AFX_OK;
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, args...);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+// ... and of one on a grid the entry lays out itself (a row per wave or per work-group, 2-D tiles), work-groups of 256
+template <typename... P, typename... A>
+static int launch_grid(void (*kernel)(P...), dim3 grid, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args...);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+// The LoRA-dropout constants of a drop probability 0 <= p < 1: an element is kept where its hash (lora_drop_keep, afx_common.h) is at
+// least thresh, and kept elements are scaled by inv_keep
+struct DropConsts { uint32_t thresh; float inv_keep; };
+static inline DropConsts drop_consts(float p) { return {(uint32_t)((double)p * 4294967296.0), 1.0f / (1.0f - p)}; }
+
 // The value of a *_ws_bytes entry: `batch` samples x `parts` slots of K doubles, or the refusal (negative) by the entry's name.
 static inline int64_t ws_bytes_or_fail(const char* name, bool bad, const char* rule, int32_t batch, int64_t parts, int K) {
   if (bad) return (int64_t)fail(AFX_E_INVALID, "bad argument to %s%s", name, rule);

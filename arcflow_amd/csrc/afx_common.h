@@ -125,6 +125,15 @@ AFX_DEV float gelu_tanh(float x) {
 
 AFX_DEV float silu(float x) { return x / (1.0f + __expf(-x)); }
 
+// LoRA input dropout: keep(row, col) is a counter-based hash of (seed, global row, col).  lora_dropout_kernel (afx_train.hip) draws the
+// forward's mask with it and the GEMM's masked residual add (EPI_GATE_RES with DROP, afx_gemm.hip) the backward's: one function, the same bits.
+AFX_DEV uint32_t mix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+AFX_DEV uint32_t lora_drop_row_hash(uint32_t seed, int64_t row) { return mix32(seed ^ (uint32_t)(row * 0x9e3779b1u)); }
+AFX_DEV bool lora_drop_keep(uint32_t hr, int col, uint32_t thresh) { return mix32(hr + (uint32_t)col * 0x85ebca77u) >= thresh; }
+
 // XCD-aware bijective remap of a 1-D grid: block b runs on XCD b%8; give every XCD a contiguous
 // chunk of logical work-group ids so neighbouring tiles share that XCD's L2.
 AFX_DEV int xcd_remap(int bid, int nwg) {

@@ -73,10 +73,6 @@ AFX_DEV __amdgpu_buffer_rsrc_t uniform_rsrc(T* p, int bytes) {
 // PRE: a bf16 [M, N] term (GemmProblem::pre, the LoRA-dropout correction) is added before the activation / gate.
 // CONV: the rows are pixels of a zero-bordered [conv_hp][conv_wp] grid (implicit 3x3 convolution): border pixels are stored as zero.
 constexpr int EPI_GELU_ALL = 3;      // (internal) EPI_GELU with every column of the wave at or past gelu_col0: no per-lane test
-AFX_DEV uint32_t drop_mix32(uint32_t h) {          // (= mix32 of afx_train.hip's lora_dropout_kernel: the masks must be the same bits)
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}) -- the index is a constant expression inside the body
 // (the epilogues name accumulator tiles by it: AccLit below needs the register NUMBER in the instruction text).
 template <class F, int... I>
@@ -362,12 +358,9 @@ AFX_DEV void epi_store_fast_acc(const GemmProblem& P, const ACC& acc, int row_ba
         for (int e = 0; e < CW; ++e) v[e] = gelu_tanh(v[e]);
       } else if constexpr (EPI == EPI_GATE_RES) {
         if constexpr (DROP) {        // the LoRA branch's input gradient: the product is masked (keep / (1 - p) or 0), then added to the residual
-          const uint32_t hr = drop_mix32(P.drop_seed ^ (uint32_t)((P.drop_row0 + row_base + ii * 16 + frow) * 0x9e3779b1u));
+          const uint32_t hr = lora_drop_row_hash(P.drop_seed, P.drop_row0 + row_base + ii * 16 + frow);
 #pragma unroll
-          for (int e = 0; e < CW; ++e) {
-            const bool keep = drop_mix32(hr + (uint32_t)(gcol[st] + e) * 0x85ebca77u) >= P.drop_thresh;
-            v[e] = keep ? v[e] * P.drop_inv_keep : 0.f;
-          }
+          for (int e = 0; e < CW; ++e) v[e] = lora_drop_keep(hr, gcol[st] + e, P.drop_thresh) ? v[e] * P.drop_inv_keep : 0.f;
         }
 #pragma unroll
         for (int e = 0; e < CW; ++e) {

@@ -61,14 +61,6 @@ int attention_fwd(const char* fn, const void* q, int64_t ldq, const void* k, int
   return AFX_OK;
 }
 
-// the mixture arguments the three ArcFlow policy entry points share
-int arcflow_args(const char* fn, bool operands, int32_t mix_dtype, int32_t batch, int32_t n_tok, int32_t K, int32_t ch, int32_t pp) {
-  if (!operands) return fail(AFX_E_INVALID, "null argument to %s", fn);
-  if (mix_dtype != AFX_DT_BF16 && mix_dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "bad mix_dtype");
-  if (batch < 0 || n_tok < 0 || K < 1 || K > 32 || ch < 1 || pp < 1 || ch % pp != 0) return fail(AFX_E_INVALID, "bad shape for %s", fn);
-  return AFX_OK;
-}
-
 // shared argument checks of the two AdaLN entry points
 int norm_joint_args(const char* fn, const void* x, int64_t ldx, int64_t ldo, int32_t rows, int32_t D, const float* scale, const float* shift,
                     const float* scale_txt, const float* shift_txt, int64_t ldmod, int32_t S, int32_t n_txt) {
@@ -139,7 +131,8 @@ int afx_linear_bf16_dropres(const void* A, int64_t lda, const void* W, int64_t l
   if (ldr % 8 || !(p >= 0.f && p < 1.f)) return fail(AFX_E_INVALID, "afx_linear_bf16_dropres: need ldr%%8==0, 0 <= p < 1");
   GemmProblem q = dense_problem(A, lda, W, ldw, nullptr, C, ldc, M, N, K);
   set_epilogue(q, EPI_GATE_RES, 0, nullptr, 0, M > 0 ? M : 1, res, ldr);
-  q.drop_on = 1; q.drop_thresh = (uint32_t)((double)p * 4294967296.0); q.drop_seed = seed; q.drop_inv_keep = 1.0f / (1.0f - p); q.drop_row0 = row0;
+  const DropConsts dc = drop_consts(p);
+  q.drop_on = 1; q.drop_thresh = dc.thresh; q.drop_seed = seed; q.drop_inv_keep = dc.inv_keep; q.drop_row0 = row0;
   HIP_TRY(launch_single(q, (hipStream_t)stream));
   return AFX_OK;
 }
@@ -336,34 +329,6 @@ int afx_gemv_bf16(const float* x, const void* W, const void* bias, float* y, int
   if (!x || !W || !y) return fail(AFX_E_INVALID, "null argument to afx_gemv_bf16");
   if (B < 1 || B > 8 || N < 1 || K < 8 || K % 8) return fail(AFX_E_INVALID, "bad gemv shape (B<=8, K%%8==0)");
   HIP_TRY(launch_gemv(x, (const uint16_t*)W, (const uint16_t*)bias, y, B, N, K, act, accumulate, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-// ---- ArcFlow policy math --------------------------------------------------------------------------
-int afx_arcflow_step(const float* x_in, const void* means, const void* logw, const void* logg, int32_t mix_dtype,
-                     float sigma_src, float sigma_start, float sigma_end, const float* sigma_vec, float eps,
-                     float* x_out, int32_t batch, int32_t n_tok, int32_t K, int32_t ch, int32_t pp, void* stream) {
-  AFX_TRY(arcflow_args("afx_arcflow_step", x_in && means && logw && logg && x_out, mix_dtype, batch, n_tok, K, ch, pp));
-  HIP_TRY(launch_arcflow_step(x_in, means, logw, logg, mix_dtype == AFX_DT_BF16, sigma_src, sigma_start, sigma_end,
-                              sigma_vec, eps, x_out, batch, n_tok, K, ch, pp, 0, nullptr, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_arcflow_step_dropout(const float* x_in, const void* means, const void* logw, const void* logg, int32_t mix_dtype,
-                             const float* sigma_vec, const uint8_t* drop_mask, float eps, float* x_out, int32_t batch,
-                             int32_t n_tok, int32_t K, int32_t ch, int32_t pp, void* stream) {
-  AFX_TRY(arcflow_args("afx_arcflow_step_dropout", x_in && means && logw && logg && x_out && sigma_vec, mix_dtype, batch, n_tok, K, ch, pp));
-  HIP_TRY(launch_arcflow_step(x_in, means, logw, logg, mix_dtype == AFX_DT_BF16, 0.f, 0.f, 0.f, sigma_vec, eps, x_out,
-                              batch, n_tok, K, ch, pp, 0, drop_mask, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_arcflow_velocity(const void* means, const void* logw, const void* logg, int32_t mix_dtype, float sigma_src,
-                         float sigma_t, const float* sigma_vec, float* u_out, int32_t batch, int32_t n_tok,
-                         int32_t K, int32_t ch, int32_t pp, void* stream) {
-  AFX_TRY(arcflow_args("afx_arcflow_velocity", means && logw && logg && u_out, mix_dtype, batch, n_tok, K, ch, pp));
-  HIP_TRY(launch_arcflow_step(u_out, means, logw, logg, mix_dtype == AFX_DT_BF16, sigma_src, sigma_t, sigma_t,
-                              sigma_vec, 1e-4f, u_out, batch, n_tok, K, ch, pp, 1, nullptr, (hipStream_t)stream));
   return AFX_OK;
 }
 

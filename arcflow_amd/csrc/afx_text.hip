@@ -275,13 +275,12 @@ hipError_t launch_quant_rows_fp8(const uint16_t* x, int64_t ldx, uint8_t* q, int
 
 using namespace afx;
 
-static inline unsigned tblocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" {
 
 int afx_embed_rows_bf16(const void* table, const int32_t* ids, const void* pos, void* out, int32_t S, int32_t D, void* stream) {
   if (!table || !ids || !out || S < 1 || D % 8) return fail(AFX_E_INVALID, "bad argument to afx_embed_rows_bf16");
-  hipLaunchKernelGGL(embed_rows_kernel, dim3(tblocks((int64_t)S * (D >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)table,
+  hipLaunchKernelGGL(embed_rows_kernel, dim3(blocks_for((int64_t)S * (D >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)table,
                      ids, (const bf16_t*)pos, (bf16_t*)out, S, D);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -301,7 +300,7 @@ int afx_act_mul_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t
                      void* stream) {
   if (!x || !out || M < 1 || F % 8 || ldx % 8 || ldo % 8 || (gate_off >= 0 && gate_off % 8) || act < 0 || act > 3)
     return fail(AFX_E_INVALID, "bad argument to afx_act_mul_bf16");
-  hipLaunchKernelGGL(act_mul_kernel, dim3(tblocks(M * (F >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
+  hipLaunchKernelGGL(act_mul_kernel, dim3(blocks_for(M * (F >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
                      (bf16_t*)out, ldo, M, F, gate_off, act);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -310,7 +309,7 @@ int afx_act_mul_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t
 int afx_rope_half_bf16(void* x, int64_t ldx, const float* cos_t, const float* sin_t, int32_t S, int32_t H, int32_t head_dim,
                        void* stream) {
   if (!x || !cos_t || !sin_t || S < 1 || H < 1 || head_dim % 16 || ldx % 8) return fail(AFX_E_INVALID, "bad argument to afx_rope_half_bf16");
-  hipLaunchKernelGGL(rope_half_kernel, dim3(tblocks((int64_t)S * H * (head_dim >> 4))), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
+  hipLaunchKernelGGL(rope_half_kernel, dim3(blocks_for((int64_t)S * H * (head_dim >> 4))), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
                      ldx, cos_t, sin_t, S, H, head_dim);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -319,7 +318,7 @@ int afx_rope_half_bf16(void* x, int64_t ldx, const float* cos_t, const float* si
 int afx_finish_f32_bf16(const float* partials, int32_t nslab, const void* res, int64_t ldr, void* out, int64_t ldo, int64_t M, int32_t N,
                         void* stream) {
   if (!partials || !out || M < 1 || N % 8 || nslab < 1 || ldo % 8 || (res && ldr % 8)) return fail(AFX_E_INVALID, "bad argument to afx_finish_f32_bf16");
-  hipLaunchKernelGGL(finish_f32_kernel, dim3(tblocks(M * (N >> 3))), dim3(256), 0, (hipStream_t)stream, partials, nslab, (const bf16_t*)res,
+  hipLaunchKernelGGL(finish_f32_kernel, dim3(blocks_for(M * (N >> 3))), dim3(256), 0, (hipStream_t)stream, partials, nslab, (const bf16_t*)res,
                      ldr, (bf16_t*)out, ldo, M, N);
   HIP_TRY(hipGetLastError());
   return AFX_OK;

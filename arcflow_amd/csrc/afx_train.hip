@@ -1,177 +1,24 @@
-// Kernels of the distillation step that the reference runs as eager torch autograd:
-//   * backward of the analytic ArcFlow transport / policy velocity w.r.t. the mixture parameters
-//     (lakonlab/models/diffusions/arcflow.py:81-110 under autograd; policies/arcflow.py:52-76)
-//   * flow MSE loss + gradient (lakonlab/models/losses/diffusion_loss.py:44-83)
-//   * head / norm_out gradient helpers (log-softmax backward, column reductions, transposes)
-//   * fused AdamW, global grad-norm, clip, Karras-EMA lerp (lakonlab/models/base.py:76-103,
-//     lakonlab/runner/hooks/ema_hook.py:86-124)
+// Kernels of the distillation step that the reference runs as eager torch autograd (the policy's own backward is afx_policy.hip), by role,
+// kernels and C entries in the same order:
+//   1. loss and optimizer: flow MSE loss + gradient (lakonlab/models/losses/diffusion_loss.py:44-83), global grad-norm, fused AdamW
+//      (fp32 and 8-bit moments), Karras-EMA lerp (lakonlab/models/base.py:76-103, lakonlab/runner/hooks/ema_hook.py:86-124), fp32 -> bf16 cast
+//   2. head and modulation gradients: log-softmax backward of the head row, transposes, column reductions, norm_out backward
+//   3. roll-out arithmetic: Euler roll, per-sample blend, CFG combine, forward diffusion into the token layout
+//   4. LoRA input dropout
+//   5. trunk backward: element-wise backward kernels of the MMDiT blocks (arcflow_amd/train/trunk.py)
 // All HBM-bound streaming kernels: 16 B per lane where the layout allows, wave64 shuffle reductions.
 #include <algorithm>
-
-#include "afx_api_util.h"
 #include <map>
 #include <mutex>
 #include <utility>
 
+#include "afx_api_util.h"
 #include "afx_common.h"
 #include "afx_kernels.h"
 
 namespace afx {
 
-// ------------------------------------------------------------------------------------------------
-// d/d(means, logw, logg) of   D[c] = sum_k softmax(logw)_k * m[k,c] * e_k
-//   step mode:      e_0 = Dt,  e_k = exp(g_k Dp) * Dt * phi(g_k Dt)       (D = displacement, x_end = x - D)
-//   velocity mode:  e_0 = 1,   e_k = exp(g_k Dp)                           (D = u)
-// given the upstream gradient gD = gscale[b] * g[c].  One wave per token, lane = packed channel (ch <= 64,
-// pp a power of two dividing 64): the reductions over the channels that share a sub-pixel q = c % pp are
-// xor-shuffles over lane bits >= log2(pp).
-constexpr int TR_MAXK = 32;
-
-template <typename MixT> AFX_DEV float tr_load(const MixT* p, int64_t i);
-template <> AFX_DEV float tr_load<float>(const float* p, int64_t i) { return p[i]; }
-template <> AFX_DEV float tr_load<bf16_t>(const bf16_t* p, int64_t i) { return bf16_to_f32(p[i]); }
-
-// phi'(z) = sum_n z^n / (n! (n + 2)) for |z| < 1.  The closed form (e^z - phi) / z subtracts two numbers near 1 there and loses u * 4 / |z|
-// relative (1e-3 at z = 1e-4, against fp64); from |z| = 1 on nothing cancels and it is kept.  Twelve terms: the first one left out,
-// z^12 / (12! * 14) <= 1.5e-10, is 1e-2 u of the smallest value on the interval, phi'(-1) = 0.26; Horner's own roundings stay below 3 u.
-AFX_DEV float dphi_series(float z) {
-  float p = 1.0f / 518918400.0f;                  // 1 / (11! * 13)
-  p = fmaf(p, z, 1.0f / 43545600.0f);             // 1 / (10! * 12)
-  p = fmaf(p, z, 1.0f / 3991680.0f);              // 1 / (9! * 11)
-  p = fmaf(p, z, 1.0f / 403200.0f);               // 1 / (8! * 10)
-  p = fmaf(p, z, 1.0f / 45360.0f);                // 1 / (7! * 9)
-  p = fmaf(p, z, 1.0f / 5760.0f);                 // 1 / (6! * 8)
-  p = fmaf(p, z, 1.0f / 840.0f);                  // 1 / (5! * 7)
-  p = fmaf(p, z, 1.0f / 144.0f);                  // 1 / (4! * 6)
-  p = fmaf(p, z, 1.0f / 30.0f);                   // 1 / (3! * 5)
-  p = fmaf(p, z, 1.0f / 8.0f);                    // 1 / (2! * 4)
-  p = fmaf(p, z, 1.0f / 3.0f);                    // 1 / (1! * 3)
-  return fmaf(p, z, 0.5f);                        // 1 / (0! * 2)
-}
-
-template <typename MixT>
-__global__ __launch_bounds__(256) void arcflow_bwd_kernel(
-    const float* __restrict__ g, const MixT* __restrict__ means, const MixT* __restrict__ logw,
-    const MixT* __restrict__ logg, float s_src, float s_start, float s_end, const float* __restrict__ sigma_vec,
-    const float* __restrict__ gscale_vec, float gscale, float eps, float* __restrict__ d_means,
-    float* __restrict__ d_logw, float* __restrict__ d_logg, int64_t tokens, int n_tok, int K, int ch, int pp,
-    int velocity_only, int accumulate) {
-  const int lane = threadIdx.x & 63;
-  const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (tok >= tokens) return;
-  const int64_t b = tok / n_tok;
-  if (sigma_vec != nullptr) {
-    s_src = sigma_vec[3 * b];
-    s_start = sigma_vec[3 * b + 1];
-    s_end = sigma_vec[3 * b + 2];
-  }
-  if (gscale_vec != nullptr) gscale *= gscale_vec[b];
-  const float d_past = s_src - s_start;
-  const float d_step = s_start - s_end;
-  const bool active = lane < ch;
-  const int c = active ? lane : 0;
-  const int q = c % pp;
-  const MixT* mt = means + tok * (int64_t)K * ch;
-  const MixT* wt = logw + tok * (int64_t)K * pp;
-  const MixT* gt = logg + tok * (int64_t)(K - 1) * pp;
-  const float gD = active ? gscale * g[tok * ch + c] : 0.f;
-
-  float w[TR_MAXK];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < TR_MAXK; ++k)
-    if (k < K) {
-      w[k] = tr_load<MixT>(wt, k * pp + q);
-      mx = fmaxf(mx, w[k]);
-    }
-  float den = 0.f;
-#pragma unroll
-  for (int k = 0; k < TR_MAXK; ++k)
-    if (k < K) {
-      w[k] = expf(w[k] - mx);
-      den += w[k];
-    }
-  const float inv = 1.0f / den;
-
-  float* dm = d_means + tok * (int64_t)K * ch;
-  float* dw = d_logw + tok * (int64_t)K * pp;
-  float* dg = d_logg + tok * (int64_t)(K - 1) * pp;
-  float a[TR_MAXK];       // a_k = e_k * sum_{c in q} gD_c m_{k,c}
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < TR_MAXK; ++k)
-    if (k < K) {
-      w[k] *= inv;
-      const float m = tr_load<MixT>(mt, (int64_t)k * ch + c);
-      float e, de;
-      if (k == 0) {
-        e = velocity_only ? 1.0f : d_step;
-        de = 0.f;
-      } else {
-        const float gam = tr_load<MixT>(gt, (k - 1) * pp + q);
-        const float dec = expf(gam * d_past);
-        if (velocity_only) {
-          e = dec;
-          de = d_past * dec;
-        } else {
-          const float z = gam * d_step;
-          const bool clamped = fabsf(z) < eps;
-          const float zs = (z < 0.f ? -1.0f : 1.0f) * fmaxf(fabsf(z), eps);
-          const float em1 = expm1f(zs);
-          const float phi = em1 / zs;
-          // phi'(z): 0 inside the clamp, its series below |z| = 1, the closed form above
-          const float dphi = clamped ? 0.f : (fabsf(zs) < 1.0f ? dphi_series(zs) : (em1 + 1.0f - phi) / zs);
-          e = dec * d_step * phi;
-          de = d_past * e + dec * d_step * dphi * d_step;
-        }
-      }
-      // gradient w.r.t. the mean of this lane's channel
-      if (active) {
-        const float v = gD * w[k] * e;
-        dm[(int64_t)k * ch + c] = accumulate ? dm[(int64_t)k * ch + c] + v : v;
-      }
-      // r_k = sum over the channels of sub-pixel q of gD_c m_{k,c}
-      float r = gD * m;
-      for (int o = pp; o < 64; o <<= 1) r += __shfl_xor(r, o, 64);
-      a[k] = e * r;
-      s += w[k] * a[k];
-      if (k > 0 && lane < pp) {
-        const float v = w[k] * de * r;
-        dg[(k - 1) * pp + q] = accumulate ? dg[(k - 1) * pp + q] + v : v;
-      }
-    }
-  if (lane < pp) {
-#pragma unroll
-    for (int k = 0; k < TR_MAXK; ++k)
-      if (k < K) {
-        const float v = w[k] * (a[k] - s);
-        dw[k * pp + q] = accumulate ? dw[k * pp + q] + v : v;
-      }
-  }
-}
-
-hipError_t launch_arcflow_bwd(const float* g, const void* means, const void* logw, const void* logg, int mix_bf16,
-                              float s_src, float s_start, float s_end, const float* sigma_vec,
-                              const float* gscale_vec, float gscale, float eps, float* d_means, float* d_logw,
-                              float* d_logg, int B, int n_tok, int K, int ch, int pp, int velocity_only,
-                              int accumulate, hipStream_t stream) {
-  if (K < 1 || K > TR_MAXK || ch < 1 || ch > 64 || pp < 1 || (pp & (pp - 1)) || 64 % pp || ch % pp)
-    return hipErrorInvalidValue;
-  const int64_t tokens = (int64_t)B * n_tok;
-  if (tokens == 0) return hipSuccess;
-  dim3 grid((unsigned)((tokens + 3) / 4)), block(256);
-  if (mix_bf16)
-    hipLaunchKernelGGL(arcflow_bwd_kernel<bf16_t>, grid, block, 0, stream, g, (const bf16_t*)means, (const bf16_t*)logw,
-                       (const bf16_t*)logg, s_src, s_start, s_end, sigma_vec, gscale_vec, gscale, eps, d_means, d_logw,
-                       d_logg, tokens, n_tok, K, ch, pp, velocity_only, accumulate);
-  else
-    hipLaunchKernelGGL(arcflow_bwd_kernel<float>, grid, block, 0, stream, g, (const float*)means, (const float*)logw,
-                       (const float*)logg, s_src, s_start, s_end, sigma_vec, gscale_vec, gscale, eps, d_means, d_logw,
-                       d_logg, tokens, n_tok, K, ch, pp, velocity_only, accumulate);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
+// ==== 1. loss and optimizer =====================================================================
 // loss += coef * 0.5 * sum (p - t)^2 ;  grad = coef * (p - t)       (coef folds scale / numel / segment size)
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ p, const float* __restrict__ t,
                                                   float coef, float* __restrict__ grad, float* __restrict__ loss,
@@ -289,7 +136,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ x, 
   }
 }
 
-// ------------------------------------------------------------------------------------------------
+// ==== 2. head and modulation gradients ==========================================================
 // Head-logit gradient row:  dY = [ d_means | log_softmax-backward(d_logw) | d_logg | 0-pad ]   (bf16)
 //   d raw[k,q] = d_lw[k,q] - exp(logw_out[k,q]) * sum_k d_lw[k,q]          (arcflux.py:246-247 backward)
 __global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict__ d_means, const float* __restrict__ d_logw,
@@ -532,6 +379,7 @@ __global__ __launch_bounds__(256) void outer_accum_kernel(const float* __restric
   dW[i] += acc;
 }
 
+// ==== 3. roll-out arithmetic ====================================================================
 // x_out = x_a + u * (sb[b] - sa[b])     teacher Euler roll of the scheduled trajectory mixing (arcflow.py:189-192)
 __global__ __launch_bounds__(256) void euler_kernel(const float* __restrict__ xa, const float* __restrict__ u,
                                                     const float* __restrict__ sa, const float* __restrict__ sb,
@@ -611,16 +459,13 @@ __global__ __launch_bounds__(256) void forward_diffuse_pack_kernel(const float* 
   }
 }
 
+// ==== 4. LoRA dropout ===========================================================================
 // LoRA input dropout (peft: y = W x + B A dropout(x); the engine folds B A into W, so what remains is the zero-mean
 // correction B A (x . delta), delta = keep / (1 - p) - 1).  keep(row, col) is a counter-based hash of (seed, global row, col):
 // the batched forward and the per-sample recompute / backward regenerate identical masks from the seed.
 //   mode 0: dst = src . delta      mode 1: dst = src . (1 + delta) = dropout(src)      mode 2: dst += src . delta
 //   mode 3: dst += src . (1 + delta)      (the input gradient of the LoRA branch: dx += ((dy B) A) . keep/(1-p))
-AFX_DEV uint32_t mix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-
+// The hash is lora_drop_row_hash / lora_drop_keep of afx_common.h, shared with the GEMM's masked residual add.
 __global__ __launch_bounds__(256) void lora_dropout_kernel(const bf16_t* __restrict__ src, int64_t lds_, bf16_t* __restrict__ dst, int64_t ldd,
                                                            int64_t M, int N, int64_t row0, uint32_t thresh, float inv_keep, uint32_t seed,
                                                            int mode) {
@@ -632,11 +477,10 @@ __global__ __launch_bounds__(256) void lora_dropout_kernel(const bf16_t* __restr
   float a[8], o[8];
   unpack8(*reinterpret_cast<const u32x4_t*>(src + m * lds_ + c * 8), a);
   if (mode >= 2) unpack8(*reinterpret_cast<const u32x4_t*>(dst + m * ldd + c * 8), o);
-  const uint32_t hr = mix32(seed ^ (uint32_t)((row0 + m) * 0x9e3779b1u));
+  const uint32_t hr = lora_drop_row_hash(seed, row0 + m);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const bool keep = mix32(hr + (uint32_t)(c * 8 + e) * 0x85ebca77u) >= thresh;
-    const float delta = keep ? inv_keep - 1.0f : -1.0f;
+    const float delta = lora_drop_keep(hr, c * 8 + e, thresh) ? inv_keep - 1.0f : -1.0f;
     if (mode == 0) o[e] = a[e] * delta;
     else if (mode == 1) o[e] = a[e] * (1.0f + delta);
     else if (mode == 2) o[e] += a[e] * delta;
@@ -645,272 +489,7 @@ __global__ __launch_bounds__(256) void lora_dropout_kernel(const bf16_t* __restr
   *reinterpret_cast<u32x4_t*>(dst + m * ldd + c * 8) = pack8(o);
 }
 
-}  // namespace afx
-
-using namespace afx;
-
-static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-extern "C" {
-
-int afx_arcflow_backward(const float* g, const void* means, const void* logw, const void* logg, int32_t mix_dtype,
-                         float sigma_src, float sigma_start, float sigma_end, const float* sigma_vec,
-                         const float* gscale_vec, float gscale, float eps, float* d_means, float* d_logw,
-                         float* d_logg, int32_t batch, int32_t n_tok, int32_t K, int32_t ch, int32_t pp,
-                         int32_t velocity_only, int32_t accumulate, void* stream) {
-  if (!g || !means || !logw || !logg || !d_means || !d_logw || !d_logg)
-    return fail(AFX_E_INVALID, "null argument to afx_arcflow_backward");
-  if (mix_dtype != AFX_DT_BF16 && mix_dtype != AFX_DT_F32) return fail(AFX_E_INVALID, "bad mix_dtype");
-  if (batch < 0 || n_tok < 0 || K < 1 || K > 32 || ch < 1 || ch > 64 || pp < 1 || (pp & (pp - 1)) || 64 % pp || ch % pp)
-    return fail(AFX_E_INVALID, "afx_arcflow_backward: need K<=32, ch<=64, pp a power of two dividing ch");
-  HIP_TRY(launch_arcflow_bwd(g, means, logw, logg, mix_dtype == AFX_DT_BF16, sigma_src, sigma_start, sigma_end, sigma_vec,
-                             gscale_vec, gscale, eps, d_means, d_logw, d_logg, batch, n_tok, K, ch, pp, velocity_only,
-                             accumulate, (hipStream_t)stream));
-  return AFX_OK;
-}
-
-int afx_mse_loss(const float* pred, const float* target, float coef, float* grad, float* loss_accum, int64_t n,
-                 void* stream) {
-  if (!pred || !target || !loss_accum || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_mse_loss");
-  if (n == 0) return AFX_OK;
-  const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(mse_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pred, target, coef, grad, loss_accum, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_sumsq(const float* x, float* out_accum, int64_t n, void* stream) {
-  if (!x || !out_accum || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_sumsq");
-  if (n == 0) return AFX_OK;
-  const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out_accum, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int32_t step, float grad_scale, int64_t n, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return fail(AFX_E_INVALID, "bad argument to afx_adamw_step");
-  if (n == 0) return AFX_OK;
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                     lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_adamw8bit_step(float* param, const float* grad, void* state1, void* state2, float* absmax1, float* absmax2,
-                       const float* qmap1, const float* qmap2, float lr, float beta1, float beta2, float eps, float weight_decay,
-                       int32_t step, float grad_scale, int64_t n, void* stream) {
-  if (!param || !grad || !state1 || !state2 || !absmax1 || !absmax2 || !qmap1 || !qmap2 || n < 0 || step < 1)
-    return fail(AFX_E_INVALID, "bad argument to afx_adamw8bit_step");
-  if (n == 0) return AFX_OK;
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw8bit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, (uint8_t*)state1,
-                     (uint8_t*)state2, absmax1, absmax2, qmap1, qmap2, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_ema_lerp(float* ema, const float* net, float beta, int64_t n, void* stream) {
-  if (!ema || !net || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_ema_lerp");
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(ema_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, ema, net, beta, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream) {
-  if (!x || !y || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_cast_f32_bf16");
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(cast_kernel, dim3(blocks_for((n + 1) / 2)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,
-                  int64_t ldy, int64_t rows, int32_t K, int32_t ch, int32_t lw, void* stream) {
-  if (!d_means || !d_logw || !d_logg || !logw_out || !dy || rows < 0 || lw < 1 || lw > 256 ||
-      ldy < (int64_t)K * ch + K * lw + (K - 1) * lw)
-    return fail(AFX_E_INVALID, "bad argument to afx_head_grad");
-  if (rows == 0) return AFX_OK;
-  hipLaunchKernelGGL(head_grad_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, d_means, d_logw, d_logg,
-                     (const bf16_t*)logw_out, (bf16_t*)dy, ldy, K, ch, lw);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_transpose_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t cols, void* stream) {
-  if (!x || !y || rows < 1 || cols < 1) return fail(AFX_E_INVALID, "bad argument to afx_transpose_bf16");
-  hipLaunchKernelGGL(transpose_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, cols);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_colsum_bf16(const void* x, int64_t ldx, float* out_accum, int32_t rows, int32_t cols, void* stream) {
-  if (!x || !out_accum || rows < 1 || cols < 1) return fail(AFX_E_INVALID, "bad argument to afx_colsum_bf16");
-  const int rpb = 256;
-  hipLaunchKernelGGL(colsum_kernel, dim3((cols + 255) / 256, (rows + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, ldx, out_accum, rows, cols, rpb);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_coldot_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, float* out_accum, int32_t rows, int32_t cols, void* stream) {
-  if (!a || !b || !out_accum || rows < 1 || cols < 8 || cols % 8 || lda % 8 || ldb % 8) return fail(AFX_E_INVALID, "bad argument to afx_coldot_bf16");
-  const int rpb = 32;
-  hipLaunchKernelGGL(coldot_kernel, dim3(((cols >> 3) + 255) / 256, (rows + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)a, lda, (const bf16_t*)b, ldb, out_accum, rows, cols, rpb);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_gate_residual_bf16(const void* y, int64_t ldy, const float* gate, const void* res, int64_t ldr, void* out, int64_t ldo,
-                           int64_t rows, int32_t cols, void* stream) {
-  if (!y || !gate || !res || !out || rows < 1 || cols % 8 || ldy % 8 || ldr % 8 || ldo % 8)
-    return fail(AFX_E_INVALID, "bad argument to afx_gate_residual_bf16");
-  hipLaunchKernelGGL(gate_residual_kernel, dim3(blocks_for(rows * (cols >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, ldy,
-                     gate, (const bf16_t*)res, ldr, (bf16_t*)out, ldo, rows, cols);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_gemv_t_bf16(const float* x, int64_t ldx, const void* W, int64_t ldw, float* out_accum, int32_t B, int64_t N, int32_t K,
-                    void* stream) {
-  if (!x || !W || !out_accum || B < 1 || B > 4 || N < 1 || K % 8 || ldw % 8) return fail(AFX_E_INVALID, "afx_gemv_t_bf16: 1 <= B <= 4, K %% 8 == 0");
-  const int rpb = 512;
-  hipLaunchKernelGGL(gemv_t_kernel, dim3(((K >> 3) + 255) / 256, (unsigned)((N + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                     (const bf16_t*)W, ldw, out_accum, B, N, K, rpb);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-static int normout_backward_impl(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale, float* d_shift, int64_t batch_stride, int32_t rows,
-                                 int32_t D, int32_t rows_per_batch, void* stream);
-
-int afx_normout_backward(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* dmod_accum, int32_t rows,
-                         int32_t D, int32_t rows_per_batch, void* stream) {
-  if (!dmod_accum) return fail(AFX_E_INVALID, "bad argument to afx_normout_backward");
-  return normout_backward_impl(x, ldx, dxn, ldd, dmod_accum, dmod_accum + D, 2 * (int64_t)D, rows, D, rows_per_batch, stream);
-}
-
-int afx_normout_backward_split(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale_accum, float* d_shift_accum, int32_t rows,
-                               int32_t D, void* stream) {
-  if (!d_scale_accum || !d_shift_accum) return fail(AFX_E_INVALID, "bad argument to afx_normout_backward_split");
-  return normout_backward_impl(x, ldx, dxn, ldd, d_scale_accum, d_shift_accum, 0, rows, D, rows, stream);
-}
-
-static int normout_backward_impl(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale, float* d_shift, int64_t batch_stride, int32_t rows,
-                                 int32_t D, int32_t rows_per_batch, void* stream) {
-  if (!x || !dxn || rows < 1 || D < 8 || D % 8 || D > 4096 || rows_per_batch < 1 || rows % rows_per_batch)
-    return fail(AFX_E_INVALID, "bad argument to afx_normout_backward");
-  // rows per wave: 8 (a 4608-row call = 576 waves on 256 CUs; the first version's 32 left it with 36 work-groups).  AFX_NORMOUT_RPW overrides.
-  static int rpw_env = -1;
-  if (rpw_env < 0) {
-    const char* e = getenv("AFX_NORMOUT_RPW");
-    rpw_env = e ? atoi(e) : 0;
-  }
-  int rpw = rpw_env > 0 ? rpw_env : 8;
-  while (rows_per_batch % rpw) rpw >>= 1;
-  const int waves = rows / rpw, wpb = rows_per_batch / rpw, nb = rows / rows_per_batch;
-  hipStream_t st = (hipStream_t)stream;
-  // [waves][2][D] fp32 scratch, kept per stream and grown on demand (hipMallocAsync / hipFreeAsync per call cost ~20 us of the 30 us a 512-row
-  // call took); calls on one stream are ordered, so the buffer is free again when the next call's first kernel starts
-  // keyed by (device, stream): the NULL stream and recycled stream handles exist on every device of a process, and a buffer of device 0
-  // must never serve a call on device 1 (ADVICE r03).  The buffers live until the library is unloaded (NormoutScratch's destructor).
-  // Growing one calls hipFree / hipMalloc -- device-synchronising, illegal under stream capture -- so it only happens when a LARGER
-  // shape shows up on that (device, stream); the split reduction below ends in float atomics over 8 splits: d_mod is reproducible to
-  // the rounding of that sum's order, not bit for bit (documented in include/arcflow_hip.h).
-  struct NormoutScratch {
-    std::mutex mu;
-    std::map<std::pair<int, hipStream_t>, std::pair<float*, size_t>> map;
-    ~NormoutScratch() {
-      for (auto& kv : map)
-        if (kv.second.first != nullptr) (void)hipFree(kv.second.first);
-    }
-  };
-  static NormoutScratch ws;
-  int dev_id = 0;
-  HIP_TRY(hipGetDevice(&dev_id));
-  float* part = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(ws.mu);
-    auto& e = ws.map[std::make_pair(dev_id, st)];
-    const size_t need = (size_t)waves * 2 * D * sizeof(float);
-    if (e.second < need) {
-      if (e.first != nullptr) HIP_TRY(hipFree(e.first));          // (synchronises: only when a larger shape shows up)
-      e.first = nullptr; e.second = 0;
-      HIP_TRY(hipMalloc((void**)&e.first, need));
-      e.second = need;
-    }
-    part = e.first;
-  }
-  hipLaunchKernelGGL(normout_bwd_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, (const bf16_t*)x, ldx, (const bf16_t*)dxn, ldd, part, rows, D,
-                     rows_per_batch, rpw);
-  const int splits = wpb >= 64 ? 8 : 1;
-  hipLaunchKernelGGL(normout_reduce_kernel, dim3((2 * D + 255) / 256, nb * splits), dim3(256), 0, st, part, d_scale, d_shift, batch_stride, wpb, 2 * D, splits);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_outer_accum(const float* dmod, const float* x, float* dW_accum, int32_t B, int32_t J, int32_t Kd, void* stream) {
-  if (!dmod || !x || !dW_accum || B < 1 || J < 1 || Kd < 1) return fail(AFX_E_INVALID, "bad argument to afx_outer_accum");
-  hipLaunchKernelGGL(outer_accum_kernel, dim3(blocks_for((int64_t)J * Kd)), dim3(256), 0, (hipStream_t)stream, dmod, x,
-                     dW_accum, B, J, Kd);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_euler_roll(const float* x_a, const float* u, const float* sigma_a, const float* sigma_b, float* out,
-                   int32_t batch, int64_t per_sample, void* stream) {
-  if (!x_a || !u || !sigma_a || !sigma_b || !out || batch < 0 || per_sample < 1) return fail(AFX_E_INVALID, "bad argument to afx_euler_roll");
-  const int64_t n = (int64_t)batch * per_sample;
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(euler_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, x_a, u, sigma_a, sigma_b, out,
-                     per_sample, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_forward_diffuse_pack(const float* x0, const float* noise, const float* sigma, float* xt_f32, void* xt_bf16,
-                             int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-  if (!x0 || !noise || !sigma || !xt_f32 || B < 0 || C * 4 != 64 || H < 2 || W < 2 || (H & 1) || (W & 1))
-    return fail(AFX_E_INVALID, "bad argument to afx_forward_diffuse_pack (need 4 C = 64 channels, even H and W)");
-  if (((uintptr_t)x0 & 7) || ((uintptr_t)noise & 15) || ((uintptr_t)xt_f32 & 15) || ((uintptr_t)xt_bf16 & 15))
-    return fail(AFX_E_INVALID, "afx_forward_diffuse_pack: x0 must be 8-byte aligned, noise / xt_f32 / xt_bf16 16-byte aligned");
-  const int64_t total = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
-  if (total == 0) return AFX_OK;
-  hipLaunchKernelGGL(forward_diffuse_pack_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x0, noise, sigma,
-                     xt_f32, (bf16_t*)xt_bf16, C, H, W, total);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_axpby_rows(const float* a, const float* alpha, const float* b, const float* beta, float* out, int32_t batch,
-                   int64_t per_sample, void* stream) {
-  if (!a || !alpha || !b || !beta || !out || batch < 0 || per_sample < 1) return fail(AFX_E_INVALID, "bad argument to afx_axpby_rows");
-  const int64_t n = (int64_t)batch * per_sample;
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, a, alpha, b, beta, out, per_sample, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_cfg_combine(const float* pos, const float* neg, float scale, float* out, int64_t n, void* stream) {
-  if (!pos || !neg || !out || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_cfg_combine");
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(cfg_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pos, neg, scale, out, n);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-}  // extern "C"
-
-// ====================================================================================================
-// Element-wise backward kernels of the MMDiT trunk (used by arcflow_amd/train/trunk.py)
-namespace afx {
-
+// ==== 5. trunk backward (arcflow_amd/train/trunk.py) ============================================
 // dx = dres + LN-backward(dxn * (1 + scale[b]))   for xn = LN(x) (1 + scale) + shift, LN without affine, eps 1e-6
 //   y = (x - mu) rstd ; g = dxn (1 + scale) ; dx = rstd (g - mean(g) - y mean(g y))
 __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const bf16_t* __restrict__ x, int64_t ldx,
@@ -1103,7 +682,212 @@ __global__ __launch_bounds__(256) void addscale_kernel(const bf16_t* __restrict_
 
 }  // namespace afx
 
+using namespace afx;
+
 extern "C" {
+
+int afx_mse_loss(const float* pred, const float* target, float coef, float* grad, float* loss_accum, int64_t n,
+                 void* stream) {
+  if (!pred || !target || !loss_accum || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_mse_loss");
+  if (n == 0) return AFX_OK;
+  const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(mse_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pred, target, coef, grad, loss_accum, n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_sumsq(const float* x, float* out_accum, int64_t n, void* stream) {
+  if (!x || !out_accum || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_sumsq");
+  if (n == 0) return AFX_OK;
+  const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out_accum, n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int32_t step, float grad_scale, int64_t n, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return fail(AFX_E_INVALID, "bad argument to afx_adamw_step");
+  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  return launch_flat(adamw_kernel, n, stream, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, n);
+}
+
+int afx_adamw8bit_step(float* param, const float* grad, void* state1, void* state2, float* absmax1, float* absmax2,
+                       const float* qmap1, const float* qmap2, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int32_t step, float grad_scale, int64_t n, void* stream) {
+  if (!param || !grad || !state1 || !state2 || !absmax1 || !absmax2 || !qmap1 || !qmap2 || n < 0 || step < 1)
+    return fail(AFX_E_INVALID, "bad argument to afx_adamw8bit_step");
+  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  return launch_flat(adamw8bit_kernel, n, stream, param, grad, (uint8_t*)state1, (uint8_t*)state2, absmax1, absmax2, qmap1, qmap2, lr, beta1,
+                     beta2, eps, weight_decay, bc1, bc2, grad_scale, n);
+}
+
+int afx_ema_lerp(float* ema, const float* net, float beta, int64_t n, void* stream) {
+  if (!ema || !net || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_ema_lerp");
+  return launch_flat(ema_kernel, n, stream, ema, net, beta, n);
+}
+
+int afx_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream) {
+  if (!x || !y || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_cast_f32_bf16");
+  if (n == 0) return AFX_OK;
+  hipLaunchKernelGGL(cast_kernel, dim3(blocks_for((n + 1) / 2)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,
+                  int64_t ldy, int64_t rows, int32_t K, int32_t ch, int32_t lw, void* stream) {
+  if (!d_means || !d_logw || !d_logg || !logw_out || !dy || rows < 0 || lw < 1 || lw > 256 ||
+      ldy < (int64_t)K * ch + K * lw + (K - 1) * lw)
+    return fail(AFX_E_INVALID, "bad argument to afx_head_grad");
+  if (rows == 0) return AFX_OK;
+  return launch_grid(head_grad_kernel, dim3((unsigned)rows), stream, d_means, d_logw, d_logg, (const bf16_t*)logw_out, (bf16_t*)dy, ldy, K, ch, lw);
+}
+
+int afx_transpose_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t cols, void* stream) {
+  if (!x || !y || rows < 1 || cols < 1) return fail(AFX_E_INVALID, "bad argument to afx_transpose_bf16");
+  return launch_grid(transpose_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, cols);
+}
+
+int afx_colsum_bf16(const void* x, int64_t ldx, float* out_accum, int32_t rows, int32_t cols, void* stream) {
+  if (!x || !out_accum || rows < 1 || cols < 1) return fail(AFX_E_INVALID, "bad argument to afx_colsum_bf16");
+  const int rpb = 256;
+  return launch_grid(colsum_kernel, dim3((cols + 255) / 256, (rows + rpb - 1) / rpb), stream, (const bf16_t*)x, ldx, out_accum, rows, cols, rpb);
+}
+
+int afx_coldot_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, float* out_accum, int32_t rows, int32_t cols, void* stream) {
+  if (!a || !b || !out_accum || rows < 1 || cols < 8 || cols % 8 || lda % 8 || ldb % 8) return fail(AFX_E_INVALID, "bad argument to afx_coldot_bf16");
+  const int rpb = 32;
+  return launch_grid(coldot_kernel, dim3(((cols >> 3) + 255) / 256, (rows + rpb - 1) / rpb), stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                     out_accum, rows, cols, rpb);
+}
+
+int afx_gate_residual_bf16(const void* y, int64_t ldy, const float* gate, const void* res, int64_t ldr, void* out, int64_t ldo,
+                           int64_t rows, int32_t cols, void* stream) {
+  if (!y || !gate || !res || !out || rows < 1 || cols % 8 || ldy % 8 || ldr % 8 || ldo % 8)
+    return fail(AFX_E_INVALID, "bad argument to afx_gate_residual_bf16");
+  return launch_flat(gate_residual_kernel, rows * (cols >> 3), stream, (const bf16_t*)y, ldy, gate, (const bf16_t*)res, ldr, (bf16_t*)out, ldo,
+                     rows, cols);
+}
+
+int afx_gemv_t_bf16(const float* x, int64_t ldx, const void* W, int64_t ldw, float* out_accum, int32_t B, int64_t N, int32_t K,
+                    void* stream) {
+  if (!x || !W || !out_accum || B < 1 || B > 4 || N < 1 || K % 8 || ldw % 8) return fail(AFX_E_INVALID, "afx_gemv_t_bf16: 1 <= B <= 4, K %% 8 == 0");
+  const int rpb = 512;
+  return launch_grid(gemv_t_kernel, dim3(((K >> 3) + 255) / 256, (unsigned)((N + rpb - 1) / rpb)), stream, x, ldx, (const bf16_t*)W, ldw, out_accum,
+                     B, N, K, rpb);
+}
+
+static int normout_backward_impl(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale, float* d_shift, int64_t batch_stride, int32_t rows,
+                                 int32_t D, int32_t rows_per_batch, void* stream);
+
+int afx_normout_backward(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* dmod_accum, int32_t rows,
+                         int32_t D, int32_t rows_per_batch, void* stream) {
+  if (!dmod_accum) return fail(AFX_E_INVALID, "bad argument to afx_normout_backward");
+  return normout_backward_impl(x, ldx, dxn, ldd, dmod_accum, dmod_accum + D, 2 * (int64_t)D, rows, D, rows_per_batch, stream);
+}
+
+int afx_normout_backward_split(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale_accum, float* d_shift_accum, int32_t rows,
+                               int32_t D, void* stream) {
+  if (!d_scale_accum || !d_shift_accum) return fail(AFX_E_INVALID, "bad argument to afx_normout_backward_split");
+  return normout_backward_impl(x, ldx, dxn, ldd, d_scale_accum, d_shift_accum, 0, rows, D, rows, stream);
+}
+
+static int normout_backward_impl(const void* x, int64_t ldx, const void* dxn, int64_t ldd, float* d_scale, float* d_shift, int64_t batch_stride, int32_t rows,
+                                 int32_t D, int32_t rows_per_batch, void* stream) {
+  if (!x || !dxn || rows < 1 || D < 8 || D % 8 || D > 4096 || rows_per_batch < 1 || rows % rows_per_batch)
+    return fail(AFX_E_INVALID, "bad argument to afx_normout_backward");
+  // rows per wave: 8 (a 4608-row call = 576 waves on 256 CUs; the first version's 32 left it with 36 work-groups).  AFX_NORMOUT_RPW overrides.
+  static int rpw_env = -1;
+  if (rpw_env < 0) {
+    const char* e = getenv("AFX_NORMOUT_RPW");
+    rpw_env = e ? atoi(e) : 0;
+  }
+  int rpw = rpw_env > 0 ? rpw_env : 8;
+  while (rows_per_batch % rpw) rpw >>= 1;
+  const int waves = rows / rpw, wpb = rows_per_batch / rpw, nb = rows / rows_per_batch;
+  hipStream_t st = (hipStream_t)stream;
+  // [waves][2][D] fp32 scratch, kept per stream and grown on demand (hipMallocAsync / hipFreeAsync per call cost ~20 us of the 30 us a 512-row
+  // call took); calls on one stream are ordered, so the buffer is free again when the next call's first kernel starts
+  // keyed by (device, stream): the NULL stream and recycled stream handles exist on every device of a process, and a buffer of device 0
+  // must never serve a call on device 1 (ADVICE r03).  The buffers live until the library is unloaded (NormoutScratch's destructor).
+  // Growing one calls hipFree / hipMalloc -- device-synchronising, illegal under stream capture -- so it only happens when a LARGER
+  // shape shows up on that (device, stream); the split reduction below ends in float atomics over 8 splits: d_mod is reproducible to
+  // the rounding of that sum's order, not bit for bit (documented in include/arcflow_hip.h).
+  struct NormoutScratch {
+    std::mutex mu;
+    std::map<std::pair<int, hipStream_t>, std::pair<float*, size_t>> map;
+    ~NormoutScratch() {
+      for (auto& kv : map)
+        if (kv.second.first != nullptr) (void)hipFree(kv.second.first);
+    }
+  };
+  static NormoutScratch ws;
+  int dev_id = 0;
+  HIP_TRY(hipGetDevice(&dev_id));
+  float* part = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(ws.mu);
+    auto& e = ws.map[std::make_pair(dev_id, st)];
+    const size_t need = (size_t)waves * 2 * D * sizeof(float);
+    if (e.second < need) {
+      if (e.first != nullptr) HIP_TRY(hipFree(e.first));          // (synchronises: only when a larger shape shows up)
+      e.first = nullptr; e.second = 0;
+      HIP_TRY(hipMalloc((void**)&e.first, need));
+      e.second = need;
+    }
+    part = e.first;
+  }
+  hipLaunchKernelGGL(normout_bwd_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, (const bf16_t*)x, ldx, (const bf16_t*)dxn, ldd, part, rows, D,
+                     rows_per_batch, rpw);
+  const int splits = wpb >= 64 ? 8 : 1;
+  hipLaunchKernelGGL(normout_reduce_kernel, dim3((2 * D + 255) / 256, nb * splits), dim3(256), 0, st, part, d_scale, d_shift, batch_stride, wpb, 2 * D, splits);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_outer_accum(const float* dmod, const float* x, float* dW_accum, int32_t B, int32_t J, int32_t Kd, void* stream) {
+  if (!dmod || !x || !dW_accum || B < 1 || J < 1 || Kd < 1) return fail(AFX_E_INVALID, "bad argument to afx_outer_accum");
+  return launch_flat(outer_accum_kernel, (int64_t)J * Kd, stream, dmod, x, dW_accum, B, J, Kd);
+}
+
+int afx_euler_roll(const float* x_a, const float* u, const float* sigma_a, const float* sigma_b, float* out,
+                   int32_t batch, int64_t per_sample, void* stream) {
+  if (!x_a || !u || !sigma_a || !sigma_b || !out || batch < 0 || per_sample < 1) return fail(AFX_E_INVALID, "bad argument to afx_euler_roll");
+  const int64_t n = (int64_t)batch * per_sample;
+  return launch_flat(euler_kernel, n, stream, x_a, u, sigma_a, sigma_b, out, per_sample, n);
+}
+
+int afx_axpby_rows(const float* a, const float* alpha, const float* b, const float* beta, float* out, int32_t batch,
+                   int64_t per_sample, void* stream) {
+  if (!a || !alpha || !b || !beta || !out || batch < 0 || per_sample < 1) return fail(AFX_E_INVALID, "bad argument to afx_axpby_rows");
+  const int64_t n = (int64_t)batch * per_sample;
+  return launch_flat(axpby_kernel, n, stream, a, alpha, b, beta, out, per_sample, n);
+}
+
+int afx_cfg_combine(const float* pos, const float* neg, float scale, float* out, int64_t n, void* stream) {
+  if (!pos || !neg || !out || n < 0) return fail(AFX_E_INVALID, "bad argument to afx_cfg_combine");
+  return launch_flat(cfg_kernel, n, stream, pos, neg, scale, out, n);
+}
+
+int afx_forward_diffuse_pack(const float* x0, const float* noise, const float* sigma, float* xt_f32, void* xt_bf16,
+                             int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+  if (!x0 || !noise || !sigma || !xt_f32 || B < 0 || C * 4 != 64 || H < 2 || W < 2 || (H & 1) || (W & 1))
+    return fail(AFX_E_INVALID, "bad argument to afx_forward_diffuse_pack (need 4 C = 64 channels, even H and W)");
+  if (((uintptr_t)x0 & 7) || ((uintptr_t)noise & 15) || ((uintptr_t)xt_f32 & 15) || ((uintptr_t)xt_bf16 & 15))
+    return fail(AFX_E_INVALID, "afx_forward_diffuse_pack: x0 must be 8-byte aligned, noise / xt_f32 / xt_bf16 16-byte aligned");
+  const int64_t total = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
+  return launch_flat(forward_diffuse_pack_kernel, total, stream, x0, noise, sigma, xt_f32, (bf16_t*)xt_bf16, C, H, W, total);
+}
+
+int afx_lora_dropout_bf16(const void* src, int64_t lds_, void* dst, int64_t ldd, int64_t M, int32_t N, int64_t row0, float p,
+                          uint32_t seed, int32_t mode, void* stream) {
+  if (!src || !dst || M < 1 || N % 8 || lds_ % 8 || ldd % 8 || !(p >= 0.f && p < 1.f) || mode < 0 || mode > 3)
+    return fail(AFX_E_INVALID, "bad argument to afx_lora_dropout_bf16");
+  const DropConsts dc = drop_consts(p);
+  return launch_flat(lora_dropout_kernel, M * (N >> 3), stream, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd, M, N, row0, dc.thresh, dc.inv_keep, seed,
+                     mode);
+}
 
 int afx_ln_modulate_backward(const void* x, int64_t ldx, const void* dxn, int64_t ldd, const float* scale, int64_t ldmod,
                              int32_t rows_per_batch, const void* dres, int64_t ldr, void* dx, int64_t ldo, int32_t rows,
@@ -1111,10 +895,8 @@ int afx_ln_modulate_backward(const void* x, int64_t ldx, const void* dxn, int64_
   if (!x || !dxn || !scale || !dx || rows < 0 || D < 8 || D % 8 || D > 4096 || rows_per_batch < 1)
     return fail(AFX_E_INVALID, "bad argument to afx_ln_modulate_backward");
   if (rows == 0) return AFX_OK;
-  hipLaunchKernelGGL(ln_mod_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
-                     (const bf16_t*)dxn, ldd, scale, ldmod, rows_per_batch, (const bf16_t*)dres, ldr, (bf16_t*)dx, ldo, rows, D);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
+  return launch_grid(ln_mod_bwd_kernel, dim3((rows + 3) / 4), stream, (const bf16_t*)x, ldx, (const bf16_t*)dxn, ldd, scale, ldmod, rows_per_batch,
+                     (const bf16_t*)dres, ldr, (bf16_t*)dx, ldo, rows, D);
 }
 
 int afx_qk_norm_rope_oop_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, const void* dy, int64_t lddy,
@@ -1124,45 +906,22 @@ int afx_qk_norm_rope_oop_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, 
     return fail(AFX_E_INVALID, "null argument to afx_qk_norm_rope_oop_bf16");
   const int64_t total = (int64_t)batch * S * heads * 16;
   if (total <= 0) return fail(AFX_E_INVALID, "bad qk_norm_rope shape");
-  hipLaunchKernelGGL(qk_norm_rope_oop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)dy, lddy, w_txt, w_img, rope_cos, rope_sin, S,
-                     n_txt, heads, total, backward);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
+  return launch_flat(qk_norm_rope_oop_kernel, total, stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)dy, lddy, w_txt, w_img, rope_cos,
+                     rope_sin, S, n_txt, heads, total, backward);
 }
 
 int afx_gelu_bf16(const void* pre, int64_t ldp, const void* dh, int64_t ldh, void* out, int64_t ldo, int64_t rows,
                   int32_t cols, void* stream) {
   if (!pre || !out || rows < 0 || cols < 8 || cols % 8) return fail(AFX_E_INVALID, "bad argument to afx_gelu_bf16");
-  const int64_t n = rows * (cols >> 3);
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(gelu_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pre, ldp,
-                     (const bf16_t*)dh, ldh, (bf16_t*)out, ldo, rows, cols);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
+  return launch_flat(gelu_kernel, rows * (cols >> 3), stream, (const bf16_t*)pre, ldp, (const bf16_t*)dh, ldh, (bf16_t*)out, ldo, rows, cols);
 }
 
 int afx_add_scale_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, const float* gate, int64_t ldg,
                        int32_t rows_per_batch, void* out, int64_t ldo, int64_t rows, int32_t cols, void* stream) {
   if (!a || !out || rows < 0 || cols < 8 || cols % 8 || (gate && rows_per_batch < 1))
     return fail(AFX_E_INVALID, "bad argument to afx_add_scale_bf16");
-  const int64_t n = rows * (cols >> 3);
-  if (n == 0) return AFX_OK;
-  hipLaunchKernelGGL(addscale_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda,
-                     (const bf16_t*)b, ldb, gate, ldg, rows_per_batch > 0 ? rows_per_batch : 1, (bf16_t*)out, ldo, rows, cols);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
-}
-
-int afx_lora_dropout_bf16(const void* src, int64_t lds_, void* dst, int64_t ldd, int64_t M, int32_t N, int64_t row0, float p,
-                          uint32_t seed, int32_t mode, void* stream) {
-  if (!src || !dst || M < 1 || N % 8 || lds_ % 8 || ldd % 8 || !(p >= 0.f && p < 1.f) || mode < 0 || mode > 3)
-    return fail(AFX_E_INVALID, "bad argument to afx_lora_dropout_bf16");
-  const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);
-  hipLaunchKernelGGL(lora_dropout_kernel, dim3((unsigned)((M * (N >> 3) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src,
-                     lds_, (bf16_t*)dst, ldd, M, N, row0, thresh, 1.0f / (1.0f - p), seed, mode);
-  HIP_TRY(hipGetLastError());
-  return AFX_OK;
+  return launch_flat(addscale_kernel, rows * (cols >> 3), stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, gate, ldg,
+                     rows_per_batch > 0 ? rows_per_batch : 1, (bf16_t*)out, ldo, rows, cols);
 }
 
 }  // extern "C"

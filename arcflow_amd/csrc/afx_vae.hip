@@ -427,7 +427,6 @@ __global__ __launch_bounds__(256) void posterior_kernel(const bf16_t* __restrict
 
 using namespace afx;
 
-static inline unsigned vblocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" {
 
@@ -494,7 +493,7 @@ int afx_conv3x3s2_bf16(const void* x, const void* w, const void* bias, void* y, 
   if (!x || !w || !y || !ws || H < 2 || W < 2 || (H & 1) || (W & 1) || Cin < 64 || Cin % 64 || Cout < 8 || Cout % 8)
     return fail(AFX_E_INVALID, "afx_conv3x3s2_bf16: need even H, W >= 2, Cin %% 64 == 0, Cout %% 8 == 0 and a workspace grid");
   if ((int64_t)(H / 2 + 2) * (W / 2 + 2) * 4 * Cin * 2 >= (1ll << 31)) return fail(AFX_E_INVALID, "afx_conv3x3s2_bf16: workspace grid >= 2 GiB");
-  hipLaunchKernelGGL(space_to_depth_kernel, dim3(vblocks((int64_t)(H / 2 + 2) * (W / 2 + 2) * 4 * (Cin >> 3))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(space_to_depth_kernel, dim3(blocks_for((int64_t)(H / 2 + 2) * (W / 2 + 2) * 4 * (Cin >> 3))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (bf16_t*)ws, H, W, Cin);
   HIP_TRY(hipGetLastError());
   return conv3x3_impl(ws, w, bias, y, H / 2, W / 2, 4 * Cin, Cout, nullptr, gn_stats, groups, stream);
@@ -502,7 +501,7 @@ int afx_conv3x3s2_bf16(const void* x, const void* w, const void* bias, void* y, 
 
 int afx_image_to_cols27(const void* img, int32_t img_bf16, void* y, int32_t H, int32_t W, int32_t from01, void* stream) {
   if (!img || !y || H < 1 || W < 1 || (int64_t)(H + 2) * (W + 2) * 64 * 2 >= (1ll << 31)) return fail(AFX_E_INVALID, "bad argument to afx_image_to_cols27");
-  const dim3 grid(vblocks((int64_t)(H + 2) * (W + 2) * 8)), blk(256);
+  const dim3 grid(blocks_for((int64_t)(H + 2) * (W + 2) * 8)), blk(256);
   if (img_bf16) hipLaunchKernelGGL(image_to_cols27_kernel<bf16_t>, grid, blk, 0, (hipStream_t)stream, (const bf16_t*)img, (bf16_t*)y, H, W, from01);
   else hipLaunchKernelGGL(image_to_cols27_kernel<float>, grid, blk, 0, (hipStream_t)stream, (const float*)img, (bf16_t*)y, H, W, from01);
   HIP_TRY(hipGetLastError());
@@ -514,7 +513,7 @@ int afx_posterior_latents(const void* grid, int32_t Cpad, int32_t h, int32_t w, 
   if (!grid || !sub || !fac || !out || !moments || Cpad < 32 || h < 1 || w < 1 || (A == nullptr) != (b == nullptr) || (packed && ((h & 1) || (w & 1))) ||
       (int64_t)h * w * 32 >= (1ll << 31))
     return fail(AFX_E_INVALID, "afx_posterior_latents: need Cpad >= 32, A and b together, even h, w for the packed layout");
-  hipLaunchKernelGGL(posterior_kernel, dim3(vblocks((int64_t)16 * h * w)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)grid, Cpad, h, w, A, b, eps,
+  hipLaunchKernelGGL(posterior_kernel, dim3(blocks_for((int64_t)16 * h * w)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)grid, Cpad, h, w, A, b, eps,
                      sub, fac, divide, out, packed, moments);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -567,7 +566,7 @@ int afx_groupnorm_nhwc_from_stats(const void* x, void* y, const double* gn_stats
 
 int afx_upsample2x_nhwc(const void* x, void* y, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y || C % 8) return fail(AFX_E_INVALID, "bad argument to afx_upsample2x_nhwc");
-  hipLaunchKernelGGL(upsample2x_kernel, dim3(vblocks((int64_t)(2 * H + 2) * (2 * W + 2) * (C >> 3))), dim3(256), 0,
+  hipLaunchKernelGGL(upsample2x_kernel, dim3(blocks_for((int64_t)(2 * H + 2) * (2 * W + 2) * (C >> 3))), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, H, W, C);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -576,7 +575,7 @@ int afx_upsample2x_nhwc(const void* x, void* y, int32_t H, int32_t W, int32_t C,
 int afx_interior_nhwc(void* padded, void* compact, const void* res_padded, int32_t H, int32_t W, int32_t C, int32_t scatter,
                       void* stream) {
   if (!padded || !compact || C % 8) return fail(AFX_E_INVALID, "bad argument to afx_interior_nhwc");
-  hipLaunchKernelGGL(interior_kernel, dim3(vblocks((int64_t)H * W * (C >> 3))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(interior_kernel, dim3(blocks_for((int64_t)H * W * (C >> 3))), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)padded, (bf16_t*)compact, (const bf16_t*)res_padded, H, W, C, scatter);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -597,7 +596,7 @@ int afx_latent_to_nhwc(const float* tokens, void* y, int32_t hp, int32_t wp, int
                        float shift_factor, void* stream) {
   if (!tokens || !y || Cpad < 16 || Cpad % 8) return fail(AFX_E_INVALID, "bad argument to afx_latent_to_nhwc");
   const int64_t total = (int64_t)(2 * hp + 2) * (2 * wp + 2) * Cpad;
-  hipLaunchKernelGGL(latent_to_nhwc_kernel, dim3(vblocks(total)), dim3(256), 0, (hipStream_t)stream, tokens, (bf16_t*)y, hp, wp,
+  hipLaunchKernelGGL(latent_to_nhwc_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, tokens, (bf16_t*)y, hp, wp,
                      Cpad, 1.0f / scaling_factor, shift_factor);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -607,7 +606,7 @@ int afx_latent_to_nhwc_affine(const float* tokens, void* y, int32_t hp, int32_t 
                               void* stream) {
   if (!tokens || !y || !A || !b || Cpad < 16 || Cpad % 8) return fail(AFX_E_INVALID, "bad argument to afx_latent_to_nhwc_affine");
   const int64_t total = (int64_t)(2 * hp + 2) * (2 * wp + 2) * Cpad;
-  hipLaunchKernelGGL(latent_to_nhwc_affine_kernel, dim3(vblocks(total)), dim3(256), 0, (hipStream_t)stream, tokens, (bf16_t*)y, hp,
+  hipLaunchKernelGGL(latent_to_nhwc_affine_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, tokens, (bf16_t*)y, hp,
                      wp, Cpad, A, b);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
@@ -634,7 +633,7 @@ int afx_rmsnorm_nhwc(const void* x, void* y, int64_t rows, int32_t Cpad, int32_t
 
 int afx_nhwc_to_image(const void* x, float* img, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !img || C < 3) return fail(AFX_E_INVALID, "bad argument to afx_nhwc_to_image");
-  hipLaunchKernelGGL(nhwc_to_image_kernel, dim3(vblocks((int64_t)3 * H * W)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(nhwc_to_image_kernel, dim3(blocks_for((int64_t)3 * H * W)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, img, H, W, C);
   HIP_TRY(hipGetLastError());
   return AFX_OK;

@@ -321,21 +321,28 @@ def _mix_dtype(means, logw, logg) -> Tuple[int, torch.Tensor, torch.Tensor, torc
     return _lib.AFX_DT_F32, means.float().contiguous(), logw.float().contiguous(), logg.float().contiguous()
 
 
+def _sigma_vec(B, device, *sig):
+    cols = [torch.as_tensor(x, dtype=torch.float32, device=device).flatten().expand(B) for x in sig]
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def _mix_operands(means, logw, logg):
+    """(B, N, K, ch, pp), the mixture's dtype code and its three tensors, contiguous in that dtype"""
+    return (*means.shape, logw.shape[-1]), *_mix_dtype(means, logw, logg)
+
+
 def arcflow_step(x: torch.Tensor, means: torch.Tensor, logw: torch.Tensor, logg: torch.Tensor, sigma_src, sigma_start,
                  sigma_end, eps: float = 1e-4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Analytic ArcFlow transport in the token layout: x [B,N,ch] f32, means [B,N,K,ch], logw [B,N,K,pp],
     logg [B,N,K-1,pp]  ->  x_end [B,N,ch] f32.  sigmas: python floats, or [B] tensors (per-sample)."""
     lib = _lib.load()
-    B, N, K, ch = means.shape
-    pp = logw.shape[-1]
+    (B, N, K, ch, pp), dt, means, logw, logg = _mix_operands(means, logw, logg)
     x = _cuda(x, torch.float32)
-    dt, means, logw, logg = _mix_dtype(means, logw, logg)
     if out is None:
         out = torch.empty_like(x)
     sv = None
     if any(isinstance(s, torch.Tensor) and s.numel() > 1 for s in (sigma_src, sigma_start, sigma_end)):
-        cols = [torch.as_tensor(s, dtype=torch.float32, device=x.device).flatten().expand(B) for s in (sigma_src, sigma_start, sigma_end)]
-        sv = torch.stack(cols, dim=1).contiguous()
+        sv = _sigma_vec(B, x.device, sigma_src, sigma_start, sigma_end)
         s0 = s1 = s2 = 0.0
     else:
         s0, s1, s2 = (float(s) for s in (sigma_src, sigma_start, sigma_end))
@@ -347,14 +354,11 @@ def arcflow_step(x: torch.Tensor, means: torch.Tensor, logw: torch.Tensor, logg:
 def arcflow_velocity(means: torch.Tensor, logw: torch.Tensor, logg: torch.Tensor, sigma_src, sigma_t) -> torch.Tensor:
     """u(sigma_t) of the momentum mixture, token layout -> [B,N,ch] f32."""
     lib = _lib.load()
-    B, N, K, ch = means.shape
-    pp = logw.shape[-1]
-    dt, means, logw, logg = _mix_dtype(means, logw, logg)
+    (B, N, K, ch, pp), dt, means, logw, logg = _mix_operands(means, logw, logg)
     out = torch.empty(B, N, ch, dtype=torch.float32, device=means.device)
     sv = None
     if any(isinstance(s, torch.Tensor) and s.numel() > 1 for s in (sigma_src, sigma_t)):
-        cols = [torch.as_tensor(s, dtype=torch.float32, device=out.device).flatten().expand(B) for s in (sigma_src, sigma_t, sigma_t)]
-        sv = torch.stack(cols, dim=1).contiguous()
+        sv = _sigma_vec(B, out.device, sigma_src, sigma_t, sigma_t)
         s0 = s1 = 0.0
     else:
         s0, s1 = float(sigma_src), float(sigma_t)
@@ -364,18 +368,11 @@ def arcflow_velocity(means: torch.Tensor, logw: torch.Tensor, logg: torch.Tensor
 
 # ---------------------------------------------------------------------------------------------------
 # distillation-step kernels
-def _sigma_vec(B, device, *sig):
-    cols = [torch.as_tensor(x, dtype=torch.float32, device=device).flatten().expand(B) for x in sig]
-    return torch.stack(cols, dim=1).contiguous()
-
-
 def arcflow_step_dropout(x, means, logw, logg, sigma_src, sigma_start, sigma_end, drop_mask=None, eps: float = 1e-4):
     """Roll-out step of the detached policy with per-sample sigmas and GM dropout mask [B,K] (bool/uint8)."""
     lib = _lib.load()
-    B, N, K, ch = means.shape
-    pp = logw.shape[-1]
+    (B, N, K, ch, pp), dt, means, logw, logg = _mix_operands(means, logw, logg)
     x = _cuda(x, torch.float32)
-    dt, means, logw, logg = _mix_dtype(means, logw, logg)
     sv = _sigma_vec(B, x.device, sigma_src, sigma_start, sigma_end)
     dm = None if drop_mask is None else drop_mask.to(device=x.device, dtype=torch.uint8).reshape(B, K).contiguous()
     out = torch.empty_like(x)
@@ -389,10 +386,8 @@ def arcflow_backward(g, means, logw, logg, sigma_src, sigma_start, sigma_end, gs
     """Gradients of the displacement (or velocity) w.r.t. the mixture.  g [B,N,ch] upstream gradient, gscale [B]
     optional per-sample factor.  grads = (d_means, d_logw, d_logg) fp32 to accumulate into, else fresh tensors."""
     lib = _lib.load()
-    B, N, K, ch = means.shape
-    pp = logw.shape[-1]
+    (B, N, K, ch, pp), dt, means, logw, logg = _mix_operands(means, logw, logg)
     g = _cuda(g, torch.float32)
-    dt, means, logw, logg = _mix_dtype(means, logw, logg)
     sv = _sigma_vec(B, g.device, sigma_src, sigma_start, sigma_end)
     gs = None if gscale is None else _cuda(torch.as_tensor(gscale, device=g.device).flatten().expand(B), torch.float32)
     acc = grads is not None

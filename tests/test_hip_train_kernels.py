@@ -387,6 +387,23 @@ def test_linear_dropres_matches_product_then_masked_add(ops, M, N, K, p):
     assert _lib.load().afx_gemm_dropres_available() == 1
 
 
+def test_linear_dropres_and_lora_dropout_draw_the_same_mask_across_the_row_wrap(ops):
+    """The GEMM's masked residual add and lora_dropout_kernel hash (seed, row0 + row, col) with one function: the elements linear_dropres leaves equal to
+    the residual are exactly the ones lora_dropout(mode=1) zeroes -- two index sets, no tolerance -- with row0 = 2^31 - 3, so that the global row
+    passes 2^31 inside the matrix (the row hash keeps the low 32 bits of a 64-bit product).  Every product is >= 64 * 0.25 = 16 against residuals
+    of order 1: no product is an exact zero and no kept sum rounds back to its residual."""
+    M, N, K, p, seed, row0 = 256, 256, 64, 0.25, 0x1234567, 2 ** 31 - 3
+    g = torch.Generator(device='cuda').manual_seed(7)
+    a = (torch.rand(M, K, generator=g, device='cuda') + 0.5).bfloat16()
+    w = (torch.rand(N, K, generator=g, device='cuda') + 0.5).bfloat16()
+    res = torch.randn(M, N, generator=g, device='cuda').bfloat16()
+    new = res.clone()
+    ops.linear_dropres(a, w, new, p, seed, row0, out=new)
+    dropped = ops.lora_dropout(torch.ones(M, N, device='cuda', dtype=torch.bfloat16), p, seed, row0, mode=1) == 0
+    assert torch.equal(new == res, dropped)
+    assert abs(float(dropped.float().mean()) - p) < 0.01
+
+
 # ------------------------------------------------------------------------------------------ full-width parity against fp64
 # The distillation backward at the production shapes (D = 3072, H = 24, MLP 12288; 4608 = 4096 + 512 FLUX rows, 4224 = 4096 + 128 Qwen rows,
 # and a ragged 4133), against a plain fp64 torch reference built from the same bf16 / fp32 inputs.  How tight each check is:
