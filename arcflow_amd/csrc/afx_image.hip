@@ -12,6 +12,11 @@
 //   Both accumulate in fp32 by fma in tap order.  Every source index is clamped into [0, n_in - 1] and count is capped at taps before
 //   any load: a bad table gives wrong pixels, never a read outside the source.
 //   Traffic for a 4000 x 3000 x 3 uint8 photo -> 1024 x 1024: 36 MB read, 36.9 MB of ws written and read again, 12.6 MB written = 122 MB.
+// The way back, for an edit that ran on a window of a larger photo (afx_mask_bbox finds the window, afx_image_paste returns the edit):
+//   * mask_bbox_kernel: the half-open bounding box of the mask's pixels > 0 per image, by integer min / max atomics.
+//   * afx_image_paste: resample_h_kernel<false, 1> on the decoded image (and the mask), then paste_kernel: per pixel of the uint8 photo the
+//     vertical taps, p = 0.5 v + 0.5, the blend m p + (1 - m) byte / 255 and the rounding to a byte; the source's own bytes outside the
+//     window and where m == 0.  The same tables, the same clamped indices: no filter formula, no read outside an operand.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -23,6 +28,7 @@ namespace afx {
 
 constexpr int kResampleBlock = 256;
 constexpr int64_t kResampleMaxRows = 65535;         // gridDim.y; further rows are taken by the row-stride loop
+constexpr int64_t kBboxMaxBlocks = 1024;            // work-groups per image of mask_bbox_kernel (4 per CU); further pixels by its grid-stride loop
 
 // rows: U8 ? B * H (each gives C rows of ws) : B * C * H
 template <bool U8, int C>
@@ -76,6 +82,101 @@ __global__ __launch_bounds__(kResampleBlock) void resample_v_kernel(const float*
     for (int k = 0; k < n; ++k) acc = __builtin_fmaf(wy[k], in[(int64_t)min(max(s0 + k, 0), H_in - 1) * W_out], acc);
     if (clamp) acc = fminf(fmaxf(acc, 0.0f), 1.0f);
     dst[row * W_out + x] = acc;
+  }
+}
+
+// bbox [B, 4] = (W, H, 0, 0): the identity of the (min, min, max, max) that mask_bbox_kernel folds in
+__global__ __launch_bounds__(64) void mask_bbox_init_kernel(int32_t* __restrict__ bbox, int batch, int H, int W) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch) return;
+  int32_t* o = bbox + 4 * b;
+  o[0] = W; o[1] = H; o[2] = 0; o[3] = 0;
+}
+
+// One lane per pixel of one image (blockIdx.y), grid-stride over its H * W pixels.  A lane keeps the box of its own pixels, a wave folds
+// its 64 boxes by shuffles, and lane 0 of a wave that saw a pixel folds the wave's box into bbox[b] with four integer atomics: integer
+// min / max give the same result in every arrival order.  U8: m > 0 is byte != 0.  fp32: the bit pattern as a signed integer is in
+// (0, 0x7f800000] exactly for the positive values, denormals and +inf included and every NaN and negative excluded, whatever the
+// denormal mode of the float compare.
+template <bool U8>
+__global__ __launch_bounds__(kResampleBlock) void mask_bbox_kernel(const void* __restrict__ mask, int32_t* __restrict__ bbox, int H, int W) {
+  const int64_t n = (int64_t)H * W;
+  const int b = blockIdx.y;
+  int x0 = W, y0 = H, x1 = 0, y1 = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kResampleBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kResampleBlock) {
+    bool on;
+    if constexpr (U8) {
+      on = static_cast<const uint8_t*>(mask)[b * n + i] != 0;
+    } else {
+      const int32_t bits = static_cast<const int32_t*>(mask)[b * n + i];
+      on = bits > 0 && bits <= 0x7f800000;
+    }
+    if (on) {
+      const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
+      x0 = min(x0, x); y0 = min(y0, y); x1 = max(x1, x + 1); y1 = max(y1, y + 1);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
+    x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0 && x1 > 0) {
+    int32_t* o = bbox + 4 * b;
+    atomicMin(o + 0, x0); atomicMin(o + 1, y0); atomicMax(o + 2, x1); atomicMax(o + 3, y1);
+  }
+}
+
+// The vertical taps of one output pixel: column x of the horizontal result `in` [H_in, W_out] of one plane, fp32 fma in tap order as in
+// resample_v_kernel; s0, n and wy are the row's (wave-uniform) table entries.
+AFX_DEV float paste_v_taps(const float* __restrict__ in, int s0, int n, const float* __restrict__ wy, int H_in, int W_out, int x) {
+  float acc = 0.0f;
+  for (int k = 0; k < n; ++k) acc = __builtin_fmaf(wy[k], in[(int64_t)min(max(s0 + k, 0), H_in - 1) * W_out + x], acc);
+  return acc;
+}
+
+// The second pass of afx_image_paste: dst uint8 [B, H, W, 3], one lane per pixel, a work-group works on one row of dst at a time (rows =
+// B * H), so whether the row crosses the window, and the vertical tables' entries where it does, are wave-uniform.  ws_img [B, 3, h, ww] and
+// ws_mask [mask_batch, h, ww] (NULL: m = 1) are the horizontal results, ww = x1 - x0.  Outside the window, and inside it where m == 0, the
+// source's bytes are stored as they are: no float stands between them, and nothing of img (a NaN included) can reach them.
+__global__ __launch_bounds__(kResampleBlock) void paste_kernel(const float* __restrict__ ws_img, const float* __restrict__ ws_mask,
+                                                               const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                               const int32_t* __restrict__ iv_start, const int32_t* __restrict__ iv_count,
+                                                               const float* __restrict__ iv_w, int iv_taps,
+                                                               const int32_t* __restrict__ mv_start, const int32_t* __restrict__ mv_count,
+                                                               const float* __restrict__ mv_w, int mv_taps, int64_t rows, int mask_batch, int h,
+                                                               int H, int W, int x0, int y0, int x1, int y1) {
+  const int X = blockIdx.x * kResampleBlock + threadIdx.x;
+  if (X >= W) return;
+  const int ww = x1 - x0, xx = X - x0;
+  for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int64_t b = row / H;
+    const int Y = (int)(row - b * H);
+    const int64_t px = (row * W + X) * 3;
+    const uint8_t s0 = src[px], s1 = src[px + 1], s2 = src[px + 2];
+    uint8_t q[3] = {s0, s1, s2};
+    if (Y >= y0 && Y < y1 && X >= x0 && X < x1) {
+      const int yy = Y - y0;
+      float m = 1.0f;
+      if (ws_mask) {
+        const int64_t mb = mask_batch == 1 ? 0 : b;
+        m = paste_v_taps(ws_mask + mb * h * ww, mv_start[yy], min(mv_count[yy], mv_taps), mv_w + (int64_t)yy * mv_taps, h, ww, xx);
+        m = fminf(fmaxf(m, 0.0f), 1.0f);
+      }
+      if (m != 0.0f) {
+        const int is0 = iv_start[yy], in = min(iv_count[yy], iv_taps);
+        const float* wy = iv_w + (int64_t)yy * iv_taps;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float v = paste_v_taps(ws_img + (b * 3 + c) * h * ww, is0, in, wy, h, ww, xx);
+          const float p = __builtin_fmaf(0.5f, v, 0.5f);
+          const float s = __fdiv_rn((float)q[c], 255.0f);
+          const float r = __builtin_fmaf(m, p, (1.0f - m) * s);
+          q[c] = (uint8_t)__builtin_rintf(255.0f * fminf(fmaxf(r, 0.0f), 1.0f));
+        }
+      }
+    }
+    dst[px] = q[0]; dst[px + 1] = q[1]; dst[px + 2] = q[2];
   }
 }
 
@@ -221,6 +322,100 @@ int afx_image_resample(const void* src, int32_t src_u8, int32_t batch, int32_t C
   const int64_t vrows = (int64_t)batch * C * H_out;
   hipLaunchKernelGGL(resample_v_kernel, dim3(gx, (unsigned)std::min(vrows, kResampleMaxRows)), dim3(kResampleBlock), 0, st, wsf, v_start,
                      v_count, v_w, v_taps, dst, vrows, H_in, H_out, W_out, clamp);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int afx_mask_bbox(const void* mask, int32_t mask_u8, int32_t batch, int32_t H, int32_t W, int32_t* bbox, void* stream) {
+  if (!mask || !bbox) return fail(AFX_E_INVALID, "null argument to afx_mask_bbox (mask and bbox are required)");
+  if (batch < 1 || H < 1 || W < 1) return fail(AFX_E_INVALID, "bad argument to afx_mask_bbox (batch, H and W must be >= 1)");
+  if (batch > (int32_t)kResampleMaxRows) return fail(AFX_E_INVALID, "afx_mask_bbox: batch must be <= %d", (int)kResampleMaxRows);
+  if ((!mask_u8 && ((uintptr_t)mask & 3)) || ((uintptr_t)bbox & 3))
+    return fail(AFX_E_INVALID, "afx_mask_bbox: an fp32 mask and bbox must be 4-byte aligned");
+  const int64_t n = (int64_t)H * W;
+  if (ranges_overlap(bbox, (int64_t)batch * 16, mask, (int64_t)batch * n * (mask_u8 ? 1 : 4)))
+    return fail(AFX_E_INVALID, "afx_mask_bbox: bbox overlaps the mask");
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mask_bbox_init_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, bbox, batch, H, W);
+  HIP_TRY(hipGetLastError());
+  const dim3 grid((unsigned)std::min<int64_t>((n + kResampleBlock - 1) / kResampleBlock, kBboxMaxBlocks), (unsigned)batch);
+  if (mask_u8)
+    hipLaunchKernelGGL(mask_bbox_kernel<true>, grid, dim3(kResampleBlock), 0, st, mask, bbox, H, W);
+  else
+    hipLaunchKernelGGL(mask_bbox_kernel<false>, grid, dim3(kResampleBlock), 0, st, mask, bbox, H, W);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+int64_t afx_image_paste_ws_bytes(int32_t batch, int32_t mask_batch, int32_t h, int32_t win_w) {
+  if (batch < 1 || mask_batch < 0 || (mask_batch > 1 && mask_batch != batch) || h < 1 || win_w < 1)
+    return fail(AFX_E_INVALID, "bad argument to afx_image_paste_ws_bytes (batch, h, win_w >= 1; mask_batch 0 (no mask), 1 or batch)");
+  return ((int64_t)batch * 3 + mask_batch) * h * win_w * 4;
+}
+
+int afx_image_paste(const float* img, const float* mask, int32_t mask_batch, const void* src, void* dst, int32_t batch, int32_t h, int32_t w,
+                    int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t n_out_w, int32_t n_out_h,
+                    const int32_t* ih_start, const int32_t* ih_count, const float* ih_w, int32_t ih_taps, const int32_t* iv_start,
+                    const int32_t* iv_count, const float* iv_w, int32_t iv_taps, const int32_t* mh_start, const int32_t* mh_count,
+                    const float* mh_w, int32_t mh_taps, const int32_t* mv_start, const int32_t* mv_count, const float* mv_w, int32_t mv_taps,
+                    void* ws, int64_t ws_bytes, void* stream) {
+  if (!img || !src || !dst || !ih_start || !ih_count || !ih_w || !iv_start || !iv_count || !iv_w)
+    return fail(AFX_E_INVALID, "null argument to afx_image_paste (img, src, dst and both axes' image tables are required)");
+  if (mask && (!mh_start || !mh_count || !mh_w || !mv_start || !mv_count || !mv_w))
+    return fail(AFX_E_INVALID, "null argument to afx_image_paste (a mask needs both axes' mask tables)");
+  if (batch < 1 || h < 1 || w < 1 || H < 1 || W < 1)
+    return fail(AFX_E_INVALID, "bad argument to afx_image_paste (batch and every size must be >= 1)");
+  if (mask ? (mask_batch != 1 && mask_batch != batch) : mask_batch != 0)
+    return fail(AFX_E_INVALID, "afx_image_paste: mask_batch must be 1 or batch with a mask and 0 without, got %d", (int)mask_batch);
+  if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > W || y1 > H)
+    return fail(AFX_E_INVALID, "afx_image_paste: the window (%d, %d, %d, %d) must be non-empty and inside the %d x %d source", (int)x0, (int)y0,
+                (int)x1, (int)y1, (int)H, (int)W);
+  if (x1 - x0 != n_out_w || y1 - y0 != n_out_h)
+    return fail(AFX_E_INVALID, "afx_image_paste: the window is %d x %d, the tables are for %d x %d", (int)(y1 - y0), (int)(x1 - x0), (int)n_out_h,
+                (int)n_out_w);
+  const int32_t taps[] = {ih_taps, iv_taps, mh_taps, mv_taps};
+  for (int i = 0; i < (mask ? 4 : 2); ++i)
+    if (taps[i] < 1 || taps[i] > AFX_RESAMPLE_MAX_TAPS)
+      return fail(AFX_E_INVALID, "afx_image_paste: every tap count must be in [1, %d], got %d", (int)AFX_RESAMPLE_MAX_TAPS, (int)taps[i]);
+  const int ww = x1 - x0, wh = y1 - y0;
+  const void* tabs[] = {ih_start, ih_count, ih_w, iv_start, iv_count, iv_w, mh_start, mh_count, mh_w, mv_start, mv_count, mv_w};
+  const int64_t tbytes[] = {(int64_t)ww * 4, (int64_t)ww * 4, (int64_t)ww * ih_taps * 4, (int64_t)wh * 4, (int64_t)wh * 4, (int64_t)wh * iv_taps * 4,
+                            (int64_t)ww * 4, (int64_t)ww * 4, (int64_t)ww * mh_taps * 4, (int64_t)wh * 4, (int64_t)wh * 4, (int64_t)wh * mv_taps * 4};
+  const int ntabs = mask ? 12 : 6;
+  uintptr_t bits = (uintptr_t)img | (uintptr_t)mask | (uintptr_t)ws;
+  for (int i = 0; i < ntabs; ++i) bits |= (uintptr_t)tabs[i];
+  if (bits & 3) return fail(AFX_E_INVALID, "afx_image_paste: img, mask, ws and the tables must be 4-byte aligned");
+  const int64_t need = ((int64_t)batch * 3 + mask_batch) * h * ww * 4;
+  if (!ws || ws_bytes < need)
+    return fail(AFX_E_WORKSPACE, "afx_image_paste: workspace missing or too small (%lld bytes, need afx_image_paste_ws_bytes = %lld)",
+                (long long)(ws ? ws_bytes : 0), (long long)need);
+  const int64_t ibytes = (int64_t)batch * 3 * h * w * 4, mbytes = (int64_t)mask_batch * h * w * 4, sbytes = (int64_t)batch * H * W * 3;
+  if (ranges_overlap(dst, sbytes, src, sbytes) || ranges_overlap(dst, sbytes, img, ibytes) || ranges_overlap(dst, sbytes, mask, mbytes) ||
+      ranges_overlap(dst, sbytes, ws, need) || ranges_overlap(ws, need, src, sbytes) || ranges_overlap(ws, need, img, ibytes) ||
+      ranges_overlap(ws, need, mask, mbytes))
+    return fail(AFX_E_INVALID, "afx_image_paste: dst or ws overlaps an operand, or each other");
+  for (int i = 0; i < ntabs; ++i)
+    if (ranges_overlap(dst, sbytes, tabs[i], tbytes[i]) || ranges_overlap(ws, need, tabs[i], tbytes[i]))
+      return fail(AFX_E_INVALID, "afx_image_paste: dst or ws overlaps a table");
+
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 block(kResampleBlock);
+  const unsigned gx = (unsigned)((ww + kResampleBlock - 1) / kResampleBlock);
+  float* ws_img = (float*)ws;
+  float* ws_mask = mask ? ws_img + (int64_t)batch * 3 * h * ww : nullptr;
+  const int64_t irows = (int64_t)batch * 3 * h, mrows = (int64_t)mask_batch * h;
+  hipLaunchKernelGGL((resample_h_kernel<false, 1>), dim3(gx, (unsigned)std::min(irows, kResampleMaxRows)), block, 0, st, (const void*)img,
+                     ih_start, ih_count, ih_w, ih_taps, ws_img, irows, h, w, ww);
+  HIP_TRY(hipGetLastError());
+  if (mask) {
+    hipLaunchKernelGGL((resample_h_kernel<false, 1>), dim3(gx, (unsigned)std::min(mrows, kResampleMaxRows)), block, 0, st, (const void*)mask,
+                       mh_start, mh_count, mh_w, mh_taps, ws_mask, mrows, h, w, ww);
+    HIP_TRY(hipGetLastError());
+  }
+  const int64_t rows = (int64_t)batch * H;
+  hipLaunchKernelGGL(paste_kernel, dim3((unsigned)((W + kResampleBlock - 1) / kResampleBlock), (unsigned)std::min(rows, kResampleMaxRows)), block,
+                     0, st, ws_img, ws_mask, (const uint8_t*)src, (uint8_t*)dst, iv_start, iv_count, iv_w, iv_taps, mv_start, mv_count, mv_w,
+                     mv_taps, rows, mask_batch, h, H, W, x0, y0, x1, y1);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }

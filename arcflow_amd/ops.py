@@ -720,6 +720,63 @@ def mask_feather(mask: torch.Tensor, sigma: float) -> torch.Tensor:
     return _resample(mask, dims, H, W, tab_h, tab_w, True)
 
 
+def mask_bbox(mask: torch.Tensor) -> torch.Tensor:
+    """int32 [B, 4] on the device = (x0, y0, x1, y1), the half-open bounding box of the pixels with m > 0 of every image of ``mask``
+    (afx_mask_bbox): uint8 [B, H, W, 1] or float32 [B, 1, H, W].  A NaN is not > 0, a positive denormal is; an image without such a pixel
+    gives (W, H, 0, 0).  Integer min / max: the same result on every run.  Nothing is copied or cast: a wrong dtype or layout raises."""
+    _gpu(mask, name='mask')
+    u8 = mask.dtype == torch.uint8
+    ok = mask.dim() == 4 and mask.dtype in (torch.uint8, torch.float32) and mask.shape[3 if u8 else 1] == 1 and mask.is_contiguous()
+    if not ok or min(mask.shape) < 1:
+        raise ValueError(f'mask: need a contiguous, non-empty uint8 [B, H, W, 1] or float32 [B, 1, H, W], got {tuple(mask.shape)} {mask.dtype} '
+                         f'strides {mask.stride()}')
+    B, H, W = (mask.shape[0], mask.shape[1], mask.shape[2]) if u8 else (mask.shape[0], mask.shape[2], mask.shape[3])
+    out = torch.empty(B, 4, dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().afx_mask_bbox(_p(mask), int(u8), B, H, W, _p(out), _s()))
+    return out
+
+
+def image_paste(img: torch.Tensor, mask: Optional[torch.Tensor], src_u8: torch.Tensor, window, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Paste an edit back into the photo it was cut from (afx_image_paste) -> uint8 [B, H, W, 3].  ``img`` float32 [B, 3, h, w] in [-1, 1]
+    (the decoder's output) is resampled to the integer ``window`` = (x0, y0, x1, y1) of ``src_u8`` uint8 [B, H, W, 3] with Lanczos-3,
+    ``mask`` float32 [B or 1, 1, h, w] in [0, 1] (None: 1 everywhere in the window) with the triangle filter, and per channel the byte is
+    rint(255 clamp(m (0.5 v + 0.5) + (1 - m) byte / 255, 0, 1)).  Outside the window, and inside it where m == 0, the result holds the
+    source's own bytes.  The tables are built once per geometry and kept (``_device_table``).  Nothing is copied or cast: a wrong dtype or
+    layout raises.  ``out``: a uint8 [B, H, W, 3] buffer to write (not ``src_u8``)."""
+    lib = _lib.load()
+    _gpu(img, mask, src_u8, out)
+    if img.dim() != 4 or img.shape[1] != 3 or min(img.shape) < 1:
+        raise ValueError(f'img: need a non-empty float32 [B, 3, h, w], got {tuple(img.shape)}')
+    B, _, h, w = img.shape
+    img = _packed(img, torch.float32, img.shape, 'img')
+    if src_u8.dim() != 4 or src_u8.shape[0] != B or src_u8.shape[3] != 3 or min(src_u8.shape) < 1:
+        raise ValueError(f'src_u8: need a non-empty uint8 [{B}, H, W, 3], got {tuple(src_u8.shape)}')
+    src_u8 = _packed(src_u8, torch.uint8, src_u8.shape, 'src_u8')
+    H, W = src_u8.shape[1:3]
+    if mask is not None:
+        if mask.dim() != 4 or mask.shape[0] not in (1, B):
+            raise ValueError(f'mask: need float32 [{B} or 1, 1, {h}, {w}], got {tuple(mask.shape)}')
+        mask = _packed(mask, torch.float32, (mask.shape[0], 1, h, w), 'mask')
+    x0, y0, x1, y1 = (int(v) for v in window)
+    if any(int(v) != v for v in window) or not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+        raise ValueError(f'window: need integers (x0, y0, x1, y1) of a non-empty window inside the {H} x {W} source, got {tuple(window)}')
+    out = torch.empty_like(src_u8) if out is None else _packed(out, torch.uint8, src_u8.shape, 'out')
+    dev = str(img.device)
+    itab = (_device_table(w, x1 - x0, _lib.AFX_FILTER_LANCZOS3, 0.0, float(w), 0.0, dev),
+            _device_table(h, y1 - y0, _lib.AFX_FILTER_LANCZOS3, 0.0, float(h), 0.0, dev))
+    mtab = ((None, None, None),) * 2 if mask is None else (_device_table(w, x1 - x0, _lib.AFX_FILTER_TRIANGLE, 0.0, float(w), 0.0, dev),
+                                                         _device_table(h, y1 - y0, _lib.AFX_FILTER_TRIANGLE, 0.0, float(h), 0.0, dev))
+    mb = 0 if mask is None else mask.shape[0]
+    need = lib.afx_image_paste_ws_bytes(B, mb, h, x1 - x0)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=img.device)
+    tabs = [a for tab in itab + mtab for a in (_p(tab[0]), _p(tab[1]), _p(tab[2]), 0 if tab[2] is None else tab[2].shape[1])]
+    _lib.check(lib.afx_image_paste(_p(img), _p(mask), mb, _p(src_u8), _p(out), B, h, w, H, W, x0, y0, x1, y1, x1 - x0, y1 - y0, *tabs,
+                                   _p(ws), need, _s()))
+    return out
+
+
 def _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
     """The operands every teacher step shares, checked: -> (x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n), out and out_bf16
     allocated when None.  sigma and sigma_to may be None (the UniPC step takes its weights instead)."""

@@ -24,7 +24,7 @@ import torch
 
 from .. import ops
 from ..engine import MMDiTEngine
-from ..schedule import FlowMatchEulerDiscreteScheduler, calculate_shift, edit_raw_timesteps, mask_to_tokens, retrieve_raw_timesteps
+from ..schedule import FlowMatchEulerDiscreteScheduler, calculate_shift, edit_raw_timesteps, mask_crop_window, mask_to_tokens, retrieve_raw_timesteps
 from .arcflow_loader import ArcFlowLoaderMixin
 
 POLICY_CLASSES = ('ArcFlow',)
@@ -216,16 +216,63 @@ class _PipelineBase(ArcFlowLoaderMixin):
             out.append(None if t is None else ops.image_resample(t, height, width, filt, box, clamp=True))
         return out[0], out[1], height, width
 
-    def _edit_inputs(self, image, image_latents, mask_image, strength, height, width, resize=None, mask_blur=0.0):
+    def _edit_inputs_cropped(self, image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop, output_type):
+        """The ``padding_mask_crop`` branch of ``_edit_inputs``: the edit runs at the call's size on a window around the mask of an 8-bit
+        photo of any size and ``_finish`` pastes it back (ops.image_paste).  -> (edit, height, width); ``edit['paste']`` holds the photo's
+        bytes on the GPU (uint8 [B, H, W, 3]) and the window (x0, y0, x1, y1)."""
+        import numpy as np
+        pad = padding_mask_crop
+        if isinstance(pad, bool) or not isinstance(pad, (int, np.integer)) or pad < 0:
+            raise ValueError(f'`padding_mask_crop`: None or an integer >= 0 (pixels of the source around the mask), got {pad!r}')
+        if resize is not None:
+            raise ValueError('`padding_mask_crop` and `resize` exclude each other: the crop to the mask is the resize')
+        if image_latents is not None:
+            raise ValueError('`padding_mask_crop` takes `image`, not `image_latents`: the result is pasted into the image\'s own pixels')
+        if image is None or mask_image is None:
+            raise ValueError('`padding_mask_crop` needs `image` and `mask_image`')
+        if output_type == 'latent':
+            raise ValueError("`padding_mask_crop` returns the image at its own size: output_type 'pil', 'np' or 'pt', not 'latent'")
+        pils = isinstance(image, (list, tuple)) and len(image) and all(hasattr(im, 'convert') for im in image)
+        if not (pils or hasattr(image, 'convert') or (isinstance(image, np.ndarray) and image.dtype == np.uint8)):
+            raise ValueError('`padding_mask_crop` needs 8-bit pixels, a PIL image (or a list) or a uint8 numpy array [B, H, W, 3]: the result '
+                             f'keeps the image\'s own bytes; got {type(image).__name__}' + (f' {image.dtype}' if hasattr(image, 'dtype') else ''))
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f'`strength` must be in (0, 1], got {strength}')
+        height = height or self.default_sample_size * self.vae_scale_factor
+        width = width or self.default_sample_size * self.vae_scale_factor
+        if height % 16 or width % 16:
+            raise ValueError(f'`height` and `width` have to be divisible by 16, got {height} x {width}')
+        src = self._resize_source(image, 'image', 3)
+        msrc = self._resize_source(mask_image, 'mask_image', 1)
+        H, W = src.shape[1:3]
+        mhw = tuple(msrc.shape[1:3]) if msrc.dtype == torch.uint8 else tuple(msrc.shape[2:])
+        if mhw != (H, W):
+            raise ValueError(f'`mask_image` is {mhw[0]} x {mhw[1]}, `image` is {H} x {W}: with `padding_mask_crop` the mask has the image\'s size')
+        box = ops.mask_bbox(msrc).cpu()                     # 16 B per image: the one host round trip of the way in
+        union = (int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 2].max()), int(box[:, 3].max()))
+        window = mask_crop_window(union, H, W, height, width, int(pad))
+        fbox = tuple(float(v) for v in window)
+        img = ops.image_resample(src, height, width, 'lanczos3', fbox, clamp=True)
+        mask = ops.image_resample(msrc, height, width, 'triangle', fbox, clamp=True)
+        if mask_blur:
+            mask = ops.mask_feather(mask, mask_blur)
+        return dict(image=img, image_latents=None, mask=mask, strength=float(strength), paste=dict(source=src, window=window)), height, width
+
+    def _edit_inputs(self, image, image_latents, mask_image, strength, height, width, resize=None, mask_blur=0.0, padding_mask_crop=None,
+                     output_type=None):
         """Host-side half of the edit arguments: -> (edit, height, width), ``edit`` None on the text-to-image path.  Normalises ``image`` and
         ``mask_image`` to fp32 [B, C, H, W], takes ``height`` / ``width`` from them when not given.  ``resize`` None: nothing is resized, an
         input of another size raises.  'stretch' / 'crop': both are resampled to the call's size on the GPU (ops.image_resample: the image
         with Lanczos-3, the mask with the triangle filter, soft values kept), 'crop' from the largest centred window of the call's aspect
         ratio; ``height`` / ``width`` then default to the source's sides rounded to multiples of 16.  ``mask_blur`` > 0: the
-        image-resolution mask is feathered by a Gaussian of that sigma in output pixels (ops.mask_feather) after any resize."""
+        image-resolution mask is feathered by a Gaussian of that sigma in output pixels (ops.mask_feather) after any resize.
+        ``padding_mask_crop`` (an integer; with it ``output_type`` is checked too): ``_edit_inputs_cropped``."""
         mask_blur = float(mask_blur)
         if not 0.0 <= mask_blur < float('inf'):
             raise ValueError(f'`mask_blur` must be a finite sigma >= 0, got {mask_blur}')
+        if padding_mask_crop is not None:
+            return self._edit_inputs_cropped(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
+                                             output_type)
         if image is None and image_latents is None:
             if mask_image is not None:
                 raise ValueError('`mask_image` needs `image` or `image_latents`')
@@ -285,9 +332,10 @@ class _PipelineBase(ArcFlowLoaderMixin):
             edit['mask_tokens'] = mask_to_tokens(edit['mask'].to(device), hp, wp).expand(B, -1, -1).contiguous()
         return edit
 
-    def _composite(self, image, edit, composite):
-        """Paste the original pixels back outside the mask: m decoded + (1 - m) original, in the decoder's range [-1, 1] and dtype."""
-        if not composite or edit is None or edit['image'] is None or edit['mask'] is None:
+    def _composite(self, image, edit, composite, padding_mask_crop=None):
+        """Paste the original pixels back outside the mask: m decoded + (1 - m) original, in the decoder's range [-1, 1] and dtype.  With
+        ``padding_mask_crop`` nothing happens here: the blend is part of the paste into the photo (``_paste``)."""
+        if not composite or edit is None or edit['image'] is None or edit['mask'] is None or padding_mask_crop is not None:
             return image
         m = edit['mask'].to(image.device, torch.float32)
         orig = (edit['image'].to(image.device) * 2 - 1).to(image.dtype).to(torch.float32)
@@ -436,6 +484,33 @@ class _PipelineBase(ArcFlowLoaderMixin):
         from PIL import Image
         return [Image.fromarray((x * 255).round().astype('uint8')) for x in img]
 
+    def _paste(self, image, edit, composite) -> torch.Tensor:
+        """The decoded edit [B, 3, h, w] in [-1, 1] back into the photo it was cut from -> uint8 [B, H, W, 3] on the GPU (ops.image_paste):
+        the window takes the edit resampled to its size, blended with the photo by the call's mask (``composite`` off: the whole window is
+        the edit); every other byte is the photo's own."""
+        paste = edit['paste']
+        src = paste['source']
+        if src.shape[0] != image.shape[0]:
+            if src.shape[0] != 1:
+                raise ValueError(f'`image` has batch {src.shape[0]}, the call has {image.shape[0]} (a batch of 1 broadcasts)')
+            src = src.expand(image.shape[0], -1, -1, -1).contiguous()
+        return ops.image_paste(image.to(torch.float32).contiguous(), edit['mask'] if composite else None, src, paste['window'])
+
+    def _output(self, image, edit, composite, output_type, padding_mask_crop=None):
+        """The decoded image -> what the call returns.  With ``padding_mask_crop``: the photo's size, from the bytes of ``_paste`` ('pt': the
+        uint8 [B, H, W, 3] device tensor, 'np': bytes / 255 as float32 [B, H, W, 3], 'pil': images of the bytes)."""
+        if padding_mask_crop is None:
+            return self._postprocess(self._composite(image, edit, composite), output_type)
+        out = self._paste(image, edit, composite)
+        if output_type == 'pt':
+            return out
+        arr = out.cpu().numpy()
+        if output_type == 'np':
+            import numpy as np
+            return arr.astype(np.float32) / np.float32(255.0)
+        from PIL import Image
+        return [Image.fromarray(x) for x in arr]
+
 
 class ArcFluxPipeline(_PipelineBase):
     r"""Policy-based FLUX pipeline, 2-NFE capable (reference arcflux_pipeline.py:73)."""
@@ -556,7 +631,7 @@ class ArcFluxPipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0):
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None):
         """Text-to-image by default.  ``image`` (or its packed latents ``image_latents``) starts the sampler from the image noised to
         ``strength`` in (0, 1] instead of from pure noise (image-to-image); ``mask_image`` (1 = repaint) keeps the unmasked region on the
         image's own trajectory (inpainting) and, with ``composite``, pastes the original pixels back there after decoding.  ``height`` /
@@ -565,8 +640,16 @@ class ArcFluxPipeline(_PipelineBase):
         the largest centred window of the call's aspect ratio, PIL and uint8 numpy inputs uploaded as uint8; ``height`` / ``width`` then
         default to the image's sides rounded to multiples of 16.  With ``resize`` a uint8 numpy array is 8-bit pixels, read as x / 255
         (with ``resize=None`` it is taken, as before, as values already in [0, 1]); a uint8 torch tensor raises with ``resize``.  ``mask_blur``: sigma in output pixels of a Gaussian feather of the mask
-        (0 = none), which feeds the latent blend and the composite alike.  ``latents`` / ``generator`` give the start noise as before."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
+        (0 = none), which feeds the latent blend and the composite alike.  ``latents`` / ``generator`` give the start noise as before.
+        ``padding_mask_crop`` (an integer number of source pixels; needs ``image`` as 8-bit pixels -- PIL or a uint8 numpy array -- and a
+        ``mask_image`` of the image's size, of ANY size; not with ``resize`` or ``image_latents``): the edit runs at the call's size
+        (``height`` / ``width``, default 1024) on a window around the mask's bounding box, padded by that many pixels and grown to the call's
+        aspect ratio (``schedule.mask_crop_window``), and the result is the image at ITS OWN size: the window holds the edit, resampled back
+        and blended by the mask (``composite=False``: unblended), every other byte is the image's own (``ops.image_paste``).  'pil' comes
+        from those bytes, 'np' is bytes / 255 as float32 [B, H, W, 3], 'pt' the uint8 [B, H, W, 3] device tensor; 'latent' raises.
+        diffusers' ``padding_mask_crop`` + ``apply_overlay`` as recalled; parity unpinned."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
+                                                output_type)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -600,9 +683,9 @@ class ArcFluxPipeline(_PipelineBase):
             return self.transformer.prepare_steps(sigmas, pooled, guidance, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare, edit=edit)
-        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite)
+        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)
 
-    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True):
+    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True, padding_mask_crop=None):
         """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``.  An inpainting call
         (``edit`` with an image and a mask) gets the original pixels pasted back outside the mask unless ``composite`` is off."""
         if output_type == 'latent':
@@ -617,7 +700,7 @@ class ArcFluxPipeline(_PipelineBase):
                 lat = self._unpack(latents, hp, wp)
                 lat = lat / self.vae.config.scaling_factor + self.vae.config.shift_factor
                 image = self.vae.decode(lat.to(next(self.vae.parameters()).dtype), return_dict=False)[0]
-            image = self._postprocess(self._composite(image, edit, composite), output_type)
+            image = self._output(image, edit, composite, output_type, padding_mask_crop)
         self.maybe_free_model_hooks()
         if not return_dict:
             return (image,)
@@ -635,7 +718,8 @@ class ArcFluxPipeline(_PipelineBase):
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
-                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0):
+                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0,
+                       padding_mask_crop: Optional[int] = None):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
@@ -654,8 +738,10 @@ class ArcFluxPipeline(_PipelineBase):
         (``schedule.truncate_by_strength``); with a mask every step also puts the unmasked latent pixels back on the image's own
         trajectory with the start noise (fused into the step kernel, ``afx_teacher_edit_step``).  These follow diffusers' img2img /
         inpaint pipelines as recalled; the reference has no image-conditioned sampling and nothing pins them.  ``resize``
-        and ``mask_blur`` are ``__call__``'s too: the device resize of ``image`` / ``mask_image`` and the Gaussian feather of the mask."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
+        and ``mask_blur`` are ``__call__``'s too: the device resize of ``image`` / ``mask_image`` and the Gaussian feather of the mask, and so
+        is ``padding_mask_crop``: the edit of a window around the mask, pasted back into the image at its own size."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
+                                                output_type)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -676,4 +762,4 @@ class ArcFluxPipeline(_PipelineBase):
             cond.update(negative_prompt_embeds=ne, negative_pooled=npooled)
         out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, guidance_scale, true_cfg_scale,
                                                  generator, latents, guidance_interval, orthogonal_guidance, sampler, h, edit, solver_order, solver_type)
-        return self._finish(out, hp, wp, output_type, return_dict, edit, composite)
+        return self._finish(out, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)

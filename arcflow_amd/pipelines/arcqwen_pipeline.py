@@ -119,11 +119,13 @@ class ArcQwenImagePipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0):
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None):
         """Text-to-image by default; ``image`` / ``image_latents``, ``strength``, ``mask_image``, ``composite``, ``resize`` and ``mask_blur``
         as on ``ArcFluxPipeline.__call__`` (image-to-image and inpainting; ``resize='stretch'|'crop'`` resamples inputs of any size on the GPU,
-        ``mask_blur`` feathers the mask)."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
+        ``mask_blur`` feathers the mask), and ``padding_mask_crop`` as there: the edit runs on a window around the mask of an 8-bit image of any size
+        and is pasted back into it at the image's own size."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
+                                                output_type)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -155,9 +157,9 @@ class ArcQwenImagePipeline(_PipelineBase):
             return self.transformer.prepare_steps(sigmas, None, None, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare, edit=edit)
-        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite)
+        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)
 
-    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True):
+    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True, padding_mask_crop=None):
         """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``.  An inpainting call
         (``edit`` with an image and a mask) gets the original pixels pasted back outside the mask unless ``composite`` is off."""
         device = self._execution_device
@@ -168,13 +170,13 @@ class ArcQwenImagePipeline(_PipelineBase):
                 raise RuntimeError("no VAE decoder attached: use output_type='latent' or set pipe.vae")
             from ..vae import AutoencoderKLQwenImageDecoder
             if isinstance(self.vae, AutoencoderKLQwenImageDecoder):   # HIP decoder: un-normalisation + unpack fused into its first kernel
-                image = self._postprocess(self._composite(self.vae.decode_packed(latents, hp, wp), edit, composite), output_type)
+                image = self._output(self.vae.decode_packed(latents, hp, wp), edit, composite, output_type, padding_mask_crop)
                 return (image,) if not return_dict else QwenImagePipelineOutput(images=image)
             lat = self._unpack(latents, hp, wp)[:, :, None]
             mean = torch.tensor(self.vae.config.latents_mean, device=device).view(1, -1, 1, 1, 1)
             std = torch.tensor(self.vae.config.latents_std, device=device).view(1, -1, 1, 1, 1)
             image = self.vae.decode((lat * std + mean).to(next(self.vae.parameters()).dtype), return_dict=False)[0][:, :, 0]
-            image = self._postprocess(self._composite(image, edit, composite), output_type)
+            image = self._output(image, edit, composite, output_type, padding_mask_crop)
         if not return_dict:
             return (image,)
         return QwenImagePipelineOutput(images=image)
@@ -200,7 +202,8 @@ class ArcQwenImagePipeline(_PipelineBase):
                        num_images_per_prompt: int = 1, max_sequence_length: int = 512, sampler: str = 'FlowEulerODE',
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
-                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0):
+                       solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0,
+                       padding_mask_crop: Optional[int] = None):
         """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
         ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
@@ -212,8 +215,9 @@ class ArcQwenImagePipeline(_PipelineBase):
         ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.  ``image`` / ``image_latents``,
         ``strength``, ``mask_image`` and ``composite``: the teacher's image-to-image and inpainting, as on
         ``ArcFluxPipeline.sample_teacher`` (a suffix of the schedule chosen by ``strength``; unpinned semantics); ``resize`` and
-        ``mask_blur`` as on ``ArcFluxPipeline.__call__``."""
-        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur)
+        ``mask_blur`` and ``padding_mask_crop`` as on ``ArcFluxPipeline.__call__``."""
+        edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
+                                                output_type)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -236,4 +240,4 @@ class ArcQwenImagePipeline(_PipelineBase):
             cond['negative_prompt_embeds'] = ne
         out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
                                                  latents, guidance_interval, orthogonal_guidance, sampler, h, edit, solver_order, solver_type)
-        return self._finish(out, hp, wp, output_type, return_dict, edit, composite)
+        return self._finish(out, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)

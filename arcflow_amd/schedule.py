@@ -85,6 +85,34 @@ def mask_to_tokens(mask: torch.Tensor, hp: int, wp: int, reduce: str = 'max') ->
     return red.permute(0, 1, 3, 2, 4).reshape(mask.shape[0], hp * wp, 4).contiguous()
 
 
+def mask_crop_window(bbox, src_h: int, src_w: int, height: int, width: int, pad: int) -> Tuple[int, int, int, int]:
+    """The window (x0, y0, x1, y1) of a ``src_h`` x ``src_w`` image that an edit with ``padding_mask_crop=pad`` works on, from the mask's
+    half-open bounding box ``bbox`` = (x0, y0, x1, y1) (``ops.mask_bbox``) and the call's ``height`` x ``width``.  Host integer arithmetic:
+    the box is padded by ``pad`` pixels on each side and clipped to the image; then the shorter side (measured against the call's aspect
+    ratio) grows to ``want = min(side of the image, ceil(other side * aspect))``, half of the growth on either side, shifted back inside
+    where that would cross a border.  The window always contains the padded box and lies inside the image.  It has the call's aspect
+    ratio up to the integer rounding UNLESS the image is too small for it (``want`` was cut to the image's side): the resample to the
+    call's size then stretches.  An empty box (no mask pixel > 0: ``x1 <= x0`` or ``y1 <= y0``) raises ValueError."""
+    x0, y0, x1, y1 = (int(v) for v in bbox)
+    H, W, pad = int(src_h), int(src_w), int(pad)
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError(f'the mask has no pixel > 0 (bounding box {(x0, y0, x1, y1)}): `padding_mask_crop` has nothing to crop to')
+    if pad < 0 or height < 1 or width < 1 or x0 < 0 or y0 < 0 or x1 > W or y1 > H:
+        raise ValueError(f'need pad >= 0, height, width >= 1 and a box inside the {H} x {W} image, got box {(x0, y0, x1, y1)}, pad {pad}, '
+                         f'{height} x {width}')
+    x0, y0, x1, y1 = max(x0 - pad, 0), max(y0 - pad, 0), min(x1 + pad, W), min(y1 + pad, H)
+    cw, ch = x1 - x0, y1 - y0
+    if cw * height < ch * width:            # narrower than the call: widen
+        want = min(W, -(-ch * width // height))
+        x0 = min(max(x0 - (want - cw) // 2, 0), W - want)
+        x1 = x0 + want
+    else:                                   # heighten (want == ch when the aspect is the call's already)
+        want = min(H, -(-cw * height // width))
+        y0 = min(max(y0 - (want - ch) // 2, 0), H - want)
+        y1 = y0 + want
+    return x0, y0, x1, y1
+
+
 def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
                    num_train_timesteps: int = 1000) -> List[float]:
     """sigma at the start of every student step plus the terminal 0, as the pipelines' ``__call__`` walks them: the raw sub-step grid

@@ -403,6 +403,32 @@ int afx_image_resample(const void* src, int32_t src_u8, int32_t batch, int32_t C
                        const int32_t* h_count, const float* h_w, int32_t h_taps, const int32_t* v_start, const int32_t* v_count,
                        const float* v_w, int32_t v_taps, float* dst, int32_t H_out, int32_t W_out, int32_t clamp, void* ws,
                        int64_t ws_bytes, void* stream);
+/* The way back from an edit that ran on a window of a larger photo (the pipelines' padding_mask_crop).
+ * afx_mask_bbox: mask uint8 [batch, H, W, 1] (mask_u8 = 1) or fp32 [batch, 1, H, W] -> bbox int32 [batch, 4] = (x0, y0, x1, y1), the half-open
+ * bounding box of the pixels with m > 0 (a NaN is not, a positive denormal and +inf are); an image without such a pixel gives (W, H, 0, 0).
+ * Integer min / max atomics: the result does not depend on arrival order.  Two launches, all on the device.  AFX_E_INVALID before any
+ * launch for a NULL or misaligned (4 bytes; a uint8 mask: none) pointer, a size < 1, batch > 65535, or bbox overlapping the mask.
+ * afx_image_paste: img fp32 [batch, 3, h, w] in [-1, 1] (the decoder's output), mask fp32 [mask_batch, 1, h, w] in [0, 1] (mask_batch 1 =
+ * shared, or batch) or NULL (mask_batch 0: m = 1 inside the window), src and dst uint8 [batch, H, W, 3], the integer window (x0, y0, x1, y1)
+ * inside the source.  ih_* / iv_* are the image's afx_resample_table tables of the W axis (w -> x1 - x0, n_out_w rows of stride ih_taps) and
+ * of the H axis (h -> y1 - y0, n_out_h rows), mh_* / mv_* the mask's (same n_out; ignored without a mask), all DEVICE pointers.  Every byte
+ * of dst is written: outside the window src's three bytes; inside, per channel,
+ *     v = vertical taps of the horizontal taps of img (fp32 fma in tap order, as afx_image_resample), p = fma(0.5, v, 0.5),
+ *     m = clamp(the same taps of mask, 0, 1), s = float(byte) / 255.0f, r = fma(m, p, (1 - m) s), byte' = rint(255 clamp(r, 0, 1)), ties to even;
+ * where m == 0 src's bytes are stored as they are, and nothing of img (a NaN included) reaches them.  ws: afx_image_paste_ws_bytes(batch,
+ * mask_batch, h, x1 - x0) = 4 (3 batch + mask_batch) h (x1 - x0) bytes, the horizontal results, private to the call until it completes.
+ * Two launches, three with a mask.  Indices are clamped and counts capped as in afx_image_resample.  AFX_E_INVALID before any launch for a
+ * NULL img, src, dst or image table (with a mask: a mask table), a size < 1, a mask_batch other than 0 / 1 / batch, a window that is empty,
+ * not inside the source or not n_out_w x n_out_h, taps outside [1, AFX_RESAMPLE_MAX_TAPS], a misaligned fp32 pointer (4 bytes), or dst or ws
+ * overlapping an operand, a table or each other; AFX_E_WORKSPACE for a NULL or short ws. */
+int afx_mask_bbox(const void* mask, int32_t mask_u8, int32_t batch, int32_t H, int32_t W, int32_t* bbox, void* stream);
+int64_t afx_image_paste_ws_bytes(int32_t batch, int32_t mask_batch, int32_t h, int32_t win_w);
+int afx_image_paste(const float* img, const float* mask, int32_t mask_batch, const void* src, void* dst, int32_t batch, int32_t h, int32_t w,
+                    int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t n_out_w, int32_t n_out_h,
+                    const int32_t* ih_start, const int32_t* ih_count, const float* ih_w, int32_t ih_taps, const int32_t* iv_start,
+                    const int32_t* iv_count, const float* iv_w, int32_t iv_taps, const int32_t* mh_start, const int32_t* mh_count,
+                    const float* mh_w, int32_t mh_taps, const int32_t* mv_start, const int32_t* mv_count, const float* mv_w, int32_t mv_taps,
+                    void* ws, int64_t ws_bytes, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,

@@ -3,7 +3,8 @@
 ``pipe(image=..., strength=..., mask_image=...)`` of ArcFluxPipeline / ArcQwenImagePipeline.  The image is encoded by the snapshot's VAE
 encoder, noised to ``--strength``, denoised in ``--nfe`` student steps and decoded; with a mask the unmasked region stays on the image's
 own trajectory and the original pixels are pasted back after decoding.  Nothing is resized: the image (and the mask) must be a multiple of
-16 pixels on both sides.
+16 pixels on both sides -- unless ``--resize`` resamples them to the call's size, or ``--padding-mask-crop N`` edits a window around the mask of a
+photo of any size and writes the photo at its own size, every kept pixel byte for byte.
 
     python tools/edit_image.py --family flux --snapshot /path/to/FLUX.1-dev --adapter /path/to/arcflow --image in.png --mask mask.png \\
         --prompt "a red door" --strength 0.8 --out out.png
@@ -109,6 +110,9 @@ def main(argv=None):
     ap.add_argument('--mask-blur', type=float, default=0.0, help='sigma in output pixels of a Gaussian feather of the mask (0 = none)')
     ap.add_argument('--height', type=int, help='with --resize: the output height (default: the image\'s, rounded to a multiple of 16)')
     ap.add_argument('--width', type=int, help='with --resize: the output width')
+    ap.add_argument('--padding-mask-crop', type=int, metavar='N', help='inpaint a photo of any size at its own size: edit a window around the '
+                    'mask\'s bounding box, padded by N source pixels, at --height x --width (default 1024 x 1024) and paste the result back; every '
+                    'pixel outside the mask keeps the photo\'s own bytes.  Needs --mask; not with --resize')
     args = ap.parse_args(argv)
     gen = torch.Generator().manual_seed(args.seed)
     kw = dict(strength=args.strength, num_inference_steps=args.nfe, timestep_ratio=1.0 if args.nfe == 2 else 0.5, generator=gen)
@@ -155,24 +159,29 @@ def main(argv=None):
     if not student and not args.teacher:
         raise SystemExit('no ArcFlow student loaded: pass --adapter, or --teacher for the base model\'s own edit')
     out = lat = None
-    if (args.height or args.width) and not args.resize:
-        raise SystemExit('--height / --width need --resize (without it the call has the image\'s size)')
+    crop = args.padding_mask_crop
+    if crop is not None and (mask is None or args.resize):
+        raise SystemExit('--padding-mask-crop needs --mask and excludes --resize')
+    if (args.height or args.width) and not args.resize and crop is None:
+        raise SystemExit('--height / --width need --resize or --padding-mask-crop (without them the call has the image\'s size)')
     kw.update(resize=args.resize, mask_blur=args.mask_blur if mask is not None else 0.0, height=args.height, width=args.width)
+    if crop is not None:
+        kw.update(padding_mask_crop=crop)             # the result has the photo's size; there are no latents of that size to score
     if student:
-        lat = pipe(prompt=args.prompt, image=image, mask_image=mask, output_type='latent', **kw).images
+        lat = None if crop is not None else pipe(prompt=args.prompt, image=image, mask_image=mask, output_type='latent', **kw).images
         out = pipe(prompt=args.prompt, image=image, mask_image=mask, **dict(kw, generator=torch.Generator().manual_seed(args.seed))).images[0]
         out.save(args.out)
         print(f'wrote {args.out} ({out.size[0]} x {out.size[1]})')
     if args.teacher:
         tkw = dict(prompt=args.prompt, image=image, mask_image=mask, strength=args.strength, num_inference_steps=args.steps,
                    true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt if args.true_cfg_scale > 1.0 else None,
-                   resize=kw['resize'], mask_blur=kw['mask_blur'], height=args.height, width=args.width)
-        tlat = pipe.sample_teacher(output_type='latent', generator=torch.Generator().manual_seed(args.seed), **tkw).images
+                   resize=kw['resize'], mask_blur=kw['mask_blur'], height=args.height, width=args.width, padding_mask_crop=crop)
+        tlat = None if crop is not None else pipe.sample_teacher(output_type='latent', generator=torch.Generator().manual_seed(args.seed), **tkw).images
         tea = pipe.sample_teacher(generator=torch.Generator().manual_seed(args.seed), **tkw).images[0]
         tea.save(_teacher_path(args.out))
         print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}')
         if student:
-            print(f'student vs teacher: {dict(score_latents(lat, tlat), **score_images(out, tea, mask))}')
+            print(f'student vs teacher: {dict(score_latents(lat, tlat) if crop is None else {}, **score_images(out, tea, mask))}')
         out = tea if out is None else out
     return out
 
