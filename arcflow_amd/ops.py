@@ -777,6 +777,64 @@ def image_paste(img: torch.Tensor, mask: Optional[torch.Tensor], src_u8: torch.T
     return out
 
 
+@functools.lru_cache(maxsize=16)
+def _device_plan(H: int, W: int, tile: int, overlap: int, device: str):
+    """``schedule.tile_plan`` with its origin lists and tables on the GPU, kept for the next call of the same geometry, uploaded and waited
+    for in the manner of ``_device_table``: -> (plan, oy, ox, (y_start, y_count, y_w), (x_start, x_count, x_w)).  A plan of a 4500 x 6000
+    canvas is 0.25 MB."""
+    from .schedule import tile_plan
+    plan = tile_plan(H, W, tile, overlap)
+    up = lambda a: torch.from_numpy(a).to(device)          # noqa: E731
+    dev = (plan, up(plan.oy), up(plan.ox), tuple(up(a) for a in plan.y), tuple(up(a) for a in plan.x))
+    torch.cuda.current_stream(dev[1].device).synchronize()
+    return dev
+
+
+def _plan_on(plan, device=None):
+    """The checked plan alone, or with a device its ``_device_plan``."""
+    from .schedule import TilePlan
+    if not isinstance(plan, TilePlan):
+        raise ValueError(f'plan: need a schedule.TilePlan (schedule.tile_plan), got {type(plan).__name__}')
+    return plan if device is None else _device_plan(plan.H, plan.W, plan.tile, plan.overlap, str(device))
+
+
+def tiles_cut(canvas: torch.Tensor, plan) -> torch.Tensor:
+    """Cut the canvas float32 [3, H, W] (or [1, 3, H, W]) into the overlapping tiles of ``plan`` = ``schedule.tile_plan(H, W, tile, overlap)``
+    (afx_tiles_cut) -> float32 [T, 3, th, tw], tile iy * kx + ix from the corner (oy[iy], ox[ix]), values bit for bit.  The plan's lists
+    are uploaded once per geometry and kept.  Nothing is copied or cast: a wrong dtype or layout raises."""
+    _gpu(canvas, name='canvas')
+    plan = _plan_on(plan)
+    if canvas.dim() == 4 and canvas.shape[0] == 1:
+        canvas = canvas[0]
+    if canvas.dim() != 3 or tuple(canvas.shape) != (3, plan.H, plan.W):
+        raise ValueError(f'canvas: need float32 [3, H, W] of the plan\'s canvas ({plan.H} x {plan.W}), got {tuple(canvas.shape)}')
+    canvas = _packed(canvas, torch.float32, canvas.shape, 'canvas')
+    plan, oy, ox, _, _ = _plan_on(plan, canvas.device)
+    tiles = torch.empty(plan.T, 3, plan.th, plan.tw, dtype=torch.float32, device=canvas.device)
+    _lib.check(_lib.load().afx_tiles_cut(_p(canvas), plan.H, plan.W, _p(oy), plan.ky, _p(ox), plan.kx, plan.th, plan.tw, _p(tiles), _s()))
+    return tiles
+
+
+def tiles_merge(tiles: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cross-fade decoded tiles float32 [T, 3, th, tw] in [-1, 1] back into one image (afx_tiles_merge) -> uint8 [H, W, 3]: per pixel and
+    channel, in fp32, taps ascending, rows outer and columns inner, acc = sum_a wy[y, a] (sum_b wx[x, b] fma(0.5, v_ab, 0.5)) over the
+    tiles that cover the pixel with the weights of ``plan`` (``schedule.tile_plan``), byte = rint(255 clamp(acc, 0, 1)).  One launch, no
+    atomics: the same bits on every run.  ``out``: a uint8 [H, W, 3] buffer to write.  A wrong dtype or layout raises."""
+    _gpu(tiles, out, name='tiles')
+    plan = _plan_on(plan)
+    want = (plan.T, 3, plan.th, plan.tw)
+    if tiles.dim() != 4 or tuple(tiles.shape) != want:
+        raise ValueError(f'tiles: need float32 {list(want)} (the plan\'s T, 3, th, tw), got {tuple(tiles.shape)}')
+    tiles = _packed(tiles, torch.float32, tiles.shape, 'tiles')
+    plan, oy, ox, ytab, xtab = _plan_on(plan, tiles.device)
+    out = torch.empty(plan.H, plan.W, 3, dtype=torch.uint8, device=tiles.device) if out is None else \
+        _packed(out, torch.uint8, (plan.H, plan.W, 3), 'out')
+    _lib.check(_lib.load().afx_tiles_merge(_p(tiles), plan.T, plan.th, plan.tw, _p(oy), plan.ky, _p(ox), plan.kx, _p(ytab[0]), _p(ytab[1]),
+                                           _p(ytab[2]), ytab[2].shape[1], _p(xtab[0]), _p(xtab[1]), _p(xtab[2]), xtab[2].shape[1], _p(out),
+                                           plan.H, plan.W, _s()))
+    return out
+
+
 def _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
     """The operands every teacher step shares, checked: -> (x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n), out and out_bf16
     allocated when None.  sigma and sigma_to may be None (the UniPC step takes its weights instead)."""

@@ -10,7 +10,8 @@ module is attached as ``pipe.vae``.
 
 Beyond the reference: ``__call__`` of both pipelines takes the keyword-only ``image`` / ``image_latents``, ``strength``, ``mask_image`` and
 ``composite`` (image-to-image and inpainting); one more C-ABI call, ``afx_edit_blend``, forms the noised start and, with a
-mask, follows every step.  Without them the call is the text-to-image path unchanged.
+mask, follows every step.  Without them the call is the text-to-image path unchanged.  ``enhance(photo, prompt, scale=, tile=, overlap=,
+strength=)`` of both pipelines reworks a photo of any size through that call on overlapping tiles.
 """
 from __future__ import annotations
 
@@ -53,6 +54,7 @@ def load_transformer_dir(path: str):
 
 class _PipelineBase(ArcFlowLoaderMixin):
     _family = 'flux'
+    _output_class = FluxPipelineOutput
     vae_scale_factor = 8
     default_sample_size = 128
 
@@ -511,6 +513,74 @@ class _PipelineBase(ArcFlowLoaderMixin):
         from PIL import Image
         return [Image.fromarray(x) for x in arr]
 
+    # tiled image-to-image: a photo of any size reworked at its own (or a larger) size -------------------------
+    def _enhance_conditioning(self, prompt, **conditioning) -> Dict[str, Any]:
+        """The family's half of ``enhance``: encode the prompt once -> the conditioning keywords of ``__call__`` for a batch of 1."""
+        raise NotImplementedError
+
+    @torch.inference_mode()
+    def enhance(self, image, prompt: Union[str, List[str]] = None, *, scale: float = 1.0, tile: int = 1024, overlap: int = 128,
+                strength: float = 0.3, tile_batch: int = 4, num_inference_steps: int = 2, timestep_ratio: float = 1.0,
+                total_substeps: int = 128, generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None,
+                output_type: Optional[str] = 'pil', return_dict: bool = True, **conditioning):
+        """Rework one photo of any size at its own size, or ``scale`` times it (the "tile upscale / detail pass"): the photo is resampled
+        to the canvas H' = round(H scale), W' = round(W scale) with Lanczos-3 (``ops.image_resample``; at scale 1 the source's values
+        exactly), the canvas is cut into overlapping tiles of at most ``tile`` pixels a side (``schedule.tile_plan``: sides multiples of
+        16, neighbours sharing at least ``overlap`` pixels; ``ops.tiles_cut``), the tiles go in order, ``tile_batch`` at a time, through
+        this pipeline's own image-to-image call at ``strength`` -- ``self(image=tiles, strength=..., latents=noise, output_type='pt', ...)``,
+        so the result is by construction the merge of ordinary calls --, and the decoded tiles are cross-faded into bytes with one rounding
+        (``ops.tiles_merge``).  Both sides of the canvas must be at least 16 pixels.
+
+        ``image``: one picture in any form ``resize=`` takes (a PIL image, a uint8 numpy array [H, W, 3], a float tensor [3, H, W] in
+        [0, 1]); a batch other than 1 raises.  The prompt is encoded once; the conditioning keywords are the family's, as on ``__call__``
+        (FLUX: ``prompt_embeds``, ``pooled_prompt_embeds``, ``guidance_scale``, ``max_sequence_length``; Qwen-Image: ``prompt_embeds``,
+        ``prompt_embeds_mask``, ``max_sequence_length``).  The tiles' start noise is ``latents`` [T, (th / 16) (tw / 16), 64] if given, else
+        one draw of that shape from ``generator``.  The result has the canvas' size, as with ``padding_mask_crop``: 'pt' the uint8
+        [1, H', W', 3] device tensor, 'np' bytes / 255 as float32, 'pil' images of the bytes; 'latent' raises.
+
+        Out of scope: the teacher (``sample_teacher``), masks, one noise field shared by overlapping tiles (every tile has its own), lists
+        of photos, and equal bits for different ``tile_batch`` values (a batched forward is not promised to equal single ones)."""
+        from ..schedule import tile_plan
+        if output_type == 'latent':
+            raise ValueError("`enhance` returns the image at the canvas' size: output_type 'pil', 'np' or 'pt', not 'latent'")
+        if isinstance(tile_batch, bool) or int(tile_batch) != tile_batch or tile_batch < 1:
+            raise ValueError(f'`tile_batch`: an integer >= 1, got {tile_batch!r}')
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f'`strength` must be in (0, 1], got {strength}')
+        if not 0.0 < float(scale) < float('inf'):
+            raise ValueError(f'`scale` must be positive and finite, got {scale}')
+        src = self._resize_source(image, 'image', 3)
+        B, H, W = (src.shape[0], src.shape[1], src.shape[2]) if src.dtype == torch.uint8 else (src.shape[0], src.shape[2], src.shape[3])
+        if B != 1:
+            raise ValueError(f'`image`: `enhance` takes one picture, got a batch of {B}')
+        Hc, Wc = round(H * float(scale)), round(W * float(scale))
+        if min(Hc, Wc) < 16:
+            raise ValueError(f'the canvas is {Hc} x {Wc} ({H} x {W} at scale {scale}): both sides must be at least 16 pixels')
+        plan = tile_plan(Hc, Wc, tile, overlap)
+        T, hp, wp = plan.T, plan.th // 16, plan.tw // 16
+        if latents is not None and tuple(latents.shape) != (T, hp * wp, 64):
+            raise ValueError(f'`latents` (the tiles\' start noise): need [{T}, {hp * wp}, 64] for {T} tiles of {plan.th} x {plan.tw}, '
+                             f'got {tuple(latents.shape)}')
+        cond = self._enhance_conditioning(prompt, **conditioning)
+        noise, _, _ = self._prepare_latents(T, plan.th, plan.tw, generator, latents)
+        tiles = ops.tiles_cut(ops.image_resample(src, Hc, Wc, 'lanczos3', clamp=True), plan)
+        decoded = torch.empty_like(tiles)
+        for i in range(0, T, int(tile_batch)):
+            n = min(int(tile_batch), T - i)
+            decoded[i:i + n] = self(image=tiles[i:i + n], strength=strength, latents=noise[i:i + n], num_images_per_prompt=n,
+                                    num_inference_steps=num_inference_steps, timestep_ratio=timestep_ratio, total_substeps=total_substeps,
+                                    output_type='pt', **cond).images
+        out = ops.tiles_merge(decoded, plan)[None]
+        if output_type != 'pt':
+            arr = out.cpu().numpy()
+            if output_type == 'np':
+                import numpy as np
+                out = arr.astype(np.float32) / np.float32(255.0)
+            else:
+                from PIL import Image
+                out = [Image.fromarray(x) for x in arr]
+        return self._output_class(images=out) if return_dict else (out,)
+
 
 class ArcFluxPipeline(_PipelineBase):
     r"""Policy-based FLUX pipeline, 2-NFE capable (reference arcflux_pipeline.py:73)."""
@@ -617,6 +687,14 @@ class ArcFluxPipeline(_PipelineBase):
             raise ValueError('If `prompt_embeds` are provided, `pooled_prompt_embeds` also have to be passed.')
         if max_sequence_length is not None and max_sequence_length > 512:
             raise ValueError(f'`max_sequence_length` cannot be greater than 512 but is {max_sequence_length}')
+
+    def _enhance_conditioning(self, prompt, prompt_embeds=None, pooled_prompt_embeds=None, guidance_scale: float = 3.5,
+                              max_sequence_length: int = 512) -> Dict[str, Any]:
+        self.check_inputs(prompt, 16, 16, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
+        if (prompt_embeds.shape[0] if prompt is None else (1 if isinstance(prompt, str) else len(prompt))) != 1:
+            raise ValueError('`enhance` takes one prompt (the tiles share it)')
+        pe, pooled = self.encode_prompt(prompt, None, prompt_embeds, pooled_prompt_embeds, self._execution_device, 1, max_sequence_length)
+        return dict(prompt_embeds=pe, pooled_prompt_embeds=pooled, guidance_scale=guidance_scale, max_sequence_length=max_sequence_length)
 
     @torch.inference_mode()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,

@@ -24,6 +24,7 @@ class QwenImagePipelineOutput:
 
 class ArcQwenImagePipeline(_PipelineBase):
     _family = 'qwen'
+    _output_class = QwenImagePipelineOutput
 
     def __init__(self, scheduler=None, vae=None, text_encoder=None, tokenizer=None, transformer=None,
                  policy_type: str = 'ArcFlow', policy_kwargs: Optional[Dict[str, Any]] = None):
@@ -107,6 +108,17 @@ class ArcQwenImagePipeline(_PipelineBase):
         embeds = torch.stack([torch.cat([r, r.new_zeros(T - r.shape[0], r.shape[1])]) for r in rows])
         emask = torch.stack([torch.cat([torch.ones(r.shape[0], dtype=torch.long), torch.zeros(T - r.shape[0], dtype=torch.long)]) for r in rows])
         return embeds[:, :max_sequence_length], emask[:, :max_sequence_length].to(hidden.device)
+
+    def _enhance_conditioning(self, prompt, prompt_embeds=None, prompt_embeds_mask=None, max_sequence_length: int = 512) -> Dict[str, Any]:
+        if prompt is not None and prompt_embeds is not None:
+            raise ValueError('Cannot forward both `prompt` and `prompt_embeds`.')
+        if prompt_embeds is None:
+            if prompt is None:
+                raise ValueError('Provide either `prompt` or `prompt_embeds`.')
+            prompt_embeds, prompt_embeds_mask = self.encode_prompt(prompt, max_sequence_length=max_sequence_length)
+        if prompt_embeds.shape[0] != 1:
+            raise ValueError('`enhance` takes one prompt (the tiles share it)')
+        return dict(prompt_embeds=prompt_embeds, prompt_embeds_mask=prompt_embeds_mask, max_sequence_length=max_sequence_length)
 
     @torch.inference_mode()
     def __call__(self, prompt: Union[str, List[str]] = None, height: Optional[int] = None, width: Optional[int] = None,

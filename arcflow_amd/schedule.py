@@ -113,6 +113,106 @@ def mask_crop_window(bbox, src_h: int, src_w: int, height: int, width: int, pad:
     return x0, y0, x1, y1
 
 
+AFX_TILE_MAX_TAPS = 4          # arcflow_hip.h: the most tiles that may cover one pixel along an axis
+
+
+def tile_axis_weights(L: int, t: int, origins) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The cross-fade of tiles of side ``t`` at ``origins`` (strictly increasing, first 0, last L - t, no gap) along an axis of ``L``
+    pixels, in fp64: -> (start [L] int32, count [L] int32, w [L, max(count)] float64, zero padded).  Tile i weighs pixel x of its span
+    with u_i(x) = min(x - o_i + 1 if i > 0 else inf, o_i + t - x if i < k - 1 else inf) (1 when both are infinite: a single tile), a ramp
+    that rises from 1 at an inner edge, and w_i(x) = u_i(x) / sum_j u_j(x): a linear cross-fade over whatever the overlap is, full weight
+    on the canvas borders, a partition of unity everywhere.  The tiles covering x are consecutive: start[x] .. start[x] + count[x] - 1."""
+    o = np.asarray(origins, dtype=np.int64)
+    k = int(o.size)
+    x = np.arange(L, dtype=np.int64)
+    first = np.searchsorted(o + t, x, side='right')            # the first tile with o_i + t > x
+    last = np.searchsorted(o, x, side='right') - 1             # the last tile with o_i <= x
+    count = last - first + 1
+    if k < 1 or o[0] != 0 or o[-1] != L - t or (count < 1).any():
+        raise ValueError(f'origins {o.tolist()} with tile side {t} do not cover [0, {L})')
+    taps = int(count.max())
+    w = np.zeros((L, taps), dtype=np.float64)
+    for a in range(taps):
+        i = np.minimum(first + a, k - 1)
+        dl = np.where(i > 0, x - o[i] + 1, np.inf)
+        dr = np.where(i < k - 1, o[i] + t - x, np.inf)
+        u = np.minimum(dl, dr)
+        w[:, a] = np.where(a < count, np.where(np.isinf(u), 1.0, u), 0.0)
+    w /= w.sum(axis=1, keepdims=True)
+    return first.astype(np.int32), count.astype(np.int32), w
+
+
+def tile_axis(L: int, tile: int, overlap: int) -> Tuple[int, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The tile plan of one axis of ``L`` canvas pixels (``pipe.enhance``): -> (t, origins [k] int32, start [L] int32, count [L] int32,
+    w [L, taps] float32), the last three in the form of ``ops.resample_tables`` (numpy here: host integer and fp64 arithmetic only).
+
+        t   = min(tile, 16 (L // 16))                                      the tile's side: the model's size, or all the axis has
+        k   = 1 if L == t else 1 + ceil((L - t) / (t - ov))                ov = min(overlap, t // 2)
+        o_i = (2 i (L - t) + (k - 1)) // (2 (k - 1))                       the even spread of k tiles over [0, L - t], rounded half up
+
+    so o_0 = 0, o_{k-1} = L - t, the origins increase strictly and neighbours share at least ``ov`` pixels (= ``overlap`` whenever the axis
+    holds a whole tile; on a shorter axis, where t < tile, the overlap is capped at half of the tile that fits).  The weights are
+    ``tile_axis_weights`` rounded to fp32 once.  count <= AFX_TILE_MAX_TAPS = 4 by construction (for k >= 3 the real stride exceeds t / 4
+    and the rounded origins keep o_{i+4} - o_i >= t); asserted.  Refused with a ValueError naming the argument: L < 16, tile < 32 or no
+    multiple of 16, overlap no integer in [0, tile // 2]."""
+    for name, v in (('L', L), ('tile', tile), ('overlap', overlap)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'{name}: need an integer, got {v!r}')
+    L, tile, overlap = int(L), int(tile), int(overlap)
+    if L < 16:
+        raise ValueError(f'L: an axis of at least 16 pixels, got {L}')
+    if tile < 32 or tile % 16:
+        raise ValueError(f'tile: a multiple of 16 that is >= 32, got {tile}')
+    if not 0 <= overlap <= tile // 2:
+        raise ValueError(f'overlap: an integer in [0, tile // 2 = {tile // 2}], got {overlap}')
+    t = min(tile, 16 * (L // 16))
+    ov = min(overlap, t // 2)
+    k = 1 if L == t else 1 + -(-(L - t) // (t - ov))
+    origins = np.array([0] if k == 1 else [(2 * i * (L - t) + (k - 1)) // (2 * (k - 1)) for i in range(k)], dtype=np.int32)
+    start, count, w = tile_axis_weights(L, t, origins)
+    assert origins[0] == 0 and origins[-1] == L - t and (np.diff(origins) > 0).all() and (np.diff(origins) <= t - ov).all()
+    assert 1 <= int(count.min()) and int(count.max()) <= AFX_TILE_MAX_TAPS, (L, tile, overlap, int(count.max()))
+    return t, origins, start, count, w.astype(np.float32)
+
+
+class TilePlan(NamedTuple):
+    """``tile_plan``'s result: tile iy * kx + ix of side th x tw has its corner at (oy[iy], ox[ix]); y and x are the axes' (start, count, w)."""
+    H: int
+    W: int
+    tile: int
+    overlap: int
+    th: int
+    tw: int
+    oy: np.ndarray
+    ox: np.ndarray
+    y: Tuple[np.ndarray, np.ndarray, np.ndarray]
+    x: Tuple[np.ndarray, np.ndarray, np.ndarray]
+
+    @property
+    def ky(self) -> int:
+        return int(self.oy.size)
+
+    @property
+    def kx(self) -> int:
+        return int(self.ox.size)
+
+    @property
+    def T(self) -> int:
+        return self.ky * self.kx
+
+
+def tile_plan(H: int, W: int, tile: int, overlap: int) -> TilePlan:
+    """``tile_axis`` of both axes of an ``H`` x ``W`` canvas: ky x kx tiles of th x tw pixels, tile index iy * kx + ix."""
+    try:
+        th, oy, *ytab = tile_axis(H, tile, overlap)
+        tw, ox, *xtab = tile_axis(W, tile, overlap)
+    except ValueError as e:
+        if str(e).startswith('L:'):
+            raise ValueError(f'H, W: both sides of the canvas must be at least 16 pixels, got {H} x {W}') from None
+        raise
+    return TilePlan(int(H), int(W), int(tile), int(overlap), th, tw, oy, ox, tuple(ytab), tuple(xtab))
+
+
 def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
                    num_train_timesteps: int = 1000) -> List[float]:
     """sigma at the start of every student step plus the terminal 0, as the pipelines' ``__call__`` walks them: the raw sub-step grid

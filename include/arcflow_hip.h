@@ -429,6 +429,26 @@ int afx_image_paste(const float* img, const float* mask, int32_t mask_batch, con
                     const int32_t* iv_count, const float* iv_w, int32_t iv_taps, const int32_t* mh_start, const int32_t* mh_count,
                     const float* mh_w, int32_t mh_taps, const int32_t* mv_start, const int32_t* mv_count, const float* mv_w, int32_t mv_taps,
                     void* ws, int64_t ws_bytes, void* stream);
+/* Tiled image-to-image (the pipelines' enhance): a canvas of any size is cut into ky x kx overlapping th x tw tiles with their corners at
+ * (oy[iy], ox[ix]), tile index iy * kx + ix, each tile is edited on its own, and the decoded tiles are cross-faded back into bytes.
+ * oy [ky] and ox [kx] int32, and the axes' tables y_* (H rows) and x_* (W rows) -- start, count [n] int32, w [n, taps] fp32, the tiles
+ * start[i] .. start[i] + count[i] - 1 cover pixel i with the weights w[i, :], which sum to 1 -- are DEVICE pointers (host side:
+ * arcflow_amd.schedule.tile_plan).  th and tw are multiples of 16.
+ * afx_tiles_cut: canvas fp32 [3, H, W] -> tiles fp32 [ky kx, 3, th, tw], values copied bit for bit; 16-byte stores, and 16-byte loads where
+ * the source address allows (else four 4-byte loads).  An origin is clamped into [0, H - th] / [0, W - tw] before any load.  One launch.
+ * afx_tiles_merge: tiles fp32 [T, 3, th, tw] in the decoder's range [-1, 1] -> dst uint8 [H, W, 3] (the layout afx_image_paste writes), per
+ * pixel and channel in fp32, taps in ascending order, rows outer and columns inner, v_ab the value of tile (y_start[y] + a, x_start[x] + b):
+ *     acc = sum_a y_w[y, a] ( sum_b x_w[x, b] fma(0.5, v_ab, 0.5) )   (both sums by fma from 0),   byte = rint(255 clamp(acc, 0, 1)), ties to even.
+ * No atomics and no accumulator canvas: the same bits on every run.  Every byte of dst is written.  Tile indices and in-tile coordinates
+ * are clamped and counts capped at the taps before any load: a bad table gives wrong pixels, never a read outside tiles.  One launch.
+ * AFX_E_INVALID before any launch for a NULL pointer, a misaligned one (4 bytes; afx_tiles_cut's tiles: 16), a size < 1, th or tw no
+ * multiple of 16 or larger than the canvas, T != ky kx, taps outside [1, AFX_TILE_MAX_TAPS], or an output that overlaps an operand. */
+#define AFX_TILE_MAX_TAPS 4
+int afx_tiles_cut(const float* canvas, int32_t H, int32_t W, const int32_t* oy, int32_t ky, const int32_t* ox, int32_t kx, int32_t th,
+                  int32_t tw, float* tiles, void* stream);
+int afx_tiles_merge(const float* tiles, int32_t T, int32_t th, int32_t tw, const int32_t* oy, int32_t ky, const int32_t* ox, int32_t kx,
+                    const int32_t* y_start, const int32_t* y_count, const float* y_w, int32_t y_taps, const int32_t* x_start,
+                    const int32_t* x_count, const float* x_w, int32_t x_taps, void* dst, int32_t H, int32_t W, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,
