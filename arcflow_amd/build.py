@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBNAME = 'libarcflow_hip.so'
-SOURCES = ['afx_gemm.hip', 'afx_attn.hip', 'afx_attn3.hip', 'afx_attn_bwd.hip', 'afx_attn_bwd3.hip', 'afx_elementwise.hip', 'afx_policy.hip', 'afx_train.hip', 'afx_sampler.hip', 'afx_score.hip', 'afx_edit.hip', 'afx_image.hip', 'afx_vae.hip', 'afx_text.hip', 'afx_tn.hip', 'afx_lora.hip', 'afx_ops_api.hip', 'afx_engine.hip']
+SOURCES = ['afx_gemm.hip', 'afx_attn.hip', 'afx_attn3.hip', 'afx_attn_bwd.hip', 'afx_attn_bwd3.hip', 'afx_elementwise.hip', 'afx_policy.hip', 'afx_train.hip', 'afx_sampler.hip', 'afx_score.hip', 'afx_edit.hip', 'afx_image.hip', 'afx_color.hip', 'afx_vae.hip', 'afx_text.hip', 'afx_tn.hip', 'afx_lora.hip', 'afx_ops_api.hip', 'afx_engine.hip']
 HEADERS = ['afx_common.h', 'afx_kernels.h', 'afx_gemm_plan.h', 'afx_gemm_problem.h', 'afx_api_util.h', 'afx_reduce.h', 'afx_attn_bwd3_kernel.inc', os.path.join('..', '..', 'include', 'arcflow_hip.h')]
 HEADERS += [os.path.join('gen', f) for f in sorted(os.listdir(os.path.join(CSRC, 'gen'))) if f.endswith('.inc')]
 

@@ -835,6 +835,53 @@ def tiles_merge(tiles: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -
     return out
 
 
+COLOR_FIX_MODES = {'adain': _lib.AFX_COLOR_ADAIN, 'wavelet': _lib.AFX_COLOR_WAVELET, 'wavelet_levels': _lib.AFX_COLOR_WAVELET_LEVELS}
+
+
+def _color_mode(mode) -> int:
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"mode: 'adain' or 'wavelet' ('wavelet_levels': the per-pass form of 'wavelet', the same bits), got {mode!r}")
+    return COLOR_FIX_MODES[mode]
+
+
+def color_fix_ws(mode: str, batch: int, channels: int, height: int, width: int, device='cuda') -> torch.Tensor:
+    """Workspace of color_fix for a [batch, channels, height, width] edit (afx_color_fix_ws_bytes): 'adain' the fp64 partial sums and the
+    (a, b) pairs, 'wavelet' nothing (one element), 'wavelet_levels' two fp32 copies of the edit's shape."""
+    return _ws(_lib.load().afx_color_fix_ws_bytes, _color_mode(mode), batch, channels, height, width, device=device, min_one=True)
+
+
+def color_fix(edit: torch.Tensor, source: torch.Tensor, mode: str = 'wavelet', src01: bool = True, out: Optional[torch.Tensor] = None,
+              stats: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Give a decoded edit the colours of the picture it was made from (afx_color_fix) -> float32 [B, C, H, W], not clamped.
+    ``edit`` [B, C, H, W] fp32 or bf16 in the decoder's range [-1, 1]; ``source`` float32 [Bs, C, H, W], Bs 1 (shared) or B, in [0, 1]
+    (``src01``, read as 2 s - 1) or already in [-1, 1].  'wavelet': the edit's low band -- five levels of the [1, 2, 1] / 4 blur at
+    dilations 1..16, replicate borders -- is replaced by the source's, out = e + low(s' - e) in one fused launch; 'adain': the edit takes
+    the source's per-(image, channel) mean and deviation, out = fma(a, e, b) with fp64 moments.  Both are bit-reproducible and a batch
+    gives the bits of its single calls; the full rules are in arcflow_hip.h.  ``stats``: a float64 [B, C, 4] buffer that 'adain' fills
+    with (mu_e, var_e, mu_s, var_s).  ``out`` / ``ws``: reuse buffers (ops.color_fix_ws); ``out`` may not be an operand.  Nothing is
+    copied or cast: a CPU tensor, a wrong dtype or a wrong layout raises."""
+    m = _color_mode(mode)
+    _gpu(edit, source, out, stats, ws, name='color_fix')
+    if edit.dim() != 4 or edit.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'edit: need a float32 or bfloat16 [B, C, H, W] tensor, got {tuple(edit.shape)} {edit.dtype}')
+    B, Cn, H, W = edit.shape
+    if source.dim() != 4 or source.shape[0] not in (1, B) or tuple(source.shape[1:]) != (Cn, H, W):
+        raise ValueError(f'source: need float32 [1 or {B}, {Cn}, {H}, {W}] (the edit\'s shape), got {tuple(source.shape)}')
+    edit = _packed(edit, edit.dtype, edit.shape, 'edit')
+    source = _packed(source, torch.float32, source.shape, 'source')
+    out = torch.empty(B, Cn, H, W, dtype=torch.float32, device=edit.device) if out is None else _packed(out, torch.float32, (B, Cn, H, W), 'out')
+    if stats is not None:
+        stats = _packed(stats, torch.float64, (B, Cn, 4), 'stats')
+    if ws is None:
+        ws = color_fix_ws(mode, B, Cn, H, W, edit.device)
+    elif not ws.is_contiguous():
+        raise ValueError('ws: need a contiguous GPU buffer (ops.color_fix_ws)')
+    dt = _lib.AFX_DT_BF16 if edit.dtype == torch.bfloat16 else _lib.AFX_DT_F32
+    _lib.check(_lib.load().afx_color_fix(_p(edit), dt, _p(source), source.shape[0], int(bool(src01)), m, _p(out), _p(stats), _p(ws),
+                                         ws.numel() * ws.element_size(), B, Cn, H, W, _s()))
+    return out
+
+
 def _step_operands(x, pos, neg, sigma, sigma_to, coef, out, out_bf16):
     """The operands every teacher step shares, checked: -> (x, pos, neg, sigma, sigma_to, coef, out, out_bf16, B, n), out and out_bf16
     allocated when None.  sigma and sigma_to may be None (the UniPC step takes its weights instead)."""

@@ -260,15 +260,32 @@ class _PipelineBase(ArcFlowLoaderMixin):
             mask = ops.mask_feather(mask, mask_blur)
         return dict(image=img, image_latents=None, mask=mask, strength=float(strength), paste=dict(source=src, window=window)), height, width
 
+    @staticmethod
+    def _check_color_fix(color_fix, image, mask_image, padding_mask_crop, output_type) -> None:
+        """What ``color_fix`` refuses, before anything runs."""
+        if color_fix is None:
+            return
+        if color_fix not in ('adain', 'wavelet'):
+            raise ValueError(f"`color_fix`: None, 'adain' or 'wavelet', got {color_fix!r}")
+        if image is None:
+            raise ValueError('`color_fix` needs `image`: text-to-image and `image_latents` have no pixels to match the result to')
+        if mask_image is not None or padding_mask_crop is not None:
+            raise ValueError('`color_fix` does not go with `mask_image` (or `padding_mask_crop`): matching a repaint\'s colours to what it '
+                             'replaces undoes the inpainting')
+        if output_type == 'latent':
+            raise ValueError("`color_fix` works on decoded pixels: output_type 'pil', 'np' or 'pt', not 'latent'")
+
     def _edit_inputs(self, image, image_latents, mask_image, strength, height, width, resize=None, mask_blur=0.0, padding_mask_crop=None,
-                     output_type=None):
+                     output_type=None, color_fix=None):
         """Host-side half of the edit arguments: -> (edit, height, width), ``edit`` None on the text-to-image path.  Normalises ``image`` and
         ``mask_image`` to fp32 [B, C, H, W], takes ``height`` / ``width`` from them when not given.  ``resize`` None: nothing is resized, an
         input of another size raises.  'stretch' / 'crop': both are resampled to the call's size on the GPU (ops.image_resample: the image
         with Lanczos-3, the mask with the triangle filter, soft values kept), 'crop' from the largest centred window of the call's aspect
         ratio; ``height`` / ``width`` then default to the source's sides rounded to multiples of 16.  ``mask_blur`` > 0: the
         image-resolution mask is feathered by a Gaussian of that sigma in output pixels (ops.mask_feather) after any resize.
-        ``padding_mask_crop`` (an integer; with it ``output_type`` is checked too): ``_edit_inputs_cropped``."""
+        ``padding_mask_crop`` (an integer; with it ``output_type`` is checked too): ``_edit_inputs_cropped``.  ``color_fix`` is checked
+        first (``_check_color_fix``) and kept in ``edit['color_fix']`` for ``_output``."""
+        self._check_color_fix(color_fix, image, mask_image, padding_mask_crop, output_type)
         mask_blur = float(mask_blur)
         if not 0.0 <= mask_blur < float('inf'):
             raise ValueError(f'`mask_blur` must be a finite sigma >= 0, got {mask_blur}')
@@ -296,7 +313,7 @@ class _PipelineBase(ArcFlowLoaderMixin):
         if image_latents is not None and (image_latents.dim() != 3 or tuple(image_latents.shape[1:]) != ((height // 16) * (width // 16), 64)):
             raise ValueError(f'`image_latents`: need packed [B, {(height // 16) * (width // 16)}, 64] for {height} x {width}, '
                              f'got {tuple(image_latents.shape)}')
-        return dict(image=img, image_latents=image_latents, mask=mask, strength=float(strength)), height, width
+        return dict(image=img, image_latents=image_latents, mask=mask, strength=float(strength), color_fix=color_fix), height, width
 
     def _edit_inputs_as_given(self, image, mask_image, height, width):
         """The ``resize=None`` branch of ``_edit_inputs``: -> (img, mask, height, width); every input must have the call's size."""
@@ -500,8 +517,13 @@ class _PipelineBase(ArcFlowLoaderMixin):
 
     def _output(self, image, edit, composite, output_type, padding_mask_crop=None):
         """The decoded image -> what the call returns.  With ``padding_mask_crop``: the photo's size, from the bytes of ``_paste`` ('pt': the
-        uint8 [B, H, W, 3] device tensor, 'np': bytes / 255 as float32 [B, H, W, 3], 'pil': images of the bytes)."""
+        uint8 [B, H, W, 3] device tensor, 'np': bytes / 255 as float32 [B, H, W, 3], 'pil': images of the bytes).  With ``color_fix`` the
+        decoded image is first matched to the call's ``image`` (ops.color_fix) and is float32 from there on."""
         if padding_mask_crop is None:
+            if edit is not None and edit.get('color_fix') is not None:
+                if image.dtype not in (torch.float32, torch.bfloat16):
+                    image = image.to(torch.float32)
+                image = ops.color_fix(image.contiguous(), edit['image'].to(image.device, torch.float32).contiguous(), edit['color_fix'])
             return self._postprocess(self._composite(image, edit, composite), output_type)
         out = self._paste(image, edit, composite)
         if output_type == 'pt':
@@ -522,7 +544,7 @@ class _PipelineBase(ArcFlowLoaderMixin):
     def enhance(self, image, prompt: Union[str, List[str]] = None, *, scale: float = 1.0, tile: int = 1024, overlap: int = 128,
                 strength: float = 0.3, tile_batch: int = 4, num_inference_steps: int = 2, timestep_ratio: float = 1.0,
                 total_substeps: int = 128, generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None,
-                output_type: Optional[str] = 'pil', return_dict: bool = True, **conditioning):
+                output_type: Optional[str] = 'pil', return_dict: bool = True, color_fix: Optional[str] = None, **conditioning):
         """Rework one photo of any size at its own size, or ``scale`` times it (the "tile upscale / detail pass"): the photo is resampled
         to the canvas H' = round(H scale), W' = round(W scale) with Lanczos-3 (``ops.image_resample``; at scale 1 the source's values
         exactly), the canvas is cut into overlapping tiles of at most ``tile`` pixels a side (``schedule.tile_plan``: sides multiples of
@@ -538,11 +560,15 @@ class _PipelineBase(ArcFlowLoaderMixin):
         one draw of that shape from ``generator``.  The result has the canvas' size, as with ``padding_mask_crop``: 'pt' the uint8
         [1, H', W', 3] device tensor, 'np' bytes / 255 as float32, 'pil' images of the bytes; 'latent' raises.
 
+        ``color_fix`` ('adain' or 'wavelet'; None: off) is handed to that call: every decoded tile is matched to the canvas tile it was cut
+        from (``ops.color_fix``) before the merge, so a tile cannot drift in colour or brightness on its own.
+
         Out of scope: the teacher (``sample_teacher``), masks, one noise field shared by overlapping tiles (every tile has its own), lists
         of photos, and equal bits for different ``tile_batch`` values (a batched forward is not promised to equal single ones)."""
         from ..schedule import tile_plan
         if output_type == 'latent':
             raise ValueError("`enhance` returns the image at the canvas' size: output_type 'pil', 'np' or 'pt', not 'latent'")
+        self._check_color_fix(color_fix, image, None, None, output_type)
         if isinstance(tile_batch, bool) or int(tile_batch) != tile_batch or tile_batch < 1:
             raise ValueError(f'`tile_batch`: an integer >= 1, got {tile_batch!r}')
         if not 0.0 < float(strength) <= 1.0:
@@ -569,7 +595,7 @@ class _PipelineBase(ArcFlowLoaderMixin):
             n = min(int(tile_batch), T - i)
             decoded[i:i + n] = self(image=tiles[i:i + n], strength=strength, latents=noise[i:i + n], num_images_per_prompt=n,
                                     num_inference_steps=num_inference_steps, timestep_ratio=timestep_ratio, total_substeps=total_substeps,
-                                    output_type='pt', **cond).images
+                                    output_type='pt', color_fix=color_fix, **cond).images
         out = ops.tiles_merge(decoded, plan)[None]
         if output_type != 'pt':
             arr = out.cpu().numpy()
@@ -709,7 +735,8 @@ class ArcFluxPipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None):
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None,
+                 color_fix: Optional[str] = None):
         """Text-to-image by default.  ``image`` (or its packed latents ``image_latents``) starts the sampler from the image noised to
         ``strength`` in (0, 1] instead of from pure noise (image-to-image); ``mask_image`` (1 = repaint) keeps the unmasked region on the
         image's own trajectory (inpainting) and, with ``composite``, pastes the original pixels back there after decoding.  ``height`` /
@@ -725,9 +752,14 @@ class ArcFluxPipeline(_PipelineBase):
         aspect ratio (``schedule.mask_crop_window``), and the result is the image at ITS OWN size: the window holds the edit, resampled back
         and blended by the mask (``composite=False``: unblended), every other byte is the image's own (``ops.image_paste``).  'pil' comes
         from those bytes, 'np' is bytes / 255 as float32 [B, H, W, 3], 'pt' the uint8 [B, H, W, 3] device tensor; 'latent' raises.
-        diffusers' ``padding_mask_crop`` + ``apply_overlay`` as recalled; parity unpinned."""
+        diffusers' ``padding_mask_crop`` + ``apply_overlay`` as recalled; parity unpinned.
+        ``color_fix`` ('adain' or 'wavelet'; None: off, and every result as before): the decoded image is matched to ``image`` before
+        anything else is done with it (``ops.color_fix``: 'wavelet' swaps the edit's low band for the image's, 'adain' gives it the image's
+        per-channel mean and deviation), so an image-to-image call keeps the image's colours and lighting.  With it 'pt' returns float32
+        whatever the decoder's dtype.  It needs ``image`` and goes with neither ``mask_image``, ``padding_mask_crop`` nor 'latent'
+        (DESIGN.md 6.3.4)."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
-                                                output_type)
+                                                output_type, color_fix)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)
@@ -797,7 +829,7 @@ class ArcFluxPipeline(_PipelineBase):
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
                        solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0,
-                       padding_mask_crop: Optional[int] = None):
+                       padding_mask_crop: Optional[int] = None, color_fix: Optional[str] = None):
         """Sample the TEACHER (plain FLUX.1-dev): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings), ``guidance_scale`` = the distilled guidance embedding, ``true_cfg_scale`` > 1 = true classifier-free
         guidance against ``negative_prompt`` / ``negative_prompt_embeds`` (a second forward per step; ``guidance_interval`` in
@@ -817,9 +849,10 @@ class ArcFluxPipeline(_PipelineBase):
         trajectory with the start noise (fused into the step kernel, ``afx_teacher_edit_step``).  These follow diffusers' img2img /
         inpaint pipelines as recalled; the reference has no image-conditioned sampling and nothing pins them.  ``resize``
         and ``mask_blur`` are ``__call__``'s too: the device resize of ``image`` / ``mask_image`` and the Gaussian feather of the mask, and so
-        is ``padding_mask_crop``: the edit of a window around the mask, pasted back into the image at its own size."""
+        is ``padding_mask_crop``: the edit of a window around the mask, pasted back into the image at its own size, and ``color_fix``:
+        the decoded image matched to ``image`` ('pt' is float32 then)."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
-                                                output_type)
+                                                output_type, color_fix)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds, max_sequence_length)

@@ -131,13 +131,15 @@ class ArcQwenImagePipeline(_PipelineBase):
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ['latents'], max_sequence_length: int = 512, *,
                  image=None, image_latents: Optional[torch.Tensor] = None, strength: float = 1.0, mask_image=None,
-                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None):
+                 composite: bool = True, resize: Optional[str] = None, mask_blur: float = 0.0, padding_mask_crop: Optional[int] = None,
+                 color_fix: Optional[str] = None):
         """Text-to-image by default; ``image`` / ``image_latents``, ``strength``, ``mask_image``, ``composite``, ``resize`` and ``mask_blur``
         as on ``ArcFluxPipeline.__call__`` (image-to-image and inpainting; ``resize='stretch'|'crop'`` resamples inputs of any size on the GPU,
         ``mask_blur`` feathers the mask), and ``padding_mask_crop`` as there: the edit runs on a window around the mask of an 8-bit image of any size
-        and is pasted back into it at the image's own size."""
+        and is pasted back into it at the image's own size.  ``color_fix`` ('adain' or 'wavelet') as there too: the decoded image is matched
+        to ``image`` (``ops.color_fix``), and 'pt' is float32 then."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
-                                                output_type)
+                                                output_type, color_fix)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:
@@ -215,7 +217,7 @@ class ArcQwenImagePipeline(_PipelineBase):
                        h: Optional[Union[float, str]] = None, *, image=None, image_latents: Optional[torch.Tensor] = None,
                        strength: float = 1.0, mask_image=None, composite: bool = True, solver_order: Optional[int] = None,
                        solver_type: Optional[str] = None, resize: Optional[str] = None, mask_blur: float = 0.0,
-                       padding_mask_crop: Optional[int] = None):
+                       padding_mask_crop: Optional[int] = None, color_fix: Optional[str] = None):
         """Sample the TEACHER (plain Qwen-Image): ``num_inference_steps`` Euler ODE steps (FlowEulerODEScheduler on this pipeline's
         shift settings) with true classifier-free guidance ``true_cfg_scale`` against ``negative_prompt`` /
         ``negative_prompt_embeds`` (+ masks) when it is > 1; ``guidance_scale`` is accepted for signature parity and unused
@@ -227,9 +229,9 @@ class ArcQwenImagePipeline(_PipelineBase):
         ``set_adapters`` do not apply: the teacher is the plain model.  Decoding is ``__call__``'s.  ``image`` / ``image_latents``,
         ``strength``, ``mask_image`` and ``composite``: the teacher's image-to-image and inpainting, as on
         ``ArcFluxPipeline.sample_teacher`` (a suffix of the schedule chosen by ``strength``; unpinned semantics); ``resize`` and
-        ``mask_blur`` and ``padding_mask_crop`` as on ``ArcFluxPipeline.__call__``."""
+        ``mask_blur``, ``padding_mask_crop`` and ``color_fix`` as on ``ArcFluxPipeline.__call__``."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
-                                                output_type)
+                                                output_type, color_fix)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if height % 16 or width % 16:

@@ -449,6 +449,45 @@ int afx_tiles_cut(const float* canvas, int32_t H, int32_t W, const int32_t* oy, 
 int afx_tiles_merge(const float* tiles, int32_t T, int32_t th, int32_t tw, const int32_t* oy, int32_t ky, const int32_t* ox, int32_t kx,
                     const int32_t* y_start, const int32_t* y_count, const float* y_w, int32_t y_taps, const int32_t* x_start,
                     const int32_t* x_count, const float* x_w, int32_t x_taps, void* dst, int32_t H, int32_t W, void* stream);
+/* Colour matching of a decoded edit to the picture it was made from (the pipelines' color_fix=; "wavelet" and "AdaIN" colour fix of tile
+ * upscalers: StableSR's wavelet_reconstruction and adaptive_instance_normalization restated as recalled, parity unpinned).
+ * edit e [batch, C, H, W], `dtype` AFX_DT_F32 or AFX_DT_BF16 (widened to fp32, exactly), in the decoder's range [-1, 1]; src s fp32
+ * [src_batch, C, H, W], src_batch 1 (shared by the batch) or batch; out fp32 [batch, C, H, W], not clamped.  src01 1: the source is in
+ * [0, 1] and is read as s' = fma(2, s, -1), one rounding; src01 0: s' = s.  C, H, W >= 1: an image narrower than a dilation is legal.
+ * AFX_COLOR_WAVELET: the low band of the edit is replaced by the low band of the source, as ONE chain on the difference (high(e) =
+ * e - low(e) and low is linear): per element, in fp32,
+ *     d = s' - e                                                                       (one rounding)
+ *     for r in (1, 2, 4, 8, 16), cl = the clamp of an index into the image (replicate borders, at every level):
+ *         q(y, x) = fma(0.5, d(y, x), 0.25 (d(y, cl(x - r)) + d(y, cl(x + r))))        (two roundings: the sum and the fma)
+ *         d(y, x) = fma(0.5, q(y, x), 0.25 (q(cl(y - r), x) + q(cl(y + r), x)))        (two roundings)
+ *     out = e + d                                                                      (one rounding)
+ * The per-element order is fixed, so the launch structure cannot change a bit: one launch, every level of a 64 x 64 tile and its
+ * 31-pixel apron in LDS; e and s are read once from memory and out is written once (37.7 MB per 3 x 1024 x 1024 fp32 image).  No
+ * workspace (afx_color_fix_ws_bytes = 0; ws is ignored).  AFX_COLOR_WAVELET_LEVELS: the same values, bit for bit, by one launch per pass
+ * through two fp32 planes of ws (8 batch C H W bytes) -- about four times the traffic; the plain form the fused one is checked against.
+ * AFX_COLOR_ADAIN: the edit takes the source's mean and deviation per (image, channel): with n = H W and every element widened to fp64
+ * (the source after the s' transform), both images by the same sequence of operations,
+ *     mu = sum / n,  var = sumsq / n - mu mu  (population variance),  sd = sqrt(var + 1e-5),
+ *     a = float(sd_s / sd_e),  b = float(mu_s - (sd_s / sd_e) mu_e)     (formed in fp64, rounded once each),   out = fma(a, e, b).
+ * Identical planes give a == 1 and b == 0 exactly.  The sums are deterministic on the scheme of afx_image_ssim: one work-group and one
+ * slot of ws (sum, sumsq) per 4096 consecutive elements of a plane (a function of H W alone), the slots of a plane added by a second
+ * launch in that entry's fixed order (lane l of one wave the slots l, l + 64, ... in index order, then the 64 lanes by the shuffle tree);
+ * no atomics, bit-reproducible, and a batch gives the bits of its single calls.  With src_batch 1 the source's moments are those of the
+ * one source.  stats (may be NULL; ignored by the wavelet modes): fp64 [batch, C, 4] = (mu_e, var_e, mu_s, var_s).  Three launches.
+ * ws: afx_color_fix_ws_bytes(mode, batch, C, H, W) bytes (adain: 8 batch C (4 ceil(H W / 4096) + 1)), 8-byte aligned, private to the call
+ * until it completes.
+ * Grid limit: batch C and H W must be below 2^31, and so must the work-groups of a launch -- batch C ceil(H / 64) ceil(W / 64) (wavelet),
+ * 2 batch C ceil(H W / 4096) (adain); the per-pass form walks rows beyond 65535 by a loop.  A shape past it is AFX_E_INVALID.
+ * Every refusal precedes the first launch and leaves out untouched: AFX_E_INVALID for a NULL edit, src or out, a bad dtype or mode, a
+ * src01 other than 0 / 1, a src_batch outside {1, batch}, a size < 1, a misaligned pointer (edit: its element; src, out: 4 bytes; stats,
+ * ws: 8), or out, stats or ws overlapping an operand or each other (in-place operation is refused in every mode); AFX_E_WORKSPACE for a
+ * NULL or short ws when the mode needs one. */
+#define AFX_COLOR_ADAIN 0
+#define AFX_COLOR_WAVELET 1
+#define AFX_COLOR_WAVELET_LEVELS 2
+int64_t afx_color_fix_ws_bytes(int32_t mode, int32_t batch, int32_t C, int32_t H, int32_t W);
+int afx_color_fix(const void* edit, int32_t dtype, const float* src, int32_t src_batch, int32_t src01, int32_t mode, float* out,
+                  double* stats, void* ws, int64_t ws_bytes, int32_t batch, int32_t C, int32_t H, int32_t W, void* stream);
 
 /* Head-logit gradient rows dY = [d_means | log_softmax^T(d_logw) | d_logg | 0] as bf16 (arcflux.py:243-249 backward) */
 int afx_head_grad(const float* d_means, const float* d_logw, const float* d_logg, const void* logw_out, void* dy,

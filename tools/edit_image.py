@@ -113,7 +113,11 @@ def main(argv=None):
     ap.add_argument('--padding-mask-crop', type=int, metavar='N', help='inpaint a photo of any size at its own size: edit a window around the '
                     'mask\'s bounding box, padded by N source pixels, at --height x --width (default 1024 x 1024) and paste the result back; every '
                     'pixel outside the mask keeps the photo\'s own bytes.  Needs --mask; not with --resize')
+    ap.add_argument('--color-fix', choices=['adain', 'wavelet'], help='image-to-image only: match the decoded edit to --image (wavelet: its low '
+                    'band; adain: its per-channel mean and deviation).  Not with --mask or --synthetic')
     args = ap.parse_args(argv)
+    if args.color_fix and (args.mask or args.synthetic):
+        raise SystemExit('--color-fix matches pixels to --image: not with --mask (it would undo the inpainting) or --synthetic (latents only)')
     gen = torch.Generator().manual_seed(args.seed)
     kw = dict(strength=args.strength, num_inference_steps=args.nfe, timestep_ratio=1.0 if args.nfe == 2 else 0.5, generator=gen)
     if args.synthetic:
@@ -169,7 +173,8 @@ def main(argv=None):
         kw.update(padding_mask_crop=crop)             # the result has the photo's size; there are no latents of that size to score
     if student:
         lat = None if crop is not None else pipe(prompt=args.prompt, image=image, mask_image=mask, output_type='latent', **kw).images
-        out = pipe(prompt=args.prompt, image=image, mask_image=mask, **dict(kw, generator=torch.Generator().manual_seed(args.seed))).images[0]
+        out = pipe(prompt=args.prompt, image=image, mask_image=mask, color_fix=args.color_fix,
+                   **dict(kw, generator=torch.Generator().manual_seed(args.seed))).images[0]
         out.save(args.out)
         print(f'wrote {args.out} ({out.size[0]} x {out.size[1]})')
     if args.teacher:
@@ -177,7 +182,7 @@ def main(argv=None):
                    true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt if args.true_cfg_scale > 1.0 else None,
                    resize=kw['resize'], mask_blur=kw['mask_blur'], height=args.height, width=args.width, padding_mask_crop=crop)
         tlat = None if crop is not None else pipe.sample_teacher(output_type='latent', generator=torch.Generator().manual_seed(args.seed), **tkw).images
-        tea = pipe.sample_teacher(generator=torch.Generator().manual_seed(args.seed), **tkw).images[0]
+        tea = pipe.sample_teacher(generator=torch.Generator().manual_seed(args.seed), color_fix=args.color_fix, **tkw).images[0]
         tea.save(_teacher_path(args.out))
         print(f'wrote the teacher\'s edit ({args.steps} steps) to {_teacher_path(args.out)}')
         if student:

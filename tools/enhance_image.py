@@ -71,8 +71,10 @@ def main(argv=None):
     ap.add_argument('--tile', type=int, default=1024, help='the largest tile side, a multiple of 16 (the size the model works at)')
     ap.add_argument('--overlap', type=int, default=128, help='pixels neighbouring tiles share at least, cross-faded; at most tile // 2')
     ap.add_argument('--tile-batch', type=int, default=4, help='tiles per denoiser call')
+    ap.add_argument('--color-fix', choices=['adain', 'wavelet'], help='match every decoded tile to the canvas tile it was cut from before the '
+                    'merge: wavelet swaps the tile\'s low band for the canvas\', adain gives it the canvas\' per-channel mean and deviation')
     args = ap.parse_args(argv)
-    kw = dict(scale=args.scale, tile=args.tile, overlap=args.overlap, strength=args.strength, tile_batch=args.tile_batch,
+    kw = dict(scale=args.scale, tile=args.tile, overlap=args.overlap, strength=args.strength, tile_batch=args.tile_batch, color_fix=args.color_fix,
               num_inference_steps=args.nfe, timestep_ratio=1.0 if args.nfe == 2 else 0.5, generator=torch.Generator().manual_seed(args.seed))
     if args.synthetic:
         import numpy as np
