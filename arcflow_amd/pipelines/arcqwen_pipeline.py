@@ -5,7 +5,6 @@ transformer, arcqwen_pipeline.py:393 / arcqwen.py:325-330), QwenEmbedRope tables
 de-normalisation before the (3-D, T=1) VAE."""
 from __future__ import annotations
 
-import json
 import os
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Union
@@ -14,7 +13,8 @@ import torch
 
 from ..engine import MMDiTEngine
 from ..schedule import FlowMatchEulerDiscreteScheduler
-from .arcflux_pipeline import _PipelineBase, load_transformer_dir
+from .base import ArcFlowPipelineBase, load_scheduler_config, load_transformer_dir
+from .edit_inputs import resolve_size
 
 
 @dataclass
@@ -22,7 +22,7 @@ class QwenImagePipelineOutput:
     images: Any
 
 
-class ArcQwenImagePipeline(_PipelineBase):
+class ArcQwenImagePipeline(ArcFlowPipelineBase):
     _family = 'qwen'
     _output_class = QwenImagePipelineOutput
 
@@ -44,11 +44,7 @@ class ArcQwenImagePipeline(_PipelineBase):
         if not os.path.isdir(os.path.join(root, 'transformer')):
             raise EnvironmentError(f'{root}/transformer not found: pass a local Qwen-Image snapshot directory')
         cfg, sd = load_transformer_dir(os.path.join(root, 'transformer'))
-        sched_cfg = {}
-        sp = os.path.join(root, 'scheduler', 'scheduler_config.json')
-        if os.path.exists(sp):
-            sched_cfg = json.load(open(sp))
-        pipe = cls(scheduler=FlowMatchEulerDiscreteScheduler.from_config(sched_cfg))
+        pipe = cls(scheduler=FlowMatchEulerDiscreteScheduler.from_config(load_scheduler_config(root)))
         pipe._transformer_config, pipe._base_state_dict = cfg, sd
         if os.path.isdir(os.path.join(root, 'vae')):          # AutoencoderKLQwenImage decoder on the HIP engine
             from ..vae import AutoencoderKLQwenImageDecoder
@@ -69,15 +65,6 @@ class ArcQwenImagePipeline(_PipelineBase):
         if 'proj_out.weight' in sd:
             pipe.transformer = pipe._build_engine(teacher_head=True)
             pipe.transformer.load_state_dict(sd)
-        return pipe
-
-    @classmethod
-    def from_state_dict(cls, transformer_config, state_dict, scheduler=None, student=True, **kw):
-        pipe = cls(scheduler=scheduler, **kw)
-        pipe._transformer_config, pipe._base_state_dict = dict(transformer_config), state_dict
-        pipe.transformer = pipe._build_engine(transformer_config.get('num_gaussians', 16),
-                                              transformer_config.get('logweights_channels', 4), teacher_head=not student)
-        pipe.transformer.load_state_dict(state_dict)
         return pipe
 
     # diffusers QwenImagePipeline prompt template (the reference inherits encode_prompt from it: arcqwen_pipeline.py:65,346)
@@ -140,10 +127,7 @@ class ArcQwenImagePipeline(_PipelineBase):
         to ``image`` (``ops.color_fix``), and 'pt' is float32 then."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
                                                 output_type, color_fix)
-        height = height or self.default_sample_size * self.vae_scale_factor
-        width = width or self.default_sample_size * self.vae_scale_factor
-        if height % 16 or width % 16:
-            raise ValueError('`height` and `width` have to be divisible by 16')
+        height, width = resolve_size(height, width, self.default_sample_size * self.vae_scale_factor)
         if prompt is not None and prompt_embeds is not None:
             raise ValueError('Cannot forward both `prompt` and `prompt_embeds`.')
         if prompt_embeds is None:
@@ -171,29 +155,18 @@ class ArcQwenImagePipeline(_PipelineBase):
             return self.transformer.prepare_steps(sigmas, None, None, B, hp * wp, prompt_embeds.shape[1])
         latents = self._denoise(latents, hp, wp, num_inference_steps, total_substeps, timestep_ratio, fwd,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds, prepare, edit=edit)
-        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)
+        return self._finish(latents, hp, wp, output_type, return_dict, edit, composite)
 
-    def _finish(self, latents, hp, wp, output_type, return_dict, edit=None, composite=True, padding_mask_crop=None):
-        """Packed latents -> the call's result: decode through the attached VAE unless ``output_type='latent'``.  An inpainting call
-        (``edit`` with an image and a mask) gets the original pixels pasted back outside the mask unless ``composite`` is off."""
-        device = self._execution_device
-        if output_type == 'latent':
-            image = latents
-        else:
-            if self.vae is None:
-                raise RuntimeError("no VAE decoder attached: use output_type='latent' or set pipe.vae")
-            from ..vae import AutoencoderKLQwenImageDecoder
-            if isinstance(self.vae, AutoencoderKLQwenImageDecoder):   # HIP decoder: un-normalisation + unpack fused into its first kernel
-                image = self._output(self.vae.decode_packed(latents, hp, wp), edit, composite, output_type, padding_mask_crop)
-                return (image,) if not return_dict else QwenImagePipelineOutput(images=image)
-            lat = self._unpack(latents, hp, wp)[:, :, None]
-            mean = torch.tensor(self.vae.config.latents_mean, device=device).view(1, -1, 1, 1, 1)
-            std = torch.tensor(self.vae.config.latents_std, device=device).view(1, -1, 1, 1, 1)
-            image = self.vae.decode((lat * std + mean).to(next(self.vae.parameters()).dtype), return_dict=False)[0][:, :, 0]
-            image = self._output(image, edit, composite, output_type, padding_mask_crop)
-        if not return_dict:
-            return (image,)
-        return QwenImagePipelineOutput(images=image)
+    def _decode(self, latents, hp, wp) -> torch.Tensor:
+        """AutoencoderKLQwenImage (3-D, T = 1): packed latents -> the image [B, 3, 16 hp, 16 wp] in [-1, 1]."""
+        from ..vae import AutoencoderKLQwenImageDecoder
+        if isinstance(self.vae, AutoencoderKLQwenImageDecoder):   # HIP decoder: un-normalisation + unpack fused into its first kernel
+            return self.vae.decode_packed(latents, hp, wp)
+        device = self._execution_device                           # any module with the diffusers AutoencoderKLQwenImage interface
+        lat = self._unpack(latents, hp, wp)[:, :, None]
+        mean = torch.tensor(self.vae.config.latents_mean, device=device).view(1, -1, 1, 1, 1)
+        std = torch.tensor(self.vae.config.latents_std, device=device).view(1, -1, 1, 1, 1)
+        return self.vae.decode((lat * std + mean).to(next(self.vae.parameters()).dtype), return_dict=False)[0][:, :, 0]
 
     def _teacher_text(self, prompt, embeds, mask, num_images_per_prompt, max_sequence_length):
         """-> [B, T_real, D] bf16 on the device: only the real tokens enter the transformer, as in ``__call__``."""
@@ -232,10 +205,7 @@ class ArcQwenImagePipeline(_PipelineBase):
         ``mask_blur``, ``padding_mask_crop`` and ``color_fix`` as on ``ArcFluxPipeline.__call__``."""
         edit, height, width = self._edit_inputs(image, image_latents, mask_image, strength, height, width, resize, mask_blur, padding_mask_crop,
                                                 output_type, color_fix)
-        height = height or self.default_sample_size * self.vae_scale_factor
-        width = width or self.default_sample_size * self.vae_scale_factor
-        if height % 16 or width % 16:
-            raise ValueError('`height` and `width` have to be divisible by 16')
+        height, width = resolve_size(height, width, self.default_sample_size * self.vae_scale_factor)
         if prompt is not None and prompt_embeds is not None:
             raise ValueError('Cannot forward both `prompt` and `prompt_embeds`.')
         if prompt is None and prompt_embeds is None:
@@ -254,4 +224,4 @@ class ArcQwenImagePipeline(_PipelineBase):
             cond['negative_prompt_embeds'] = ne
         out, hp, wp, edit = self._sample_teacher(cond, pe.shape[0], height, width, num_inference_steps, None, true_cfg_scale, generator,
                                                  latents, guidance_interval, orthogonal_guidance, sampler, h, edit, solver_order, solver_type)
-        return self._finish(out, hp, wp, output_type, return_dict, edit, composite, padding_mask_crop)
+        return self._finish(out, hp, wp, output_type, return_dict, edit, composite)

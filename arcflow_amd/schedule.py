@@ -231,7 +231,7 @@ def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep
 
 def student_edit_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
                         strength: float = 1.0, num_train_timesteps: int = 1000) -> List[float]:
-    """``student_sigmas`` of an edit, as the pipelines' ``_denoise_edit`` walks them: the raw grid of ``edit_raw_timesteps`` (every raw time
+    """``student_sigmas`` of an edit, as the pipelines' ``_denoise`` walks them: the raw grid of ``edit_raw_timesteps`` (every raw time
     multiplied by ``strength`` in (0, 1]) through the same static shift in fp32, every step reading the first sub-step of its segment, plus
     the terminal 0.  The first entry is the sigma the source is noised to.  strength == 1.0 returns ``student_sigmas``' list."""
     raw, per_step, total = edit_raw_timesteps(num_inference_steps, total_substeps, timestep_ratio, strength)

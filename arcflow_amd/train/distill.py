@@ -366,7 +366,7 @@ class ArcFlowDistiller:
         ``ops.arcflow_step`` to the next step's sigma (schedule.student_sigmas with cfg.shift / cfg.total_substeps; defaults cfg.nfe,
         cfg.timestep_ratio).  ema=True: on the EMA weights (ema_weights()).  B > 4 runs as micro-batches of 4, as TeacherSampler does.
 
-        ``x0`` [B, N, 64] (packed latents of a source image, fp32): an edit, with the semantics of the pipelines' ``_denoise_edit`` -- start
+        ``x0`` [B, N, 64] (packed latents of a source image, fp32): an edit, with the semantics of the pipelines' ``_denoise`` with an ``edit`` -- start
         on (1 - sigma_0) x0 + sigma_0 noise (``ops.edit_blend``), ``nfe`` steps over ``schedule.student_edit_sigmas(..., strength)``, and with
         ``mask`` [B or 1, N, 4] (1 = repaint: ``schedule.mask_to_tokens``) after every step the kept latent pixels are put back on the
         source's trajectory at the sigma the step landed on, with the same noise every time and none at sigma 0; the next forward reads the

@@ -149,19 +149,19 @@ def test_edit_inputs_normalise_every_accepted_form():
     for name, image in forms.items():
         edit, h, w = pipe._edit_inputs(image, None, None, 0.5, None, None)
         n = 2 if name in ('torch4', 'numpy4', 'pils') else 1
-        assert (h, w) == (32, 48) and edit['image'].dtype == torch.float32 and torch.equal(edit['image'], want[:n]), name
-        assert edit['strength'] == 0.5 and edit['mask'] is None
+        assert (h, w) == (32, 48) and edit.image.dtype == torch.float32 and torch.equal(edit.image, want[:n]), name
+        assert edit.strength == 0.5 and edit.mask is None
     m8 = (torch.rand(32, 48, generator=g) > 0.5).to(torch.uint8) * 255
     mwant = (m8.float() / 255)[None, None]
     for name, mask in {'torch2': mwant[0, 0], 'torch3': mwant[0], 'torch4': mwant, 'numpy2': mwant[0, 0].numpy(), 'numpy3': mwant[0].numpy(),
                        'pil': Image.fromarray(m8.numpy())}.items():
         edit, h, w = pipe._edit_inputs(want, None, mask, 1.0, None, None)
-        assert torch.equal(edit['mask'], mwant), name
+        assert torch.equal(edit.mask, mwant), name
     # the text-to-image path is untouched: no edit, the sizes as given
     assert pipe._edit_inputs(None, None, None, 1.0, None, 512) == (None, None, 512)
     # with latents only, the mask gives the size
     edit, h, w = pipe._edit_inputs(None, torch.zeros(1, 6, 64), mwant, 1.0, None, None)
-    assert (h, w) == (32, 48) and edit['image'] is None
+    assert (h, w) == (32, 48) and edit.image is None
 
 
 def test_edit_prepare_batch_mismatch_and_missing_encoder():

@@ -163,6 +163,32 @@ def test_mask_is_honoured_per_sub_pixel(S):
     assert torch.equal(_bits(soft[~moved]), _bits(S.x0[~moved])) and (soft[moved] != out[moved]).all() and (soft[moved] != S.x0[moved]).all()
 
 
+def test_latents_replaced_by_the_callback_feed_the_next_forward(S):
+    """The loop hands the blend kernel's own bf16 copy of the latents to the next forward.  A callback that returns other latents after
+    step 0 must make that copy stale: the result is, bit for bit, the continuation written out here from the replaced latents -- one
+    forward on THEIR bf16 rounding, ``ops.arcflow_step`` to sigma 0, the masked blend."""
+    from arcflow_amd import ops
+    from arcflow_amd.schedule import edit_raw_timesteps, mask_to_tokens
+    mask = _row_mask(range(8))
+    repl = torch.randn(1, HP * WP, 64, generator=torch.Generator().manual_seed(21))
+
+    def cb(pipe, i, t, kw):
+        return dict(latents=repl.cuda()) if i == 0 else {}
+    got = S.call(image_latents=S.x0, strength=0.6, mask_image=mask, callback_on_step_end=cb)
+    raw, per_step, total = edit_raw_timesteps(NFE, 128, RATIO, 0.6)
+    ts = S.pipe._retrieve_timesteps(raw, 'cuda', HP * WP).float().cpu().tolist()
+    assert sum(per_step) == len(ts)                                 # the second step is the last: it lands on sigma 0
+    t1, ntt = ts[per_step[0]], S.pipe.scheduler.config.num_train_timesteps
+    x, eng = repl.cuda(), S.pipe.transformer
+    pooled = S.pooled.cuda() if S.family == 'flux' else None
+    guidance = torch.full((1,), 3.5, device='cuda', dtype=torch.float32) if S.family == 'flux' and eng.guidance_embeds else None
+    out = eng(x.to(torch.bfloat16), torch.full((1,), t1 / 1000.0, device='cuda'), S.pe.cuda(), pooled, guidance, HP, WP)
+    x = ops.arcflow_step(x, out.means, out.logweights, out.loggammas, t1 / ntt, t1 / ntt, 0.0, eps=1e-4)
+    want, _ = ops.edit_blend(x, S.x0.cuda(), None, mask_to_tokens(mask.cuda(), HP, WP), torch.zeros(1, device='cuda'))
+    assert torch.isfinite(got).all() and torch.equal(_bits(got), _bits(want.cpu()))
+    assert not torch.equal(got, S.call(image_latents=S.x0, strength=0.6, mask_image=mask))           # ... and the replacement was felt
+
+
 def test_determinism_and_generator_equals_explicit_noise(S):
     kw = dict(image_latents=S.x0, strength=0.6, mask_image=_row_mask(range(8)))
     a = S.call(generator=torch.Generator().manual_seed(7), **kw)

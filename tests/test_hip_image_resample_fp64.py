@@ -110,7 +110,7 @@ def test_more_rows_than_the_grid(which):
 
 def test_all_uint8_values_pass_an_identity_table_bit_exactly():
     from arcflow_amd import ops
-    want = np.arange(256, dtype=np.float32) / 255                                     # numpy's float32 x / 255: what _images01 returns today
+    want = np.arange(256, dtype=np.float32) / 255                                     # numpy's float32 x / 255: what edit_inputs.images01 returns today
     for channels in (1, 3):
         src = torch.arange(256, dtype=torch.uint8).view(1, 16, 16, 1).expand(1, 16, 16, channels).contiguous()
         for name in ('lanczos3', 'triangle'):

@@ -177,16 +177,16 @@ def _pipe(family='flux'):
 
 
 def test_default_size_rounding_and_crop_box():
-    pipe = _pipe()
+    from arcflow_amd.pipelines.edit_inputs import crop_box, default_side
     for n, want in ((1, 16), (7, 16), (8, 16), (16, 16), (23, 16), (24, 32), (39, 32), (40, 48), (56, 64), (57, 64), (3000, 3008), (4000, 4000)):
-        assert pipe._default_side(n) == want, n
-    assert pipe._crop_box(40, 56, 32, 32) == (8.0, 0.0, 48.0, 40.0)                    # wider source: centred columns
-    assert pipe._crop_box(56, 40, 32, 32) == (0.0, 8.0, 40.0, 48.0)                    # taller source: centred rows
-    assert pipe._crop_box(30, 100, 32, 16) == (42.5, 0.0, 57.5, 30.0)                  # fractional
-    assert pipe._crop_box(100, 30, 16, 32) == (0.0, 42.5, 30.0, 57.5)
-    assert pipe._crop_box(60, 80, 24, 32) == (0.0, 0.0, 80.0, 60.0)                    # the target aspect already: the whole image
+        assert default_side(n) == want, n
+    assert crop_box(40, 56, 32, 32) == (8.0, 0.0, 48.0, 40.0)                    # wider source: centred columns
+    assert crop_box(56, 40, 32, 32) == (0.0, 8.0, 40.0, 48.0)                    # taller source: centred rows
+    assert crop_box(30, 100, 32, 16) == (42.5, 0.0, 57.5, 30.0)                  # fractional
+    assert crop_box(100, 30, 16, 32) == (0.0, 42.5, 30.0, 57.5)
+    assert crop_box(60, 80, 24, 32) == (0.0, 0.0, 80.0, 60.0)                    # the target aspect already: the whole image
     for sh, sw, h, w in ((37, 53, 48, 32), (3000, 4000, 1024, 1024), (5, 7, 32, 16)):
-        l, u, r, b = pipe._crop_box(sh, sw, h, w)
+        l, u, r, b = crop_box(sh, sw, h, w)
         assert 0 <= l < r <= sw and 0 <= u < b <= sh and abs((r - l) * h - (b - u) * w) < 1e-9 * sw * h          # inside, the call's aspect ...
         assert abs((l + r) / 2 - sw / 2) < 1e-9 and abs((u + b) / 2 - sh / 2) < 1e-9 and (r - l == sw or b - u == sh)       # ... centred, largest
 

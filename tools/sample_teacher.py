@@ -56,8 +56,8 @@ def load_edit(image: str, mask=None, encoder=None, device='cuda'):
         if encoder is None:
             raise SystemExit('--image needs a snapshot whose vae/ holds encoder weights (or a .pt file of latents)')
         from PIL import Image
-        from arcflow_amd.pipelines import ArcFluxPipeline
-        img = ArcFluxPipeline._images01(Image.open(image))
+        from arcflow_amd.pipelines.edit_inputs import images01
+        img = images01(Image.open(image))
         if img.shape[2] % 16 or img.shape[3] % 16:
             raise SystemExit(f'--image {image}: sides must be multiples of 16, got {img.shape[2]} x {img.shape[3]}')
         x0 = encoder.encode_images01(img, sample=False, packed=True).to(torch.float32)
@@ -69,8 +69,8 @@ def load_edit(image: str, mask=None, encoder=None, device='cuda'):
             tokens = m.view(1, h // 2, 2, w // 2, 2).permute(0, 1, 3, 2, 4).reshape(1, (h // 2) * (w // 2), 4).contiguous().to(device)
         else:
             from PIL import Image
-            from arcflow_amd.pipelines import ArcFluxPipeline
-            m = ArcFluxPipeline._images01(Image.open(mask), 'mask', 1)
+            from arcflow_amd.pipelines.edit_inputs import images01
+            m = images01(Image.open(mask), 'mask', 1)
             if tuple(m.shape[2:]) != (8 * h, 8 * w):
                 raise SystemExit(f'--mask {mask} is {m.shape[2]} x {m.shape[3]}, the image is {8 * h} x {8 * w}')
             tokens = mask_to_tokens(m.to(device), h // 2, w // 2)
