@@ -1302,10 +1302,36 @@ def sumsq(x, out_accum):
     return out_accum
 
 
+# The optimizer, EMA and cast wrappers update flat buffers in place through raw pointers and a length: nothing may be converted (a converted
+# copy would take the update and be dropped) and nothing may be shorter than the length passed.
+def _flat(t, dtype, name: str, n: Optional[int] = None) -> int:
+    """A flat operand of an in-place kernel: a GPU tensor of ``dtype``, contiguous, of ``n`` values when given.  -> its numel."""
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise ValueError(f'{name}: need a GPU tensor (the kernel takes a device pointer)')
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f'{name}: need a contiguous {dtype} tensor, got {t.dtype} strides {t.stride()}')
+    if n is not None and t.numel() != n:
+        raise ValueError(f'{name}: {t.numel()} values, need {n}')
+    return t.numel()
+
+
+def _opt_step(step) -> int:
+    if int(step) != step or step < 1:
+        raise ValueError(f'step: the bias corrections need an integer step >= 1, got {step!r}')
+    return int(step)
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     lib = _lib.load()
+    n = _flat(param, torch.float32, 'adamw_step param')
+    _flat(grad, torch.float32, 'adamw_step grad', n)
+    _flat(exp_avg, torch.float32, 'adamw_step exp_avg', n)
+    _flat(exp_avg_sq, torch.float32, 'adamw_step exp_avg_sq', n)
+    step = _opt_step(step)
+    if n == 0:
+        return
     _lib.check(lib.afx_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), lr, betas[0], betas[1], eps,
-                                  weight_decay, step, grad_scale, param.numel(), _s()))
+                                  weight_decay, step, grad_scale, n, _s()))
 
 
 def dynamic_map(signed: bool = True, max_exponent_bits: int = 7, total_bits: int = 8) -> torch.Tensor:
@@ -1364,21 +1390,44 @@ class AdamW8bitState:
 
 def adamw8bit_step(param, grad, st: AdamW8bitState, lr, step, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     lib = _lib.load()
-    assert param.numel() == st.n
+    n = _flat(param, torch.float32, 'adamw8bit_step param')
+    _flat(grad, torch.float32, 'adamw8bit_step grad', n)
+    nb = (n + AdamW8bitState.BLOCK - 1) // AdamW8bitState.BLOCK
+    if st.n != n:
+        raise ValueError(f'adamw8bit_step: the state holds {st.n} values, the parameter {n}')
+    _flat(st.state1, torch.uint8, 'adamw8bit_step state1', n)
+    _flat(st.state2, torch.uint8, 'adamw8bit_step state2', n)
+    _flat(st.absmax1, torch.float32, 'adamw8bit_step absmax1', nb)
+    _flat(st.absmax2, torch.float32, 'adamw8bit_step absmax2', nb)
+    _flat(st.qmap1, torch.float32, 'adamw8bit_step qmap1', 256)
+    _flat(st.qmap2, torch.float32, 'adamw8bit_step qmap2', 256)
+    step = _opt_step(step)
+    if n == 0:
+        return
     _lib.check(lib.afx_adamw8bit_step(_p(param), _p(grad), _p(st.state1), _p(st.state2), _p(st.absmax1), _p(st.absmax2), _p(st.qmap1),
-                                      _p(st.qmap2), lr, betas[0], betas[1], eps, weight_decay, step, grad_scale, param.numel(), _s()))
+                                      _p(st.qmap2), lr, betas[0], betas[1], eps, weight_decay, step, grad_scale, n, _s()))
 
 
 def ema_lerp(ema, net, beta: float):
     lib = _lib.load()
-    _lib.check(lib.afx_ema_lerp(_p(ema), _p(net), beta, ema.numel(), _s()))
+    n = _flat(ema, torch.float32, 'ema_lerp ema')
+    _flat(net, torch.float32, 'ema_lerp net', n)
+    if n == 0:
+        return
+    _lib.check(lib.afx_ema_lerp(_p(ema), _p(net), beta, n, _s()))
 
 
 def cast_bf16(x, out=None):
     lib = _lib.load()
+    n = _flat(x, torch.float32, 'cast_bf16 x')
     if out is None:
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-    _lib.check(lib.afx_cast_f32_bf16(_p(x), _p(out), x.numel(), _s()))
+    _flat(out, torch.bfloat16, 'cast_bf16 out', n)
+    if out.device != x.device:
+        raise ValueError(f'cast_bf16 out: on {out.device}, x on {x.device}')
+    if n == 0:
+        return out
+    _lib.check(lib.afx_cast_f32_bf16(_p(x), _p(out), n, _s()))
     return out
 
 

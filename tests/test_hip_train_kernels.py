@@ -787,7 +787,9 @@ def test_cast_bf16_round_to_nearest_even(ops):
 def test_wrappers_reject_bad_operands_before_launch(ops):
     """The wrappers pass base pointers and row strides only: a transposed view, a wrong dtype, operands of different shapes, a strided or
     short accumulator, or a multi-row gate / scale without a matching rows_per_batch must raise -- before any kernel runs (the sentinel
-    outputs and accumulators stay as they were)."""
+    outputs and accumulators stay as they were).  So must the in-place adamw_step, adamw8bit_step, ema_lerp and cast_bf16 for an operand
+    that is not on the GPU, not of the kernel's dtype, not contiguous or not of the call's length, an AdamW8bitState whose arrays do not
+    match n and ceil(n / 256), a code book that is not 256 float32 entries, or a step below 1."""
     R, C = 256, 512
     g = _gen(1)
     a = torch.randn(R, C, generator=g, device='cuda').bfloat16()
@@ -827,8 +829,57 @@ def test_wrappers_reject_bad_operands_before_launch(ops):
                                                            out=out[1:, :256]),
         'sumsq strided x': lambda: ops.sumsq(x32.t(), acc[:1]),
     }
+    # the in-place optimizer / EMA / cast wrappers: raw pointers and a length, so every operand must be a contiguous GPU tensor of the
+    # kernel's dtype and of that length -- and never a converted copy, which would take the update and be dropped
+    n8 = 512
+    pw, mw, vw, gw = acc[:256], acc[256:512], acc[512:768], x32[0, :256]
+    st_ok = ops.AdamW8bitState(n8, 'cuda')
+
+    def st8(**kw):
+        st = ops.AdamW8bitState(n8, 'cuda')
+        for k, val in kw.items():
+            setattr(st, k, val(getattr(st, k)))
+        return st
+    cases.update({
+        'adamw_step cpu grad': lambda: ops.adamw_step(pw, gw.cpu(), mw, vw, 1e-3, 1),
+        'adamw_step cpu param': lambda: ops.adamw_step(pw.cpu(), gw, mw, vw, 1e-3, 1),
+        'adamw_step bf16 param': lambda: ops.adamw_step(out[0, :256], gw, mw, vw, 1e-3, 1),
+        'adamw_step bf16 grad': lambda: ops.adamw_step(pw, gw.bfloat16(), mw, vw, 1e-3, 1),
+        'adamw_step strided param': lambda: ops.adamw_step(acc[:512:2], gw, mw, vw, 1e-3, 1),
+        'adamw_step strided grad': lambda: ops.adamw_step(pw, x32[0, ::2], mw, vw, 1e-3, 1),
+        'adamw_step grad length': lambda: ops.adamw_step(pw, gw[:255], mw, vw, 1e-3, 1),
+        'adamw_step short exp_avg': lambda: ops.adamw_step(pw, gw, mw[:255], vw, 1e-3, 1),
+        'adamw_step long exp_avg_sq': lambda: ops.adamw_step(pw, gw, mw, acc[512:769], 1e-3, 1),
+        'adamw_step step 0': lambda: ops.adamw_step(pw, gw, mw, vw, 1e-3, 0),
+        'adamw8bit_step cpu param': lambda: ops.adamw8bit_step(acc[:n8].cpu(), x32[0], st_ok, 1e-3, 1),
+        'adamw8bit_step bf16 param': lambda: ops.adamw8bit_step(out[0], x32[0], st_ok, 1e-3, 1),
+        'adamw8bit_step strided param': lambda: ops.adamw8bit_step(acc[::2], x32[0], st_ok, 1e-3, 1),
+        'adamw8bit_step grad length': lambda: ops.adamw8bit_step(acc[:n8], x32[0, 1:], st_ok, 1e-3, 1),
+        'adamw8bit_step state of another n': lambda: ops.adamw8bit_step(acc[:n8 - 1], x32[0, 1:], st_ok, 1e-3, 1),
+        'adamw8bit_step short codes': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(state2=lambda t: t[:-1]), 1e-3, 1),
+        'adamw8bit_step float codes': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(state1=lambda t: t.float()), 1e-3, 1),
+        'adamw8bit_step short absmax': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(absmax1=lambda t: t[:-1]), 1e-3, 1),
+        'adamw8bit_step cpu absmax': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(absmax2=lambda t: t.cpu()), 1e-3, 1),
+        'adamw8bit_step code book of 255': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(qmap1=lambda t: t[1:]), 1e-3, 1),
+        'adamw8bit_step fp64 code book': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st8(qmap2=lambda t: t.double()), 1e-3, 1),
+        'adamw8bit_step step 0': lambda: ops.adamw8bit_step(acc[:n8], x32[0], st_ok, 1e-3, 0),
+        'ema_lerp cpu net': lambda: ops.ema_lerp(pw, gw.cpu(), 0.5),
+        'ema_lerp cpu ema': lambda: ops.ema_lerp(pw.cpu(), gw, 0.5),
+        'ema_lerp bf16 ema': lambda: ops.ema_lerp(out[0, :256], gw, 0.5),
+        'ema_lerp strided ema': lambda: ops.ema_lerp(acc[:512:2], gw, 0.5),
+        'ema_lerp net length': lambda: ops.ema_lerp(pw, gw[1:], 0.5),
+        'cast_bf16 out size': lambda: ops.cast_bf16(x32[0], out=out[0, 1:]),
+        'cast_bf16 fp32 out': lambda: ops.cast_bf16(x32[0], out=acc[:C]),
+        'cast_bf16 cpu out': lambda: ops.cast_bf16(x32[0], out=out[0].cpu()),
+        'cast_bf16 strided out': lambda: ops.cast_bf16(x32[0, :256], out=out[0, ::2]),
+        'cast_bf16 bf16 x': lambda: ops.cast_bf16(a[0], out=out[0]),
+        'cast_bf16 strided x': lambda: ops.cast_bf16(x32[0, ::2], out=out[0, :256]),
+        'cast_bf16 cpu x': lambda: ops.cast_bf16(x32[0].cpu(), out=out[0]),
+    })
     for name, call in cases.items():
         with pytest.raises(ValueError):
             call()
         torch.cuda.synchronize()
         assert bool((acc == 4.0).all()) and bool((out == 4.0).all()), f'{name}: something ran before the error'
+        assert not bool(st_ok.state1.any()) and not bool(st_ok.state2.any()) and not bool(st_ok.absmax1.any()) and not bool(st_ok.absmax2.any()), \
+            f'{name}: the 8-bit state was touched before the error'
