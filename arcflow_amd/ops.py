@@ -835,6 +835,61 @@ def tiles_merge(tiles: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -
     return out
 
 
+CANVAS_FILLS = {'edge': _lib.AFX_FILL_EDGE, 'reflect': _lib.AFX_FILL_REFLECT}
+
+
+def _count(v, name: str) -> int:
+    """An integral value >= 0 as an int (a bool, a fraction or a negative value raises)."""
+    if isinstance(v, bool) or int(v) != v or v < 0:
+        raise ValueError(f'{name}: need an integer >= 0, got {v!r}')
+    return int(v)
+
+
+def canvas_extend(src_u8: torch.Tensor, left: int, top: int, right: int, bottom: int, fill: str = 'reflect',
+                  blend: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The photo ``src_u8`` uint8 [B, H, W, 3] on a canvas extended by ``left``, ``top``, ``right``, ``bottom`` pixels (afx_canvas_extend) ->
+    (canvas uint8 [B, Hc, Wc, 3], mask float32 [1, 1, Hc, Wc]), one launch.  The new pixels are filled from the photo, ``fill`` 'edge'
+    (the border repeated) or 'reflect' (mirrored without repeating the border: ``np.pad``'s modes, for pads of any length); inside the
+    photo's rectangle the canvas holds the photo's bytes.  The mask is 1 on the new pixels, max(0, 1 - (d + 1) / (blend + 1)) inside the
+    rectangle at distance d from the nearest extended side, so ``blend`` pixels inside each extended side are partly repainted and
+    ``blend=0`` gives a binary mask.  Nothing is copied or cast: a wrong dtype, layout or device raises."""
+    if fill not in CANVAS_FILLS:
+        raise ValueError(f"fill: 'edge' or 'reflect', got {fill!r}")
+    if src_u8.dim() != 4 or src_u8.shape[3] != 3 or min(src_u8.shape) < 1 or src_u8.dtype != torch.uint8 or not src_u8.is_contiguous():
+        raise ValueError(f'src_u8: need a contiguous, non-empty uint8 [B, H, W, 3], got {tuple(src_u8.shape)} {src_u8.dtype} '
+                         f'strides {src_u8.stride()}')
+    left, top, right, bottom = (_count(v, n) for v, n in ((left, 'left'), (top, 'top'), (right, 'right'), (bottom, 'bottom')))
+    blend = _count(blend, 'blend')
+    if not (left or top or right or bottom):
+        raise ValueError('left, top, right, bottom: at least one extent must be > 0')
+    _gpu(src_u8, name='src_u8')
+    B, H, W = src_u8.shape[:3]
+    canvas = torch.empty(B, H + top + bottom, W + left + right, 3, dtype=torch.uint8, device=src_u8.device)
+    mask = torch.empty(1, 1, H + top + bottom, W + left + right, dtype=torch.float32, device=src_u8.device)
+    _lib.check(_lib.load().afx_canvas_extend(_p(src_u8), B, H, W, left, top, right, bottom, CANVAS_FILLS[fill], blend, _p(canvas), _p(mask),
+                                             _s()))
+    return canvas, mask
+
+
+def canvas_mark(mask: torch.Tensor, window, blend: int) -> torch.Tensor:
+    """Mark the integer ``window`` = (x0, y0, x1, y1) as painted in the outpainting mask state ``mask`` float32 [1, 1, Hc, Wc] (or [Hc, Wc]),
+    in place (afx_canvas_mark): M = min(M, max(0, 1 - (d + 1) / (blend + 1))) on the window's pixels, d the distance to the nearest window
+    side that is not on the canvas border -- 0 in the window's interior, a ramp of ``blend`` pixels inside each inner side, which the next
+    window cross-fades over.  Pixels outside the window are not touched.  Returns ``mask``.  A wrong dtype, layout or device raises."""
+    if mask.dim() not in (2, 4) or (mask.dim() == 4 and tuple(mask.shape[:2]) != (1, 1)) or min(mask.shape) < 1 or \
+            mask.dtype != torch.float32 or not mask.is_contiguous():
+        raise ValueError(f'mask: need a contiguous, non-empty float32 [1, 1, Hc, Wc] or [Hc, Wc], got {tuple(mask.shape)} {mask.dtype} '
+                         f'strides {mask.stride()}')
+    Hc, Wc = mask.shape[-2:]
+    x0, y0, x1, y1 = (int(v) for v in window)
+    if any(int(v) != v for v in window) or not (0 <= x0 < x1 <= Wc and 0 <= y0 < y1 <= Hc):
+        raise ValueError(f'window: need integers (x0, y0, x1, y1) of a non-empty window inside the {Hc} x {Wc} canvas, got {tuple(window)}')
+    blend = _count(blend, 'blend')
+    _gpu(mask, name='mask')
+    _lib.check(_lib.load().afx_canvas_mark(_p(mask), Hc, Wc, x0, y0, x1, y1, blend, _s()))
+    return mask
+
+
 COLOR_FIX_MODES = {'adain': _lib.AFX_COLOR_ADAIN, 'wavelet': _lib.AFX_COLOR_WAVELET, 'wavelet_levels': _lib.AFX_COLOR_WAVELET_LEVELS}
 
 

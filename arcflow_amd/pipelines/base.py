@@ -1,6 +1,6 @@
 """``ArcFlowPipelineBase``, what ``ArcFluxPipeline`` and ``ArcQwenImagePipeline`` share: the diffusers-style plumbing, the start noise,
 the one student loop (``_denoise``: two C-ABI calls per step, ``afx_mmdit_forward`` and ``afx_arcflow_step``, on latents that never leave
-the packed token layout), the teacher sampling, the way out (``_finish``: the family's ``_decode``, then ``_output``) and ``enhance``."""
+the packed token layout), the teacher sampling, the way out (``_finish``: the family's ``_decode``, then ``_output``), ``enhance`` and ``outpaint``."""
 from __future__ import annotations
 
 import glob
@@ -371,4 +371,65 @@ class ArcFlowPipelineBase(ArcFlowLoaderMixin):
                                     num_inference_steps=num_inference_steps, timestep_ratio=timestep_ratio, total_substeps=total_substeps,
                                     output_type='pt', color_fix=color_fix, **cond).images
         out = edit_inputs.bytes_output(ops.tiles_merge(decoded, plan)[None], output_type)
+        return self._output_class(images=out) if return_dict else (out,)
+
+    # outpainting: the photo on a larger canvas, the new pixels painted window by window ------------------------
+    @torch.inference_mode()
+    def outpaint(self, image, prompt: Union[str, List[str]] = None, *, left: int = 0, right: int = 0, top: int = 0, bottom: int = 0,
+                 tile: int = 1024, overlap: int = 256, blend: int = 32, fill: str = 'reflect', strength: float = 1.0,
+                 num_inference_steps: int = 2, timestep_ratio: float = 1.0, total_substeps: int = 128,
+                 generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None, output_type: Optional[str] = 'pil',
+                 return_dict: bool = True, **conditioning):
+        """Make one photo larger by ``left``, ``right``, ``top``, ``bottom`` pixels and paint what lies beyond its borders.  The photo is
+        laid on the extended canvas, the new pixels filled from it (``fill``: 'reflect' mirrors the photo, 'edge' repeats its border;
+        ``ops.canvas_extend``, which also gives the mask state M: 1 on the new pixels, a ramp over ``blend`` pixels inside every extended
+        side).  ``schedule.outpaint_plan`` lays windows of at most ``tile`` pixels a side over the new area -- the left and right bands
+        first, then the top and bottom bands with the corners, each window ``overlap`` pixels over what is already known -- and every
+        window, in order, is one ordinary inpainting call of this pipeline at the window's size,
+        ``self(image=window of the canvas, mask_image=window of M, strength=..., latents=noise[k], composite=False, output_type='pt')``,
+        whose result ``ops.image_paste`` blends into the canvas by that same mask (once: hence ``composite=False``; where M is 0 the
+        canvas keeps its bytes) and ``ops.canvas_mark`` then marks as painted, leaving a ramp of ``blend`` pixels inside the window's inner
+        sides for the next window to cross-fade over.  A window sees what the windows before it painted: they run one per call, in the
+        plan's order, and cannot be batched.
+
+        ``image``: one photo as 8-bit pixels, a PIL image or a uint8 numpy array [H, W, 3] (the result keeps the photo's bytes); a batch
+        other than 1 raises.  The prompt is encoded once; the conditioning keywords are the family's, as on ``enhance``.  ``strength`` is
+        the inpainting call's (1: the new pixels start from pure noise, the fill only steers through the unmasked context).  The windows'
+        start noise is ``latents`` [T, (wh / 16) (ww / 16), 64] for the plan's T windows of wh x ww, else one draw of that shape from
+        ``generator``.  The result has the canvas' size, (H + top + bottom) x (W + left + right): 'pt' the uint8 [1, Hc, Wc, 3] device
+        tensor, 'np' bytes / 255 as float32, 'pil' images of the bytes; 'latent' raises.  With ``blend=0`` every byte of the photo is kept;
+        otherwise every byte deeper than ``blend`` pixels inside its extended sides.  What is refused (``schedule.outpaint_plan``'s rules
+        among it) is refused before anything runs.
+
+        Out of scope: the teacher (``sample_teacher``), batches of windows, windows of differing sizes, other fills, ``color_fix`` (it
+        refuses masks), lists of photos."""
+        from ..schedule import outpaint_plan
+        if output_type == 'latent':
+            raise ValueError("`outpaint` returns the image at the canvas' size: output_type 'pil', 'np' or 'pt', not 'latent'")
+        if fill not in ops.CANVAS_FILLS:
+            raise ValueError(f"`fill`: 'edge' or 'reflect', got {fill!r}")
+        photo = edit_inputs.photo_bytes(image, 'image', 'the result keeps the photo\'s own bytes')
+        edit_inputs.check_strength(strength)
+        H, W = photo.shape[1:3]
+        plan = outpaint_plan(H, W, left, top, right, bottom, tile, overlap, blend)
+        T, hp, wp = len(plan.windows), plan.wh // 16, plan.ww // 16
+        if latents is not None and tuple(latents.shape) != (T, hp * wp, 64):
+            raise ValueError(f'`latents` (the windows\' start noise): need [{T}, {hp * wp}, 64] for {T} windows of {plan.wh} x {plan.ww}, '
+                             f'got {tuple(latents.shape)}')
+        cond = self._enhance_conditioning(prompt, **conditioning)
+        noise, _, _ = self._prepare_latents(T, plan.wh, plan.ww, generator, latents)
+        src = edit_inputs.resize_source(photo, 'image', 3, self._device)
+        canvas, M = ops.canvas_extend(src, plan.photo[0], plan.photo[1], plan.Wc - plan.photo[2], plan.Hc - plan.photo[3], fill, blend)
+        other = torch.empty_like(canvas)
+        for k, window in enumerate(plan.windows):
+            x0, y0, x1, y1 = window
+            # the window as the call reads it, float(byte) / 255 exactly: a same-size resample of the window's rows is the identity
+            win = ops.image_resample(canvas[:, y0:y1], plan.wh, plan.ww, 'lanczos3', (float(x0), 0.0, float(x1), float(plan.wh)), clamp=True)
+            mwin = M[:, :, y0:y1, x0:x1].contiguous()
+            out = self(image=win, mask_image=mwin, strength=strength, latents=noise[k:k + 1], num_images_per_prompt=1, composite=False,
+                       num_inference_steps=num_inference_steps, timestep_ratio=timestep_ratio, total_substeps=total_substeps,
+                       output_type='pt', **cond).images
+            canvas, other = ops.image_paste(out.to(torch.float32).contiguous(), mwin, canvas, window, out=other), canvas
+            ops.canvas_mark(M, window, blend)
+        out = edit_inputs.bytes_output(canvas, output_type)
         return self._output_class(images=out) if return_dict else (out,)

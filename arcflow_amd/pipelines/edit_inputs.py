@@ -134,6 +134,25 @@ def resize_source(image, name, channels, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
 
 
+def photo_bytes(image, name: str, why: str) -> np.ndarray:
+    """One photo given as 8-bit pixels -- a PIL image (or a list of one) or a uint8 numpy array [H, W, 3] / [1, H, W, 3] -- as uint8
+    [1, H, W, 3] on the host; anything else, or a batch other than 1, raises (``why``: what the caller needs the bytes for)."""
+    if isinstance(image, (list, tuple)) and len(image) and all(hasattr(im, 'convert') for im in image):
+        arr = np.stack([np.array(im.convert('RGB'), dtype=np.uint8) for im in image])
+    elif hasattr(image, 'convert'):
+        arr = np.array(image.convert('RGB'), dtype=np.uint8)[None]
+    elif isinstance(image, np.ndarray) and image.dtype == np.uint8:
+        arr = image[None] if image.ndim == 3 else image
+        if arr.ndim != 4 or arr.shape[3] != 3 or min(arr.shape) < 1:
+            raise ValueError(f'`{name}`: cannot read uint8 {tuple(image.shape)} as [H, W, 3]')
+    else:
+        raise ValueError(f'`{name}` needs 8-bit pixels, a PIL image or a uint8 numpy array [H, W, 3]: {why}; got {type(image).__name__}'
+                         + (f' {image.dtype}' if hasattr(image, 'dtype') else ''))
+    if arr.shape[0] != 1:
+        raise ValueError(f'`{name}`: one picture, got a batch of {arr.shape[0]}')
+    return np.ascontiguousarray(arr)
+
+
 # the three ways in -----------------------------------------------------------------------------------
 def inputs_as_given(image, mask_image, height, width, default_size):
     """``resize=None``: -> (img, mask, height, width) on the host; every input must have the call's size."""

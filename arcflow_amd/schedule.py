@@ -213,6 +213,117 @@ def tile_plan(H: int, W: int, tile: int, overlap: int) -> TilePlan:
     return TilePlan(int(H), int(W), int(tile), int(overlap), th, tw, oy, ox, tuple(ytab), tuple(xtab))
 
 
+class OutpaintPlan(NamedTuple):
+    """``outpaint_plan``'s result: the canvas ``Hc`` x ``Wc``, the photo's rectangle (x0, y0, x1, y1) on it, and the windows (x0, y0, x1, y1),
+    all of ``wh`` x ``ww`` pixels, in the order in which they are painted."""
+    Hc: int
+    Wc: int
+    photo: Tuple[int, int, int, int]
+    wh: int
+    ww: int
+    windows: Tuple[Tuple[int, int, int, int], ...]
+
+
+def _ramp_positive(n: int, lo_inner: bool, hi_inner: bool, blend: int) -> np.ndarray:
+    """Along one axis of a rectangle of ``n`` pixels: where the distance to the nearest counted side (``lo_inner`` / ``hi_inner``: the low /
+    high side counts) is below ``blend``, which is where max(0, 1 - (d + 1) / (blend + 1)) is > 0, in fp32 as in fp64."""
+    i = np.arange(n)
+    pos = np.zeros(n, dtype=bool)
+    if lo_inner:
+        pos |= i < blend
+    if hi_inner:
+        pos |= (n - 1 - i) < blend
+    return pos
+
+
+def _growth_positions(first: int, side: int, overlap: int, limit: int, forward: bool) -> List[int]:
+    """Window origins along the axis a band grows on (``limit`` canvas pixels): the window at ``first`` shifted into the canvas, then every
+    further one ``overlap`` pixels before the end of the one before (``forward``: towards ``limit``; else towards 0), until the border."""
+    out = [min(max(first, 0), limit - side)]
+    while (out[-1] + side < limit) if forward else (out[-1] > 0):
+        nxt = out[-1] + side - overlap if forward else out[-1] - side + overlap
+        out.append(min(max(nxt, 0), limit - side))
+    return out
+
+
+def _band_positions(a: int, L: int, side: int, overlap: int, limit: int) -> List[int]:
+    """Window origins along a band's span [a, a + L): one centred window where the span fits one, else n = ceil((L - side) / (side - overlap))
+    + 1 windows spread evenly from a to a + L - side; each shifted into the canvas of ``limit`` pixels."""
+    if L <= side:
+        starts = [a + (L - side) // 2]
+    else:
+        n = -(-(L - side) // (side - overlap)) + 1
+        starts = [a + (j * (L - side)) // (n - 1) for j in range(n)]
+    return [min(max(s, 0), limit - side) for s in starts]
+
+
+def outpaint_plan(H: int, W: int, left: int, top: int, right: int, bottom: int, tile: int = 1024, overlap: int = 256,
+                  blend: int = 32) -> OutpaintPlan:
+    """The windows in which ``pipe.outpaint`` extends an ``H`` x ``W`` photo by ``left``, ``top``, ``right``, ``bottom`` pixels: host integer
+    arithmetic only.  The canvas is Hc = H + top + bottom by Wc = W + left + right; every window is wh = min(tile, 16 (Hc // 16)) by
+    ww = min(tile, 16 (Wc // 16)) pixels.
+
+    The bands go left, right, top, bottom (those with an extent > 0).  The left and right bands span the photo's rows [top, top + H); the
+    top and bottom bands span the whole canvas width, the side bands being known by then, so they also paint the corners.  Along the axis
+    a band grows on, the first window reaches ``overlap`` pixels back into what is known, each further one starts ``overlap`` pixels before
+    the end of the one before, until the canvas border is reached; along the band, a span [a, a + L) that fits one window gets one, centred,
+    a longer one n = ceil((L - side) / (side - overlap)) + 1 windows at a + floor(j (L - side) / (n - 1)).  A window that would cross the
+    canvas border is shifted inside.  For each growth position come all positions along the band.
+
+    The planner replays the mask state on the host -- ``ops.canvas_extend``'s mask, then the minimum with each window's ramp
+    (``ops.canvas_mark``), of both only whether a pixel is > 0, which is exactly ``d < blend`` -- and drops a window that holds no pixel > 0
+    when its turn comes.
+
+    Refused with a ValueError: sizes or extents that are not integers, H or W < 1, a negative extent or extents that are all 0, a ``tile``
+    that is no multiple of 16 or below 32, a canvas with a side under 16, ``overlap`` outside [1, tile // 2] or not below min(wh, ww),
+    ``blend`` outside [0, overlap // 2]."""
+    vals = dict(H=H, W=W, left=left, top=top, right=right, bottom=bottom, tile=tile, overlap=overlap, blend=blend)
+    for name, v in vals.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'{name}: need an integer, got {v!r}')
+    H, W, left, top, right, bottom, tile, overlap, blend = (int(v) for v in vals.values())
+    if H < 1 or W < 1:
+        raise ValueError(f'H, W: a photo of at least 1 x 1 pixels, got {H} x {W}')
+    if min(left, top, right, bottom) < 0 or not (left or top or right or bottom):
+        raise ValueError(f'left, top, right, bottom: extents >= 0 with at least one > 0, got {(left, top, right, bottom)}')
+    if tile < 32 or tile % 16:
+        raise ValueError(f'tile: a multiple of 16 that is >= 32, got {tile}')
+    Hc, Wc = H + top + bottom, W + left + right
+    if min(Hc, Wc) < 16:
+        raise ValueError(f'the canvas is {Hc} x {Wc}: both sides must be at least 16 pixels')
+    wh, ww = min(tile, 16 * (Hc // 16)), min(tile, 16 * (Wc // 16))
+    if not 1 <= overlap <= tile // 2 or overlap >= min(wh, ww):
+        raise ValueError(f'overlap: an integer in [1, tile // 2 = {tile // 2}] below the window\'s sides {wh} x {ww}, got {overlap}')
+    if not 0 <= blend <= overlap // 2:
+        raise ValueError(f'blend: an integer in [0, overlap // 2 = {overlap // 2}], got {blend}')
+
+    windows: List[Tuple[int, int, int, int]] = []
+    if left:
+        rows = _band_positions(top, H, wh, overlap, Hc)
+        windows += [(x, y, x + ww, y + wh) for x in _growth_positions(left + overlap - ww, ww, overlap, Wc, False) for y in rows]
+    if right:
+        rows = _band_positions(top, H, wh, overlap, Hc)
+        windows += [(x, y, x + ww, y + wh) for x in _growth_positions(left + W - overlap, ww, overlap, Wc, True) for y in rows]
+    if top:
+        cols = _band_positions(0, Wc, ww, overlap, Wc)
+        windows += [(x, y, x + ww, y + wh) for y in _growth_positions(top + overlap - wh, wh, overlap, Hc, False) for x in cols]
+    if bottom:
+        cols = _band_positions(0, Wc, ww, overlap, Wc)
+        windows += [(x, y, x + ww, y + wh) for y in _growth_positions(top + H - overlap, wh, overlap, Hc, True) for x in cols]
+
+    # the replay of the mask state, as booleans: > 0 outside the photo and less than `blend` pixels inside each of its extended sides
+    live = np.ones((Hc, Wc), dtype=bool)
+    live[top:top + H, left:left + W] = _ramp_positive(H, top > 0, bottom > 0, blend)[:, None] | _ramp_positive(W, left > 0, right > 0, blend)[None, :]
+    kept = []
+    for x0, y0, x1, y1 in windows:
+        view = live[y0:y1, x0:x1]
+        if not view.any():
+            continue
+        view &= _ramp_positive(wh, y0 > 0, y1 < Hc, blend)[:, None] | _ramp_positive(ww, x0 > 0, x1 < Wc, blend)[None, :]
+        kept.append((x0, y0, x1, y1))
+    return OutpaintPlan(Hc, Wc, (left, top, left + W, top + H), wh, ww, tuple(kept))
+
+
 def student_sigmas(num_inference_steps: int, total_substeps: int = 128, timestep_ratio: float = 1.0, shift: float = 3.2,
                    num_train_timesteps: int = 1000) -> List[float]:
     """sigma at the start of every student step plus the terminal 0, as the pipelines' ``__call__`` walks them: the raw sub-step grid

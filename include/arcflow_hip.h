@@ -449,6 +449,28 @@ int afx_tiles_cut(const float* canvas, int32_t H, int32_t W, const int32_t* oy, 
 int afx_tiles_merge(const float* tiles, int32_t T, int32_t th, int32_t tw, const int32_t* oy, int32_t ky, const int32_t* ox, int32_t kx,
                     const int32_t* y_start, const int32_t* y_count, const float* y_w, int32_t y_taps, const int32_t* x_start,
                     const int32_t* x_count, const float* x_w, int32_t x_taps, void* dst, int32_t H, int32_t W, void* stream);
+/* Outpainting (the pipelines' outpaint): the photo on a larger canvas, and the mask state that the windows of
+ * arcflow_amd.schedule.outpaint_plan work through one after the other.
+ * afx_canvas_extend: src uint8 [batch, H, W, 3], extents left, top, right, bottom >= 0 (one of them > 0) -> canvas uint8 [batch, Hc, Wc, 3]
+ * with Hc = H + top + bottom, Wc = W + left + right, and mask fp32 [Hc, Wc], both in one launch.  Canvas pixel (y, x) is the photo's pixel
+ * (iy(y - top), ix(x - left)), a bit copy; inside the photo's rectangle the canvas is the photo.  Along an axis of n pixels,
+ *     AFX_FILL_EDGE:     the index is clamp(i, 0, n - 1);
+ *     AFX_FILL_REFLECT:  with p = 2 (n - 1), j = ((i mod p) + p) mod p, the index is j if j < n, else p - j; 0 for n == 1
+ * (numpy's pad modes 'edge' and 'reflect', for pads of any length).  The mask is 1 outside the photo's rectangle and ramp(d) inside it,
+ *     ramp(d) = max(0, 1 - (d + 1) / (blend + 1)),   in fp32: 1.0f - float(d + 1) / float(blend + 1), an IEEE quotient,
+ * d the pixel's distance to the nearest side of the rectangle whose extent is > 0 (0 on the side itself): `blend` pixels inside every
+ * extended side are partly repainted, blend = 0 gives a binary mask.
+ * afx_canvas_mark: mask[y, x] = min(mask[y, x], ramp(d)) in place for the pixels of the integer window (x0, y0, x1, y1) of mask fp32
+ * [Hc, Wc], d the distance to the nearest window side that does not lie on the canvas border (none: the window's area becomes 0).  No
+ * pixel outside the window is read or written.  The state only decreases, so it does not depend on the order of the marks.  One launch.
+ * AFX_E_INVALID before any launch for a NULL pointer, batch, H, W, Hc or Wc < 1, an unknown fill, a negative extent or extents that are
+ * all 0, blend < 0, a window that is empty or not inside the canvas, a mask that is not 4-byte aligned, canvas overlapping src, mask
+ * overlapping either, or a canvas past the grid's index range (a side above 2^31 - 1, batch Hc Wc above 2^59). */
+#define AFX_FILL_EDGE 0
+#define AFX_FILL_REFLECT 1
+int afx_canvas_extend(const void* src, int32_t batch, int32_t H, int32_t W, int32_t left, int32_t top, int32_t right, int32_t bottom,
+                      int32_t fill, int32_t blend, void* canvas, float* mask, void* stream);
+int afx_canvas_mark(float* mask, int32_t Hc, int32_t Wc, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t blend, void* stream);
 /* Colour matching of a decoded edit to the picture it was made from (the pipelines' color_fix=; "wavelet" and "AdaIN" colour fix of tile
  * upscalers: StableSR's wavelet_reconstruction and adaptive_instance_normalization restated as recalled, parity unpinned).
  * edit e [batch, C, H, W], `dtype` AFX_DT_F32 or AFX_DT_BF16 (widened to fp32, exactly), in the decoder's range [-1, 1]; src s fp32
