@@ -1,7 +1,8 @@
 """Shared checks of the fp64 parity tests (test_hip_train_kernels.py, test_text_encoders.py, test_hip_forward_operands.py, test_hip_gemm_fp64.py,
 test_hip_attention_fp64.py, test_hip_vae_fp64.py, test_hip_attention_bwd_fp64.py with attention_bwd_ref.py and test_attention_bwd_ref_cpu.py,
 test_hip_attention_ext_fp64.py with attention_ext_ref.py and test_attention_ext_ref_cpu.py,
-test_hip_forward_frame_fp64.py with forward_frame_ref.py and test_forward_frame_ref_cpu.py): bf16 / fp32
+test_hip_forward_frame_fp64.py with forward_frame_ref.py and test_forward_frame_ref_cpu.py,
+test_hip_gemm_f32out_fp64.py with splitk_ref.py and test_splitk_ref_cpu.py): bf16 / fp32
 outputs against an fp64 reference, the fp64 GEMM reference with its fp32 summation bound and the fp64 convolution reference built from shifted matmuls."""
 import math
 

@@ -6,6 +6,7 @@ fp32 ArcFlow step: rel 1e-5.
 import numpy as np
 import pytest
 import torch
+from splitk_ref import check_quant_codes, quant_scale_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -514,6 +515,9 @@ def test_fp8_quant_and_linear():
     assert torch.allclose(asc, a.float().abs().amax(1) / 448.0, rtol=1e-6)
     ref_codes = (a.float() / asc[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
     assert (aq != ref_codes).float().mean().item() < 1e-3          # ties on the bf16 -> fp32 product may differ in the last bit
+    for x_, q_, s_ in ((a, aq, asc), (w, wq, wsc)):                # ... and every code, a mismatching one included, is one the definition admits
+        assert torch.equal(s_.cpu(), quant_scale_f32(x_))
+        check_quant_codes(x_, q_, s_, what='test_fp8_quant_and_linear', cap=None)
     ad = aq.view(torch.float8_e4m3fn).float() * asc[:, None]
     wd = wq.view(torch.float8_e4m3fn).float() * wsc[:, None]
     exact = ad @ wd.t()                                             # what the fp8 GEMM must reproduce exactly (fp32 accumulate)
@@ -542,6 +546,8 @@ def test_fp8_row_quantiser_register_kernel(K):
     assert torch.allclose(asc, a.float().abs().amax(1) / 448.0, rtol=1e-6)
     ref = (a.float() / asc[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
     assert (aq != ref).float().mean().item() < 1e-3
+    assert torch.equal(asc.cpu(), quant_scale_f32(a))
+    check_quant_codes(a, aq, asc, what=f'quant_rows_fp8 K={K}', cap=None)       # per element (tests/splitk_ref.py): no code outside its admissible set
 
 
 @pytest.mark.gpu

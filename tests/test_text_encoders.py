@@ -1,9 +1,12 @@
 """Prompt encoders (arcflow_amd/text_encoders.py) against the real transformers modules (fp32, CPU, random-init small
 configs of the same architecture): T5 v1.1 encoder, CLIP text model, Qwen2.5-VL language model."""
+import copy
+
 import numpy as np
 import pytest
 import torch
-from bf16_parity import U32, check_bf16
+from bf16_parity import U32, bf16_ulp, check_bf16, proj64
+from splitk_ref import splitk_chunks, splitk_operands, splitk_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -341,3 +344,161 @@ def test_prompt_cache_round_trip_and_online_cond(tmp_path):
     assert (batch['hp'], batch['wp']) == (8, 8)
     assert _rel(batch['prompt_embeds'], online['prompt_embeds'].cpu()) < 4e-3          # fp16 storage of bf16 values
     assert _rel(batch['pooled'], online['pooled'].cpu()) < 4e-3
+
+
+# ------------------------------------------------------------------------------------------ _linear at every released launch shape, per element
+# Widths from the released configurations the tests above quote (T5 v1.1 XXL: d_model 4096, 64 heads of 64, d_ff 10240, gated; CLIP ViT-L/14 text:
+# 768 / 3072, biases; Qwen2.5-VL-7B language model: 3584, 28 + 4 + 4 heads of 128 -> q|k|v 4608 with bias, gate|up 2 x 18944) and the stacking of
+# text_encoders.py.  route: what _Base._linear does with the shape -- 'plain' (ops.linear), 8 / 16 (ops.linear_splitk with that many chunks asked
+# for: K >= 8192) or 0 (ops.linear_splitk, automatic chunking: K >= 3072 and at most 80 tiles of 128 x 128).  A change of the rule changes this table.
+# (encoder, site, M, N, K, bias, residual, route)
+def _qwen_rows(S, qkv_o_route):
+    return [('qwen', 'qkv', S, 4608, 3584, True, False, qkv_o_route), ('qwen', 'o', S, 3584, 3584, False, True, qkv_o_route),
+            ('qwen', 'gate_up', S, 37888, 3584, False, False, 'plain'), ('qwen', 'down', S, 3584, 18944, False, True, 16)]
+
+
+LINEAR_TABLE = [
+    ('t5', 'qkv', 512, 12288, 4096, False, False, 'plain'), ('t5', 'o', 512, 4096, 4096, False, True, 'plain'),
+    ('t5', 'wi', 512, 20480, 4096, False, False, 'plain'), ('t5', 'wo', 512, 4096, 10240, False, True, 8),
+    ('clip', 'qkv', 77, 2304, 768, True, False, 'plain'), ('clip', 'out', 77, 768, 768, True, True, 'plain'),
+    ('clip', 'fc1', 77, 3072, 768, True, False, 'plain'), ('clip', 'fc2', 77, 768, 3072, True, True, 0),
+] + _qwen_rows(40, 0) + _qwen_rows(162, 0) + _qwen_rows(1058, 'plain')
+
+
+@pytest.mark.parametrize('row', LINEAR_TABLE, ids=[f'{r[0]}-{r[1]}-{r[2]}' for r in LINEAR_TABLE])
+def test_linear_rule_every_released_shape_vs_fp64(row, monkeypatch):
+    """The encoders' own _linear on one released launch: the route it takes (recorded round ops.linear / ops.linear_splitk) and the result per
+    element against fp64 with the bound of that route -- splitk_ref.py's for the split-K routes; proj64 (K / 32 + 33) for the plain ones, with the
+    gate_res floor of test_hip_gemm_fp64.py (gate 1: + 2 u (|y| + |r|)) where a residual is added.  Teeth: K column K - 1 left out."""
+    from arcflow_amd import ops
+    from arcflow_amd.text_encoders import _Base
+    enc, site, M, N, K, bias, res, route = row
+    a, w, b, r = splitk_operands(M, N, K, bias, res, seed=M + N + K, device='cuda', draw_on='cuda')
+    calls = []
+    real_splitk, real_linear = ops.linear_splitk, ops.linear
+
+    def rec_splitk(x, w_, b_=None, residual=None, out=None, split_k=0):
+        calls.append(split_k)
+        return real_splitk(x, w_, b_, residual, out=out, split_k=split_k)
+
+    def rec_linear(*args, **kw):
+        calls.append('plain')
+        return real_linear(*args, **kw)
+    monkeypatch.setattr(ops, 'linear_splitk', rec_splitk)
+    monkeypatch.setattr(ops, 'linear', rec_linear)
+    out = _Base('cuda')._linear(a, w, b, r)
+    torch.cuda.synchronize()
+    assert calls == [route], f'{enc} {site} {M}x{N}x{K}: _linear took {calls}, the table says {route}'
+    what = f'_linear {enc} {site} {M}x{N}x{K} route={route}'
+    if route == 'plain':
+        y, fl = proj64(a, w, b)
+        if r is not None:
+            fl = fl + 2 * U32 * (y.abs() + r.double().abs())
+            y = y + r.double()
+    else:
+        y, fl, _ = splitk_ref(a, w, b, r, splitk_chunks(M, N, K, route)[0])
+    check_bf16(out, y, floor=fl, what=what)
+    print(f'{what}: worst err / tol {((out.double() - y).abs() / (bf16_ulp(y) + fl)).max().item():.3f}')
+    with pytest.raises(AssertionError, match='beyond one bf16 ulp'):
+        check_bf16(out, y - a[:, K - 1].double()[:, None] * w[:, K - 1].double()[None, :], floor=fl, min_equal=0.0, what=f'{what}: one K column dropped')
+
+
+# ------------------------------------------------------------------------------------------ one layer of each encoder at its released width
+# The transformers module itself, one layer, a vocabulary of a few hundred, weights rounded to bf16: evaluated on the device in fp64 (the reference;
+# the modules' own fp32 islands -- T5's norm variance and softmax -- stay fp32, 1e-7 against a bar of 1e-3) and as the eager bf16 module.  The bar
+# is test_full_depth_parity.py's: rel-L2(hip, fp64) <= 1.5 x rel-L2(eager bf16, fp64) + 2e-3, per output.  At these widths _linear takes its
+# split-K routes (T5 wo: K = 10240; Qwen down: 18944, q|k|v and o: automatic; CLIP fc2: 3072), which no toy configuration reaches.
+FACTOR, FLOOR = 1.5, 2e-3
+
+
+def _rel64(x, ref):
+    return ((x.double() - ref.double()).norm() / ref.double().norm()).item()
+
+
+def _layer_parity(name, m, run_module, run_hip):
+    """run_module(module) -> tuple of outputs; run_hip() -> the same tuple from the HIP encoder.  Prints and asserts the bar per output."""
+    m.config._attn_implementation = 'eager'
+    m16 = copy.deepcopy(m).to('cuda', torch.bfloat16)
+    hip = run_hip()
+    m64 = m.to('cuda', torch.float64)
+    with torch.no_grad():
+        ref, eag = run_module(m64), run_module(m16)
+    for i, (h, r64, e16) in enumerate(zip(hip, ref, eag)):
+        eh, ee = _rel64(h, r64), _rel64(e16, r64)
+        print(f'{name} output {i}: rel-L2 hip {eh:.3e}, eager bf16 {ee:.3e}')
+        assert eh <= FACTOR * ee + FLOOR, (name, i, eh, ee)
+
+
+def test_t5_xxl_one_layer_vs_fp64():
+    from transformers import T5Config, T5EncoderModel
+    from arcflow_amd.text_encoders import T5Encoder
+    torch.manual_seed(10)
+    cfg = T5Config(vocab_size=300, d_model=4096, d_kv=64, d_ff=10240, num_layers=1, num_heads=64, feed_forward_proj='gated-gelu',
+                   relative_attention_num_buckets=32, relative_attention_max_distance=128, dropout_rate=0.0)
+    m = T5EncoderModel(cfg).eval()
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if 'relative_attention_bias' in n:
+                p.copy_(torch.randn_like(p) * 0.5)
+            if 'layer_norm' in n:
+                p.copy_(1 + 0.2 * torch.randn_like(p))
+    m = _bf16_weights(m)
+    ids = torch.randint(0, 300, (1, 512))
+    enc = T5Encoder(m.state_dict(), num_layers=1, num_heads=64, d_kv=64)
+    _layer_parity('t5-xxl 1 layer S=512', m, lambda mod: (mod(input_ids=ids.cuda()).last_hidden_state[0],), lambda: (enc(ids)[0],))
+
+
+def test_clip_l_one_layer_vs_fp64():
+    from transformers import CLIPTextConfig, CLIPTextModel
+    from arcflow_amd.text_encoders import CLIPTextEncoder
+    torch.manual_seed(11)
+    cfg = CLIPTextConfig(vocab_size=300, hidden_size=768, intermediate_size=3072, num_hidden_layers=1, num_attention_heads=12,
+                         max_position_embeddings=77, hidden_act='quick_gelu', eos_token_id=2, bos_token_id=298, pad_token_id=299)
+    m = CLIPTextModel(cfg).eval()
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if 'layer_norm' in n and n.endswith('weight'):
+                p.copy_(1 + 0.2 * torch.randn_like(p))
+            if n.endswith('bias'):
+                p.copy_(0.3 * torch.randn_like(p))
+    m = _bf16_weights(m)
+    ids = torch.randint(0, 290, (1, 77))
+    ids[0, 0], ids[0, 30:] = 298, 299
+    enc = CLIPTextEncoder(m.state_dict(), num_layers=1, num_heads=12, eos_token_id=2)
+
+    def run_module(mod):
+        o = mod(input_ids=ids.cuda())
+        return o.last_hidden_state[0], o.pooler_output[0]
+
+    def run_hip():
+        hs, pooled = enc(ids)
+        return hs[0], pooled[0]
+    _layer_parity('clip-l 1 layer S=77', m, run_module, run_hip)
+
+
+def test_qwen25_7b_one_layer_vs_fp64():
+    from transformers import Qwen2_5_VLConfig, Qwen2_5_VLForConditionalGeneration
+    from arcflow_amd.text_encoders import Qwen25TextEncoder
+    torch.manual_seed(12)
+    text = dict(vocab_size=400, hidden_size=3584, intermediate_size=18944, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4,
+                max_position_embeddings=2048, rope_theta=1e6, rms_norm_eps=1e-6, tie_word_embeddings=False,
+                rope_scaling=dict(type='mrope', mrope_section=[16, 24, 24]))
+    vis = dict(depth=1, hidden_size=64, intermediate_size=128, num_heads=2, out_hidden_size=3584)
+    try:
+        cfg = Qwen2_5_VLConfig(text_config=text, vision_config=vis)
+    except TypeError:
+        cfg = Qwen2_5_VLConfig(vision_config=vis, **text)
+    m = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if 'layernorm' in n or n.endswith('norm.weight'):
+                p.copy_(1 + 0.2 * torch.randn_like(p))
+            if n.endswith('proj.bias'):
+                p.copy_(0.3 * torch.randn_like(p))
+    m = _bf16_weights(m)
+    ids = torch.randint(0, 390, (1, 162))
+    enc = Qwen25TextEncoder(m.state_dict(), num_layers=1, num_heads=28, num_kv_heads=4)
+    if hasattr(m.config, 'text_config'):
+        m.config.text_config._attn_implementation = 'eager'
+    _layer_parity('qwen2.5-7b 1 layer S=162', m, lambda mod: (mod(input_ids=ids.cuda(), output_hidden_states=True).hidden_states[-1][0],),
+                  lambda: (enc(ids)[0],))
