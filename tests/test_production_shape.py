@@ -10,7 +10,8 @@
   * attention alone at S = 4608 / 4224 / 4173, H = 24 against fp32 softmax(QK^T)V evaluated by torch on the device.
   * one full 19 + 38 block forward at 4096 + 512 tokens: finite, exp(logweights) sums to 1 over K, a second run is
     bit-identical, block 0's output equals a 1-block engine bound to the same tensors, and the LAST single block
-    (rows 1 047 552.. of the stacked modulation matrix) equals the oracle's single block on the engine's own input.
+    (rows 1 047 552.. of the stacked modulation matrix) equals the oracle's single block on the engine's own input -- over the whole
+    matrix, and per row and per column of its increment against the fp64 block (tests/mmdit_block_ref.py).
 
 Tolerances: bf16 trunk vs fp32 oracle on identical bf16-rounded weights, rel-L2 <= 1e-2 on the token matrix after
 ONE block (output rounding of 4-6 chained bf16 GEMMs + bf16 P in attention), 2.5e-2 through the heads.
@@ -239,6 +240,19 @@ def test_full_flux12b_forward_properties_and_block_parity():
     # the increment itself (residual removed): a dead block would pass the check above
     inc = rel_l2(x_last.float().cpu()[None] - xin, ref - xin)
     assert inc < 8e-2, inc
+    # ---- the same block per row and per column (tests/mmdit_block_ref.py): one wrong row of 4608 is 1.5e-2 of the whole matrix at the most,
+    # below both bounds above.  The fp64 block and the oracle's eager-bf16 block, from the engine's own input, stay on the device.
+    import mmdit_block_ref as R
+    wd = {k: v.cuda() for k, v in w.items()}
+    p = f'single_transformer_blocks.{i}.'
+    tables = R.rope_tables('flux_single', hp, hp, T, 'cuda')
+    x_in = ck[nd + i][None]
+    y64 = R.block64('flux_single', wd, p, 24, x_in, temb, T, tables)
+    with D.eager_bf16():
+        y_eager = R.oracle_block('flux_single', wd, p, 24, x_in, temb, T, tables)
+    ratios = R.assert_rows_cols(R.block_row_col_errors(x_in, x_last[None], y64, T), R.block_row_col_errors(x_in, y_eager, y64, T), 1.5,
+                                f'single block {i} of 38 at {N} + {T} rows')
+    print(f'last single block, rows and columns, hip max / eager max: {R.format_ratios(ratios)}')
 
 
 @pytest.mark.parametrize('family,hp,T,B', [('flux', 32, 128, 2), ('qwen', 32, 128, 2), ('flux', 16, 77, 1)])
