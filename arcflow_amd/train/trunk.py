@@ -9,8 +9,10 @@ Design for MI355X:
     step: only the B columns are refreshed), and small updates of B A are not lost in W's bf16 grid.
   * The training forward KEEPS every block's GEMM / attention outputs in HBM (the stash: 54 GB for FLUX at 4 samples; the reference
     checkpoints and recomputes every block, arcflux.py:181-189, to fit 80 GB).  BACKWARD walks the blocks in reverse, reads them back, redoes
-    the element-wise work only (LayerNorm-modulate, RMSNorm + RoPE, GELU, dropout masks) and differentiates by hand (ARCFLOW_TRAIN_RECOMPUTE=1:
-    each block is recomputed from its checkpoint with the same kernels instead): the input gradient and dT = dy B come out of ONE GEMM on the transposed frozen weight with r extra rows
+    the element-wise work only (LayerNorm-modulate, RMSNorm + RoPE, GELU, dropout masks) and differentiates by hand.  Three levels (`_Stash`), the
+    highest that fits: outputs + the adapters' dropped inputs, outputs only, or nothing (ARCFLOW_TRAIN_RECOMPUTE=1: each block is recomputed from
+    its checkpoint with the same kernels).  Per block kind one function per mode: `_double_forward` / `_single_forward` (training forward),
+    `_*_from_stash` and `_*_recompute` (the backward's operands, picked once per block by `backward_sample`), `_*_backward`: the input gradient and dT = dy B come out of ONE GEMM on the transposed frozen weight with r extra rows
     [dx0 | dT] = dy [W^T ; B^T]^T  (N-extension; "wtcat"), then dx = dx0 + ((dT A) . keep/(1-p));
     flash-attention backward, LN / RMSNorm+RoPE / GELU backward kernels.
   * LoRA gradients per adapted linear:   dB += dy^T t,  dA += dT^T dropout(x)   (rank-r products over the tokens, fp32 accumulate-into; round 5:
@@ -27,6 +29,8 @@ import contextlib
 import ctypes as C
 import os
 import math
+import warnings
+from collections import namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -72,6 +76,45 @@ def lora_targets(family: str, num_double: int, num_single: int, D: int) -> List[
     t.append(('time_text_embed.timestep_embedder.linear_1', 'temb.t.l1', 0, D, 256))
     t.append(('time_text_embed.timestep_embedder.linear_2', 'temb.t.l2', 0, D, D))
     return t
+
+
+class _Stash:
+    """What the training forward keeps in HBM for the backward of one batch, one [blocks, rows, columns] bf16 buffer per entry of `table`.
+    Two levels: keep_xd -- the GEMM / attention outputs AND the adapters' dropped inputs, the backward redoes RMSNorm + RoPE only -- or the
+    outputs only: the backward regenerates the dropped inputs element-wise.  The third level is no stash at all (LoraTrunk.stash is None):
+    the backward recomputes every block from its checkpoint.  `_stash_for` picks the highest level that fits.  A stash of no rows keeps
+    nothing: it is what the training forward is handed where there is no stash."""
+
+    @staticmethod
+    def table(nd: int, ns: int, D: int, rp: int, keep_xd: bool) -> List[Tuple[str, int, int]]:
+        """(name, blocks, columns per token).  Double blocks: k|v|q pre-norm, X1, the mlp pre-activation; single blocks: the fused k|v|q|mlp
+        pre-activation; every block: O, and t = dropout(x) A^T of its two adapters.  keep_xd: dropout(x) of every adapted linear, double
+        blocks' mlp1 / mlp2 and single blocks' proj_mlp / proj_out."""
+        t = [('qkv', nd, 3 * D), ('o', nd + ns, D), ('x1', nd, D), ('pre', nd, 4 * D), ('fp', ns, 7 * D), ('t', 2 * (nd + ns), rp)]
+        if keep_xd:
+            t += [('xd1', nd, D), ('xd2', nd, 4 * D), ('xdm', ns, D), ('xdo', ns, 5 * D)]
+        return t
+
+    @classmethod
+    def nbytes(cls, rows: int, *dims) -> int:
+        return 2 * rows * sum(n * c for _, n, c in cls.table(*dims))
+
+    def __init__(self, rows: int, nd: int, ns: int, D: int, rp: int, keep_xd: bool, device):
+        self.rows, self.keep_xd = rows, keep_xd
+        self.buf = {name: torch.empty(n, rows, c, dtype=torch.bfloat16, device=device) for name, n, c in self.table(nd, ns, D, rp, keep_xd)}
+        self.lse: Dict[Tuple[int, int], torch.Tensor] = {}       # (block, row0) -> the attention's L of that sample's forward
+
+    def view(self, name: str, block: int, R: slice) -> torch.Tensor:
+        """Rows R (one sample's) of `block` in buffer `name`; from a stash of no rows a fresh temporary of that shape."""
+        b = self.buf[name]
+        return b[block, R] if self.rows else b.new_empty(R.stop - R.start, b.shape[2])
+
+
+# What a block's backward reads, as views of the stash or of the recompute's buffers (the names are the forward's).
+# keep[stream] = (xd1, t1, xd2, t2): dropout(x) and t of the stream's mlp1 / mlp2 adapters, None where the linear is not adapted.
+# held: buffers the backward does not read but that stay allocated until it is done (the allocator sees the lifetimes it always saw).
+_DoubleSaved = namedtuple('_DoubleSaved', 'Kp V Qp K Q O lse X1 Pre keep held')
+_SingleSaved = namedtuple('_SingleSaved', 'Kp V Qp Mp K Q O lse xd_m t_m xd_o t_o held')
 
 
 class LoraTrunk:
@@ -148,8 +191,9 @@ class LoraTrunk:
         # nobody until the block's slice is exchanged, and their launches have 12-60 tiles: they go to a THIRD stream behind the dgrad
         # GEMM that produced dT and run beside the input-gradient chain (ARCFLOW_TRAIN_WGRAD_STREAM=0: in line).
         self.aux = torch.cuda.Stream(device=self.dev) if os.environ.get('ARCFLOW_TRAIN_WGRAD_STREAM', '1') != '0' else None
-        self.stash: Optional[Dict[str, torch.Tensor]] = None
-        self._lse: Dict[Tuple[int, int], torch.Tensor] = {}
+        self.stash: Optional[_Stash] = None          # None until a training forward built one, and after a fall to recompute
+        self._bf = dict(dtype=torch.bfloat16, device=self.dev)
+        self._no_stash = _Stash(0, self.nd, self.ns, D, self.rp, False, self.dev)
         self.fp8 = False            # block linears' forward / recompute on the fp8 MFMA (enable_fp8)
         self.wq: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}     # packed key -> (e4m3 [out, in], row scales fp32 [out]) of the FROZEN weight
         self._build_frozen_transposes()
@@ -441,170 +485,214 @@ class LoraTrunk:
 
     # ------------------------------------------------------------------ the stash of one student forward
     def stash_bytes(self, rows: int) -> int:
-        D = self.D
-        xd = (self.nd * 5 * D + self.ns * 6 * D) if self.keep_xd else 0
-        return 2 * rows * (self.nd * 9 * D + self.ns * 8 * D + 2 * (self.nd + self.ns) * self.rp + xd)
+        return _Stash.nbytes(rows, self.nd, self.ns, self.D, self.rp, self.keep_xd)
 
-    def _stash_for(self, rows: int) -> Optional[Dict[str, torch.Tensor]]:
-        """Per (block, token): double blocks k|v|q pre-norm (3D), O (D), X1 (D), the mlp pre-activation (4D); single blocks the fused
-        k|v|q|mlp pre-activation (7D) and O (D); t = dropout(x) A^T of both adapters of every block (2 rp); with keep_xd the adapters' dropped
-        inputs (5D / 6D).  FLUX at 4 samples: 54 GB + 37 GB."""
-        if self.stash is None or self.stash['rows'] < rows:      # grow-only: prompt lengths (Qwen-Image) vary from batch to batch, the row ranges used are [0, B S)
-            D, bf = self.D, dict(dtype=torch.bfloat16, device=self.dev)
-            self.stash = None
-            self._lse.clear()
+    def _stash_for(self, rows: int) -> Optional[_Stash]:
+        """The stash of a forward over `rows` tokens at the highest level that fits beside 8 GiB of head-room (FLUX at 4 samples: 54 GB + 37 GB of
+        dropped inputs), or None: the backward recomputes.  A fall flips keep_xd / use_stash on the trunk, so it is tried once."""
+        if self.stash is None or self.stash.rows < rows:         # grow-only: prompt lengths (Qwen-Image) vary from batch to batch, the row ranges used are [0, B S)
+            self.stash = None                                    # (and its LSE tensors)
             free, _ = torch.cuda.mem_get_info(self.dev)
             room = free + torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev) - (8 << 30)
             need = self.stash_bytes(rows)
             if need > room and self.keep_xd:
-                # three levels, the cheapest one that fits (ADVICE r05): GEMM outputs + dropped adapter inputs > GEMM outputs only (round 4's stash) > recompute
-                import warnings
                 self.keep_xd = False
                 warnings.warn(f'LoraTrunk: {need / 2**30:.0f} GiB of kept forward outputs do not fit ({room / 2**30:.0f} GiB available): keeping the GEMM / '
                               f'attention outputs only ({self.stash_bytes(rows) / 2**30:.0f} GiB; the adapters\' dropped inputs are recomputed in the backward)')
                 need = self.stash_bytes(rows)
             if need > room:
                 # not enough HBM for this batch / sequence: the reference's schedule (recompute every block from its checkpoint) still works
-                import warnings
                 warnings.warn(f'LoraTrunk: {need / 2**30:.0f} GiB of kept forward outputs do not fit ({room / 2**30:.0f} GiB available): '
                               f'falling back to recomputing every block in the backward')
                 self.use_stash = False
                 return None
-            self.stash = dict(rows=rows, qkv=torch.empty(self.nd, rows, 3 * D, **bf), o=torch.empty(self.nd + self.ns, rows, D, **bf),
-                              x1=torch.empty(self.nd, rows, D, **bf), pre=torch.empty(self.nd, rows, 4 * D, **bf),
-                              fp=torch.empty(self.ns, rows, 7 * D, **bf), t=torch.empty(2 * (self.nd + self.ns), rows, self.rp, **bf))
-            if self.keep_xd:      # dropout(x) of every adapted linear: double blocks mlp1 (D) / mlp2 (4D) inputs, single blocks proj_mlp (D) / proj_out (5D) inputs
-                self.stash.update(xd1=torch.empty(self.nd, rows, D, **bf), xd2=torch.empty(self.nd, rows, 4 * D, **bf),
-                                  xdm=torch.empty(self.ns, rows, D, **bf), xdo=torch.empty(self.ns, rows, 5 * D, **bf))
+            self.stash = _Stash(rows, self.nd, self.ns, self.D, self.rp, self.keep_xd, self.dev)
         return self.stash
 
-    # ------------------------------------------------------------------ block forward / recompute + backward (one sample)
-    def _double_block(self, i: int, X: torch.Tensor, mod: torch.Tensor, cos, sin, T: int, dXo: Optional[torch.Tensor], grads,
-                      fwd_only: bool = False) -> torch.Tensor:
-        """X [S, D] block input, mod [n_mod] f32 of this sample.  fwd_only: returns the block output (training forward with
-        LoRA dropout).  Otherwise dXo [S, D] is the grad of the block output: recompute, backward, returns the grad of X."""
-        D, S = self.D, X.shape[0]
-        dev = self.dev
-        pk, p = self.packed, f'd{i}.'
-        m0 = i * 12 * D
+    # ------------------------------------------------------------------ steps shared by the modes of a block (one sample)
+    def _double_mod(self, i: int, mod: torch.Tensor):
+        """(offset of double block i in the modulation vector, its [D] slices by (stream, c): c = shift1 scale1 gate1 shift2 scale2 gate2)."""
+        D, m0 = self.D, i * 12 * self.D
         mv = {('img', c): mod[m0 + c * D:m0 + (c + 1) * D] for c in range(6)}
         mv.update({('txt', c): mod[m0 + (6 + c) * D:m0 + (7 + c) * D] for c in range(6)})
-        qkn = pk[p + 'qknorm']                                   # [img_q, img_k, txt_q, txt_k]
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        R = slice(self.row0, self.row0 + S)
-        st = self.stash if self.use_stash else None
-        restore = st is not None and not fwd_only           # backward with the forward's GEMM / attention outputs at hand
-        keepf = st is not None and fwd_only                 # forward that leaves them there
-        kxd = st is not None and 'xd1' in st                # ... and the adapters' dropped inputs
-        QKVp = st['qkv'][i, R] if st is not None else torch.empty(S, 3 * D, **bf)       # pre-norm k | v | q
-        if not restore:
-            Xn1 = torch.empty(S, D, **bf)
-            for s, rows, _, on_stream in self._streams(T, S):
-                with on_stream:
-                    ops.norm_modulate(X[rows], mv[(s, 1)], mv[(s, 0)], out=Xn1[rows])
-                    self._lin(Xn1[rows], p + s + '_qkv', out=QKVp[rows])
-            self._join()
-        Kp, V, Qp = QKVp[:, :D], QKVp[:, D:2 * D], QKVp[:, 2 * D:]
-        K, Q = torch.empty(S, D, **bf), torch.empty(S, D, **bf)
-        O = st['o'][i, R] if st is not None else torch.empty(S, D, **bf)
-        self._rope(Kp, K, qkn[3], qkn[1], cos, sin, S, T)
-        self._rope(Qp, Q, qkn[2], qkn[0], cos, sin, S, T)
-        if restore:
-            lse = self._lse[(i, self.row0)]
+        return m0, mv
+
+    def _single_mod(self, i: int, mod: torch.Tensor):
+        """(offset of single block i in the modulation vector, shift, scale, gate)."""
+        D, m0 = self.D, self.nd * 12 * self.D + i * 3 * self.D
+        return m0, mod[m0:m0 + D], mod[m0 + D:m0 + 2 * D], mod[m0 + 2 * D:m0 + 3 * D]
+
+    def _norm1_qkv(self, p: str, X: torch.Tensor, mv, T: int, Xn1: torch.Tensor, QKVp: torch.Tensor) -> None:
+        """Both streams of double block `p`: LayerNorm-modulate of the block input into Xn1, then the k|v|q GEMM into QKVp."""
+        S = X.shape[0]
+        for s, rows, _, on_stream in self._streams(T, S):
+            with on_stream:
+                ops.norm_modulate(X[rows], mv[(s, 1)], mv[(s, 0)], out=Xn1[rows])
+                self._lin(Xn1[rows], p + s + '_qkv', out=QKVp[rows])
+        self._join()
+
+    def _qk_norms(self, p: str):
+        """The RMSNorm weights of block `p` as ((k text, k image), (q text, q image)); a single block has one pair for all rows."""
+        w = self.packed[p + 'qknorm']                            # double: [img_q, img_k, txt_q, txt_k]; single: [q, k]
+        return ((w[3], w[1]), (w[2], w[0])) if len(w) == 4 else ((w[1], w[1]), (w[0], w[0]))
+
+    def _kvq(self, p: str, P, cos, sin, T: int):
+        """(Kp, V, Qp, K, Q): the pre-norm k | v | q in the first 3D columns of P, and RMSNorm + RoPE of k and q."""
+        D, S, (wk, wq) = self.D, P.shape[0], self._qk_norms(p)
+        Kp, V, Qp = P[:, :D], P[:, D:2 * D], P[:, 2 * D:3 * D]
+        K, Q = torch.empty(S, self.D, **self._bf), torch.empty(S, self.D, **self._bf)
+        self._rope(Kp, K, wk[0], wk[1], cos, sin, S, T)
+        self._rope(Qp, Q, wq[0], wq[1], cos, sin, S, T)
+        return Kp, V, Qp, K, Q
+
+    def _mlp1_gelu(self, p: str, s: str, rows: slice, X1, mv, Xe2, Pre, He, xd_out=None, t_out=None):
+        """Stream s of double block `p` from X1 to the mlp2 operand: Xn2 = LayerNorm-modulate(X1) into Xe2, mlp1 into Pre, GELU into He.
+        xd_out / t_out: where the adapter's dropout(Xn2) and t are kept (stash rows).  Returns (xd1, t1): None without an adapter."""
+        D = self.D
+        ops.norm_modulate(X1[rows], mv[(s, 4)], mv[(s, 3)], out=Xe2[rows][:, :D])
+        sp1, xd1, t1 = self._spec(p + s + '_mlp1'), None, None
+        if sp1 is not None:
+            xd1, t1, _ = self._adapted(sp1, Xe2[rows], rows.start, out=Pre[rows], xd_out=xd_out)
+            if t_out is not None:
+                t_out.copy_(Xe2[rows][:, D:])
         else:
-            lse = ops.attention_fwd_lse_2d(Q, K, V, O, 1, S, self.H)
-            if keepf:
-                self._lse[(i, self.row0)] = lse
-        X1 = st['x1'][i, R] if st is not None else torch.empty(S, D, **bf)
-        Xe2 = self._xe(S, D)                                     # [Xn2 | t1]: the mlp1 operand
-        He = self._xe(S, 4 * D)                                  # [gelu(Pre) | t2]: the mlp2 operand
+            self._lin(Xe2[rows][:, :D], p + s + '_mlp1', out=Pre[rows])
+        ops.gelu(Pre[rows], out=He[rows][:, :4 * D])
+        return xd1, t1
+
+    # ------------------------------------------------------------------ double block (one sample): forward, the backward's operands, backward
+    def _double_forward(self, i: int, st: _Stash, X: torch.Tensor, dm, cos, sin, T: int) -> torch.Tensor:
+        """Training forward (LoRA dropout active): X [S, D] block input, dm = _double_mod(i, mod) of this sample's [n_mod] f32 vector; returns the block output.  The pre-gate
+        branch outputs stay in ybuf (the backward needs them for d_gate); a stash with rows has the GEMMs and the attention write into it,
+        and t and (keep_xd) the adapters' dropped inputs are kept there too."""
+        D, S, p = self.D, X.shape[0], f'd{i}.'
+        R = slice(self.row0, self.row0 + S)
+        _, mv = dm
+        QKVp, Xn1 = st.view('qkv', i, R), torch.empty(S, D, **self._bf)         # pre-norm k | v | q
+        self._norm1_qkv(p, X, mv, T, Xn1, QKVp)
+        Kp, V, Qp, K, Q = self._kvq(p, QKVp, cos, sin, T)
+        O = st.view('o', i, R)
+        lse = ops.attention_fwd_lse_2d(Q, K, V, O, 1, S, self.H)
+        if st.rows:
+            st.lse[(i, self.row0)] = lse
+        X1 = st.view('x1', i, R)
+        Xe2, He = self._xe(S, D), self._xe(S, 4 * D)                            # [Xn2 | t1], [gelu(Pre) | t2]: the mlp1 / mlp2 operands
+        Pre = st.view('pre', i, R)
+        Xo = torch.empty(S, D, **self._bf)
+        for s, rows, _, on_stream in self._streams(T, S):
+            with on_stream:
+                y1, y2 = self.ybuf[2 * i, R][rows], self.ybuf[2 * i + 1, R][rows]
+                self._lin(O[rows], p + s + '_out', out=y1)
+                ops.gate_residual(y1, mv[(s, 2)], X[rows], out=X1[rows])
+                self._mlp1_gelu(p, s, rows, X1, mv, Xe2, Pre, He, xd_out=st.view('xd1', i, R)[rows] if st.keep_xd else None,
+                                t_out=st.view('t', 2 * i, R)[rows] if st.rows else None)
+                sp2 = self._spec(p + s + '_mlp2')
+                if sp2 is not None:
+                    self._adapted(sp2, He[rows], rows.start, out=y2, xd_out=st.view('xd2', i, R)[rows] if st.keep_xd else None)
+                    if st.rows:
+                        st.view('t', 2 * i + 1, R)[rows].copy_(He[rows][:, 4 * D:])
+                else:
+                    self._lin(He[rows][:, :4 * D], p + s + '_mlp2', out=y2)
+                ops.gate_residual(y2, mv[(s, 5)], X1[rows], out=Xo[rows])
+        self._join()
+        return Xo
+
+    def _double_from_stash(self, i: int, st: _Stash, dm, cos, sin, T: int, S: int) -> _DoubleSaved:
+        """The backward's operands read back from the stash: RMSNorm + RoPE is redone, and without keep_xd the adapters' dropped inputs are
+        regenerated element-wise (LayerNorm-modulate of X1 / GELU of Pre, then the dropout mask)."""
+        D, r, p = self.D, self.r, f'd{i}.'
+        R = slice(self.row0, self.row0 + S)
+        _, mv = dm
+        QKVp, X1, Pre = st.view('qkv', i, R), st.view('x1', i, R), st.view('pre', i, R)
+        Kp, V, Qp, K, Q = self._kvq(p, QKVp, cos, sin, T)
+        Xe2, He = self._xe(S, D), self._xe(S, 4 * D)            # the forward's mlp1 / mlp2 operands: written without keep_xd only, allocated and held at both levels
         Xn2, Hh = Xe2[:, :D], He[:, :4 * D]
-        Pre = st['pre'][i, R] if st is not None else torch.empty(S, 4 * D, **bf)
-        Xo = torch.empty(S, D, **bf) if fwd_only else None
-        keep = {}                                                # per stream: (xd1, t1, xd2, t2) of the two adapters
+        keep = {}
         for s, rows, _, on_stream in self._streams(T, S):
             with on_stream:
                 sp1, sp2 = self._spec(p + s + '_mlp1'), self._spec(p + s + '_mlp2')
-                if restore:         # t1 / t2 come back from the stash, and so do the dropped inputs (keep_xd) -- else element-wise work only: Xn2 -> dropout, gelu(Pre) -> dropout
-                    xd1 = t1 = xd2 = t2 = None
-                    if sp1 is not None:
-                        if kxd:
-                            xd1 = st['xd1'][i, R][rows]
-                        else:
-                            ops.norm_modulate(X1[rows], mv[(s, 4)], mv[(s, 3)], out=Xn2[rows])
-                            xd1 = self._dropped(sp1, Xn2[rows], rows.start)
-                        t1 = st['t'][2 * i, R][rows][:, :self.r]
-                    if sp2 is not None:
-                        if kxd:
-                            xd2 = st['xd2'][i, R][rows]
-                        else:
-                            ops.gelu(Pre[rows], out=Hh[rows])
-                            xd2 = self._dropped(sp2, Hh[rows], rows.start)
-                        t2 = st['t'][2 * i + 1, R][rows][:, :self.r]
-                    keep[s] = (xd1, t1, xd2, t2)
-                    continue
-                if fwd_only:        # keep the pre-gate branch output: the backward needs it for d_gate
-                    y1 = self.ybuf[2 * i, self.row0:self.row0 + S][rows]
-                    self._lin(O[rows], p + s + '_out', out=y1)
-                    ops.gate_residual(y1, mv[(s, 2)], X[rows], out=X1[rows])
-                else:
-                    self._lin(O[rows], p + s + '_out', epilogue='gate_res', gate=mv[(s, 2)], residual=X[rows], out=X1[rows])
-                ops.norm_modulate(X1[rows], mv[(s, 4)], mv[(s, 3)], out=Xn2[rows])
+                xd1 = t1 = xd2 = t2 = None
                 if sp1 is not None:
-                    xd1, t1, _ = self._adapted(sp1, Xe2[rows], rows.start, out=Pre[rows], xd_out=st['xd1'][i, R][rows] if (keepf and kxd) else None)
-                    if keepf:
-                        st['t'][2 * i, R][rows].copy_(Xe2[rows][:, D:])
-                else:
-                    xd1 = t1 = None
-                    self._lin(Xn2[rows], p + s + '_mlp1', out=Pre[rows])
-                ops.gelu(Pre[rows], out=Hh[rows])
-                y2 = self.ybuf[2 * i + 1, self.row0:self.row0 + S][rows] if fwd_only else None
+                    if st.keep_xd:
+                        xd1 = st.view('xd1', i, R)[rows]
+                    else:
+                        ops.norm_modulate(X1[rows], mv[(s, 4)], mv[(s, 3)], out=Xn2[rows])
+                        xd1 = self._dropped(sp1, Xn2[rows], rows.start)
+                    t1 = st.view('t', 2 * i, R)[rows][:, :r]
                 if sp2 is not None:
-                    xd2, t2, _ = self._adapted(sp2, He[rows], rows.start, out=y2, main=fwd_only, xd_out=st['xd2'][i, R][rows] if (keepf and kxd) else None)
-                    if keepf:
-                        st['t'][2 * i + 1, R][rows].copy_(He[rows][:, 4 * D:])
-                else:
-                    xd2 = t2 = None
-                    if fwd_only:
-                        self._lin(Hh[rows], p + s + '_mlp2', out=y2)
-                if fwd_only:
-                    ops.gate_residual(y2, mv[(s, 5)], X1[rows], out=Xo[rows])
+                    if st.keep_xd:
+                        xd2 = st.view('xd2', i, R)[rows]
+                    else:
+                        ops.gelu(Pre[rows], out=Hh[rows])
+                        xd2 = self._dropped(sp2, Hh[rows], rows.start)
+                    t2 = st.view('t', 2 * i + 1, R)[rows][:, :r]
                 keep[s] = (xd1, t1, xd2, t2)
         self._join()
-        if fwd_only:
-            return Xo
-        # ---- backward ----
-        dX1 = torch.empty(S, D, **bf)
-        dO = torch.empty(S, D, **bf)
+        return _DoubleSaved(Kp, V, Qp, K, Q, st.view('o', i, R), st.lse[(i, self.row0)], X1, Pre, keep, (Xe2, He))
+
+    def _double_recompute(self, i: int, X: torch.Tensor, dm, cos, sin, T: int) -> _DoubleSaved:
+        """The backward's operands recomputed from the block input.  Against the training forward: X1 = X + gate . (O W^T) comes out of the
+        out-projection's epilogue (the pre-gate branch outputs are in ybuf already), and mlp2 runs only its adapter's xd and t."""
+        D, S, p = self.D, X.shape[0], f'd{i}.'
+        _, mv = dm
+        QKVp, Xn1 = torch.empty(S, 3 * D, **self._bf), torch.empty(S, D, **self._bf)
+        self._norm1_qkv(p, X, mv, T, Xn1, QKVp)
+        Kp, V, Qp, K, Q = self._kvq(p, QKVp, cos, sin, T)
+        O = torch.empty(S, D, **self._bf)
+        lse = ops.attention_fwd_lse_2d(Q, K, V, O, 1, S, self.H)
+        X1 = torch.empty(S, D, **self._bf)
+        Xe2, He = self._xe(S, D), self._xe(S, 4 * D)
+        Pre = torch.empty(S, 4 * D, **self._bf)
+        keep = {}
+        for s, rows, _, on_stream in self._streams(T, S):
+            with on_stream:
+                self._lin(O[rows], p + s + '_out', epilogue='gate_res', gate=mv[(s, 2)], residual=X[rows], out=X1[rows])
+                xd1, t1 = self._mlp1_gelu(p, s, rows, X1, mv, Xe2, Pre, He)
+                sp2, xd2, t2 = self._spec(p + s + '_mlp2'), None, None
+                if sp2 is not None:
+                    xd2, t2, _ = self._adapted(sp2, He[rows], rows.start, main=False)
+                keep[s] = (xd1, t1, xd2, t2)
+        self._join()
+        return _DoubleSaved(Kp, V, Qp, K, Q, O, lse, X1, Pre, keep, (Xn1, Xe2, He))
+
+    def _double_backward(self, i: int, X: torch.Tensor, dm, cos, sin, T: int, sv: _DoubleSaved, dXo: torch.Tensor,
+                         grads: torch.Tensor) -> torch.Tensor:
+        """dXo [S, D]: the gradient of the block output.  Accumulates the adapters' gradients into `grads` and the modulation gradients into
+        dmod; returns the gradient of the block input X."""
+        D, S, p = self.D, X.shape[0], f'd{i}.'
+        R = slice(self.row0, self.row0 + S)
+        (m0, mv), (wk, wq) = dm, self._qk_norms(p)
+        dX1 = torch.empty(S, D, **self._bf)
+        dO = torch.empty(S, D, **self._bf)
         for s, rows, _, on_stream in self._streams(T, S):
             with on_stream:
                 dY2 = ops.add_scale(dXo[rows], gate=mv[(s, 5)])
                 sp1, sp2 = self._spec(p + s + '_mlp1'), self._spec(p + s + '_mlp2')
-                xd1, t1, xd2, t2 = keep[s]
+                xd1, t1, xd2, t2 = sv.keep[s]
                 if sp2 is not None:
                     dH = self._adapted_backward(sp2, dY2, xd2, t2, grads, rows.start)
                 else:
                     dH = ops.linear(dY2, self.wt[p + s + '_mlp2'])
-                dPre = ops.gelu(Pre[rows], dh=dH)
+                dPre = ops.gelu(sv.Pre[rows], dh=dH)
                 if sp1 is not None:
                     dXn2 = self._adapted_backward(sp1, dPre, xd1, t1, grads, rows.start)
                 else:
                     dXn2 = ops.linear(dPre, self.wt[p + s + '_mlp1'])
-                ops.ln_modulate_backward(X1[rows], dXn2, mv[(s, 4)], dres=dXo[rows], out=dX1[rows])
+                ops.ln_modulate_backward(sv.X1[rows], dXn2, mv[(s, 4)], dres=dXo[rows], out=dX1[rows])
                 if self.dmod is not None:      # d(shift3, scale4, gate5, gate2) of this stream
                     so = m0 + (0 if s == 'img' else 6) * D
-                    ops.coldot(dXo[rows], self.ybuf[2 * i + 1, self.row0:self.row0 + S][rows], self.dmod[so + 5 * D:so + 6 * D])
-                    self._dmod_ln(X1[rows], dXn2, so + 4 * D, so + 3 * D)
-                    ops.coldot(dX1[rows], self.ybuf[2 * i, self.row0:self.row0 + S][rows], self.dmod[so + 2 * D:so + 3 * D])
+                    ops.coldot(dXo[rows], self.ybuf[2 * i + 1, R][rows], self.dmod[so + 5 * D:so + 6 * D])
+                    self._dmod_ln(sv.X1[rows], dXn2, so + 4 * D, so + 3 * D)
+                    ops.coldot(dX1[rows], self.ybuf[2 * i, R][rows], self.dmod[so + 2 * D:so + 3 * D])
                 dYo = ops.add_scale(dX1[rows], gate=mv[(s, 2)])
                 ops.linear(dYo, self.wt[p + s + '_out'], out=dO[rows])
         self._join()
-        dQ, dK = torch.empty(S, D, **bf), torch.empty(S, D, **bf)
-        dQKVp = torch.empty(S, 3 * D, **bf)
-        ops.attention_bwd_2d(Q, K, V, O, dO, lse, dQ, dK, dQKVp[:, D:2 * D], 1, S, self.H)
-        self._rope(Kp, dQKVp[:, :D], qkn[3], qkn[1], cos, sin, S, T, dy=dK)
-        self._rope(Qp, dQKVp[:, 2 * D:], qkn[2], qkn[0], cos, sin, S, T, dy=dQ)
-        dX = torch.empty(S, D, **bf)
+        dQ, dK = torch.empty(S, D, **self._bf), torch.empty(S, D, **self._bf)
+        dQKVp = torch.empty(S, 3 * D, **self._bf)
+        ops.attention_bwd_2d(sv.Q, sv.K, sv.V, sv.O, dO, sv.lse, dQ, dK, dQKVp[:, D:2 * D], 1, S, self.H)
+        self._rope(sv.Kp, dQKVp[:, :D], wk[0], wk[1], cos, sin, S, T, dy=dK)
+        self._rope(sv.Qp, dQKVp[:, 2 * D:], wq[0], wq[1], cos, sin, S, T, dy=dQ)
+        dX = torch.empty(S, D, **self._bf)
         for s, rows, _, on_stream in self._streams(T, S):
             with on_stream:
                 dXn1 = ops.linear(dQKVp[rows], self.wt[p + s + '_qkv'])
@@ -615,77 +703,88 @@ class LoraTrunk:
         self._join()
         return dX
 
-    def _single_block(self, i: int, X: torch.Tensor, mod: torch.Tensor, cos, sin, T: int, dXo: Optional[torch.Tensor], grads,
-                      fwd_only: bool = False) -> torch.Tensor:
-        D, S = self.D, X.shape[0]
-        dev = self.dev
-        pk, p = self.packed, f's{i}.'
-        m0 = self.nd * 12 * D + i * 3 * D
-        sh, sc, gt = mod[m0:m0 + D], mod[m0 + D:m0 + 2 * D], mod[m0 + 2 * D:m0 + 3 * D]
-        qkn = pk[p + 'qknorm']                                   # [q, k]
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        sp_out, sp_mlp = self._spec(p + 'out'), self._spec(p + 'fused')
+    # ------------------------------------------------------------------ single block (one sample): the same four
+    def _single_forward(self, i: int, st: _Stash, X: torch.Tensor, sm, cos, sin, T: int) -> torch.Tensor:
+        D, S, p, bi = self.D, X.shape[0], f's{i}.', self.nd + i                 # bi: the block's index in the o / t / lse stashes
         R = slice(self.row0, self.row0 + S)
-        st = self.stash if self.use_stash else None
-        restore = st is not None and not fwd_only
-        keepf = st is not None and fwd_only
-        bi = self.nd + i                                         # block index in the o / t / lse stashes
-        kxd = st is not None and 'xdm' in st
-        Fp = st['fp'][i, R] if st is not None else torch.empty(S, 7 * D, **bf)          # pre-activation k|v|q|mlp
-        if restore and kxd:
-            xd_m, t_m = st['xdm'][i, R], st['t'][2 * bi, R][:, :self.r]
+        _, sh, sc, gt = sm
+        Fp = st.view('fp', i, R)                                         # pre-activation k|v|q|mlp
+        Xe = self._xe(S, D)                                                     # [Xn | t_mlp]: operand of the fused k|v|q|mlp launch
+        ops.norm_modulate(X, sc, sh, out=Xe[:, :D])
+        self._adapted(self._spec(p + 'fused'), Xe, 0, out=Fp, xd_out=st.view('xdm', i, R) if st.keep_xd else None)   # (the k|v|q rows of wcat carry zero B columns)
+        if st.rows:
+            st.view('t', 2 * bi, R).copy_(Xe[:, D:])
+        Kp, V, Qp, K, Q = self._kvq(p, Fp, cos, sin, T)
+        y = self.ybuf[2 * self.nd + i, R]                                       # the pre-gate branch output, kept for d_gate
+        Ge = self._xe(S, 5 * D)                                                 # [O | gelu(mlp) | t_out] = proj_out operand
+        lse = ops.attention_fwd_lse_2d(Q, K, V, Ge[:, :D], 1, S, self.H)
+        if st.rows:
+            st.lse[(bi, self.row0)] = lse
+            st.view('o', bi, R).copy_(Ge[:, :D])
+        ops.gelu(Fp[:, 3 * D:], out=Ge[:, D:5 * D])
+        self._adapted(self._spec(p + 'out'), Ge, 0, out=y, xd_out=st.view('xdo', i, R) if st.keep_xd else None)
+        if st.rows:
+            st.view('t', 2 * bi + 1, R).copy_(Ge[:, 5 * D:])
+        return ops.gate_residual(y, gt, X)
+
+    def _single_from_stash(self, i: int, st: _Stash, X: torch.Tensor, sm, cos, sin, T: int) -> _SingleSaved:
+        """keep_xd: O, t and the dropped inputs all come back from the stash -- no GELU pass, no copy, no dropout pass.  Without: the two adapter
+        inputs are rebuilt (LayerNorm-modulate of X; [O | gelu(mlp)]) and dropped again."""
+        D, S, r, p, bi = self.D, X.shape[0], self.r, f's{i}.', self.nd + i
+        R = slice(self.row0, self.row0 + S)
+        _, sh, sc, _ = sm
+        Fp = st.view('fp', i, R)
+        Mp = Fp[:, 3 * D:]
+        t_m, t_o, lse = st.view('t', 2 * bi, R)[:, :r], st.view('t', 2 * bi + 1, R)[:, :r], st.lse[(bi, self.row0)]
+        held = ()
+        if st.keep_xd:
+            Kp, V, Qp, K, Q = self._kvq(p, Fp, cos, sin, T)
+            O, xd_m, xd_o = st.view('o', bi, R), st.view('xdm', i, R), st.view('xdo', i, R)
         else:
-            Xe = self._xe(S, D)                                  # [Xn | t_mlp]: operand of the fused k|v|q|mlp launch
-            Xn = Xe[:, :D]
+            Xn = self._xe(S, D)[:, :D]                                          # (laid out as the forward's operands)
             ops.norm_modulate(X, sc, sh, out=Xn)
-        if restore and not kxd:
-            xd_m, t_m = self._dropped(sp_mlp, Xn, 0), st['t'][2 * bi, R][:, :self.r]
-        elif not restore:
-            xd_m, t_m, _ = self._adapted(sp_mlp, Xe, 0, out=Fp, xd_out=st['xdm'][i, R] if (keepf and kxd) else None)  # (the k|v|q rows of wcat carry zero B columns)
-            if keepf:
-                st['t'][2 * bi, R].copy_(Xe[:, D:])
-        Kp, V, Qp, Mp = Fp[:, :D], Fp[:, D:2 * D], Fp[:, 2 * D:3 * D], Fp[:, 3 * D:]
-        K, Q = torch.empty(S, D, **bf), torch.empty(S, D, **bf)
-        self._rope(Kp, K, qkn[1], qkn[1], cos, sin, S, T)
-        self._rope(Qp, Q, qkn[0], qkn[0], cos, sin, S, T)
-        y = self.ybuf[2 * self.nd + i, self.row0:self.row0 + S] if fwd_only else None
-        if restore and kxd:         # O, t and dropout([O | gelu(mlp)]) all come back from the stash: no GELU pass, no copy, no dropout pass
-            lse = self._lse[(bi, self.row0)]
-            O = st['o'][bi, R]
-            xd_o, t_o = st['xdo'][i, R], st['t'][2 * bi + 1, R][:, :self.r]
-        else:
-            Ge = self._xe(S, 5 * D)                              # [O | gelu(mlp) | t_out] = proj_out operand
-            G = Ge[:, :5 * D]
+            xd_m = self._dropped(self._spec(p + 'fused'), Xn, 0)
+            Kp, V, Qp, K, Q = self._kvq(p, Fp, cos, sin, T)
+            G = self._xe(S, 5 * D)[:, :5 * D]
             O = G[:, :D]
-            if restore:
-                lse = self._lse[(bi, self.row0)]
-                G[:, :D].copy_(st['o'][bi, R])
-            else:
-                lse = ops.attention_fwd_lse_2d(Q, K, V, G[:, :D], 1, S, self.H)
-                if keepf:
-                    self._lse[(bi, self.row0)] = lse
-                    st['o'][bi, R].copy_(G[:, :D])
+            O.copy_(st.view('o', bi, R))
             ops.gelu(Mp, out=G[:, D:])
-            if restore:
-                xd_o, t_o = self._dropped(sp_out, G, 0), st['t'][2 * bi + 1, R][:, :self.r]
-            else:
-                xd_o, t_o, _ = self._adapted(sp_out, Ge, 0, out=y, main=fwd_only, xd_out=st['xdo'][i, R] if (keepf and kxd) else None)
-            if keepf:
-                st['t'][2 * bi + 1, R].copy_(Ge[:, 5 * D:])
-        if fwd_only:
-            return ops.gate_residual(y, gt, X)
-        # ---- backward ----
+            xd_o, held = self._dropped(self._spec(p + 'out'), G, 0), (Xn,)
+        return _SingleSaved(Kp, V, Qp, Mp, K, Q, O, lse, xd_m, t_m, xd_o, t_o, held)
+
+    def _single_recompute(self, i: int, X: torch.Tensor, sm, cos, sin, T: int) -> _SingleSaved:
+        """The training forward again, but proj_out runs only its adapter's xd and t."""
+        D, S, p = self.D, X.shape[0], f's{i}.'
+        _, sh, sc, _ = sm
+        Fp = torch.empty(S, 7 * D, **self._bf)
+        Xe = self._xe(S, D)
+        ops.norm_modulate(X, sc, sh, out=Xe[:, :D])
+        xd_m, t_m, _ = self._adapted(self._spec(p + 'fused'), Xe, 0, out=Fp)
+        Kp, V, Qp, K, Q = self._kvq(p, Fp, cos, sin, T)
+        Ge = self._xe(S, 5 * D)
+        O = Ge[:, :D]
+        lse = ops.attention_fwd_lse_2d(Q, K, V, O, 1, S, self.H)
+        Mp = Fp[:, 3 * D:]
+        ops.gelu(Mp, out=Ge[:, D:5 * D])
+        xd_o, t_o, _ = self._adapted(self._spec(p + 'out'), Ge, 0, main=False)
+        return _SingleSaved(Kp, V, Qp, Mp, K, Q, O, lse, xd_m, t_m, xd_o, t_o, ())
+
+    def _single_backward(self, i: int, X: torch.Tensor, sm, cos, sin, T: int, sv: _SingleSaved, dXo: torch.Tensor,
+                         grads: torch.Tensor) -> torch.Tensor:
+        D, S, p = self.D, X.shape[0], f's{i}.'
+        R = slice(self.row0, self.row0 + S)
+        (m0, _, sc, gt), (wk, wq) = sm, self._qk_norms(p)
         dY = ops.add_scale(dXo, gate=gt)
-        dG = self._adapted_backward(sp_out, dY, xd_o, t_o, grads, 0)          # [S, 5D] (view)
-        dFp = torch.empty(S, 7 * D, **bf)
-        ops.gelu(Mp, dh=dG[:, D:], out=dFp[:, 3 * D:])
-        dQ, dK = torch.empty(S, D, **bf), torch.empty(S, D, **bf)
-        ops.attention_bwd_2d(Q, K, V, O, dG[:, :D], lse, dQ, dK, dFp[:, D:2 * D], 1, S, self.H)
-        self._rope(Kp, dFp[:, :D], qkn[1], qkn[1], cos, sin, S, T, dy=dK)
-        self._rope(Qp, dFp[:, 2 * D:3 * D], qkn[0], qkn[0], cos, sin, S, T, dy=dQ)
-        dXn = self._adapted_backward(sp_mlp, dFp, xd_m, t_m, grads, 0)        # dgrad over all 7D columns; dT / dB from the mlp columns
+        dG = self._adapted_backward(self._spec(p + 'out'), dY, sv.xd_o, sv.t_o, grads, 0)          # [S, 5D] (view)
+        dFp = torch.empty(S, 7 * D, **self._bf)
+        ops.gelu(sv.Mp, dh=dG[:, D:], out=dFp[:, 3 * D:])
+        dQ, dK = torch.empty(S, D, **self._bf), torch.empty(S, D, **self._bf)
+        ops.attention_bwd_2d(sv.Q, sv.K, sv.V, sv.O, dG[:, :D], sv.lse, dQ, dK, dFp[:, D:2 * D], 1, S, self.H)
+        self._rope(sv.Kp, dFp[:, :D], wk[0], wk[1], cos, sin, S, T, dy=dK)
+        self._rope(sv.Qp, dFp[:, 2 * D:3 * D], wq[0], wq[1], cos, sin, S, T, dy=dQ)
+        dXn = self._adapted_backward(self._spec(p + 'fused'), dFp, sv.xd_m, sv.t_m, grads, 0)      # dgrad over all 7D columns; dT / dB from the mlp columns
         if self.dmod is not None:          # d(shift, scale, gate) of the single-stream AdaLN
-            ops.coldot(dXo, self.ybuf[2 * self.nd + i, self.row0:self.row0 + S], self.dmod[m0 + 2 * D:m0 + 3 * D])
+            ops.coldot(dXo, self.ybuf[2 * self.nd + i, R], self.dmod[m0 + 2 * D:m0 + 3 * D])
             self._dmod_ln(X, dXn, m0 + D, m0)
         return ops.ln_modulate_backward(X, dXn, sc, dres=dXo)
 
@@ -704,15 +803,14 @@ class LoraTrunk:
         cos, sin = self.eng.rope_tables(hp, wp, T)
         if self.ybuf is None or self.ybuf.shape[1] != x_tokens.shape[0]:
             self.ybuf = torch.empty(2 * self.nd + self.ns, x_tokens.shape[0], self.D, dtype=torch.bfloat16, device=self.dev)
-        if self.use_stash:
-            self._stash_for(x_tokens.shape[0])
+        st = (self._stash_for(x_tokens.shape[0]) if self.use_stash else None) or self._no_stash
         X = x_tokens[b * S:(b + 1) * S]
         for i in range(self.nd):
             ckpt[i, b * S:(b + 1) * S].copy_(X)
-            X = self._double_block(i, X, mod, cos, sin, T, None, None, fwd_only=True)
+            X = self._double_forward(i, st, X, self._double_mod(i, mod), cos, sin, T)
         for i in range(self.ns):
             ckpt[self.nd + i, b * S:(b + 1) * S].copy_(X)
-            X = self._single_block(i, X, mod, cos, sin, T, None, None, fwd_only=True)
+            X = self._single_forward(i, st, X, self._single_mod(i, mod), cos, sin, T)
         x_tokens[b * S:(b + 1) * S].copy_(X)
 
     # ------------------------------------------------------------------ whole-trunk backward of one sample
@@ -731,15 +829,22 @@ class LoraTrunk:
         fin = (self.nd * 12 + self.ns * 3) * D
         dX = torch.zeros(S, D, dtype=torch.bfloat16, device=self.dev)
         ops.ln_modulate_backward(x_final_img, dxn_img, mod[fin:fin + D], out=dX[T:])     # norm_out: scale first
+        st = self.stash if self.use_stash else None      # the backward's operands: read back from the stash, or recomputed from the checkpoint
         for i in reversed(range(self.ns)):
             X = ckpt[self.nd + i, b * S:(b + 1) * S]
-            dX = self._single_block(i, X, mod, cos, sin, T, dX, grads)
+            sm = self._single_mod(i, mod)
+            sv = self._single_from_stash(i, st, X, sm, cos, sin, T) if st is not None else self._single_recompute(i, X, sm, cos, sin, T)
+            dX = self._single_backward(i, X, sm, cos, sin, T, sv, dX, grads)
+            del sv                                       # (its temporaries go back to the allocator before the next block takes its own)
             if on_block_done is not None:
                 self._join_wgrad()
                 on_block_done(self.nd + i)
         for i in reversed(range(self.nd)):
             X = ckpt[i, b * S:(b + 1) * S]
-            dX = self._double_block(i, X, mod, cos, sin, T, dX, grads)
+            dm = self._double_mod(i, mod)
+            sv = self._double_from_stash(i, st, dm, cos, sin, T, S) if st is not None else self._double_recompute(i, X, dm, cos, sin, T)
+            dX = self._double_backward(i, X, dm, cos, sin, T, sv, dX, grads)
+            del sv
             if on_block_done is not None:
                 self._join_wgrad()
                 on_block_done(i)
