@@ -1616,10 +1616,14 @@ def attention_bwd_2d(q, k, v, o, dout, lse, dq, dk, dv, B: int, S: int, H: int):
                                           _p(dv), dv.stride(0), _p(ws), B, H, S, _s()))
 
 
-def lora_fold(base: torch.Tensor, dst: torch.Tensor, A=(), B=(), scales=()) -> torch.Tensor:
+def lora_fold(base: torch.Tensor, dst: torch.Tensor, A=(), B=(), scales=(), row_gains=None) -> torch.Tensor:
     """dst = bf16(base + sum_j scales[j] * B[j] @ A[j]) (``afx_lora_fold``): base, dst [O, I] bf16 row slices (any row stride >= I) of
     packed weights that do not overlap, A[j] [r_j, I] and B[j] [O, r_j] contiguous bf16 of any rank >= 1, scales[j] python floats applied
-    in fp32 to adapter j's fp32-accumulated product.  One rounding, at the store; bit-reproducible; no adapters = a copy."""
+    in fp32 to adapter j's fp32-accumulated product.  One rounding, at the store; bit-reproducible; no adapters = a copy.
+
+    row_gains (``afx_lora_fold_rows``): one entry per adapter, None for a plain LoRA or the fp32 [O] row gains of a DoRA adapter
+    (``lora_row_gain``): dst = bf16(c * base + sum_j g_j * scales[j] * B[j] @ A[j]) row by row, c = 1 + sum_j (g_j - 1) over the adapters with
+    gains.  row_gains=None is the plain fold above, the call it always was."""
     lib = _lib.load()
     _mat(base, torch.bfloat16, 'lora_fold base')
     _mat(dst, torch.bfloat16, 'lora_fold dst', base.shape)
@@ -1638,5 +1642,34 @@ def lora_fold(base: torch.Tensor, dst: torch.Tensor, A=(), B=(), scales=()) -> t
     pb = (C.c_void_p * n)(*[b.data_ptr() for b in B])
     rk = (C.c_int32 * n)(*[a.shape[0] for a in A])
     sc = (C.c_float * n)(*[float(s) for s in scales])
-    _lib.check(lib.afx_lora_fold(_p(base), base.stride(0), _p(dst), dst.stride(0), O, I, J, pa, pb, rk, sc, _s()))
+    if row_gains is None:
+        _lib.check(lib.afx_lora_fold(_p(base), base.stride(0), _p(dst), dst.stride(0), O, I, J, pa, pb, rk, sc, _s()))
+        return dst
+    if len(row_gains) != J:
+        raise ValueError(f'lora_fold: {J} adapters and {len(row_gains)} row_gains')
+    for j, g in enumerate(row_gains):
+        if g is not None:
+            _acc(g, (O,), f'lora_fold row_gains[{j}]')
+    pg = (C.c_void_p * n)(*[None if g is None else g.data_ptr() for g in row_gains])
+    _lib.check(lib.afx_lora_fold_rows(_p(base), base.stride(0), _p(dst), dst.stride(0), O, I, J, pa, pb, rk, sc, pg, _s()))
     return dst
+
+
+def lora_row_gain(base: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: float, magnitude: torch.Tensor, out=None) -> torch.Tensor:
+    """The row gains of one DoRA adapter on one linear (``afx_lora_row_gain``): gain[o] = magnitude[o] / || (base + scale * B @ A)[o, :] ||, fp32
+    [O]; base [O, I] bf16 (any row stride >= I), A [r, I] and B [O, r] contiguous bf16 of any rank >= 1, magnitude fp32 [O].  The rows are
+    formed as ``lora_fold`` forms them and their squares summed in fp32 in a fixed order: bit-reproducible.  A row of zeros gets gain 0."""
+    lib = _lib.load()
+    _mat(base, torch.bfloat16, 'lora_row_gain base')
+    _mat(A, torch.bfloat16, 'lora_row_gain A')
+    _mat(B, torch.bfloat16, 'lora_row_gain B')
+    O, I = base.shape
+    r = A.shape[0]
+    if not (A.is_contiguous() and B.is_contiguous()) or tuple(A.shape) != (r, I) or tuple(B.shape) != (O, r):
+        raise ValueError(f'lora_row_gain: needs contiguous A [r, {I}] and B [{O}, r], got {tuple(A.shape)} and {tuple(B.shape)}')
+    _acc(magnitude, (O,), 'lora_row_gain magnitude')
+    if out is None:
+        out = torch.empty(O, dtype=torch.float32, device=base.device)
+    _acc(out, (O,), 'lora_row_gain out')
+    _lib.check(lib.afx_lora_row_gain(_p(base), base.stride(0), O, I, _p(A), _p(B), r, float(scale), _p(magnitude), _p(out), _s()))
+    return out

@@ -210,9 +210,19 @@ class ArcFlowLoaderMixin:
         """diffusers' `pipe.load_lora_weights(...)` for transformer (style) LoRAs, to be combined with the ArcFlow adapter through
         `set_adapters` as inference_flux.py:9 suggests.  Reads a local `.safetensors` file, a directory + `weight_name`
         (default `pytorch_lora_weights.safetensors`), or a state dict; never the network.  Keys: see `parse_lora_state_dict`
-        (`text_encoder*` keys are skipped with one warning; Kohya / ComfyUI `lora_unet_*` checkpoints are refused).  A module the
-        transformer does not have, or a shape that does not fit its linear, raises ValueError; so does a duplicate `adapter_name`.
-        The new adapter becomes active with weight 1.0; the other adapters keep their state.  Returns the adapter's name.
+        (`text_encoder*` keys are skipped with one warning).  Kohya / ComfyUI checkpoints (`lora_unet_*`, `lora_transformer_*`,
+        `diffusion_model.*` keys: BFL module names with fused qkv / linear1 tensors on FLUX, underscored diffusers names on either family)
+        and DoRA magnitudes (`dora_scale`, `lora_magnitude_vector`) go through `lora_formats.convert_community_lora` first; its BFL <->
+        diffusers table is diffusers' conversion as recalled and is not pinned against diffusers.  LoHa / LoKr / diff / conv tensors are
+        refused by name.  A module the transformer does not have, or a shape that does not fit its linear, raises ValueError; so does a
+        duplicate `adapter_name`.  The new adapter becomes active with weight 1.0; the other adapters keep their state.  Returns the
+        adapter's name.
+
+        DoRA: an adapter with a magnitude m on a linear contributes (g - 1) W_base + g s B A there, g[o] = m[o] / ||(W_base + s B A)[o, :]||
+        with its own effective scale s -- peft's rule for several active adapters as recalled, not checked against peft.  `afx_lora_row_gain`
+        computes g on the device whenever s changed (the vectors are cached per adapter and linear) and `afx_lora_fold_rows` folds with it:
+        still one rounding.  An active DoRA adapter at weight 0 still applies its magnitude ((m / ||W_base|| - 1) W_base, as peft does); an
+        adapter left out of `set_adapters` contributes nothing.  A row with ||.|| = 0 gets g = 0 where peft divides by zero.
 
         Every adapter's tensors are uploaded once as bf16: fp32 / fp16 files are rounded once here, as `weights._merge_one` does for the
         ArcFlow adapter.  Its factor is `alpha / r` per module (1 without `alpha`); the effective scale of adapter j is
@@ -244,34 +254,45 @@ class ArcFlowLoaderMixin:
             adapter_name = f'default_{n}'
         if adapter_name in known:
             raise ValueError(f'adapter {adapter_name!r} is already loaded (loaded: {known})')
+        from . import lora_formats
+        magnitudes = {}
+        if lora_formats.needs_conversion(sd):
+            sd, magnitudes, _ = lora_formats.convert_community_lora(sd, self._family, self._transformer_config, student=True)
         mods, _ = parse_lora_state_dict(sd)
         if not mods:
             raise ValueError('no transformer LoRA weights were found')
+        for m, v in magnitudes.items():
+            if m not in mods:
+                raise ValueError(f'adapter {adapter_name!r}: a DoRA magnitude for {m!r}, which has no lora_A / lora_B pair in this file')
+            mods[m]['magnitude'] = v
         sty = getattr(self, '_style', None)
         fresh = sty is None
         if fresh:
             from ..weights import packed_row_slices
             sty = dict(slices=packed_row_slices(self._family, self._transformer_config, True, eng.num_gaussians, eng.logweights_channels),
-                       loras={}, active={}, base={}, arc={}, folded={})
+                       loras={}, active={}, base={}, arc={}, folded={}, magnitude={}, gain={})
             arc = self._arcflow_adapter_name()
             if arc is not None:
                 arc_mods, _ = parse_lora_state_dict(self._adapter_state['lora'])
                 sty['arc'] = self._upload_adapter(sty, arc_mods, eng.device, 'the ArcFlow adapter')
                 sty['active'][arc] = float(self._adapter_state['weight'])
-        new = self._upload_adapter(sty, mods, eng.device, f'adapter {adapter_name!r}')
+        mag = {}
+        new = self._upload_adapter(sty, mods, eng.device, f'adapter {adapter_name!r}', mag)
         base_sd = self._adapter_state['base'] if getattr(self, '_adapter_state', None) is not None else self._base_state_dict
         for m in list(sty['arc']) + list(new):
             if m not in sty['base']:
                 w = base_sd.get(m + '.weight', base_sd.get(m + '.base_layer.weight'))
                 sty['base'][m] = w.to(device=eng.device, dtype=torch.bfloat16).contiguous()
         sty['loras'][adapter_name] = new
+        sty['magnitude'][adapter_name] = mag
         sty['active'][adapter_name] = 1.0
         self._style = sty
         self._adapters = known + [adapter_name]
         return adapter_name
 
-    def _upload_adapter(self, sty, mods, device, what: str):
-        """{module: dict(A, B, alpha)} -> {module: (A bf16 on the device, B bf16 on the device, alpha / r)}, checked against the linear it adapts."""
+    def _upload_adapter(self, sty, mods, device, what: str, magnitude: Optional[Dict] = None):
+        """{module: dict(A, B, alpha)} -> {module: (A bf16 on the device, B bf16 on the device, alpha / r)}, checked against the linear it adapts.
+        A module's DoRA magnitude (its 'magnitude' entry, [rows]) goes into `magnitude` as fp32 on the device."""
         out = {}
         for m, e in mods.items():
             if m not in sty['slices']:
@@ -285,6 +306,10 @@ class ArcFlowLoaderMixin:
             r = a.shape[0]
             out[m] = (a.to(device=device, dtype=torch.bfloat16).contiguous(), b.to(device=device, dtype=torch.bfloat16).contiguous(),
                       1.0 if e['alpha'] is None else e['alpha'] / r)
+            if e.get('magnitude') is not None:
+                if e['magnitude'].numel() != rows:
+                    raise ValueError(f'{what}: {m!r} has {rows} output rows, its DoRA magnitude {e["magnitude"].numel()} elements')
+                magnitude[m] = e['magnitude'].reshape(rows).to(device=device, dtype=torch.float32).contiguous()
         return out
 
     def _set_style_adapters(self, names: List[str], adapter_weights) -> None:
@@ -325,6 +350,9 @@ class ArcFlowLoaderMixin:
             return
         for n in names:
             del sty['loras'][n]
+            del sty['magnitude'][n]
+            for key in [key for key in sty['gain'] if key[0] == n]:
+                del sty['gain'][key]
             sty['active'].pop(n, None)
             self._adapters.remove(n)
         if not sty['loras']:
@@ -358,7 +386,8 @@ class ArcFlowLoaderMixin:
 
     def _fold_adapters(self, call_scale: float) -> None:
         """Bring the engine's packed weights to the active adapters at `call_scale`: one `afx_lora_fold` per linear whose list of
-        (adapter, fp32 scale) differs from what is folded in now."""
+        (adapter, fp32 scale) differs from what is folded in now.  A linear with an active DoRA adapter is folded by `afx_lora_fold_rows`
+        with that adapter's row gains, computed by `afx_lora_row_gain` when its scale is not the one the cached vector was made for."""
         from .. import ops
         sty = self._style
         eng = self._lora_engine()
@@ -373,7 +402,7 @@ class ArcFlowLoaderMixin:
                 if name in sty['active'] and m in mods:
                     a, b, factor = mods[m]
                     s = ctypes.c_float(call_scale * sty['active'][name] * factor).value
-                    if s != 0.0:
+                    if s != 0.0 or m in sty['magnitude'].get(name, ()):             # a DoRA adapter at scale 0 still applies its magnitude
                         A.append(a); B.append(b); S.append(s); sig.append((name, s))
             sig = tuple(sig)
             if sty['folded'].get(m, None if m in sty['arc'] else ()) == sig:        # (the ArcFlow-only path folded the arc linears so far)
@@ -381,7 +410,19 @@ class ArcFlowLoaderMixin:
             if len(A) > MAX_FOLD_ADAPTERS:
                 raise ValueError(f'{len(A)} active adapters on {m!r}: at most {MAX_FOLD_ADAPTERS} can be folded into one linear')
             packed, r0, rows, _ = sty['slices'][m]
-            ops.lora_fold(base, eng._weights[packed][r0:r0 + rows], A, B, S)
+            gains = None
+            if any(m in sty['magnitude'].get(name, ()) for name, _ in sig):
+                gains = []
+                for j, (name, s) in enumerate(sig):
+                    mag = sty['magnitude'].get(name, {}).get(m)
+                    if mag is None:
+                        gains.append(None)
+                        continue
+                    cached = sty['gain'].get((name, m))
+                    if cached is None or cached[0] != s:
+                        cached = sty['gain'][(name, m)] = (s, ops.lora_row_gain(base, A[j], B[j], s, mag))
+                    gains.append(cached[1])
+            ops.lora_fold(base, eng._weights[packed][r0:r0 + rows], A, B, S, row_gains=gains)
             sty['folded'][m] = sig
             for k in (packed + '_q', packed[:-len('weight')] + 'wscale'):      # quantised copies of an earlier enable_fp8(): stale now, a later
                 eng._weights.pop(k, None)                                      # enable_fp8() quantises this matrix again

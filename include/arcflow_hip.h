@@ -866,6 +866,30 @@ int afx_norm_modulate_mx8(const void* x, int64_t ldx, void* q8, int64_t ldq, voi
 #define AFX_LORA_MAX_ADAPTERS 8
 int afx_lora_fold(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
                   const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, void* stream);
+/* DoRA adapters (weight-decomposed LoRA: a magnitude m[o] per output row next to A / B; `dora_scale` of Kohya files, `lora_magnitude_vector` of
+ * peft files).  An active DoRA adapter j replaces row o of the base by g_j[o] (w + s_j B_j A_j)[o, :] with the row gain
+ *   g_j[o] = m_j[o] / sqrt( sum_i ( w[o, i] + s_j sum_r B_j[o, r] A_j[r, i] )^2 ),
+ * and several active adapters add their deltas relative to the base weight, a DoRA adapter's being (g_j - 1) w + g_j s_j B_j A_j (peft's rule for
+ * several active adapters as recalled -- not checked against peft).  The whole row is needed before an element can be written: two launches.
+ *
+ * afx_lora_row_gain: gain[o] (fp32 [O]) of ONE adapter on one linear.  base [O, I] bf16 with leading dimension ld_base, A [r, I] (16-byte aligned),
+ * B [O, r] bf16, any rank >= 1, s fp32, m fp32 [O]; O, I positive multiples of 64, base 16-byte aligned with ld_base % 8 == 0, m / gain 4-byte aligned,
+ * gain overlapping none of the inputs.  Every 64 x 64 tile of w + s B A is formed as afx_lora_fold forms it (same staging, same 16x16x32 bf16 MFMA,
+ * fp32); one work-group owns 64 rows and walks the column tiles in order, the squares are summed in fp32 in a fixed order (no atomics, no
+ * workspace): bit-reproducible.  Square root and division are correctly rounded.  A row whose sum of squares is 0 gets gain 0 -- a deviation from
+ * peft, which divides by zero there.  Traffic: 2 B per element read, 4 O bytes written.
+ *
+ * afx_lora_fold_rows: afx_lora_fold's arguments plus row_gain, a HOST array of J device pointers (fp32 [O], 4-byte aligned, not overlapping dst;
+ * a null entry -- or a null array -- means a plain LoRA):
+ *   dst[o, i] = bf16_rne( c[o] float(base[o, i]) + sum_j (g_j[o] scales[j]) * ( sum_r B[j][o, r] * A[j][r, i] ) )
+ *   c[o] = 1 + sum_{j with gain} (g_j[o] - 1)   (fp32, in adapter order),   g_j[o] = 1 where the entry is null
+ * g_j[o] scales[j] is one fp32 product and c[o] w is fused with the addition of the adapters' sum: still ONE rounding to bf16, at the store.  With every
+ * entry null the result is bit-identical to afx_lora_fold.  Same guards as afx_lora_fold (AFX_E_INVALID, nothing is launched). */
+int afx_lora_row_gain(const void* base, int64_t ld_base, int32_t O, int32_t I, const void* A, const void* B, int32_t r, float s,
+                      const float* m, float* gain, void* stream);
+int afx_lora_fold_rows(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
+                       const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, const float* const* row_gain,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,7 @@ def main(argv=None):
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--skip-parent', action='store_true')
+    ap.add_argument('--dora', action='store_true', help='time afx_lora_row_gain and afx_lora_fold_rows per FLUX shape against the torch formulation, and stop')
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('lora_fold_bench needs the GPU: a CPU run measures nothing')
@@ -62,6 +63,8 @@ def main(argv=None):
     def adapters(O, I):
         return [rnd(r, I, std=0.05) for r in RANKS], [rnd(O, r, std=0.05) for r in RANKS]
     res = dict(device=torch.cuda.get_device_name(0), ranks=list(RANKS), shapes=[], double=a.double, single=a.single)
+    if a.dora:
+        return dora(a, ops, rnd, res)
     # ---- per shape
     for name, O, I in SHAPES:
         base, dst = rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device=dev)
@@ -118,6 +121,51 @@ def main(argv=None):
           + f'  ({min(total_bytes / t / 1e9 for t in new_s):.0f} .. {max(total_bytes / t / 1e9 for t in new_s):.0f} GB/s, host clock around a synchronise)')
     if par_s:
         print('merge_lora + load_state_dict, ArcFlow adapter alone, device-resident state dict (no upload): ' + ', '.join(f'{t * 1e3:.1f} ms' for t in par_s))
+    print(json.dumps(res))
+
+
+def dora(a, ops, rnd, res):
+    """--dora: one DoRA adapter of rank 16 at scale 0.8 per FLUX shape.  The gain pass (``afx_lora_row_gain``: 2 O I bytes to read), the fold with
+    its gains (``afx_lora_fold_rows``: 4 O I bytes) and, beside them, the torch formulation of the same result: ``W + s * B @ A`` in fp32,
+    ``torch.linalg.norm(dim=1)``, scale by m / norm, cast to bf16.  Device events around --iters launches after a warm-up, the three
+    alternating --reps times; the median is printed."""
+    import statistics
+    import torch
+    r, s = RANKS[1], 0.8
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    for name, O, I in SHAPES:
+        base, dst = rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device='cuda')
+        A, B = rnd(r, I, std=0.05), rnd(O, r, std=0.05)
+        m = base.float().norm(dim=1).contiguous()
+        gain = torch.empty(O, dtype=torch.float32, device='cuda')
+
+        def torch_path():
+            v = torch.addmm(base.float(), B.float(), A.float(), alpha=s)
+            return (v * (m / torch.linalg.norm(v, dim=1))[:, None]).to(torch.bfloat16)
+        paths = dict(gain=lambda: ops.lora_row_gain(base, A, B, s, m, out=gain), fold_rows=lambda: ops.lora_fold(base, dst, [A], [B], [s], row_gains=[gain]),
+                     torch=torch_path)
+        for fn in paths.values():
+            for _ in range(3):
+                fn()
+        ms = {k: [] for k in paths}
+        for _ in range(a.reps):
+            for k, fn in paths.items():
+                ms[k].append(timed(fn))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        row = dict(name=name, O=O, I=I, rank=r, gain_ms=ms['gain'], fold_rows_ms=ms['fold_rows'], torch_ms=ms['torch'],
+                   gain_gb_per_s=2.0 * O * I / (med['gain'] * 1e-3) / 1e9, fold_rows_gb_per_s=4.0 * O * I / (med['fold_rows'] * 1e-3) / 1e9)
+        res['shapes'].append(row)
+        print(f'{name:32s} [{O:6d}, {I:6d}]  gain {med["gain"] * 1e3:8.1f} us {row["gain_gb_per_s"]:7.1f} GB/s over 2 O I bytes | fold_rows '
+              f'{med["fold_rows"] * 1e3:8.1f} us {row["fold_rows_gb_per_s"]:7.1f} GB/s over 4 O I bytes | torch {med["torch"] * 1e3:8.1f} us')
+        del base, dst
     print(json.dumps(res))
 
 
