@@ -24,8 +24,15 @@ FAULT_BUDGET = 6e-3       # whole-matrix rel-L2 a planted fault is scaled to: sq
 
 # ------------------------------------------------------------------------------------------------ fp64 primitives
 def lin64(w, name, x):
+    """nn.Linear in fp64; with ``w[name + '.lora'] = (A [r, in], B [out, r], keep_scale)`` also the peft LoRA branch of dit_ref.lin:
+    y = W x + b + B A (x . keep_scale)."""
     b = w.get(name + '.bias')
-    return F.linear(x, w[name + '.weight'].double(), None if b is None else b.double())
+    y = F.linear(x, w[name + '.weight'].double(), None if b is None else b.double())
+    if name + '.lora' in w:
+        a_, b_, keep_scale = w[name + '.lora']
+        ks = keep_scale.double() if torch.is_tensor(keep_scale) else keep_scale
+        y = y + F.linear(F.linear(x * ks, a_.double()), b_.double())
+    return y
 
 
 def layer_norm64(x):
