@@ -90,6 +90,10 @@ class ModelDesc(C.Structure):
     _fields_ = parse_struct(_text, 'afx_model_desc')
 
 
+class LoraTerm(C.Structure):
+    _fields_ = parse_struct(_text, 'afx_lora_term')
+
+
 _lib: Optional[C.CDLL] = None
 
 

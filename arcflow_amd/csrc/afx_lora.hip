@@ -26,6 +26,13 @@
 //
 // (g_j = 1 where adapter j has no gain vector; c in fp32 in adapter order).  Without any gain vector every factor is s_j and c is 1: fma(1, w, d)
 // is w + d, the bits of afx_lora_fold.
+//
+// LyCORIS LoHa and LoKr adapters are no sums of low-rank products either (rules restated from memory, NOT PINNED against LyCORIS / ComfyUI):
+// LoHa's delta is (w1_a w1_b) (*) (w2_a w2_b) element by element, LoKr's is kron(w1, w2).  afx_lora_fold_terms is afx_lora_fold_rows over a list of
+// terms of three kinds: a LoRA term as above; a LoHa term, whose two products come out of lora_tile_product one after the other in the same
+// accumulator layout and are multiplied in fp32 registers (never rounded to bf16); a LoKr term, one fp32 product w1[r / c, i / d] w2[r % c, i % d]
+// per element from two dense fp32 matrices out of L2, r = row0 + o so that a row slice of a fused tensor folds without splitting the Kronecker
+// product.  Every term enters the running fp32 total by one fused multiply-add with its scale, in term order; the store is still the one rounding.
 #include "afx_api_util.h"
 #include "afx_common.h"
 
@@ -167,6 +174,126 @@ __global__ __launch_bounds__(256) void lora_fold_kernel(const bf16_t* __restrict
   }
 }
 
+// afx_lora_fold_terms: the fold over terms of three kinds (include/arcflow_hip.h).  Passed by value; the fields follow afx_lora_term.
+struct LoraTermArgs {
+  const bf16_t* down[AFX_LORA_MAX_ADAPTERS];   // LoRA A / LoHa hada_w1_b: [rank, I]
+  const bf16_t* up[AFX_LORA_MAX_ADAPTERS];     // LoRA B / LoHa hada_w1_a: [O, rank]
+  const bf16_t* down2[AFX_LORA_MAX_ADAPTERS];  // LoHa hada_w2_b
+  const bf16_t* up2[AFX_LORA_MAX_ADAPTERS];    // LoHa hada_w2_a
+  const float* w1[AFX_LORA_MAX_ADAPTERS];      // LoKr [ka, kb]
+  const float* w2[AFX_LORA_MAX_ADAPTERS];      // LoKr [kc, kd]
+  const float* g[AFX_LORA_MAX_ADAPTERS];       // LoRA: row gains or null
+  int32_t kind[AFX_LORA_MAX_ADAPTERS];
+  int32_t r[AFX_LORA_MAX_ADAPTERS];
+  int32_t r2[AFX_LORA_MAX_ADAPTERS];
+  int32_t kb[AFX_LORA_MAX_ADAPTERS];
+  int32_t kc[AFX_LORA_MAX_ADAPTERS];
+  int32_t kd[AFX_LORA_MAX_ADAPTERS];
+  int32_t row0[AFX_LORA_MAX_ADAPTERS];         // (row0 + O <= ka kc < 2^31 is checked on the host)
+  float s[AFX_LORA_MAX_ADAPTERS];
+};
+
+// lora_fold_kernel<true> with a delta per term instead of a low-rank product per adapter.  A LoRA term takes lora_fold_kernel<true>'s instructions
+// in its order (the same bits); a LoHa term forms its two products one after the other through lora_tile_product -- the same accumulator layout, so
+// the element-wise product is a register product -- and a LoKr term forms its element of kron(w1, w2) in that layout from two loads out of L2.
+__global__ __launch_bounds__(256) void lora_fold_terms_kernel(const bf16_t* __restrict__ base, int64_t ld_base, bf16_t* __restrict__ dst,
+                                                              int64_t ld_dst, int I, int J, LoraTermArgs a) {
+  __shared__ __attribute__((aligned(16))) bf16_t sB[LF_T * LF_LDK];
+  __shared__ __attribute__((aligned(16))) bf16_t sA[LF_T * LF_LDK];
+  __shared__ __attribute__((aligned(16))) float sC[LF_T * LF_LDC];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles_i = I / LF_T;
+  const int64_t o0 = (int64_t)(blockIdx.x / tiles_i) * LF_T;
+  const int i0 = (int)(blockIdx.x % tiles_i) * LF_T;
+
+  u32x4_t bw[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int idx = tid + 256 * c, row = idx >> 3, c8 = (idx & 7) * 8;
+    bw[c] = *reinterpret_cast<const u32x4_t*>(base + (o0 + row) * ld_base + i0 + c8);
+  }
+  if (J == 0) {                                             // (uniform) a plain copy: no add, so that -0 stays -0
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int idx = tid + 256 * c, row = idx >> 3, c8 = (idx & 7) * 8;
+      *reinterpret_cast<u32x4_t*>(dst + (o0 + row) * ld_dst + i0 + c8) = bw[c];
+    }
+    return;
+  }
+
+  f32x4_t tot[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) tot[n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const int er = 16 * wave + 4 * (lane >> 4);               // accumulator element e of column tile n: row er + e, column 16 n + lane % 16 of the tile
+
+  for (int j = 0; j < J; ++j) {                             // (every branch on the term is uniform)
+    const float s = a.s[j];
+    if (a.kind[j] == AFX_LORA_TERM_LOKR) {
+      const int kc = a.kc[j], kd = a.kd[j], kb = a.kb[j];
+      const float* w1 = a.w1[j];
+      const float* w2 = a.w2[j];
+      int p[4], q[4], u[4], v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = a.row0[j] + (int)o0 + er + e;       // < ka kc < 2^31
+        p[e] = row / kc;
+        q[e] = row - p[e] * kc;
+      }
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int col = i0 + 16 * n + (lane & 15);          // < I = kb kd
+        u[n] = col / kd;
+        v[n] = col - u[n] * kd;
+      }
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = __fmul_rn(w1[(int64_t)p[e] * kb + u[n]], w2[(int64_t)q[e] * kd + v[n]]);
+          tot[n][e] = fmaf(s, d, tot[n][e]);
+        }
+      continue;
+    }
+    f32x4_t acc[4];
+    lora_tile_product(a.down[j], a.up[j], a.r[j], I, o0, i0, sA, sB, acc);
+    if (a.kind[j] == AFX_LORA_TERM_LOHA) {
+      f32x4_t acc2[4];
+      lora_tile_product(a.down2[j], a.up2[j], a.r2[j], I, o0, i0, sA, sB, acc2);
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tot[n][e] = fmaf(s, __fmul_rn(acc[n][e], acc2[n][e]), tot[n][e]);
+      continue;
+    }
+    float gs[4] = {s, s, s, s};
+    if (a.g[j] != nullptr) {
+      const float* g = a.g[j] + o0 + er;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) gs[e] = g[e] * s;
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tot[n][e] = fmaf(gs[e], acc[n][e], tot[n][e]);
+  }
+
+  lora_tile_to_lds(tot, sC);
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int idx = tid + 256 * c, row = idx >> 3, c8 = (idx & 7) * 8;
+    float f[8];
+    unpack8(bw[c], f);
+    const float* d = &sC[row * LF_LDC + c8];
+    float cr = 1.f;                                         // c[o] = 1 + sum_j (g_j[o] - 1), in term order
+    for (int j = 0; j < J; ++j)
+      if (a.g[j] != nullptr) cr += a.g[j][o0 + row] - 1.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = fmaf(cr, f[e], d[e]);
+    *reinterpret_cast<u32x4_t*>(dst + (o0 + row) * ld_dst + i0 + c8) = pack8(f);       // the one rounding
+  }
+}
+
 // gain[o] = m[o] / sqrt( sum_i (w[o, i] + s (B A)[o, i])^2 ), 0 where the sum is 0.  One work-group per 64 rows.
 __global__ __launch_bounds__(256) void lora_row_gain_kernel(const bf16_t* __restrict__ base, int64_t ld_base, int I, const bf16_t* __restrict__ A,
                                                             const bf16_t* __restrict__ B, int r, float s, const float* __restrict__ m,
@@ -217,6 +344,18 @@ __global__ __launch_bounds__(256) void lora_row_gain_kernel(const bf16_t* __rest
   }
 }
 
+// what every fold asks of its two row slices: 0, or AFX_E_INVALID with the message set
+static int lora_slice_guards(const char* what, const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I) {
+  if (O < 64 || I < 64 || O % 64 || I % 64) return fail(AFX_E_INVALID, "%s: O = %d and I = %d must be positive multiples of 64", what, O, I);
+  if (ld_base < I || ld_dst < I) return fail(AFX_E_INVALID, "%s: leading dimension below I = %d", what, I);
+  if (ld_base % 8 || ld_dst % 8 || ((uintptr_t)base & 15) || ((uintptr_t)dst & 15))
+    return fail(AFX_E_INVALID, "%s: base / dst must be 16-byte aligned with leading dimensions that are multiples of 8", what);
+  if (ranges_overlap(base, ((int64_t)(O - 1) * ld_base + I) * 2, dst, ((int64_t)(O - 1) * ld_dst + I) * 2))
+    return fail(AFX_E_INVALID, "%s: dst overlaps base", what);
+  if ((int64_t)(O / 64) * (I / 64) > 0x7fffffff) return fail(AFX_E_INVALID, "%s: %lld tiles", what, (long long)(O / 64) * (I / 64));
+  return AFX_OK;
+}
+
 // the guards and the launch of afx_lora_fold (row_gain == nullptr, `rows` false) and afx_lora_fold_rows
 static int lora_fold_launch(const char* what, bool rows, const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
                             const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, const float* const* row_gain,
@@ -224,11 +363,8 @@ static int lora_fold_launch(const char* what, bool rows, const void* base, int64
   if (!base || !dst) return fail(AFX_E_INVALID, "%s: null base / dst", what);
   if (J < 0 || J > AFX_LORA_MAX_ADAPTERS) return fail(AFX_E_INVALID, "%s: %d adapters (0 .. %d)", what, J, AFX_LORA_MAX_ADAPTERS);
   if (J > 0 && (!A || !B || !ranks || !scales)) return fail(AFX_E_INVALID, "%s: null adapter array", what);
-  if (O < 64 || I < 64 || O % 64 || I % 64) return fail(AFX_E_INVALID, "%s: O = %d and I = %d must be positive multiples of 64", what, O, I);
-  if (ld_base < I || ld_dst < I) return fail(AFX_E_INVALID, "%s: leading dimension below I = %d", what, I);
-  if (ld_base % 8 || ld_dst % 8 || ((uintptr_t)base & 15) || ((uintptr_t)dst & 15))
-    return fail(AFX_E_INVALID, "%s: base / dst must be 16-byte aligned with leading dimensions that are multiples of 8", what);
-  const int64_t base_bytes = ((int64_t)(O - 1) * ld_base + I) * 2, dst_bytes = ((int64_t)(O - 1) * ld_dst + I) * 2;
+  if (int rc = lora_slice_guards(what, base, ld_base, dst, ld_dst, O, I)) return rc;
+  const int64_t dst_bytes = ((int64_t)(O - 1) * ld_dst + I) * 2;
   LoraFoldArgs args{};
   LoraGainArgs gains{};
   for (int j = 0; j < J; ++j) {
@@ -246,11 +382,69 @@ static int lora_fold_launch(const char* what, bool rows, const void* base, int64
       gains.g[j] = row_gain[j];
     }
   }
-  if (ranges_overlap(base, base_bytes, dst, dst_bytes)) return fail(AFX_E_INVALID, "%s: dst overlaps base", what);
   const int64_t tiles = (int64_t)(O / 64) * (I / 64);
-  if (tiles > 0x7fffffff) return fail(AFX_E_INVALID, "%s: %lld tiles", what, (long long)tiles);
   hipLaunchKernelGGL(rows ? lora_fold_kernel<true> : lora_fold_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)base, ld_base, (bf16_t*)dst, ld_dst, (int)I, (int)J, args, gains);
+  HIP_TRY(hipGetLastError());
+  return AFX_OK;
+}
+
+// the guards and the launch of afx_lora_fold_terms
+static int lora_fold_terms_launch(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J, const afx_lora_term* terms,
+                                  void* stream) {
+  const char* what = "afx_lora_fold_terms";
+  if (!base || !dst) return fail(AFX_E_INVALID, "%s: null base / dst", what);
+  if (J < 0 || J > AFX_LORA_MAX_ADAPTERS) return fail(AFX_E_INVALID, "%s: %d terms (0 .. %d)", what, J, AFX_LORA_MAX_ADAPTERS);
+  if (J > 0 && !terms) return fail(AFX_E_INVALID, "%s: null term array", what);
+  if (int rc = lora_slice_guards(what, base, ld_base, dst, ld_dst, O, I)) return rc;
+  const int64_t dst_bytes = ((int64_t)(O - 1) * ld_dst + I) * 2;
+  LoraTermArgs args{};
+  for (int j = 0; j < J; ++j) {
+    const afx_lora_term& t = terms[j];
+    args.kind[j] = t.kind;
+    args.s[j] = t.scale;
+    if (t.kind != AFX_LORA_TERM_LORA && t.kind != AFX_LORA_TERM_LOHA && t.kind != AFX_LORA_TERM_LOKR)
+      return fail(AFX_E_INVALID, "%s: unknown kind %d of term %d", what, t.kind, j);
+    if (t.kind != AFX_LORA_TERM_LORA && t.row_gain) return fail(AFX_E_INVALID, "%s: term %d has row gains but is no LoRA term", what, j);
+    if (t.kind == AFX_LORA_TERM_LOKR) {
+      if (!t.w1 || !t.w2) return fail(AFX_E_INVALID, "%s: null w1 / w2 of LoKr term %d", what, j);
+      if (((uintptr_t)t.w1 & 3) || ((uintptr_t)t.w2 & 3)) return fail(AFX_E_INVALID, "%s: w1 / w2 of LoKr term %d must be 4-byte aligned", what, j);
+      if (t.ka < 1 || t.kb < 1 || t.kc < 1 || t.kd < 1)
+        return fail(AFX_E_INVALID, "%s: LoKr term %d factors [%d, %d] x [%d, %d] (all >= 1)", what, j, t.ka, t.kb, t.kc, t.kd);
+      if ((int64_t)t.kb * t.kd != I) return fail(AFX_E_INVALID, "%s: LoKr term %d has kb kd = %lld columns, I = %d", what, j, (long long)t.kb * t.kd, I);
+      const int64_t vrows = (int64_t)t.ka * t.kc;
+      if (vrows > 0x7fffffff || t.row0 < 0 || t.row0 + O > vrows)
+        return fail(AFX_E_INVALID, "%s: LoKr term %d: row0 = %lld with O = %d outside the %lld rows of kron(w1, w2) (< 2^31)", what, j, (long long)t.row0, O,
+                    (long long)vrows);
+      args.w1[j] = t.w1;
+      args.w2[j] = t.w2;
+      args.kb[j] = t.kb;
+      args.kc[j] = t.kc;
+      args.kd[j] = t.kd;
+      args.row0[j] = (int32_t)t.row0;
+      continue;
+    }
+    const bool loha = t.kind == AFX_LORA_TERM_LOHA;
+    if (!t.down || !t.up || (loha && (!t.down2 || !t.up2))) return fail(AFX_E_INVALID, "%s: null down / up of term %d", what, j);
+    if (t.rank < 1 || (loha && t.rank2 < 1)) return fail(AFX_E_INVALID, "%s: rank %d of term %d (>= 1)", what, t.rank < 1 ? t.rank : t.rank2, j);
+    if (((uintptr_t)t.down & 15) || (loha && ((uintptr_t)t.down2 & 15))) return fail(AFX_E_INVALID, "%s: down of term %d must be 16-byte aligned", what, j);
+    if (((uintptr_t)t.up & 1) || (loha && ((uintptr_t)t.up2 & 1))) return fail(AFX_E_INVALID, "%s: up of term %d must be 2-byte aligned", what, j);
+    args.down[j] = (const bf16_t*)t.down;
+    args.up[j] = (const bf16_t*)t.up;
+    args.r[j] = t.rank;
+    if (loha) {
+      args.down2[j] = (const bf16_t*)t.down2;
+      args.up2[j] = (const bf16_t*)t.up2;
+      args.r2[j] = t.rank2;
+    } else if (t.row_gain) {
+      if ((uintptr_t)t.row_gain & 3) return fail(AFX_E_INVALID, "%s: the row gains of term %d must be 4-byte aligned", what, j);
+      if (ranges_overlap(t.row_gain, (int64_t)O * 4, dst, dst_bytes)) return fail(AFX_E_INVALID, "%s: dst overlaps the row gains of term %d", what, j);
+      args.g[j] = t.row_gain;
+    }
+  }
+  const int64_t tiles = (int64_t)(O / 64) * (I / 64);
+  hipLaunchKernelGGL(lora_fold_terms_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)base, ld_base, (bf16_t*)dst, ld_dst,
+                     (int)I, (int)J, args);
   HIP_TRY(hipGetLastError());
   return AFX_OK;
 }
@@ -270,6 +464,11 @@ int afx_lora_fold_rows(const void* base, int64_t ld_base, void* dst, int64_t ld_
                        const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, const float* const* row_gain,
                        void* stream) {
   return lora_fold_launch("afx_lora_fold_rows", true, base, ld_base, dst, ld_dst, O, I, J, A, B, ranks, scales, row_gain, stream);
+}
+
+int afx_lora_fold_terms(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
+                        const afx_lora_term* terms, void* stream) {
+  return lora_fold_terms_launch(base, ld_base, dst, ld_dst, O, I, J, terms, stream);
 }
 
 int afx_lora_row_gain(const void* base, int64_t ld_base, int32_t O, int32_t I, const void* A, const void* B, int32_t r, float s,

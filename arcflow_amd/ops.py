@@ -1655,6 +1655,68 @@ def lora_fold(base: torch.Tensor, dst: torch.Tensor, A=(), B=(), scales=(), row_
     return dst
 
 
+def lora_fold_terms(base: torch.Tensor, dst: torch.Tensor, terms=()) -> torch.Tensor:
+    """dst = bf16(c * base + sum_j g_j * scale_j * D_j) (``afx_lora_fold_terms``): ``lora_fold`` over terms of three kinds, each a dict with
+    a python float ``scale`` applied in fp32 to the term's fp32 delta D_j:
+
+    * ``dict(kind='lora', A=[r, I], B=[O, r], scale=s, row_gain=None or fp32 [O])``: D = B @ A, exactly ``lora_fold``'s arithmetic (a call with
+      only such terms returns its bits);
+    * ``dict(kind='loha', w1_a=[O, r1], w1_b=[r1, I], w2_a=[O, r2], w2_b=[r2, I], scale=s)``: D = (w1_a @ w1_b) * (w2_a @ w2_b), contiguous bf16
+      operands of any ranks >= 1, both products kept in fp32;
+    * ``dict(kind='lokr', w1=[a, b], w2=[c, d], scale=s, row0=0)``: D = rows row0 .. row0 + O of kron(w1, w2), contiguous fp32 factors with
+      b * d == I and row0 + O <= a * c.
+
+    base, dst as for ``lora_fold``; c and g_j are 1 without row gains.  One rounding, at the store; bit-reproducible; no terms = a copy.  The LoHa
+    and LoKr rules are LyCORIS' as recalled: not checked against LyCORIS or ComfyUI."""
+    lib = _lib.load()
+    _mat(base, torch.bfloat16, 'lora_fold_terms base')
+    _mat(dst, torch.bfloat16, 'lora_fold_terms dst', base.shape)
+    O, I = base.shape
+    J = len(terms)
+    arr = (_lib.LoraTerm * max(J, 1))()
+
+    def pair(j, up_name, down_name, t):
+        up, down = t[up_name], t[down_name]
+        _mat(up, torch.bfloat16, f'lora_fold_terms terms[{j}] {up_name}')
+        _mat(down, torch.bfloat16, f'lora_fold_terms terms[{j}] {down_name}')
+        r = down.shape[0]
+        if not (up.is_contiguous() and down.is_contiguous()) or tuple(down.shape) != (r, I) or tuple(up.shape) != (O, r):
+            raise ValueError(f'lora_fold_terms: term {j} needs contiguous {down_name} [r, {I}] and {up_name} [{O}, r], got {tuple(down.shape)} and '
+                             f'{tuple(up.shape)}')
+        return up.data_ptr(), down.data_ptr(), r
+    for j, t in enumerate(terms):
+        kind = t.get('kind')
+        c = arr[j]
+        c.scale = float(t['scale'])
+        if kind != 'lora' and t.get('row_gain') is not None:
+            raise ValueError(f'lora_fold_terms: term {j} is a {kind} term: row gains belong to LoRA terms')
+        if kind == 'lora':
+            c.kind = _lib.AFX_LORA_TERM_LORA
+            c.up, c.down, c.rank = pair(j, 'B', 'A', t)
+            if t.get('row_gain') is not None:
+                c.row_gain = _acc(t['row_gain'], (O,), f'lora_fold_terms terms[{j}] row_gain').data_ptr()
+        elif kind == 'loha':
+            c.kind = _lib.AFX_LORA_TERM_LOHA
+            c.up, c.down, c.rank = pair(j, 'w1_a', 'w1_b', t)
+            c.up2, c.down2, c.rank2 = pair(j, 'w2_a', 'w2_b', t)
+        elif kind == 'lokr':
+            c.kind = _lib.AFX_LORA_TERM_LOKR
+            w1, w2, row0 = t['w1'], t['w2'], int(t.get('row0', 0))
+            for name, w in (('w1', w1), ('w2', w2)):
+                _gpu(w, name=f'lora_fold_terms terms[{j}] {name}')
+                if w.dim() != 2 or w.dtype != torch.float32 or not w.is_contiguous() or 0 in w.shape:
+                    raise ValueError(f'lora_fold_terms: term {j} needs a contiguous 2-D float32 {name}, got {tuple(w.shape)} {w.dtype} strides {w.stride()}')
+            (ka, kb), (kc, kd) = w1.shape, w2.shape
+            if kb * kd != I or row0 < 0 or row0 + O > ka * kc:
+                raise ValueError(f'lora_fold_terms: term {j}: kron of w1 {tuple(w1.shape)} and w2 {tuple(w2.shape)} is [{ka * kc}, {kb * kd}], which does '
+                                 f'not hold rows {row0} .. {row0 + O} of {I} columns')
+            c.w1, c.w2, c.ka, c.kb, c.kc, c.kd, c.row0 = w1.data_ptr(), w2.data_ptr(), ka, kb, kc, kd, row0
+        else:
+            raise ValueError(f"lora_fold_terms: term {j} has kind {kind!r} (one of 'lora', 'loha', 'lokr')")
+    _lib.check(lib.afx_lora_fold_terms(_p(base), base.stride(0), _p(dst), dst.stride(0), O, I, J, C.cast(arr, C.c_void_p), _s()))
+    return dst
+
+
 def lora_row_gain(base: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: float, magnitude: torch.Tensor, out=None) -> torch.Tensor:
     """The row gains of one DoRA adapter on one linear (``afx_lora_row_gain``): gain[o] = magnitude[o] / || (base + scale * B @ A)[o, :] ||, fp32
     [O]; base [O, I] bf16 (any row stride >= I), A [r, I] and B [O, r] contiguous bf16 of any rank >= 1, magnitude fp32 [O].  The rows are

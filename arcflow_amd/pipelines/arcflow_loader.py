@@ -77,8 +77,15 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], prefix: str = 'transforme
     skipped ``text_encoder*`` keys).  Accepted per module, with or without the leading ``transformer.``:
     ``<module>.lora_A.weight`` / ``lora_B.weight`` (also with an adapter infix, ``lora_A.default.weight``), ``<module>.lora_down.weight``
     / ``lora_up.weight``, and an optional scalar ``<module>.alpha``.  Kohya / ComfyUI checkpoints (``lora_unet_*`` keys, fused qkv /
-    linear1 tensors) are refused: convert them to the diffusers layout first."""
+    linear1 tensors) are refused: convert them to the diffusers layout first.
+
+    LyCORIS tensors under the same module names (``<module>.hada_w1_a`` / ``hada_w1_b`` / ``hada_w2_a`` / ``hada_w2_b``; ``<module>.lokr_w1`` or
+    ``lokr_w1_a`` + ``lokr_w1_b``, the same for ``lokr_w2``, and the integer scalar ``<module>.lokr_row0`` the conversion writes for the parts of a
+    fused tensor) become entries that carry their kind, ``dict(kind='loha' | 'lokr', ...)`` as ``lora_formats.lycoris_entry`` builds them; a LoRA
+    entry has no ``kind``.  One module holds one kind per file; an incomplete group raises ValueError naming the family and a key."""
+    from . import lora_formats as F
     mods: Dict[str, Dict] = {}
+    lyc: Dict[str, Dict] = {}                       # module -> dict(t={LyCORIS tensor name: tensor}, keys={name: key}, row0=None or int)
     skipped = 0
     for k, v in sd.items():
         if k.startswith('lora_unet_') or k.startswith('lora_te'):
@@ -88,6 +95,20 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], prefix: str = 'transforme
             skipped += 1
             continue
         k2 = k[len(prefix) + 1:] if k.startswith(prefix + '.') else k
+        stem, slot = F.lycoris_slot(k2)
+        if slot is not None:
+            F._refuse_lycoris(k, v)
+            group = lyc.setdefault(stem, dict(t={}, keys={}, row0=None))
+            if slot == F.LOKR_ROW0:
+                if v.numel() != 1 or v.is_floating_point():
+                    raise ValueError(f'{k!r}: {F.LOKR_ROW0} is an integer scalar, got {tuple(v.shape)} {v.dtype}')
+                group['row0'] = int(v)
+            else:
+                group['t'][slot] = v
+            group['keys'][slot] = k
+            continue
+        if k2.rpartition('.')[2] in F._TUCKER + ('diff', 'diff_b'):
+            F._refuse_lycoris(k, v)
         m = _LORA_KEY.match(k2)
         if m is not None:
             slot = 'A' if m.group('kind') in ('lora_A', 'lora_down') else 'B'
@@ -102,8 +123,16 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], prefix: str = 'transforme
                              f'or <module>.alpha)')
     if skipped:
         warnings.warn(f'{skipped} text-encoder LoRA tensors were skipped: only transformer LoRAs are applied.')
+    for name, group in lyc.items():
+        first = group['keys'][next(iter(group['keys']))]
+        e = mods.pop(name, dict(A=None, B=None, alpha=None))
+        if e['A'] is not None or e['B'] is not None:
+            raise ValueError(f'{first!r}: module {name!r} has LoRA and LoHa / LoKr tensors: one module holds one kind per file')
+        if not group['t']:
+            raise ValueError(f'{first!r}: LoKr module {name!r} is incomplete: a {F.LOKR_ROW0} without factors')
+        mods[name] = F.lycoris_entry(name, group['t'], group['keys'], e['alpha'], group['row0'])
     for name, e in mods.items():
-        if e['A'] is None or e['B'] is None:
+        if 'kind' not in e and (e['A'] is None or e['B'] is None):
             raise ValueError(f'LoRA module {name!r}: lora_A / lora_B (lora_down / lora_up) pair is incomplete')
     return mods, skipped
 
@@ -224,6 +253,13 @@ class ArcFlowLoaderMixin:
         still one rounding.  An active DoRA adapter at weight 0 still applies its magnitude ((m / ||W_base|| - 1) W_base, as peft does); an
         adapter left out of `set_adapters` contributes nothing.  A row with ||.|| = 0 gets g = 0 where peft divides by zero.
 
+        LyCORIS LoHa (`hada_w1_a/b`, `hada_w2_a/b`) and LoKr (`lokr_w1[_a/_b]`, `lokr_w2[_a/_b]`) files load under the same module spellings
+        (`lora_formats`): a LoHa module contributes s (w1_a w1_b) (*) (w2_a w2_b), a LoKr module s kron(w1, w2), s = the effective scale below
+        with factor `alpha / r` as `lora_formats.lycoris_factor` states it.  LoHa operands are kept as bf16, LoKr factors as dense fp32 (a low-rank
+        factor is multiplied out once at load); a linear with such a term is folded by `afx_lora_fold_terms`, LoRA / DoRA / LoHa / LoKr terms
+        of all active adapters together, still with one rounding.  The LyCORIS rules are restated from memory: not checked against LyCORIS or
+        ComfyUI.  A DoRA magnitude on a LoHa / LoKr module, Tucker / convolution tensors and `diff` keys are refused.
+
         Every adapter's tensors are uploaded once as bf16: fp32 / fp16 files are rounded once here, as `weights._merge_one` does for the
         ArcFlow adapter.  Its factor is `alpha / r` per module (1 without `alpha`); the effective scale of adapter j is
         `call_scale * adapter_weights[j] * alpha_j / r_j`, with `call_scale` = `joint_attention_kwargs['scale']` (`attention_kwargs`
@@ -264,6 +300,8 @@ class ArcFlowLoaderMixin:
         for m, v in magnitudes.items():
             if m not in mods:
                 raise ValueError(f'adapter {adapter_name!r}: a DoRA magnitude for {m!r}, which has no lora_A / lora_B pair in this file')
+            if 'kind' in mods[m]:
+                raise ValueError(f'adapter {adapter_name!r}: a DoRA magnitude on the LoHa / LoKr module {m!r} is not supported')
             mods[m]['magnitude'] = v
         sty = getattr(self, '_style', None)
         fresh = sty is None
@@ -292,12 +330,35 @@ class ArcFlowLoaderMixin:
 
     def _upload_adapter(self, sty, mods, device, what: str, magnitude: Optional[Dict] = None):
         """{module: dict(A, B, alpha)} -> {module: (A bf16 on the device, B bf16 on the device, alpha / r)}, checked against the linear it adapts.
-        A module's DoRA magnitude (its 'magnitude' entry, [rows]) goes into `magnitude` as fp32 on the device."""
+        A module's DoRA magnitude (its 'magnitude' entry, [rows]) goes into `magnitude` as fp32 on the device.
+
+        A LoHa entry becomes dict(kind='loha', w1_a, w1_b, w2_a, w2_b bf16 on the device, factor); a LoKr entry dict(kind='lokr', w1 [a, b], w2 [c, d]
+        dense fp32 on the device, row0, factor), a low-rank factor multiplied out here, once, in fp32 (it is [c, d]-sized)."""
+        from . import lora_formats as F
         out = {}
         for m, e in mods.items():
             if m not in sty['slices']:
                 raise ValueError(f'{what}: the transformer has no linear {m!r}')
             _, _, rows, in_f = sty['slices'][m]
+            if 'kind' in e:
+                if rows % 64 or in_f % 64:
+                    raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear; adapters are folded on linears whose sizes are multiples of 64')
+                if e['kind'] == 'loha':
+                    for n in ('w1', 'w2'):
+                        if e[n + '_a'].shape[0] != rows or e[n + '_b'].shape[1] != in_f:
+                            raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear, hada_{n}_a {tuple(e[n + "_a"].shape)} / hada_{n}_b '
+                                             f'{tuple(e[n + "_b"].shape)} do not fit it')
+                    out[m] = dict(kind='loha', factor=F.lycoris_factor(e),
+                                  **{n: e[n].to(device=device, dtype=torch.bfloat16).contiguous() for n in ('w1_a', 'w1_b', 'w2_a', 'w2_b')})
+                else:
+                    a, b, c, d = F.lokr_shapes(e)
+                    if b * d != in_f or e['row0'] < 0 or e['row0'] + rows > a * c or (not e['sliced'] and a * c != rows):
+                        raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear; kron of lokr_w1 [{a}, {b}] and lokr_w2 [{c}, {d}] is '
+                                         f'[{a * c}, {b * d}] (a c x b d), which does not fit it at lokr_row0 = {e["row0"]}')
+                    dense = {n: e[n].float() if e[n] is not None else e[n + '_a'].float() @ e[n + '_b'].float() for n in ('w1', 'w2')}
+                    out[m] = dict(kind='lokr', factor=F.lycoris_factor(e), row0=e['row0'],
+                                  **{n: w.to(device=device, dtype=torch.float32).contiguous() for n, w in dense.items()})
+                continue
             a, b = e['A'], e['B']
             if a.dim() != 2 or b.dim() != 2 or a.shape[0] < 1 or a.shape[0] != b.shape[1] or a.shape[1] != in_f or b.shape[0] != rows:
                 raise ValueError(f'{what}: {m!r} is a [{rows}, {in_f}] linear, lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do not fit it')
@@ -387,7 +448,8 @@ class ArcFlowLoaderMixin:
     def _fold_adapters(self, call_scale: float) -> None:
         """Bring the engine's packed weights to the active adapters at `call_scale`: one `afx_lora_fold` per linear whose list of
         (adapter, fp32 scale) differs from what is folded in now.  A linear with an active DoRA adapter is folded by `afx_lora_fold_rows`
-        with that adapter's row gains, computed by `afx_lora_row_gain` when its scale is not the one the cached vector was made for."""
+        with that adapter's row gains, computed by `afx_lora_row_gain` when its scale is not the one the cached vector was made for.  A linear
+        with an active LoHa / LoKr term goes through `afx_lora_fold_terms` with all its terms; every other linear takes the call it always took."""
         from .. import ops
         sty = self._style
         eng = self._lora_engine()
@@ -400,10 +462,14 @@ class ArcFlowLoaderMixin:
             A, B, S, sig = [], [], [], []
             for name, mods in sources:
                 if name in sty['active'] and m in mods:
-                    a, b, factor = mods[m]
+                    if isinstance(mods[m], dict):                                   # a LoHa / LoKr entry: the whole entry stands where A stands
+                        a, b, factor = mods[m], None, mods[m]['factor']
+                    else:
+                        a, b, factor = mods[m]
                     s = ctypes.c_float(call_scale * sty['active'][name] * factor).value
                     if s != 0.0 or m in sty['magnitude'].get(name, ()):             # a DoRA adapter at scale 0 still applies its magnitude
                         A.append(a); B.append(b); S.append(s); sig.append((name, s))
+            lycoris = any(isinstance(a, dict) for a in A)
             sig = tuple(sig)
             if sty['folded'].get(m, None if m in sty['arc'] else ()) == sig:        # (the ArcFlow-only path folded the arc linears so far)
                 continue
@@ -422,7 +488,12 @@ class ArcFlowLoaderMixin:
                     if cached is None or cached[0] != s:
                         cached = sty['gain'][(name, m)] = (s, ops.lora_row_gain(base, A[j], B[j], s, mag))
                     gains.append(cached[1])
-            ops.lora_fold(base, eng._weights[packed][r0:r0 + rows], A, B, S, row_gains=gains)
+            if not lycoris:                                                         # the call this linear always took
+                ops.lora_fold(base, eng._weights[packed][r0:r0 + rows], A, B, S, row_gains=gains)
+            else:
+                terms = [dict(a, scale=s) if isinstance(a, dict) else dict(kind='lora', A=a, B=b, scale=s, row_gain=None if gains is None else gains[j])
+                         for j, (a, b, s) in enumerate(zip(A, B, S))]
+                ops.lora_fold_terms(base, eng._weights[packed][r0:r0 + rows], terms)
             sty['folded'][m] = sig
             for k in (packed + '_q', packed[:-len('weight')] + 'wscale'):      # quantised copies of an earlier enable_fp8(): stale now, a later
                 eng._weights.pop(k, None)                                      # enable_fp8() quantises this matrix again

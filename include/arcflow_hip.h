@@ -891,6 +891,49 @@ int afx_lora_fold_rows(const void* base, int64_t ld_base, void* dst, int64_t ld_
                        const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, const float* const* row_gain,
                        void* stream);
 
+/* LyCORIS LoHa and LoKr adapters next to LoRA / DoRA ones: the fold over a list of TERMS of three kinds,
+ *   dst[o, i] = bf16_rne( c[o] float(base[o, i]) + sum_j (g_j[o] scale_j) * D_j[o, i] ),   D_j in fp32,
+ * c and g_j as afx_lora_fold_rows defines them (g_j = 1 for a term without row gains: every LoHa / LoKr term).  NOT PINNED: the two rules below are
+ * LyCORIS' / ComfyUI's arithmetic restated from memory; neither library was at hand to check them.
+ *   AFX_LORA_TERM_LORA  D = up . down: `down` [rank, I] bf16 (16-byte aligned), `up` [O, rank] bf16, `row_gain` null or fp32 [O] (a DoRA adapter's gains).
+ *                       Exactly afx_lora_fold_rows' arithmetic: a call whose terms are all of this kind returns its bits (afx_lora_fold's without gains).
+ *   AFX_LORA_TERM_LOHA  D = (up . down) (*) (up2 . down2), the element-wise product of two low-rank products (LyCORIS hada_w1_a . hada_w1_b and
+ *                       hada_w2_a . hada_w2_b): `up` [O, rank], `down` [rank, I], `up2` [O, rank2], `down2` [rank2, I] bf16 as above, any ranks >= 1.
+ *                       Both products are formed as a LoRA term's is (bf16 MFMAs, fp32 sums over the whole rank), multiplied element by element in
+ *                       fp32 -- neither is rounded to bf16 -- and the fp32 product enters the sum by one fused multiply-add with `scale`.
+ *   AFX_LORA_TERM_LOKR  D[o, i] = fl32( w1[(row0 + o) / kc, i / kd] * w2[(row0 + o) % kc, i % kd] ): rows row0 .. row0 + O of kron(w1, w2), `w1` [ka, kb]
+ *                       and `w2` [kc, kd] dense fp32 (4-byte aligned), kb kd == I, 0 <= row0, row0 + O <= ka kc < 2^31.  kc and kd are arbitrary (no
+ *                       multiples of the tile).  row0 lets one row slice of a fused tensor be folded without splitting the Kronecker product.
+ * Fields a kind does not name are ignored, except row_gain, which must be null on a LoHa / LoKr term.  `terms` is a HOST array of J <=
+ * AFX_LORA_MAX_ADAPTERS entries read before the call returns.  One work-group owns a 64 x 64 tile and walks the terms in order, each over its whole
+ * rank: no split, no atomics, no workspace, bit-reproducible; the store is the one rounding to bf16.  J == 0 copies.  base / dst / O / I / leading
+ * dimensions and their guards as afx_lora_fold.  AFX_E_INVALID (nothing is launched) also for: an unknown kind, a null operand of the term's kind, a
+ * rank < 1, ka / kb / kc / kd < 1, kb kd != I, row0 out of range, a misaligned operand, row gains on a LoHa / LoKr term or overlapping dst.
+ * Traffic: 4 B per element of the slice + the operands out of L2: HBM-bound. */
+#define AFX_LORA_TERM_LORA 0
+#define AFX_LORA_TERM_LOHA 1
+#define AFX_LORA_TERM_LOKR 2
+typedef struct afx_lora_term {
+  int32_t kind;             /* AFX_LORA_TERM_* */
+  int32_t rank;             /* LoRA: rank; LoHa: rank of the first pair */
+  int32_t rank2;            /* LoHa: rank of the second pair */
+  float scale;              /* fp32 factor of the term's fp32 delta */
+  const void* down;         /* LoRA: A [rank, I]; LoHa: hada_w1_b [rank, I] */
+  const void* up;           /* LoRA: B [O, rank]; LoHa: hada_w1_a [O, rank] */
+  const void* down2;        /* LoHa: hada_w2_b [rank2, I] */
+  const void* up2;          /* LoHa: hada_w2_a [O, rank2] */
+  const float* row_gain;    /* LoRA: null or fp32 [O] */
+  const float* w1;          /* LoKr: fp32 [ka, kb] */
+  const float* w2;          /* LoKr: fp32 [kc, kd] */
+  int32_t ka;
+  int32_t kb;
+  int32_t kc;
+  int32_t kd;
+  int64_t row0;             /* LoKr: the slice's first row in the virtual [ka kc, kb kd] delta */
+} afx_lora_term;
+int afx_lora_fold_terms(const void* base, int64_t ld_base, void* dst, int64_t ld_dst, int32_t O, int32_t I, int32_t J,
+                        const afx_lora_term* terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@
 
 OUT holds ``transformer.<module>.lora_A.weight`` / ``lora_B.weight`` / ``alpha`` per diffusers linear (fused qkv / linear1 tensors split by rows, each
 part with its own copy of ``lora_A``) and ``transformer.<module>.lora_magnitude_vector`` where the file has a DoRA magnitude; text-encoder tensors
-are left out.  ``--transformer-config`` is the transformer's ``config.json`` (default: the released FLUX.1-dev / Qwen-Image sizes); ``--teacher``
+are left out.  LyCORIS LoHa / LoKr modules come out under the diffusers module name with LyCORIS' own tensor names
+(``transformer.<module>.hada_w1_a`` ..., ``lokr_w1`` ...; the parts of a fused LoKr share both factors and carry ``lokr_row0``, their first row in the
+fused delta) -- a layout this project's loader reads; other software may not.  ``--transformer-config`` is the transformer's ``config.json`` (default: the released FLUX.1-dev / Qwen-Image sizes); ``--teacher``
 keeps ``final_layer.linear`` as ``proj_out``, which the ArcFlow student does not have.  ``load_lora_weights`` does the same conversion in memory
 (``arcflow_amd/pipelines/lora_formats.py``, which also says what is not pinned: the BFL <-> diffusers table is restated from memory); this tool
 is for handing the result to other software.  Runs on the CPU."""
@@ -47,7 +49,9 @@ def main(argv=None):
     out, skipped = convert_file(a.src, a.dst, a.family, config, student=not a.teacher)
     n_mod = sum(k.endswith('.lora_A.weight') for k in out)
     n_mag = sum(k.endswith('.lora_magnitude_vector') for k in out)
-    print(f'{a.dst}: {n_mod} adapted linears, {n_mag} DoRA magnitudes, {len(skipped)} tensors skipped')
+    n_loha = sum(k.endswith('.hada_w1_a') for k in out)
+    n_lokr = sum(k.endswith(('.lokr_w1', '.lokr_w1_a')) for k in out)
+    print(f'{a.dst}: {n_mod} adapted linears, {n_mag} DoRA magnitudes, {n_loha} LoHa and {n_lokr} LoKr linears, {len(skipped)} tensors skipped')
 
 
 if __name__ == '__main__':

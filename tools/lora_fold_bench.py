@@ -2,6 +2,7 @@
 """Time ``afx_lora_fold`` (the device fold behind ``load_lora_weights`` / ``set_adapters``) on synthetic weights -- no snapshot needed.
 
     python tools/lora_fold_bench.py [--double 19 --single 38] [--reps 3] [--iters 20] [--skip-parent]
+    python tools/lora_fold_bench.py --lycoris [--parent-lib libarcflow_hip.so of the parent commit]
 
 Prints
   * per FLUX matrix shape: the kernel's time (device events around --iters launches, after a warm-up) and GB/s over the 4 * O * I bytes it
@@ -51,6 +52,9 @@ def main(argv=None):
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--skip-parent', action='store_true')
     ap.add_argument('--dora', action='store_true', help='time afx_lora_row_gain and afx_lora_fold_rows per FLUX shape against the torch formulation, and stop')
+    ap.add_argument('--lycoris', action='store_true', help='time afx_lora_fold_terms with a LoHa, a LoKr and a mixed term list per FLUX shape against '
+                    'the torch formulation and the plain LoRA fold, and stop')
+    ap.add_argument('--parent-lib', help='--lycoris: a libarcflow_hip.so built from the parent commit; its afx_lora_fold is timed beside this build\'s')
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('lora_fold_bench needs the GPU: a CPU run measures nothing')
@@ -65,6 +69,8 @@ def main(argv=None):
     res = dict(device=torch.cuda.get_device_name(0), ranks=list(RANKS), shapes=[], double=a.double, single=a.single)
     if a.dora:
         return dora(a, ops, rnd, res)
+    if a.lycoris:
+        return lycoris(a, ops, rnd, res)
     # ---- per shape
     for name, O, I in SHAPES:
         base, dst = rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device=dev)
@@ -165,6 +171,79 @@ def dora(a, ops, rnd, res):
         res['shapes'].append(row)
         print(f'{name:32s} [{O:6d}, {I:6d}]  gain {med["gain"] * 1e3:8.1f} us {row["gain_gb_per_s"]:7.1f} GB/s over 2 O I bytes | fold_rows '
               f'{med["fold_rows"] * 1e3:8.1f} us {row["fold_rows_gb_per_s"]:7.1f} GB/s over 4 O I bytes | torch {med["torch"] * 1e3:8.1f} us')
+        del base, dst
+    print(json.dumps(res))
+
+
+def kron_factors(n):
+    """(m, n / m) with m the largest divisor of n not above sqrt(n): LyCORIS' default factorisation (factor = -1) as recalled."""
+    m = int(n ** 0.5)
+    while n % m:
+        m -= 1
+    return m, n // m
+
+
+def lycoris(a, ops, rnd, res):
+    """--lycoris: per FLUX shape, ``afx_lora_fold_terms`` with one LoHa adapter of rank 16, one LoKr adapter at LyCORIS' default factorisation (w2 dense:
+    w1 [a, b] holds the smaller factors of O and I, w2 [c, d] the larger), and the mixed call (LoRA r = 256, LoHa and LoKr together), each beside the
+    torch formulation of the same result (``torch.kron`` / ``matmul`` / ``mul`` / ``add`` in fp32, then a cast) and beside the plain LoRA fold (r = 256
+    and r = 16) of this build and, with --parent-lib, of the parent commit's library.  Device events around --iters launches after a warm-up, the paths
+    alternating --reps times; the median is printed, all repeats go into the JSON line.  The buffers are re-used, so a matrix that fits the Infinity
+    Cache is not an HBM figure."""
+    import ctypes as C
+    import statistics
+    import torch
+    from arcflow_amd import _lib
+    parent = None
+    if a.parent_lib:
+        parent = C.CDLL(a.parent_lib)
+        parent.afx_lora_fold.restype, parent.afx_lora_fold.argtypes = _lib.PROTOTYPES['afx_lora_fold']
+    s = 0.8
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    for name, O, I in SHAPES:
+        base, dst = rnd(O, I), torch.empty(O, I, dtype=torch.bfloat16, device='cuda')
+        A, B = [rnd(r, I, std=0.05) for r in RANKS], [rnd(O, r, std=0.05) for r in RANKS]
+        loha = dict(kind='loha', w1_a=rnd(O, 16, std=0.2), w1_b=rnd(16, I, std=0.2), w2_a=rnd(O, 16, std=0.2), w2_b=rnd(16, I, std=0.2), scale=s)
+        (ka, kc), (kb, kd) = kron_factors(O), kron_factors(I)
+        lokr = dict(kind='lokr', w1=rnd(ka, kb, std=0.14).float(), w2=rnd(kc, kd, std=0.14).float(), scale=s)
+        lora = dict(kind='lora', A=A[0], B=B[0], scale=1.0)
+        pa, pb = (C.c_void_p * 2)(*[t.data_ptr() for t in A]), (C.c_void_p * 2)(*[t.data_ptr() for t in B])
+        rk, sc = (C.c_int32 * 2)(*RANKS), (C.c_float * 2)(1.0, s)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def t_loha():
+            return torch.addcmul(base.float(), loha['w1_a'].float() @ loha['w1_b'].float(), loha['w2_a'].float() @ loha['w2_b'].float(), value=s).to(torch.bfloat16)
+
+        def t_lokr():
+            return torch.add(base.float(), torch.kron(lokr['w1'], lokr['w2']), alpha=s).to(torch.bfloat16)
+
+        def t_mixed():
+            v = torch.addmm(base.float(), B[0].float(), A[0].float())
+            v = torch.addcmul(v, loha['w1_a'].float() @ loha['w1_b'].float(), loha['w2_a'].float() @ loha['w2_b'].float(), value=s)
+            return torch.add(v, torch.kron(lokr['w1'], lokr['w2']), alpha=s).to(torch.bfloat16)
+        paths = dict(loha=lambda: ops.lora_fold_terms(base, dst, [loha]), torch_loha=t_loha, lokr=lambda: ops.lora_fold_terms(base, dst, [lokr]),
+                     torch_lokr=t_lokr, mixed=lambda: ops.lora_fold_terms(base, dst, [lora, loha, lokr]), torch_mixed=t_mixed,
+                     lora_fold=lambda: ops.lora_fold(base, dst, A, B, (1.0, s)))
+        if parent is not None:
+            paths['parent_lora_fold'] = lambda: parent.afx_lora_fold(C.c_void_p(base.data_ptr()), I, C.c_void_p(dst.data_ptr()), I, O, I, 2, pa, pb, rk, sc, stream)
+        for fn in paths.values():
+            for _ in range(3):
+                fn()
+        ms = {k: [] for k in paths}
+        for _ in range(a.reps):
+            for k, fn in paths.items():
+                ms[k].append(timed(fn))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        res['shapes'].append(dict(name=name, O=O, I=I, lokr_factors=[ka, kb, kc, kd], ms=ms, gb_per_s={k: 4.0 * O * I / (v * 1e-3) / 1e9 for k, v in med.items()}))
+        print(f'{name:32s} [{O:6d}, {I:6d}] kron [{ka}, {kb}] x [{kc}, {kd}]  ' + '  '.join(f'{k} {v * 1e3:.1f} us' for k, v in med.items()))
         del base, dst
     print(json.dumps(res))
 
